@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: randomized double-pass eigensolve throughput (GDoF*rank/s) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload as|pod|kle] [--prior] [--quick]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload as|pod|kle] [--prior] [--quick] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (``--dump-outputs``) and prints the
+result line.  Everything else it can measure or check -- the oracle parity, the CPU baseline, the micro-benchmarked
+device peaks, the per-phase and literal-T steps, and (config 4 at one GPU) the extra workloads appended as extra keys --
+runs only with ``--full``.
 
 One "step" = one full double pass (Omega already in HBM -> eigenvalues on the host, eigenvectors in
 HBM) over one synthetic workload whose operator data is resident in HBM.  The default workload is
@@ -68,7 +73,7 @@ def parse_args():
                     help="exercise the multi-GPU code path (native communicator, all-reduce inside the fused solve) with one rank")
     ap.add_argument("--headline-only", action="store_true",
                     help="only the timed headline workload: skip the extra evidence lines (kernel point, configs 3 and 2, the 64-sample "
-                         "shard step) that a default --gpus 1 run of config 4 appends as extra keys (A/B runs, profiling)")
+                         "shard step) that a --full --gpus 1 run of config 4 appends as extra keys (A/B runs, profiling)")
     ap.add_argument("--kernel-point", action="store_true",
                     help="north-star kernel point instead of a solve: G = X^T Omega at N = 1e6, k = 138, n in {8 ... 2048}; one JSON line")
     ap.add_argument("--eig-large", action="store_true",
@@ -76,6 +81,14 @@ def parse_args():
                          "solve: n = 512 ... 8192, wall time of hfmi_sym_eig_small next to numpy.linalg.eigh on the host; one JSON line")
     ap.add_argument("--cpu-baseline", default="full", choices=["full", "quick"],
                     help="quick: the host legs at all threads and at one socket's cores only (no single-thread legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle parity, CPU baseline, device peaks, per-phase and literal-T steps, "
+                         "and on a default config-4 run the extra workloads as extra keys (without it: setup, warm-up, the timed "
+                         "steps, --dump-outputs, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): "
+                         "eigenvalues.npy, and eigenvectors.npy -- all rows, or a fixed seeded sample of rows (eigenvector_rows.npy) "
+                         "when the whole block would exceed the size budget")
     return ap.parse_args()
 
 
@@ -206,6 +219,31 @@ def host_reference(args, hf, wl, prior, world, Omega_host, r, hp_o):
         return hp_o.double_pass_blas3(apply_A, Omega_host, r, apply_B=lambda W: prior.R @ W,
                                       apply_Binv=lambda W: np.asfortranarray(prior.Rsolver.solve_block(W))), (lambda W: prior.R @ W)
     return hp_o.double_pass_blas3(apply_A, Omega_host, r), None
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20        # eigenvectors; with the eigenvalues and the row indices well under 64 MB in all
+DUMP_ROWS_SEED = 20240917
+
+
+def dump_outputs(outdir, d, U_dense):
+    """What a caller of the timed path receives, as float64 .npy files: the eigenvalues and the eigenvectors (N x r).
+    Beyond DUMP_BUDGET_BYTES the eigenvectors are a fixed sample of rows: seeded, sorted and a function of (N, r) only, so
+    two builds run with the same arguments write the same rows; their indices go to eigenvector_rows.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    d = np.asarray(d, dtype=np.float64)
+    U_dense = np.asarray(U_dense, dtype=np.float64)
+    N, r = U_dense.shape
+    files = {"eigenvalues": d}
+    rows_max = max(1, DUMP_BUDGET_BYTES // (8 * max(1, r)))
+    if N > rows_max:
+        rows = np.sort(np.random.default_rng(DUMP_ROWS_SEED).choice(N, size=rows_max, replace=False))
+        files["eigenvectors"] = np.ascontiguousarray(U_dense[rows])
+        files["eigenvector_rows"] = rows.astype(np.float64)
+    else:
+        files["eigenvectors"] = np.ascontiguousarray(U_dense)
+    for name, arr in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+    return sorted(files)
 
 
 def _timed(fn, *a):
@@ -719,7 +757,7 @@ def run_extras(args):
     for name, argv, limit in jobs:
         t0 = time.perf_counter()
         try:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--headline-only"] + argv, env=env, stdout=subprocess.PIPE,
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--headline-only"] + argv, env=env, stdout=subprocess.PIPE,
                                  stderr=subprocess.PIPE, timeout=limit)
             lines = [ln for ln in res.stdout.decode("utf-8", "replace").splitlines() if ln.startswith("{")]
             if res.returncode != 0 or not lines:
@@ -781,6 +819,8 @@ def spawn_and_report(args):
 def main():
     args = parse_args()
     limit_host_blas_to_cpu_quota()
+    if args.dump_outputs and (args.workload == "dipnet" or args.kernel_point or args.eig_large or args.ingest):
+        raise SystemExit("--dump-outputs belongs to the eigensolve workloads (--workload as|pod|kle)")
     if args.workload == "dipnet":
         return dipnet_line(args)
     if args.kernel_point:
@@ -823,8 +863,8 @@ def main():
 
 
 def kernel_extras_wanted(args, world):
-    """The extra evidence lines ride on the driver's default run only: config 4, one GPU, all 512 samples, plain doublePass."""
-    return (world == 1 and not args.headline_only and args.workload == "as" and not args.prior and not args.dist_single
+    """The extra evidence lines ride on a --full default run only: config 4, one GPU, all 512 samples, plain doublePass."""
+    return (args.full and world == 1 and not args.headline_only and args.workload == "as" and not args.prior and not args.dist_single
             and args.samples_total == 512)
 
 
@@ -892,9 +932,11 @@ def solve_line(args, world, rank):
     elapsed = time.perf_counter() - t0
     sysfs_after = gpu_sysfs_snapshot(pci) if rank == 0 else {}
     prof = ctx.profile_end()
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, d, U.to_dense())
     phases = ctx.profile_phases()
     phase_steps = args.steps
-    if timed_level < 2:
+    if args.full and timed_level < 2:
         _L.call("hfmi_tuning_set", b"prof_level", 2)
         phase_steps = max(1, min(3, args.steps))
         ctx.profile_begin()
@@ -910,7 +952,7 @@ def solve_line(args, world, rank):
     # the same solve with T = (A Q)^T Q formed literally, as the reference does (4 long contractions instead of 3):
     # reported next to the headline number, never part of it
     literal_ms = None
-    if not args.no_literal and B is None:
+    if args.full and not args.no_literal and B is None:
         nl = max(1, min(3, args.steps))
         step(literal_T=True)
         barrier()
@@ -948,9 +990,13 @@ def solve_line(args, world, rank):
     out["gpu_sysfs"] = {"pci_bus_id": pci, "before_timed_region": sysfs_before, "after_timed_region": sysfs_after}
     if literal_ms is not None:
         out["literal_T_ms_per_step"] = literal_ms
-    out["phases_ms_per_step"] = {name: ms / phase_steps for name, ms in phases.items()}
-    out["phases_from"] = ("the timed steps" if timed_level >= 2 else
-                          "%d extra untimed steps with per-phase events (the timed steps carry events on the big contractions only)" % phase_steps)
+    if args.full:
+        out["phases_ms_per_step"] = {name: ms / phase_steps for name, ms in phases.items()}
+        out["phases_from"] = ("the timed steps" if timed_level >= 2 else
+                              "%d extra untimed steps with per-phase events (the timed steps carry events on the big contractions only)"
+                              % phase_steps)
+    if args.dump_outputs:
+        out["dumped_outputs"] = dumped
 
     # roofline of the dominant kernel (= the (kernel, shape) group with the largest total time), from per-launch
     # HIP events recorded inside the timed region on the stream the kernels run on
@@ -998,6 +1044,19 @@ def solve_line(args, world, rank):
                            "tflops": g["flops_per_launch"] * g["launches"] / (g["ms"] * 1e-3) / 1e12}
                           for g in sorted(prof, key=lambda g: -g["ms"])]
         out["ms_per_step_in_mfma_kernels"] = mfma_ms
+    if args.full:
+        full_measurements(args, hf, ctx, out, wl, prior, world, Omega, d, U, r, p, N)
+    # release the workload's HBM before anything else is started on this GPU (the extras are child processes)
+    del wl, op, A, Omega, U, B, Binv
+    import gc
+    gc.collect()
+    ctx.synchronize()
+    return out
+
+
+def full_measurements(args, hf, ctx, out, wl, prior, world, Omega, d, U, r, p, N):
+    """--full: the measurements and checks beyond the headline, after the timed steps -- device peaks by micro-benchmark,
+    parity against the CPU oracle, the sparse triangular-solve feasibility estimate (--prior), the CPU baseline."""
     try:
         out["device_peaks_measured"] = ctx.bench_peaks()
         if "roofline" in out:     # the same fraction against what this box sustains in this job (constant-operand MFMA loop / copy kernel)
@@ -1058,12 +1117,6 @@ def solve_line(args, world, rank):
         # rank 0 alone (the other ranks have left the communicator): at N > 1 `wl` is rank 0's shard, the bounded sample is
         # drawn from it and scaled to the whole job exactly as at N = 1
         out["cpu_baseline"] = cpu_baseline(args, wl, prior, Omega_host, r, N, hp_o, hf_o)
-    # release the workload's HBM before anything else is started on this GPU (the extras are child processes)
-    del wl, op, A, Omega, U, B, Binv
-    import gc
-    gc.collect()
-    ctx.synchronize()
-    return out
 
 
 if __name__ == "__main__":

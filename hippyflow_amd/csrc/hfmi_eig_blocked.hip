@@ -1723,7 +1723,10 @@ int sym_eig_large(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, d
           const int rs2 = (j + 1) & ~(TS - 1);
           const int nb = (nr - rs2) / TS, ntiles = nb * (nb + 1) / 2;
           ta.nb = nb;
-          if (n > 4096) hipLaunchKernelGGL(k_tri_bs<16>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
+          // CB / 8 partial norms per lane, one per 64 rows from j: beyond n = 8192 the column below j can span 129 of them (j = n - 8193
+          // when n is a multiple of 128), which k_tri_bs<16> would drop
+          if (n > 8192) hipLaunchKernelGGL(k_tri_bs<32>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
+          else if (n > 4096) hipLaunchKernelGGL(k_tri_bs<16>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
           else hipLaunchKernelGGL(k_tri_bs<8>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
           ta.npvy = ntiles;
           prev_slots = true;
@@ -1798,7 +1801,8 @@ int sym_eig_large(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, d
     return (v >= 64 && v <= 256) ? v : 128;      // 128: n = 512 / 1024 5.65 / 11.5 ms against 6.06 / 11.9 with 256-row leaves, equal beyond
   }();
   int Lf = 0;
-  while (((n + (1 << Lf) - 1) >> Lf) > leaf_max) ++Lf;
+  // at most 128 leaves: the merges' node records (device workspace and pinned copy) hold 64 nodes; leaves stay <= 256 rows up to EB_MAXN
+  while (((n + (1 << Lf) - 1) >> Lf) > leaf_max && Lf < 7) ++Lf;
   HFMI_TRY(launch_dc_leaves(ctx, n, Lf, dvec, evec, D0, Q1, ld, fail));
   clk.mark(2);
   double *Dcur = D0, *Dnext = D1, *Qcur = Q1, *Qnext = Q2;

@@ -9,7 +9,7 @@
 for W in as pod; do
 for P in 2 4; do
   extra="--samples-total 64"; [ $W = pod ] && extra=""
-  python bench.py --gpus $P --workload $W --steps 1 --warmup 1 $extra --no-cpu-baseline 2>/dev/null | python3 -c "
+  python bench.py --full --gpus $P --workload $W --steps 1 --warmup 1 $extra --no-cpu-baseline 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['config']['workload'][:8], 'ranks', d['n_gpus'], d['communicator'], 'units/rank', d['config'].get('samples_per_gpu', d['config'].get('snapshots_per_gpu')), 'eig rel-err vs oracle(all samples)', d['parity']['eig_rel_err_vs_oracle'],

@@ -20,15 +20,15 @@ for w in as pod kle; do MIN_MS=0.05 bash scripts/pmc_workload.sh $w $tag > $out/
 cd $R
 python profiles/make_pmc_traffic.py $tag $out > $out/${tag}_make_pmc_traffic.log 2>&1 && cp profiles/pmc_traffic.json $out/${tag}_pmc_traffic.json
 for w in as pod kle; do
-  timeout 900 python bench.py --workload $w --headline-only > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err
+  timeout 900 python bench.py --full --workload $w --headline-only > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err
 done
-timeout 600 python bench.py --samples-total 64 --no-cpu-baseline > $out/${tag}_bench_as_shard64.json 2>/dev/null
-timeout 600 python bench.py --samples-total 64 --no-cpu-baseline --dist-single > $out/${tag}_bench_as_shard64_dist1.json 2>/dev/null
-timeout 600 python bench.py --gpus 2 --samples-total 128 --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_as_2ranks_one_gpu.json 2>/dev/null
+timeout 600 python bench.py --full --samples-total 64 --no-cpu-baseline > $out/${tag}_bench_as_shard64.json 2>/dev/null
+timeout 600 python bench.py --full --samples-total 64 --no-cpu-baseline --dist-single > $out/${tag}_bench_as_shard64_dist1.json 2>/dev/null
+timeout 600 python bench.py --full --gpus 2 --samples-total 128 --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_as_2ranks_one_gpu.json 2>/dev/null
 # the 8-rank rehearsal of the driver's --gpus 8 run: all 512 samples, 64 per rank, the eight ranks sharing this box's one GPU (p2p transport)
-timeout 900 python bench.py --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_as_8ranks_one_gpu.json 2> $out/${tag}_bench_as_8ranks_one_gpu.err
-# the driver's own command: headline + the extra evidence keys (kernel point, configs 3 / 2, shard step) in ONE line
-timeout 900 python bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+timeout 900 python bench.py --full --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_as_8ranks_one_gpu.json 2> $out/${tag}_bench_as_8ranks_one_gpu.err
+# the default config-4 command with --full: headline + the extra evidence keys (kernel point, configs 3 / 2, shard step) in ONE line
+timeout 900 python bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 timeout 600 python scripts/kernel_point.py > $out/${tag}_kernel_point.log 2>&1 && cp $out/kernel_point.json $out/${tag}_kernel_point.json
 bash scripts/shard_profile.sh ${tag}_shard64 > $out/${tag}_shard64_timeline.txt 2>&1
 bash scripts/shard_profile.sh ${tag}_shard64_dist1 --samples-total 64 --dist-single > $out/${tag}_shard64_dist1_timeline.txt 2>&1

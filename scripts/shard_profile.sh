@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$R/gpurun_out; mkdir -p $out
 rm -rf /tmp/prof_shard
-( cd $R && rocprofv3 --kernel-trace --stats -d /tmp/prof_shard -- python3 bench.py $args --headline-only --steps 5 --warmup 2 --no-cpu-baseline --no-check --no-literal > $out/${name}_bench.json 2> $out/${name}_prof.err )
+( cd $R && rocprofv3 --kernel-trace --stats -d /tmp/prof_shard -- python3 bench.py $args --full --headline-only --steps 5 --warmup 2 --no-cpu-baseline --no-check --no-literal > $out/${name}_bench.json 2> $out/${name}_prof.err )
 db=$(find /tmp/prof_shard -name "*.db" | head -1)
 python3 $R/profiles/summarize_rocpd.py $db > $out/${name}_kernel_stats.csv
 python3 - <<PY

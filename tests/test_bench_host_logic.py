@@ -5,6 +5,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -12,16 +14,62 @@ import bench  # noqa: E402
 
 def _args(**kw):
     base = dict(gpus=1, steps=10, warmup=3, workload="as", prior=False, quick=False, headline_only=False, dist_single=False,
-                samples_total=512, kernel_point=False, eig_large=False)
+                samples_total=512, kernel_point=False, eig_large=False, full=False, dump_outputs=None)
     base.update(kw)
     return argparse.Namespace(**base)
 
 
 def test_extras_ride_on_the_default_run_only():
-    assert bench.kernel_extras_wanted(_args(), 1)
+    """The extra workloads ride on the default config-4 command with --full; a plain run is the headline alone."""
+    assert bench.kernel_extras_wanted(_args(full=True), 1)
+    assert not bench.kernel_extras_wanted(_args(), 1)
     for kw in (dict(headline_only=True), dict(workload="pod"), dict(prior=True), dict(dist_single=True), dict(samples_total=64)):
-        assert not bench.kernel_extras_wanted(_args(**kw), 1)
-    assert not bench.kernel_extras_wanted(_args(), 2)
+        assert not bench.kernel_extras_wanted(_args(full=True, **kw), 1)
+    assert not bench.kernel_extras_wanted(_args(full=True), 2)
+
+
+def test_plain_run_options():
+    """--full is off by default, --dump-outputs takes a directory, --steps sets the timed steps."""
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse_args()
+        assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir"]
+        a = bench.parse_args()
+        assert a.full and a.dump_outputs == "out_dir"
+    finally:
+        sys.argv = argv
+
+
+def test_dump_outputs_small_block_is_written_whole(tmp_path):
+    rng = np.random.default_rng(0)
+    d, U = rng.standard_normal(12), rng.standard_normal((500, 12))
+    names = bench.dump_outputs(str(tmp_path / "o"), d, U)
+    assert names == ["eigenvalues", "eigenvectors"]
+    assert sorted(os.listdir(tmp_path / "o")) == ["eigenvalues.npy", "eigenvectors.npy"]
+    for name, ref in (("eigenvalues", d), ("eigenvectors", U)):
+        a = np.load(tmp_path / "o" / (name + ".npy"))
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, ref)
+
+
+def test_dump_outputs_large_block_is_a_fixed_row_sample_within_budget(tmp_path, monkeypatch):
+    """Beyond the budget the eigenvectors are a seeded sample of rows that depends on the shape only: two runs (two builds) write
+    the same rows, and everything written stays under 64 MB at the flagship's shape."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 64 * 1000)                 # 1000 rows of 64
+    rng = np.random.default_rng(1)
+    U = rng.standard_normal((5000, 64))
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), np.arange(64.0), U)
+    rows = np.load(tmp_path / "a" / "eigenvector_rows.npy")
+    assert rows.dtype == np.float64 and rows.shape == (1000,) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "b" / "eigenvector_rows.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "eigenvectors.npy"), U[rows.astype(np.int64)])
+    monkeypatch.undo()
+    N, r = 200000, 64                                                               # config 4
+    rows_max = bench.DUMP_BUDGET_BYTES // (8 * r)
+    assert rows_max < N and 8 * (rows_max * r + rows_max + r) < 64 * 2 ** 20
 
 
 def test_compact_form_of_an_extra_workload():

@@ -311,7 +311,7 @@ def test_pod_from_data_8300_snapshots_matches_the_reference(ctx, golden_dir, shi
     assert np.linalg.norm(eye - phi.T @ Mphi) / np.linalg.norm(eye) < 1e-8
 
 
-@pytest.mark.parametrize("n", [8193, 9000, 12500, 16384])
+@pytest.mark.parametrize("n", [8193, 8320, 9000, 12500, 16384])
 def test_sym_eig_blocked_beyond_8192(ctx, n):
     """8192 < n <= 16384: the first columns take full-column products (v of k_tri_b is up to 128 KB of LDS), the top merge of the divide
     and conquer keeps everything in global memory beyond 9984 poles (k_dcl_deflate<2>).  A matrix with a KNOWN spectrum (a diagonal
