@@ -1,4 +1,4 @@
-"""hippyflow_amd -- MI355X-native (gfx950) randomized double-pass eigensolve behind hippyflow's
+"""hippyflow_amd -- MI355X-native (gfx950) randomized double- and single-pass eigensolves behind hippyflow's
 model-based projectors (ActiveSubspaceProjector, KLEProjector, PODProjector).
 
 Host code is Python over a C ABI (include/hfmi.h, hippyflow_amd/libhfmi.so: hand-written HIP).
@@ -21,7 +21,8 @@ from .operators import (ComposedOperator, CsrOperator, CsrPCGSolver, DenseJacobi
 from .projectors import (ActiveSubspaceParameterList, ActiveSubspaceProjector, BoundaryRestrictedKLEProjector,
                          KLEParameterList, KLEProjector,
                          ParameterList, PODParameterList, PODProjector, PODProjectorFromData, weighted_l2_norm_vector)
-from .randomized import accuracyEnhancedSVD, doublePass, doublePassG, parRandom, svd_small, sym_eig_small
+from .randomized import (StreamedSketch, accuracyEnhancedSVD, doublePass, doublePassG, parRandom, singlePass, singlePassG,
+                         small_solve, svd_small, sym_eig_small)
 from .errors import input_output_error_test, projection_error_test
 from .io_utils import get_projectors, modify_projectors, spectrum_plot
 from .datasets import (derivative_dataset, jacobian_svds, jacobian_times_input_basis,

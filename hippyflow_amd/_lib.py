@@ -100,6 +100,10 @@ SIGNATURES = {
     "hfmi_svd_small": [_P, _P, C.c_int, _P, _P, _P],
     "hfmi_double_pass": [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
     "hfmi_double_pass_g": [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
+    "hfmi_single_pass": [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
+    "hfmi_single_pass_g": [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
+    "hfmi_sketch_eig": [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P],
+    "hfmi_small_solve": [_P, _P, _P, C.c_int, _P],
     "hfmi_bench_tsgemm_tn": [_P, _P, C.c_int, C.c_int, _P, _D],
     "hfmi_bench_tsgemm_nn": [_P, _P, _P, C.c_int, _D],
     "hfmi_bench_peaks": [_P, _D, _D, _D],

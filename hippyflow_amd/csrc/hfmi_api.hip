@@ -1660,7 +1660,13 @@ static int qr_mgs(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* R_host /* k
   return HFMI_OK;
 }
 
+// want_r: exact triangular factors in every Cholesky pass.  Without it a pass whose input is already orthonormal to ~1e-7
+// takes the kernel's first-order inverse square root, which left a 74-column single-pass sketch orthonormal to only ~1e-10.
+static int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes);
 extern "C" int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes) {
+  return borth_qr(Q, B, BQ, host_R, host_R != nullptr, method, passes);
+}
+static int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes) {
   if (!Q) HFMI_FAIL(HFMI_ERR_INVALID, "null block");
   if (BQ) HFMI_TRY(check_same_shape(Q, BQ, "borth_qr"));
   if (BQ && !B) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: BQ requested without B");
@@ -1674,7 +1680,7 @@ extern "C" int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* 
     HFMI_TRY(ctx_tmp_block(ctx, 5, Q->N, k, &save));
     HFMI_TRY(launch_copy(ctx, save->p, save->ld, Q->p, Q->ld, Q->N, k));
   }
-  int s = qr_chol(Q, B, BQ, host_R != nullptr, passes);
+  int s = qr_chol(Q, B, BQ, want_r, passes);
   if (s == HFMI_ERR_NUMERIC && method == HFMI_QR_AUTO) {
     HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, save->p, save->ld, Q->N, k));
     return qr_mgs(Q, B, BQ, host_R, passes);
@@ -1947,6 +1953,182 @@ extern "C" int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const h
                                   double* host_d, hfmi_block* U) {
   if (!B || !Binv) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass_g: B and Binv are required");
   return double_pass_impl(A, B, Binv, Omega, r, s, flags, host_d, U);
+}
+
+// ------------------------------------------------------------------ fused single pass
+// hippylib's singlePass / singlePassG (randomizedEigensolver): the Rayleigh-Ritz matrix comes from the sketch itself instead of
+// a further application of the operator.  With P = X_{s-1}, Y = X_s (X_0 = Omega, X_i = (B^-1) A X_{i-1}) and Q an
+// orthonormal (B-orthonormal) basis of range(Y):
+//   A ~ Q T Q^T (B Q T Q^T B)  =>  Q^T B Y = T (Q^T B P)  =>  Wt T^T = Zt,  Wt = P^T (B Q),  Zt = Ybar^T Q
+// (Ybar = A X_{s-1}; Ybar = Y without B), so T^T = Wt^-1 Zt, symmetrised.  The core below works on a sketch the caller
+// holds (hfmi_sketch_eig, streamed sketches) or the one single_pass_impl has just built: Q = orth(Y) with the same
+// Cholesky-QR / Gram-Schmidt rule as the double pass, the two m x m products, the LU solve (k_lu_solve writes T straight
+// into the eigensolver's slot), the eigensolve and U = Q V[:, :r], all on the context's stream.  The host waits only where the
+// double pass's checked route does (the status words of each orthogonalisation pass) and once at the end.
+// Q_work may alias Y for the generalized problem (Y itself is not needed after its orthogonalisation there).
+static int sketch_eig_core(const hfmi_block* P, const hfmi_block* Y, const hfmi_block* Ybar, hfmi_op* B, hfmi_block* Q_work,
+                           hfmi_block* BQ_work, int r, int flags, double* host_d, hfmi_block* U, const char* who) {
+  hfmi_ctx* ctx = P->ctx;
+  const int64_t N = P->N;
+  const int k = P->nvec;
+  if (Q_work->p != Y->p) HFMI_TRY(launch_copy(ctx, Q_work->p, Q_work->ld, Y->p, Y->ld, N, k));
+  int ph = phase_begin(ctx, HFMI_PHASE_QR);
+  // exact triangular factors in every pass (want_r, see borth_qr), nothing read back: U = Q V orthonormal to round-off
+  HFMI_TRY(borth_qr(Q_work, B, B ? BQ_work : nullptr, nullptr, true, (flags & 2) ? HFMI_QR_MGS : HFMI_QR_AUTO, nullptr));
+  phase_end(ctx, ph);
+  ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
+  const hfmi_block* right = B ? BQ_work : Q_work;
+  const hfmi_block* left = B ? Ybar : Y;
+  HFMI_TRY(launch_tsgemm_tn(ctx, P->p, P->ld, k, right->p, right->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_GRAM), SM_LD, 1, 0));
+  HFMI_TRY(launch_tsgemm_tn(ctx, left->p, left->ld, k, Q_work->p, Q_work->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_R), SM_LD, 1, 0));
+  HFMI_TRY(launch_lu_solve(ctx, k, SM_GRAM, SM_R, SM_TMP, SM_TMP2, SM_T));
+  phase_end(ctx, ph);
+  // the solve's status words leave for pinned memory before the eigensolver reuses them
+  void* pin = nullptr;
+  HFMI_TRY(ctx_late_pinned(ctx, &pin));
+  hfmi_status_words* lu_st = (hfmi_status_words*)pin;
+  HFMI_TRY(side_copies_begin(ctx));
+  HIP_TRY(hipMemcpyAsync(lu_st, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HFMI_TRY(side_copies_end(ctx));
+  HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
+  void* dv = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)SM_MAXK * sizeof(double), &dv));
+  ph = phase_begin(ctx, HFMI_PHASE_EIG);
+  HFMI_TRY(launch_sym_eig(ctx, k, SM_T, SM_V, (double*)dv, flags & 1, (flags >> 3) & 1));
+  phase_end(ctx, ph);
+  void* dpin = nullptr;
+  HFMI_TRY(ctx_pinned(ctx, (size_t)r * sizeof(double), &dpin));
+  HFMI_TRY(side_copies_begin(ctx));
+  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HIP_TRY(hipMemcpyAsync(dpin, dv, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
+  ph = phase_begin(ctx, HFMI_PHASE_BACK);
+  // V[:, :r] zero padded to 16 columns, as tsgemm_nn expects (the eigensolver leaves SM_V's pad columns as they were)
+  HFMI_TRY(launch_small_set_identity(ctx, k, SM_GRAM));
+  HFMI_TRY(launch_small_matmul(ctx, k, r, SM_GRAM, SM_V, SM_TMP2));
+  HFMI_TRY(launch_tsgemm_nn(ctx, Q_work->p, Q_work->ld, k, sm_ptr(ctx, SM_TMP2), SM_LD, r, 1.0, 0.0, U->p, U->ld, N));
+  phase_end(ctx, ph);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
+  HFMI_TRY(ctx_check_comm(ctx));
+  if (lu_st->failed == 1) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the sketch products W = P^T Q / Z = Y^T Q have non-finite entries", who);
+  if (lu_st->failed == 3) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the solve W^-1 Z overflowed (non-finite pivot or solution)", who);
+  if (lu_st->failed)
+    HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: rank-deficient sketch: W = P^T %sQ is singular (min |pivot| %.2e, max |pivot| %.2e); "
+              "the probe block has dependent columns or the operator's range is smaller than the sketch", who, B ? "B " : "",
+              lu_st->min_pivot_ratio, lu_st->gram_dev);
+  memcpy(host_d, dpin, (size_t)r * sizeof(double));
+  const hfmi_status_words st = *ctx->status_host;
+  print_status_dbg(&st);
+  if (st.failed) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "%s: small eigensolve did not converge (off-diagonal %.2e)", who, st.offdiag);
+  return HFMI_OK;
+}
+
+static int check_sketch_args(const hfmi_block* Omega, int r, const hfmi_block* U, const char* who) {
+  const int k = Omega->nvec;
+  if (r < 1) HFMI_FAIL(HFMI_ERR_INVALID, "%s: rank must be positive", who);
+  if (k < r) HFMI_FAIL(HFMI_ERR_INVALID, "%s: the sketch has %d vectors, need at least the rank %d", who, k, r);
+  if (k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "%s: at most %d probe vectors (got %d)", who, SM_MAXK, k);
+  if (U->N != Omega->N || U->nvec != r) HFMI_FAIL(HFMI_ERR_INVALID, "%s: U must be %lld x %d (got %lld x %d)", who, (long long)Omega->N, r,
+                                                  (long long)U->N, U->nvec);
+  return HFMI_OK;
+}
+
+static int single_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
+                            hfmi_block* U) {
+  const char* who = B ? "single_pass_g" : "single_pass";
+  if (!A || !Omega || !host_d || !U) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  hfmi_ctx* ctx = Omega->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HFMI_TRY(check_sketch_args(Omega, r, U, who));
+  if (s < 1) HFMI_FAIL(HFMI_ERR_INVALID, "%s: s must be >= 1", who);
+  const int64_t N = Omega->N;
+  const int k = Omega->nvec;
+  hfmi_block *b0, *b1, *b2, *b3 = nullptr;
+  HFMI_TRY(ctx_tmp_block(ctx, 0, N, k, &b0));
+  HFMI_TRY(ctx_tmp_block(ctx, 1, N, k, &b1));
+  HFMI_TRY(ctx_tmp_block(ctx, 2, N, k, &b2));
+  if (B) HFMI_TRY(ctx_tmp_block(ctx, 3, N, k, &b3));
+  hfmi_block X0 = *b0, X1 = *b1, W2 = *b2, W3;
+  X0.nvec = X1.nvec = W2.nvec = k;
+  if (B) {
+    W3 = *b3;
+    W3.nvec = k;
+  }
+  // power iterations without orthogonalisation (the loop of double_pass_impl); the last two iterates are kept
+  const hfmi_block* prev = Omega;
+  const hfmi_block* cur = Omega;
+  for (int it = 0; it < s; ++it) {
+    hfmi_block* dst = (cur == &X0) ? &X1 : &X0;
+    if (Binv) {
+      int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
+      HFMI_TRY(hfmi_op_apply(A, cur, &W2, 0));                 // Ybar
+      phase_end(ctx, ph);
+      ph = phase_begin(ctx, HFMI_PHASE_BINV);
+      HFMI_TRY(hfmi_op_apply(Binv, &W2, dst, 0));
+      phase_end(ctx, ph);
+    } else {
+      const int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
+      HFMI_TRY(hfmi_op_apply(A, cur, dst, 0));
+      phase_end(ctx, ph);
+    }
+    prev = cur;
+    cur = dst;
+  }
+  hfmi_block* Yb = const_cast<hfmi_block*>(cur);
+  if (B) return sketch_eig_core(prev, Yb, &W2, B, Yb, &W3, r, flags, host_d, U, who);   // Q in place of Y, B Q in W3
+  return sketch_eig_core(prev, Yb, nullptr, nullptr, &W2, nullptr, r, flags, host_d, U, who);
+}
+
+extern "C" int hfmi_single_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U) {
+  return single_pass_impl(A, nullptr, nullptr, Omega, r, s, flags, host_d, U);
+}
+extern "C" int hfmi_single_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
+                                  double* host_d, hfmi_block* U) {
+  if (!B || !Binv) HFMI_FAIL(HFMI_ERR_INVALID, "single_pass_g: B and Binv are required");
+  return single_pass_impl(A, B, Binv, Omega, r, s, flags, host_d, U);
+}
+
+extern "C" int hfmi_sketch_eig(const hfmi_block* P, const hfmi_block* Y, const hfmi_block* Ybar, hfmi_op* B, int r, int flags,
+                               double* host_d, hfmi_block* U) {
+  if (!P || !Y || !host_d || !U) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (!Ybar != !B) HFMI_FAIL(HFMI_ERR_INVALID, "sketch_eig: Ybar and B go together (generalized problem) or are both absent");
+  HFMI_TRY(check_same_shape(P, Y, "sketch_eig"));
+  if (Ybar) HFMI_TRY(check_same_shape(P, Ybar, "sketch_eig"));
+  hfmi_ctx* ctx = P->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HFMI_TRY(check_sketch_args(P, r, U, "sketch_eig"));
+  const int64_t N = P->N;
+  const int k = P->nvec;
+  hfmi_block *b2, *b3 = nullptr;
+  HFMI_TRY(ctx_tmp_block(ctx, 2, N, k, &b2));
+  if (B) HFMI_TRY(ctx_tmp_block(ctx, 3, N, k, &b3));
+  hfmi_block Qw = *b2, BQw;
+  Qw.nvec = k;
+  if (B) {
+    BQw = *b3;
+    BQw.nvec = k;
+  }
+  return sketch_eig_core(P, Y, Ybar, B, &Qw, B ? &BQw : nullptr, r, flags, host_d, U, "sketch_eig");
+}
+
+// np.linalg.solve(W, Z) of the single-pass methods on the device, host in and host out (kernel tests)
+extern "C" int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X) {
+  if (!ctx || !host_W || !host_Z || !host_X) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (m < 1 || m > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "small_solve: m=%d out of range [1,%d]", m, SM_MAXK);
+  HIP_TRY(hipSetDevice(ctx->device));
+  HFMI_TRY(upload_small(ctx, host_W, m, m, sm_ptr(ctx, SM_GRAM), SM_LD));
+  HFMI_TRY(upload_small(ctx, host_Z, m, m, sm_ptr(ctx, SM_R), SM_LD));
+  HFMI_TRY(launch_lu_solve(ctx, m, SM_GRAM, SM_R, SM_TMP, SM_TMP2, -1));
+  hfmi_status_words st;
+  HFMI_TRY(read_status(ctx, &st));
+  if (st.failed == 1) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): non-finite input", m);
+  if (st.failed == 3) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): the elimination overflowed (non-finite pivot or solution)", m);
+  if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): the matrix is singular (min |pivot| %.2e, max |pivot| %.2e)", m,
+                           st.min_pivot_ratio, st.gram_dev);
+  std::vector<double> tmp((size_t)m * SM_LD);
+  HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_TMP2), (size_t)m * SM_LD, tmp.data()));
+  for (int i = 0; i < m; ++i) memcpy(host_X + (size_t)i * m, tmp.data() + (size_t)i * SM_LD, (size_t)m * sizeof(double));
+  return HFMI_OK;
 }
 
 // ------------------------------------------------------------------ instrumentation

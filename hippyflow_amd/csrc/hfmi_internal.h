@@ -289,6 +289,10 @@ int launch_small_set_identity(hfmi_ctx* ctx, int k, int slot);
 int launch_small_matmul(hfmi_ctx* ctx, int k, int r, int slot_a, int slot_b, int slot_c);
 // R (k x k, slot_r) = U diag(s) V^T: singular values descending in svals (device), U -> slot_u, V -> slot_v (columns)
 int launch_jacobi_svd(hfmi_ctx* ctx, int k, int slot_r, int slot_u, int slot_v, double* svals);
+// X (m x m, slot_x) = W^-1 Z by LU with partial pivoting (slot_a: working copy of W), and when slot_t >= 0 also
+// T = (X + X^T) / 2 into slot_t.  Status words: min / max |pivot|, failed = 1 non-finite input, 2 singular W.
+int launch_lu_solve(hfmi_ctx* ctx, int m, int slot_w, int slot_z, int slot_a, int slot_x, int slot_t);
+int lu_panel_width(int m);   // panel width of launch_lu_solve's blocked form (m: one panel in LDS)
 
 constexpr int HFMI_EIG_MAXN = 16384;     // largest symmetric eigenproblem (hfmi_sym_eig_small / _leading, hfmi_block_gram_eig)
 // symmetric eigensolve for 256 < n <= HFMI_EIG_MAXN: host in, host out.  hfmi_eig_blocked.hip (panel tridiagonalisation on the MFMA, divide

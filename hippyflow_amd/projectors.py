@@ -32,7 +32,17 @@ from .multivector import ingest_stream, MatMvMult, MultiVector, mv_to_dense
 from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
                         SnapshotGramOperator, Solver2Operator, as_device_operator)
-from .randomized import doublePass, doublePassG, parRandom, sym_eig_small
+from .randomized import doublePass, doublePassG, parRandom, singlePass, singlePassG, sym_eig_small
+
+
+def _randomized(projector, generalized):
+    """doublePass[G], or singlePass[G] when the projector's ``randomized_eigensolver`` attribute is 'single_pass'."""
+    mode = getattr(projector, 'randomized_eigensolver', 'double_pass')
+    if mode == 'double_pass':
+        return doublePassG if generalized else doublePass
+    if mode == 'single_pass':
+        return singlePassG if generalized else singlePass
+    raise ValueError("randomized_eigensolver must be 'double_pass' or 'single_pass' (got %r)" % (mode,))
 
 
 class ParameterList(object):
@@ -250,6 +260,10 @@ def _observable_samples(observable, prior, control_distribution, n, noise, ctx):
 class ActiveSubspaceProjector:
     """Projectors from the sample-averaged GN Hessian E[J^T J] (input) and E[J J^T] (output)."""
 
+    # 'single_pass' routes the randomized eigensolve to singlePass[G] (same probe block and s; the operator is applied s times
+    # instead of s + 1).  An attribute, not a parameter key: the parameter list keeps exactly the reference's keys.
+    randomized_eigensolver = 'double_pass'
+
     def __init__(self, observable, prior, control_distribution=None, mesh_constructor_comm=None,
                  collective=None, parameters=None, ctx=None):
         # defaults made per instance: the reference's `parameters = ActiveSubspaceParameterList()` default is ONE list shared by every
@@ -429,19 +443,19 @@ class ActiveSubspaceProjector:
                     B, Binv = self.prior.R, self.prior.Rsolver
                 else:
                     B, Binv = self.prior.Hlr, self.prior.Hlr
-                self.d_GN, self.V_GN = doublePassG(average_op, B, Binv, Omega, self.parameters['rank'], s=1)
+                self.d_GN, self.V_GN = _randomized(self, True)(average_op, B, Binv, Omega, self.parameters['rank'], s=1)
                 as_decoder = self.V_GN
                 as_encoder = MultiVector(as_decoder)
                 MatMvMult(as_device_operator(B, N, self.ctx), as_decoder, as_encoder)
             else:
-                self.d_GN, self.V_GN = doublePass(average_op, Omega, self.parameters['rank'], s=1)
+                self.d_GN, self.V_GN = _randomized(self, False)(average_op, Omega, self.parameters['rank'], s=1)
                 as_decoder = self.V_GN
                 as_encoder = MultiVector(as_decoder)
             self.prior_preconditioned = prior_preconditioned
             self._input_subspace_construction_time = time.time() - t0
             result = (self.d_GN, as_decoder, as_encoder)
         else:
-            self.d_NG, self.U_NG = doublePass(average_op, Omega, self.parameters['rank'], s=1)
+            self.d_NG, self.U_NG = _randomized(self, False)(average_op, Omega, self.parameters['rank'], s=1)
             output_decoder = self.U_NG
             output_encoder = MultiVector(output_decoder)
             self._output_subspace_construction_time = time.time() - t0
@@ -654,6 +668,10 @@ class ActiveSubspaceProjector:
 class KLEProjector:
     """Input subspace from the prior covariance alone (KLEProjector.py:72-199)."""
 
+    # 'single_pass' routes the randomized eigensolve to singlePass[G] (same probe block and s; the operator is applied s times
+    # instead of s + 1).  An attribute, not a parameter key: the parameter list keeps exactly the reference's keys.
+    randomized_eigensolver = 'double_pass'
+
     prior_power_iterations = 2      # orthogonality='prior': passes of the randomized generalized solve (see construct_input_subspace)
 
     def __init__(self, prior, mesh_constructor_comm=None, collective=None, parameters=None, ctx=None):
@@ -701,13 +719,13 @@ class KLEProjector:
         KLE_Operator = MassPreconditionedCovarianceOperator(self.C, self.M)
         Omega = _draw_omega(self.N, self.parameters['rank'] + self.parameters['oversampling'], self.collective, self.ctx)
         if orthogonality.lower() == 'mass':
-            self.d_KLE, self.V_KLE = doublePassG(KLE_Operator, self.M, self._Msolver(), Omega, self.parameters['rank'], s=1)
+            self.d_KLE, self.V_KLE = _randomized(self, True)(KLE_Operator, self.M, self._Msolver(), Omega, self.parameters['rank'], s=1)
             self.M_orthogonal = True
             kle_decoder = self.V_KLE
             kle_encoder = MultiVector(kle_decoder)
             MatMvMult(self.M, kle_decoder, kle_encoder)
         elif orthogonality.lower() == 'identity':
-            self.d_KLE, self.V_KLE = doublePass(self.C, Omega, self.parameters['rank'], s=1)
+            self.d_KLE, self.V_KLE = _randomized(self, False)(self.C, Omega, self.parameters['rank'], s=1)
             self.M_orthogonal = False
             kle_decoder = self.V_KLE
             kle_encoder = MultiVector(kle_decoder)
@@ -721,8 +739,8 @@ class KLEProjector:
             # attribute, not a parameter key: the parameter lists keep exactly the reference's keys.)
             assert hasattr(self.prior, 'R') and hasattr(self.prior, 'Rsolver')
             R_op = as_device_operator(self.prior.R, self.N, self.ctx)
-            self.d_KLE, self.V_KLE = doublePassG(self.M, R_op, self.C, Omega, self.parameters['rank'],
-                                                 s=max(1, int(self.prior_power_iterations)))
+            self.d_KLE, self.V_KLE = _randomized(self, True)(self.M, R_op, self.C, Omega, self.parameters['rank'],
+                                                               s=max(1, int(self.prior_power_iterations)))
             self.M_orthogonal = False
             self.R_orthogonal = True
             kle_decoder = self.V_KLE
@@ -769,6 +787,10 @@ class BoundaryRestrictedKLEProjector:
     numerically zero.  ``B^-1`` is the reference's MUMPS LU (:360-361); on the device it is a Jacobi-PCG solve (B is
     a boundary mass matrix plus an identity block: well conditioned)."""
 
+    # 'single_pass' routes the randomized eigensolve to singlePass[G] (same probe block and s; the operator is applied s times
+    # instead of s + 1).  An attribute, not a parameter key: the parameter list keeps exactly the reference's keys.
+    randomized_eigensolver = 'double_pass'
+
     def __init__(self, prior, ds=None, parameters=None, boundary_mass=None, ctx=None):
         import scipy.sparse as sp
         self.prior = prior
@@ -809,7 +831,7 @@ class BoundaryRestrictedKLEProjector:
         oversampling = self.parameters['oversampling']
         Omega = MultiVector(self.N, rank + oversampling, ctx=self.ctx)
         parRandom.normal(1.0, Omega)                                                          # :423-425
-        self.d_KLE, self.V_KLE = doublePassG(self.KLE_Operator, self.B, self.Bsolver, Omega, rank, s=1)   # :428
+        self.d_KLE, self.V_KLE = _randomized(self, True)(self.KLE_Operator, self.B, self.Bsolver, Omega, rank, s=1)   # :428
         KLE_encoder = MultiVector(self.N, rank, ctx=self.ctx)
         MatMvMult(self.M, self.V_KLE, KLE_encoder)                                            # :431-432
         return self.d_KLE, self.V_KLE, KLE_encoder
@@ -821,6 +843,10 @@ class BoundaryRestrictedKLEProjector:
 class PODProjector:
     """Output projector from sampled observables: dominant eigenpairs of E[q q^T] by a randomized
     double pass over the snapshot-Gram operator (PODProjector.py:331-389)."""
+
+    # 'single_pass' routes the randomized eigensolve to singlePass[G] (same probe block and s; the operator is applied s times
+    # instead of s + 1).  An attribute, not a parameter key: the parameter list keeps exactly the reference's keys.
+    randomized_eigensolver = 'double_pass'
 
     def __init__(self, observable, prior, control_distribution=None, mesh_constructor_comm=None, collective=None,
                  parameters=None, ctx=None):
@@ -873,7 +899,7 @@ class PODProjector:
         LocalPODOperator = SnapshotGramOperator(X, scale=1.0 / X.nvec())                      # :359-361
         GlobalPODOperator = CollectiveOperator(LocalPODOperator, self.collective, mpi_op='avg')  # :363
         Omega_POD = _draw_omega(X.size(), self.parameters['rank'] + self.parameters['oversampling'], self.collective, self.ctx)
-        self.d, self.U_MV = doublePass(GlobalPODOperator, Omega_POD, self.parameters['rank'], s=1)   # :376
+        self.d, self.U_MV = _randomized(self, False)(GlobalPODOperator, Omega_POD, self.parameters['rank'], s=1)   # :376
         self._subspace_construction_time = time.time() - t0
         if self.parameters['verbose'] and _is_root(self.collective):
             print('Construction of POD subspace took ', self._subspace_construction_time, 's')

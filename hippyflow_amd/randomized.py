@@ -1,10 +1,13 @@
-"""Randomized double-pass eigensolvers and the probe draw: the device counterparts of the hippylib
+"""Randomized double- and single-pass eigensolvers and the probe draw: the device counterparts of the hippylib
 entry points hippyflow calls (hippylib is absent from /root/reference; call sites:
 modeling/PODProjector.py:376, modeling/KLEProjector.py:163-164,177,
 modeling/activeSubspaceProjector.py:449-463,556-577,654).
 
 ``doublePass(A, Omega, k, s=1)``             -> (d, U),   U^T U = I
 ``doublePassG(A, B, Binv, Omega, k, s=1)``   -> (d, U),   U^T B U = I,  A U ~ B U diag(d)
+``singlePass(A, Omega, k, s=1)`` / ``singlePassG(A, B, Binv, Omega, k, s=1)``: the same results from s applications of
+A instead of s + 1 (hippylib's randomizedEigensolver.singlePass[G]); ``StreamedSketch`` builds their sketch A Omega while
+the samples are produced, without storing them
 ``parRandom.normal(sigma, out)``             -> N(0, sigma^2) fill of a Vector / MultiVector
 
 Two execution routes, same arithmetic:
@@ -158,16 +161,16 @@ class _PostApplyHook:
         return False
 
 
-def _fused(A_dev, collective, mpi_op, B_dev, Binv_dev, Omega, k, s, sort_by_abs, use_mgs, literal_T=False):
+def _fused(A_dev, collective, mpi_op, B_dev, Binv_dev, Omega, k, s, sort_by_abs, use_mgs, literal_T=False, entry="hfmi_double_pass"):
     d = np.empty(k)
     U = MultiVector(Omega.size(), k, ctx=Omega.ctx)
     flags = (1 if sort_by_abs else 0) | (2 if use_mgs else 0) | (4 if literal_T else 0)
 
     def run():
         if B_dev is None:
-            L.call("hfmi_double_pass", A_dev._op, Omega.handle, int(k), int(s), flags, L.ptr(d), U.handle)
+            L.call(entry, A_dev._op, Omega.handle, int(k), int(s), flags, L.ptr(d), U.handle)
         else:
-            L.call("hfmi_double_pass_g", A_dev._op, B_dev._op, Binv_dev._op, Omega.handle, int(k), int(s), flags, L.ptr(d), U.handle)
+            L.call(entry + "_g", A_dev._op, B_dev._op, Binv_dev._op, Omega.handle, int(k), int(s), flags, L.ptr(d), U.handle)
 
     if isinstance(collective, NativeCollective):
         # the rank average runs inside the C solve on the context's stream (RCCL): no Python between the kernels
@@ -303,3 +306,217 @@ def accuracyEnhancedSVD(A, Omega, k, s=1, check=False):
     V = MultiVector(Omega.size(), k, ctx=Omega.ctx)
     MvDSmatMult(BT, np.ascontiguousarray(V_hat[:, :k]), V)
     return U, d[:k].copy(), V
+
+
+# ---------------------------------------------------------------- single pass
+# hp.singlePass / hp.singlePassG (hippylib randomizedEigensolver).  Omega (N x m, m >= k) is not modified.
+#   X_0 = Omega,  X_i = A X_{i-1}  (generalized: Ybar = A X_{i-1}, X_i = B^-1 Ybar),  i = 1..s,  no orthogonalisation;
+#   P = X_{s-1},  Y = X_s,  Q = orth(Y)  (generalized: Q, BQ = B-orth(Y), Q^T B Q = I)  -- the double pass's QR rule;
+#   Wt = P^T Q (generalized: P^T BQ),  Zt = Y^T Q (generalized: Ybar^T Q),  both m x m;
+#   Tt = Wt^-1 Zt,  T = (Tt + Tt^T) / 2,  eigh(T) sorted descending (by |d| with sort_by_abs), keep k:  d,  U = Q V[:, :k].
+# (A ~ Q T Q^T gives Q^T Y = T Q^T P, i.e. Wt T^T = Zt; generalized: Q^T B Y = Q^T Ybar = T Q^T B P.)  A is applied s times
+# (the double pass: s + 1).  Exact when rank(B^-1 A) = m; a singular Wt (rank-deficient sketch, e.g. dependent probe
+# vectors) raises HfmiError where hippylib's np.linalg.solve raises LinAlgError.
+
+def small_solve(W, Z, ctx=None):
+    """np.linalg.solve(W, Z) for square m x m operands (m <= 256) on the device: one-workgroup LU with partial pivoting,
+    the kernel behind the single-pass Rayleigh-Ritz matrix.  A singular W raises HfmiError."""
+    W, Z = L.as_f64(W), L.as_f64(Z)
+    m = W.shape[0]
+    if W.shape != (m, m) or Z.shape != (m, m):
+        raise ValueError("small_solve: W and Z must both be m x m (got %s and %s)" % (W.shape, Z.shape))
+    X = np.empty((m, m))
+    L.call("hfmi_small_solve", (ctx or L.Context.default()).handle, L.ptr(W), L.ptr(Z), m, L.ptr(X))
+    return X
+
+
+def _check_sketch_args(Omega, k, s):
+    """the C entry points' argument checks, for the generic route (HFMI_ERR_INVALID = -1)"""
+    if int(s) < 1:
+        raise L.HfmiError(-1, "single_pass: s must be >= 1 (got %d)" % int(s))
+    if not 1 <= int(k) <= Omega.nvec():
+        raise L.HfmiError(-1, "single_pass: the rank must be in [1, %d] (the number of probe vectors), got %d" % (Omega.nvec(), int(k)))
+    if Omega.nvec() > 256:
+        raise L.HfmiError(-1, "single_pass: at most 256 probe vectors (got %d)" % Omega.nvec())
+
+
+def _sketch_tail(P, Q, Wt, Zt, k, sort_by_abs, ctx):
+    """The generic route's Rayleigh-Ritz step: T from the device LU solve, eigh, U = Q V[:, :k]."""
+    Tt = small_solve(Wt, Zt, ctx)
+    d, V = sym_eig_small(0.5 * (Tt + Tt.T), sort_by_abs, ctx)
+    U = MultiVector(P.size(), k, ctx=ctx)
+    MvDSmatMult(Q, np.ascontiguousarray(V[:, :k]), U)
+    return d[:k].copy(), U
+
+
+def singlePass(A, Omega, k, s=1, check=False, sort_by_abs=False, use_mgs=False, fused=True):
+    """Randomized single pass for the dominant k eigenpairs of a Hermitian operator A (hp.singlePass): A is applied
+    s times.  Omega: MultiVector with nvec >= k probe vectors (not modified).  Returns (d, U), U^T U = I."""
+    nvec = Omega.nvec()
+    _check_sketch_args(Omega, k, s)
+    A_dev, coll, mpi_op = _unwrap_collective(A)
+    if fused and A_dev is not None:
+        return _fused(A_dev, coll, mpi_op, None, None, Omega, k, s, sort_by_abs, use_mgs, entry="hfmi_single_pass")
+    P = MultiVector(Omega)
+    Y = MultiVector(Omega.size(), nvec, ctx=Omega.ctx)
+    for i in range(s):
+        if i:
+            P.swap(Y)
+            Y.zero()          # block operators of the reference accumulate into y
+        MatMvMult(A, P, Y)
+    Q = MultiVector(Y)
+    Q.orthogonalize(L.QR_MGS if use_mgs else L.QR_AUTO)
+    return _sketch_tail(P, Q, P.dot_mv(Q), Y.dot_mv(Q), k, sort_by_abs, Omega.ctx)
+
+
+def singlePassG(A, B, Binv, Omega, k, s=1, check=False, sort_by_abs=False, use_mgs=False, fused=True):
+    """Randomized single pass for A u = lambda B u (B SPD; hp.singlePassG): A and B^-1 are applied s times each.
+    ``Binv`` is a solver object (``solve(y, x)``) as in the reference, or an operator.  Returns (d, U), U^T B U = I."""
+    nvec = Omega.nvec()
+    _check_sketch_args(Omega, k, s)
+    N = Omega.size()
+    A_dev, coll, mpi_op = _unwrap_collective(A)
+    if fused and A_dev is not None:
+        B_dev = as_device_operator(B, N, Omega.ctx)
+        Binv_dev = _as_solver_operator(Binv, N, Omega.ctx, B)
+        return _fused(A_dev, coll, mpi_op, B_dev, Binv_dev, Omega, k, s, sort_by_abs, use_mgs, entry="hfmi_single_pass")
+    Binv_op = _as_solver_operator(Binv, N, Omega.ctx, B)
+    P = MultiVector(Omega)
+    Ybar = MultiVector(N, nvec, ctx=Omega.ctx)
+    Y = MultiVector(N, nvec, ctx=Omega.ctx)
+    for i in range(s):
+        if i:
+            P.swap(Y)
+            Ybar.zero()
+        MatMvMult(A, P, Ybar)
+        MatMvMult(Binv_op, Ybar, Y)
+    BQ, _ = Y.Borthogonalize(B, L.QR_MGS if use_mgs else L.QR_AUTO)      # Y becomes Q
+    return _sketch_tail(P, Y, P.dot_mv(BQ), Ybar.dot_mv(Y), k, sort_by_abs, Omega.ctx)
+
+
+class StreamedSketch:
+    """The single-pass sketch Y = A Omega summed while the samples are produced, one batch at a time, and never stored.
+
+    ``kind="snapshots"``: ``add(X_b)`` with a (b, N) block of snapshots adds X_b^T (X_b Omega) -- A is the snapshot Gram
+    operator (1/n) sum_i x_i x_i^T (PODProjector);  ``kind="jacobian"``: ``add(J)`` with one (q, N) Jacobian adds
+    J^T Gamma^-1 J Omega -- A is the mean J^T Gamma^-1 J (active subspace), ``noise_cov_inv`` the q x q Gamma^-1 (None:
+    identity).  Batch sizes may vary.  Each batch is copied into one of two pinned buffers and uploaded on the ingest
+    stream while the producer makes the next one; the product is accumulated on the device by the snapshot-Gram / J^T J
+    kernels.  Nothing waits for the GPU except the reuse of a pinned buffer.  The scale is 1 / (number of samples over all
+    ranks); with a ``collective`` the sketch and the count are all-reduced once, at the end.  Device memory: Omega, Y,
+    the Q / BQ work blocks of the solve and two batch buffers, O(N (3 m + 2 b)), whatever the number of samples.
+
+    ``singlePass(k)`` / ``singlePassG(k, B, Binv)`` return (d, U) from the finished sketch (hfmi_sketch_eig)."""
+
+    def __init__(self, Omega, kind="snapshots", noise_cov_inv=None, collective=None):
+        if kind not in ("snapshots", "jacobian"):
+            raise ValueError("StreamedSketch: kind must be 'snapshots' or 'jacobian'")
+        self.Omega = Omega
+        self.ctx = Omega.ctx
+        self.N, self.m = Omega.size(), Omega.nvec()
+        self.kind = kind
+        self.collective = collective
+        self.noise_cov_inv = None if noise_cov_inv is None else L.as_f64(np.asarray(noise_cov_inv, dtype=np.float64))
+        self.q = None if self.noise_cov_inv is None else self.noise_cov_inv.shape[0]
+        if self.noise_cov_inv is not None and self.noise_cov_inv.shape != (self.q, self.q):
+            raise ValueError("StreamedSketch: noise_cov_inv must be square")
+        self._Y = MultiVector(self.N, self.m, ctx=self.ctx)
+        self._Y.zero()
+        self._count = 0
+        self._final = None
+        self._pinned = [None, None]
+        self._dev = [None, None]
+        self._tickets = [None, None]
+        self._ops = [{}, {}]       # batch rows -> (view, operator) over device buffer i (operators keep their own state)
+        self._nbatch = 0
+
+    @property
+    def count(self):
+        """samples added on this rank"""
+        return self._count
+
+    def add(self, batch):
+        if self._final is not None:
+            raise RuntimeError("StreamedSketch.add: the sketch has been finished (singlePass / sketch was called)")
+        arr = np.asarray(batch, dtype=np.float64)
+        if arr.ndim == 1 and self.kind == "snapshots":
+            arr = arr.reshape(1, -1)
+        if arr.ndim != 2 or arr.shape[1] != self.N or arr.shape[0] < 1:
+            raise ValueError("StreamedSketch.add: a (rows, %d) array expected, got shape %s" % (self.N, arr.shape))
+        b = arr.shape[0]
+        if self.kind == "jacobian":
+            if self.q is None:
+                self.q = b
+            elif b != self.q:
+                raise ValueError("StreamedSketch.add: a Jacobian of %d rows expected, got %d" % (self.q, b))
+        i = self._nbatch % 2
+        if self._tickets[i] is not None:
+            self.ctx.ingest_wait(self._tickets[i])
+            self._tickets[i] = None
+        if self._pinned[i] is None or self._pinned[i].shape[0] < b:
+            cap = max(b, 0 if self._pinned[i] is None else self._pinned[i].shape[0])
+            self._pinned[i] = L.pinned_empty((cap, self.N))
+            self._dev[i] = MultiVector(self.N, cap, ctx=self.ctx)
+            self._ops[i] = {}
+        rows = self._pinned[i][:b]
+        np.copyto(rows, arr)
+        entry = self._ops[i].get(b)
+        if entry is None:
+            view = self._dev[i].view(0, b)
+            if self.kind == "snapshots":
+                from .operators import SnapshotGramOperator
+                op = SnapshotGramOperator(view, scale=1.0)
+            else:
+                from .operators import MeanJTJfromDataOperator
+                op = MeanJTJfromDataOperator.from_block(view, 1, b, noise_cov_inv=self.noise_cov_inv, scale=1.0)
+            entry = self._ops[i][b] = (view, op)
+        view, op = entry
+        self._tickets[i] = view.upload_async(rows)
+        self.ctx.ingest_fence()
+        op.matMvMult(self.Omega, self._Y, accumulate=True)
+        self._count += b if self.kind == "snapshots" else 1
+        self._nbatch += 1
+
+    def _finish(self):
+        if self._final is None:
+            total = self._count
+            if self.collective is not None:
+                self.collective.allReduce(self._Y, "sum")
+                total = int(round(self.collective.allReduce(float(self._count), "sum")))
+            if total < 1:
+                raise ValueError("StreamedSketch: no samples were added")
+            self._Y.scale(1.0 / total)
+            for t in self._tickets:
+                if t is not None:
+                    self.ctx.ingest_wait(t)
+            self._tickets = [None, None]
+            self._final = total
+        return self._Y
+
+    def sketch(self):
+        """The finished sketch A Omega (MultiVector, N x m; finishes the sketch)."""
+        return self._finish()
+
+    def singlePass(self, k, sort_by_abs=False, use_mgs=False):
+        Y = self._finish()
+        if not 1 <= k <= self.m:
+            raise L.HfmiError(-1, "StreamedSketch.singlePass: k must be in [1, %d] (got %d)" % (self.m, k))
+        d = np.empty(k)
+        U = MultiVector(self.N, k, ctx=self.ctx)
+        flags = (1 if sort_by_abs else 0) | (2 if use_mgs else 0)
+        L.call("hfmi_sketch_eig", self.Omega.handle, Y.handle, None, None, int(k), flags, L.ptr(d), U.handle)
+        return d, U
+
+    def singlePassG(self, k, B, Binv, sort_by_abs=False, use_mgs=False):
+        Ybar = self._finish()
+        if not 1 <= k <= self.m:
+            raise L.HfmiError(-1, "StreamedSketch.singlePassG: k must be in [1, %d] (got %d)" % (self.m, k))
+        B_dev = as_device_operator(B, self.N, self.ctx)
+        Binv_dev = _as_solver_operator(Binv, self.N, self.ctx, B)
+        Y = MultiVector(self.N, self.m, ctx=self.ctx)
+        Binv_dev.matMvMult(Ybar, Y)
+        d = np.empty(k)
+        U = MultiVector(self.N, k, ctx=self.ctx)
+        flags = (1 if sort_by_abs else 0) | (2 if use_mgs else 0)
+        L.call("hfmi_sketch_eig", self.Omega.handle, Y.handle, Ybar.handle, B_dev._op, int(k), flags, L.ptr(d), U.handle)
+        return d, U

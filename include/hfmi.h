@@ -286,6 +286,26 @@ int hfmi_double_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flag
 int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s,
                        int flags, double* host_d, hfmi_block* U);
 
+/* hp.singlePass(A, Omega, r, s) / hp.singlePassG(A, B, Binv, Omega, r, s) (hippylib randomizedEigensolver): the same
+ * contract as hfmi_double_pass[_g], but the operator is applied s times instead of s + 1.  X_0 = Omega,
+ * X_i = (B^-1) A X_{i-1}; with P = X_{s-1}, Y = X_s, Ybar = A X_{s-1} (= Y without B) and Q = (B-)orth(Y):
+ * Wt = P^T (B) Q, Zt = Ybar^T Q, T = sym(Wt^-1 Zt) (LU with partial pivoting on the device), eigh(T), U = Q V[:, :r].
+ * flags: bit 0 = sort by |d|; bit 1 = HFMI_QR_MGS; bit 3 = Jacobi for the k x k eigenproblem (bit 2 does not apply).
+ * A singular or non-finite Wt (rank-deficient sketch, e.g. dependent probe vectors) is HFMI_ERR_NUMERIC, never NaN
+ * eigenpairs (hippylib's np.linalg.solve raises LinAlgError there).  A rank average attached to A applies to every
+ * application, as in the double pass. */
+int hfmi_single_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U);
+int hfmi_single_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
+                       double* host_d, hfmi_block* U);
+/* The single-pass core on a sketch the caller already holds (the Wt / Zt / eigh steps of hp.singlePass[G]):
+ * P and Y (N x k) as above, none modified; Ybar and B both NULL for the standard problem, both given for the
+ * generalized one (Y = B^-1 Ybar).  Used by streamed sketches, where Y = A Omega is summed while the samples arrive. */
+int hfmi_sketch_eig(const hfmi_block* P, const hfmi_block* Y, const hfmi_block* Ybar, hfmi_op* B, int r, int flags,
+                    double* host_d, hfmi_block* U);
+/* np.linalg.solve(W, Z) inside hp.singlePass[G], on the device (kernel tests): W, Z, X host row-major m x m, m <= 256.
+ * HFMI_ERR_NUMERIC for a singular W (min |pivot| <= m eps max |pivot|) or non-finite input. */
+int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X);
+
 /* ---------------------------------------------------------------- instrumentation
  * Kernel-level entry points used by bench.py / the parity tests:
  *   C (nvecA x nvecB, device partial-summed, returned on host) = A^T B with an explicit split count
