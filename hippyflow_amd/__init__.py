@@ -12,12 +12,13 @@ from .collectives import (CollectiveOperator, MatrixMultCollectiveOperator, Mult
 from .hostvec import ADJOINT, CONTROL, PARAMETER, STATE, HostMultiVector, HostVector, new_host_vector, set_host_vector_factory
 from .multivector import (MatMvMult, MatMvTranspmult, MultiVector, MvDSmatMult, Vector, dense_to_mv_local, ingest_stream, mv_to_dense,
                           mv_to_dense_local)
-from .operators import (ComposedOperator, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
+from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
                         LowRankOperator, LowRankRectangularOperator, MassPreconditionedCovarianceOperator,
                         JJT, JTJ, Jacobian, MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableControlJacobian,
                         ObservableJacobian, PriorPreconditionedProjector,
                         SeriallySampledJacobianOperator, StateSpaceIdentityOperator, npToDolfinOperator,
-                        SnapshotGramOperator, Solver2Operator, SummedListOperator, as_device_operator, npToDeviceOperator)
+                        SnapshotGramOperator, Solver2Operator, SummedListOperator, as_device_operator, device_bilaplacian_rsolver,
+                        npToDeviceOperator)
 from .projectors import (ActiveSubspaceParameterList, ActiveSubspaceProjector, BoundaryRestrictedKLEProjector,
                          KLEParameterList, KLEProjector,
                          ParameterList, PODParameterList, PODProjector, PODProjectorFromData, weighted_l2_norm_vector)

@@ -74,6 +74,13 @@ SIGNATURES = {
     "hfmi_op_csr_pcg": [_P, _P, C.c_double, C.c_int, _PP],
     "hfmi_op_solver_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "hfmi_op_compose3": [_P, _P, _P, _P, _PP],
+    "hfmi_amg_create": [_P, _P, C.c_double, C.c_double, C.c_int, _PP],
+    "hfmi_amg_add_level": [_P, _P, _P, _P, C.c_double, C.c_double],
+    "hfmi_amg_set_coarse": [_P, C.c_int, _P],
+    "hfmi_amg_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_int],
+    "hfmi_amg_destroy": [_P],
+    "hfmi_amg_vcycle": [_P, _P, _P],
+    "hfmi_op_amg_pcg": [_P, _P, C.c_double, C.c_int, _PP],
     "hfmi_op_host_callback": [_P, HOST_APPLY_FN, _P, C.c_int64, _PP],
     "hfmi_op_host_set_chunk": [_P, C.c_int],
     "hfmi_op_set_post_apply": [_P, POST_APPLY_FN, _P],

@@ -144,6 +144,7 @@ extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
   c->device = device;
   c->num_cus = prop.multiProcessorCount;
   c->own_stream = true;
+  c->compose_depth = 0;
   for (int i = 0; i < WS_NSLOTS; ++i) {
     c->ws[i] = nullptr;
     c->ws_bytes[i] = 0;
@@ -837,7 +838,24 @@ extern "C" int hfmi_op_csr_pcg(hfmi_ctx* ctx, const hfmi_csr* M, double rel_tol,
   *out = op;
   return HFMI_OK;
 }
+extern "C" int hfmi_op_amg_pcg(hfmi_ctx* ctx, hfmi_amg* amg, double rel_tol, int max_iter, hfmi_op** out) {
+  if (!ctx || !amg || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  hfmi_op* op = op_new(ctx, OP_AMG_PCG);
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  op->amg = amg;
+  op->rel_tol = rel_tol > 0 ? rel_tol : 1e-12;
+  op->max_iter = max_iter > 0 ? max_iter : 100;
+  *out = op;
+  return HFMI_OK;
+}
 extern "C" int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* method, double* lmin, double* lmax) {
+  if (op && op->kind == OP_AMG_PCG) {
+    if (iterations) *iterations = op->last_iters;
+    if (method) *method = 2;
+    if (lmin) *lmin = 0.0;
+    if (lmax) *lmax = 0.0;
+    return HFMI_OK;
+  }
   if (!op || op->kind != OP_CSR_PCG) HFMI_FAIL(HFMI_ERR_INVALID, "op_solver_info: not a sparse solver operator");
   if (iterations) *iterations = op->last_iters;
   if (method) *method = op->last_method;
@@ -1388,10 +1406,31 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       }
       return pcg_solve(op, W, Y);
     }
+    case OP_AMG_PCG: {
+      if (beta != 0.0) {
+        hfmi_block* T = nullptr;
+        HFMI_TRY(ctx_tmp_block(ctx, 13, W->N, k, &T));
+        hfmi_block tv = *T;
+        tv.nvec = k;
+        HFMI_TRY(amg_pcg_solve(op, W, &tv));
+        if (beta != 1.0) HFMI_TRY(launch_scale(ctx, Y->p, Y->ld, Y->N, k, beta));
+        return launch_axpy(ctx, Y->p, Y->ld, 1.0, T->p, T->ld, Y->N, k);
+      }
+      return amg_pcg_solve(op, W, Y);
+    }
     case OP_COMPOSE3: {
+      // a composition inside a composition (M C M with C = A^-1 M A^-1 itself composed) takes its own pair of temporaries
+      const int depth = ctx->compose_depth;
+      if (depth >= 4) HFMI_FAIL(HFMI_ERR_INVALID, "compose3: operators nested more than 4 deep");
+      struct depth_guard {
+        hfmi_ctx* c;
+        ~depth_guard() { --c->compose_depth; }
+      } guard{ctx};
+      ++ctx->compose_depth;
+      const int slot = depth == 0 ? 14 : 14 + 2 * depth + 2;
       hfmi_block *T1, *T2;
-      HFMI_TRY(ctx_tmp_block(ctx, 14, W->N, k, &T1));
-      HFMI_TRY(ctx_tmp_block(ctx, 15, W->N, k, &T2));
+      HFMI_TRY(ctx_tmp_block(ctx, slot, W->N, k, &T1));
+      HFMI_TRY(ctx_tmp_block(ctx, slot + 1, W->N, k, &T2));
       hfmi_block v1 = *T1, v2 = *T2;
       v1.nvec = k;
       v2.nvec = k;

@@ -122,6 +122,7 @@ struct hfmi_ctx {
   size_t pinned_cb_bytes;
   hipEvent_t ev_cb[4];            // D2H done x2, H2D done x2
   xfer_state* xfer;               // pinned ring + host threads of the large host <-> device transfers (hfmi_xfer.hip), lazily created
+  int compose_depth;              // OP_COMPOSE3 applications in progress (nested compositions use separate temporaries)
 };
 // large transfers between the caller's pageable arrays and device memory, pipelined through pinned chunks (hfmi_xfer.hip)
 int xfer_d2h(hfmi_ctx* ctx, void* host, const void* dev, size_t bytes);   // returns when the host array is complete
@@ -157,7 +158,7 @@ struct hfmi_csr {
   int cheb_state;
 };
 
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST };
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG };
 
 struct hfmi_op {
   hfmi_ctx* ctx;
@@ -171,7 +172,8 @@ struct hfmi_op {
   double rel_tol;
   int max_iter;
   int last_iters;
-  int last_method;        // sparse solver: 0 = block CG, 1 = Chebyshev (hfmi_op_solver_info)
+  int last_method;        // sparse solver: 0 = block CG, 1 = Chebyshev, 2 = AMG-preconditioned CG (hfmi_op_solver_info)
+  hfmi_amg* amg;          // OP_AMG_PCG: the multigrid hierarchy (not owned)
   hfmi_op *a, *b, *c;
   hfmi_host_apply_fn host_fn;
   void* host_user;
@@ -183,6 +185,8 @@ struct hfmi_op {
   int comm_op;
   bool reduced_by_panels; // the last apply already reduced its result over the ranks, panel by panel (hfmi_api.hip)
 };
+// Y = A^-1 W by AMG-preconditioned block CG (hfmi_amg.hip); Y zero-filled on error
+int amg_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
 // in-place all-reduce of `count` doubles of device memory on the communicator's context stream (hfmi_comm.hip)
 int comm_allreduce_device(hfmi_comm* c, double* data, int64_t count, int op);
 int comm_allreduce_device_on(hfmi_comm* c, double* data, int64_t count, int op, void* hip_stream /* null = the context's */);

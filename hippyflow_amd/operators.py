@@ -10,6 +10,8 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``MeanJJTfromDataOperator``                     JJT summed/averaged: modeling/jacobian.py:169-193, activeSubspaceProjector.py:640-645
 * ``npToDeviceOperator``                          npToDolfinOperator, modeling/operatorWrappers.py:19-52 (symmetric case)
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
+* ``CsrAMGSolver`` / ``BiLaplacianRsolver``       hippylib BiLaplacianPrior.Asolver (CG + AMG) and prior.Rsolver = A^-1 M A^-1
+                                                  (activeSubspaceProjector.py:447-453, KLEProjector.py:163-168)
 * ``Solver2Operator``                             hp.Solver2Operator, modeling/KLEProjector.py:103,176
 * ``MassPreconditionedCovarianceOperator``        modeling/KLEProjector.py:47-69
 * ``SummedListOperator``                          modeling/activeSubspaceProjector.py:69-95
@@ -252,6 +254,62 @@ class CsrPCGSolver(DeviceOperator):
                 "spectrum": (lo.value, hi.value) if hi.value > 0 else None}
 
 
+class CsrAMGSolver(DeviceOperator):
+    """Solver object for an SPD sparse elliptic matrix (hippylib ``BiLaplacianPrior.Asolver``: PETSc CG preconditioned by
+    algebraic multigrid, rel_tol 1e-12): ``solve(y, x)`` gives y = A^{-1} x with every vector's residual at most
+    ``rel_tol`` times its right-hand side.  The smoothed-aggregation hierarchy is built once on the host
+    (``hippyflow_amd.amg.AMGHierarchy``; ``setup_options`` go there); block CG with one V-cycle as preconditioner runs on the
+    device (hfmi_amg.hip).  ValueError for a matrix that cannot be SPD (not square or symmetric, a diagonal entry <= 0,
+    non-finite entries); HfmiError NUMERIC / NOT_CONVERGED from a solve that breaks down or runs out of iterations."""
+
+    def __init__(self, A, rel_tol=1e-12, max_iter=100, ctx=None, **setup_options):
+        from .amg import AMGHierarchy
+        ctx = ctx or L.Context.default()
+        csr = csr_from_matrix(A)
+        h = AMGHierarchy(csr if csr is not None else A, **setup_options)
+        super().__init__(ctx, h.levels[0].A.shape[0])
+        self._hierarchy = h
+        self._amg = C.c_void_p()
+        levels = h.levels
+        mats = [_Csr(lv.A, ctx) for lv in levels]
+        links = [(_Csr(lv.P, ctx), _Csr(lv.R, ctx)) for lv in levels[:-1]]
+        self._keep = mats + [m for pr in links for m in pr]
+        L.call("hfmi_amg_create", ctx.handle, mats[0].handle, levels[0].lmin, levels[0].lmax, int(h.degree), C.byref(self._amg))
+        for l in range(1, len(levels)):
+            P, R = links[l - 1]
+            L.call("hfmi_amg_add_level", self._amg, P.handle, R.handle, mats[l].handle, levels[l].lmin, levels[l].lmax)
+        inv = np.ascontiguousarray(h.coarse_inv, dtype=np.float64)
+        L.call("hfmi_amg_set_coarse", self._amg, int(inv.shape[0]), L.ptr(inv))
+        L.call("hfmi_op_amg_pcg", self.ctx.handle, self._amg, float(rel_tol), int(max_iter), C.byref(self._op))
+        self.rel_tol, self.max_iter = float(rel_tol), int(max_iter)
+
+    def solve(self, y, x):
+        self.mult(x, y)
+
+    def vcycle(self, B, X):
+        """X = V B: one V-cycle of the preconditioner on a block (MultiVectors of length N)."""
+        L.call("hfmi_amg_vcycle", self._amg, B.handle, X.handle)
+
+    def info(self):
+        """Of the last solve: {'iterations', 'method': 'amg-cg'}."""
+        it, method = C.c_int(0), C.c_int(0)
+        L.call("hfmi_op_solver_info", self._op, C.byref(it), C.byref(method), None, None)
+        return {"iterations": it.value, "method": "amg-cg" if method.value == 2 else str(method.value)}
+
+    def hierarchy(self):
+        """The host hierarchy (``sizes()``, ``nnz()``, ``operator_complexity()``, ``info()``)."""
+        return self._hierarchy
+
+    def __del__(self):
+        super().__del__()
+        try:
+            if getattr(self, "_amg", None):
+                L.load().hfmi_amg_destroy(self._amg)
+                self._amg = None
+        except Exception:
+            pass
+
+
 class HostCallbackOperator(DeviceOperator):
     """A host black box plugged into the device solve (FEniCS/hIPPYlib PDE solves stay on the host).
 
@@ -430,6 +488,55 @@ class ComposedOperator(DeviceOperator):
         super().__init__(a.ctx, c.shape[0], a.shape[1])
         self._keep = [a, b, c]
         L.call("hfmi_op_compose3", self.ctx.handle, a._op, b._op, c._op, C.byref(self._op))
+
+
+class BiLaplacianRsolver(ComposedOperator):
+    """Device ``prior.Rsolver`` of a bi-Laplacian prior: R^-1 = A^-1 M A^-1, with A = delta M + gamma K solved by ONE
+    ``CsrAMGSolver`` (its hierarchy shared by both solves) and M either the consistent mass matrix (hippylib's form) or a
+    diagonal given as a 1-D array (the lumped form of ``workloads.BiLaplacianPrior``).  ``solve(y, x)`` is hippylib's
+    solver protocol, so it plugs in as ``prior.Rsolver`` and behind ``Solver2Operator``.
+
+    ``rel_tol`` defaults to 1e-14, tighter than hippylib's 1e-12 for ``Asolver``: doublePassG(A, R, R^-1, ...) orthonormalises
+    R^-1 Y in the R inner product, and what a solve leaves in the high-frequency modes is amplified there by ||R|| ~ 1e10
+    (1e-12 gave an R-orthonormality defect 40x the sparse-LU route's at N = 5e4; 1e-14 costs about three more iterations)."""
+
+    def __init__(self, A, M, rel_tol=1e-14, max_iter=100, ctx=None, **setup_options):
+        import scipy.sparse as sp
+        ctx = ctx or L.Context.default()
+        self.Asolver = A if isinstance(A, CsrAMGSolver) else CsrAMGSolver(A, rel_tol=rel_tol, max_iter=max_iter, ctx=ctx, **setup_options)
+        if isinstance(M, DeviceOperator):
+            self.Mop = M
+        else:
+            Mcsr = csr_from_matrix(M)
+            if Mcsr is None:
+                Mcsr = sp.diags(np.asarray(M, dtype=np.float64).ravel()).tocsr()
+            self.Mop = CsrOperator(Mcsr, ctx=ctx)
+        if self.Mop.shape != self.Asolver.shape:
+            raise ValueError("BiLaplacianRsolver: M is %s, A is %s" % (self.Mop.shape, self.Asolver.shape))
+        super().__init__(self.Asolver, self.Mop, self.Asolver)
+        self.N = self.Asolver.shape[0]
+
+    def solve(self, y, x):
+        self.mult(x, y)
+
+    def info(self):
+        """Of the second A-solve of the last apply."""
+        return self.Asolver.info()
+
+
+def device_bilaplacian_rsolver(prior, rel_tol=1e-14, max_iter=100, ctx=None, **setup_options):
+    """``BiLaplacianRsolver`` from a prior's ``A`` and ``M`` (hippylib ``BiLaplacianPrior``'s attribute names; scipy, PETSc
+    or dolfin matrices, through ``csr_from_matrix``).  A prior that carries ``M_lumped`` (``workloads.BiLaplacianPrior``,
+    R = A M_l^-1 A) gets that diagonal.  A driver swaps it in with ``prior.Rsolver = device_bilaplacian_rsolver(prior)``."""
+    A = csr_from_matrix(prior.A)
+    if A is None:
+        raise TypeError("device_bilaplacian_rsolver: prior.A is not an assembled matrix (%r)" % (type(prior.A),))
+    M = getattr(prior, "M_lumped", None)
+    if M is None:
+        M = csr_from_matrix(prior.M)
+        if M is None:
+            raise TypeError("device_bilaplacian_rsolver: prior.M is not an assembled matrix (%r)" % (type(prior.M),))
+    return BiLaplacianRsolver(A, M, rel_tol=rel_tol, max_iter=max_iter, ctx=ctx, **setup_options)
 
 
 def csr_from_matrix(M):

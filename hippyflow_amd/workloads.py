@@ -334,9 +334,12 @@ class SparseLUPriorSolver:
 class BiLaplacianPrior:
     """The prior shape of the reference's tests (hp.BiLaplacianPrior, test_derivativeSubspace.py:40):
     precision R = A M_l^-1 A with A = delta M + gamma K on an nx x ny P1 grid, ``R`` as a sparse matrix (applied on the
-    device as CSR), ``Rsolver`` a host sparse-LU black box, ``M`` the consistent mass matrix."""
+    device as CSR), ``Rsolver`` a host sparse-LU black box, ``M`` the consistent mass matrix.
 
-    def __init__(self, nx, ny, delta=1.0, gamma=0.1, threads=None, processes=None):
+    ``rsolver='device'``: ``Rsolver`` is ``operators.BiLaplacianRsolver`` instead -- the same R^-1 = A^-1 M_l A^-1 with
+    both solves by AMG-preconditioned CG on the GPU (rel_tol 1e-12 on A; the hierarchy is set up on the host)."""
+
+    def __init__(self, nx, ny, delta=1.0, gamma=0.1, threads=None, processes=None, rsolver="host"):
         import scipy.sparse as sp
         self.nx, self.ny, self.delta, self.gamma = nx, ny, delta, gamma
         self.M = grid_mass_matrix(nx, ny)
@@ -344,7 +347,13 @@ class BiLaplacianPrior:
         self.A = (delta * self.M + gamma * self.K).tocsr()
         self.M_lumped = np.asarray(self.M.sum(axis=1)).ravel()
         self.R = (self.A @ sp.diags(1.0 / self.M_lumped) @ self.A).tocsr()
-        self.Rsolver = SparseLUPriorSolver(self.A, self.M_lumped, threads=threads, processes=processes)
+        if rsolver == "host":
+            self.Rsolver = SparseLUPriorSolver(self.A, self.M_lumped, threads=threads, processes=processes)
+        elif rsolver == "device":
+            from .operators import BiLaplacianRsolver
+            self.Rsolver = BiLaplacianRsolver(self.A, self.M_lumped)
+        else:
+            raise ValueError("rsolver must be 'host' or 'device', got %r" % (rsolver,))
 
     def init_vector(self, x, dim):
         x.init(self.R.shape[0])

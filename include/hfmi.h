@@ -54,6 +54,7 @@ typedef struct hfmi_block hfmi_block;
 typedef struct hfmi_csr hfmi_csr;
 typedef struct hfmi_op hfmi_op;
 typedef struct hfmi_comm hfmi_comm;
+typedef struct hfmi_amg hfmi_amg;
 
 /* ---------------------------------------------------------------- context */
 const char* hfmi_last_error(void);
@@ -158,9 +159,30 @@ int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out);
  *     scalar CG run); Jacobi-preconditioned block CG when that bracket is too wide or does not
  *     deliver the tolerance. */
 int hfmi_op_csr_pcg(hfmi_ctx* ctx, const hfmi_csr* M, double rel_tol, int max_iter, hfmi_op** out);
-/*     what the last solve of such an operator did: steps taken, method (0 block CG, 1 Chebyshev),
+/*     what the last solve of such an operator did: steps taken, method (0 block CG, 1 Chebyshev, 2 AMG-CG),
  *     and the bracket of the spectrum of D^-1 M in use (0, 0: none) */
 int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* method, double* lmin, double* lmax);
+/*     algebraic multigrid for an SPD CSR matrix A (hippylib BiLaplacianPrior.Asolver: PETSc CG with amg_method(),
+ *     rel_tol 1e-12; prior.Rsolver = A^-1 M A^-1 costs two such solves per apply, activeSubspaceProjector.py:447-453,
+ *     KLEProjector.py:163-168).  The smoothed-aggregation hierarchy is built on the host (hippyflow_amd/amg.py) and
+ *     handed over level by level; the CSR matrices are NOT copied or owned and must outlive the hierarchy.
+ *     create: level 0 = A, smoothed by a Chebyshev polynomial of `degree` on [lmin, lmax] of D^-1 A;
+ *     add_level: P (n_fine x n_c) from the new level to the current coarsest one, R = P^T (explicit), A_c = P^T A P and
+ *       its own Chebyshev interval (unused when it stays the coarsest level);
+ *     set_coarse: host n x n row-major inverse of the coarsest matrix (dense solve there); completes the hierarchy. */
+int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, double lmax, int degree, hfmi_amg** out);
+int hfmi_amg_add_level(hfmi_amg* amg, const hfmi_csr* P, const hfmi_csr* R, const hfmi_csr* Ac, double lmin, double lmax);
+int hfmi_amg_set_coarse(hfmi_amg* amg, int n, const double* host_inv);
+int hfmi_amg_info(const hfmi_amg* amg, int* levels, int64_t* rows, int max_levels);
+int hfmi_amg_destroy(hfmi_amg* amg);
+/*     X = V B: one symmetric V-cycle on a block (the preconditioner; a test hook) */
+int hfmi_amg_vcycle(hfmi_amg* amg, const hfmi_block* B, hfmi_block* X);
+/*     solver operator Y = A^-1 W: block CG with the V-cycle as preconditioner, per-vector recurrences, until every
+ *     vector's residual (the true one, checked at the end) is at most rel_tol times its right-hand side.  Errors:
+ *     HFMI_ERR_NUMERIC (non-finite input, p.Ap <= 0 or r.z <= 0: not SPD), HFMI_ERR_NOT_CONVERGED (max_iter),
+ *     HFMI_ERR_INVALID (shapes); Y is zero-filled on error.  hfmi_op_solver_info: method 2, lmin = lmax = 0.
+ *     The operator does not own the hierarchy. */
+int hfmi_op_amg_pcg(hfmi_ctx* ctx, hfmi_amg* amg, double rel_tol, int max_iter, hfmi_op** out);
 /*     Y = c (b (a W))  (MassPreconditionedCovarianceOperator M C M, KLEProjector.py:47-69) */
 int hfmi_op_compose3(hfmi_ctx* ctx, hfmi_op* a, hfmi_op* b, hfmi_op* c, hfmi_op** out);
 /*     host black box (FEniCS PDE solves, sparse LU ...): W and Y in HFMI_LAYOUT_VECTORS
