@@ -143,6 +143,9 @@ extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
   if (!c) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   c->device = device;
   c->num_cus = prop.multiProcessorCount;
+  c->lds_per_block = prop.sharedMemPerBlock;
+  c->defl1_static_lds = 0;
+  c->defl1_static_known = false;
   c->own_stream = true;
   c->compose_depth = 0;
   for (int i = 0; i < WS_NSLOTS; ++i) {

@@ -1141,7 +1141,7 @@ __global__ __launch_bounds__(256) void k_dcl_rank(dcl_args p) {
 // BIG (a node of more than 4160 poles, i.e. the top merge beyond n = 4096): only the poles and the rank-one vector stay in LDS (16
 // bytes per pole, 132 KB at 8192), the index lists live in global memory at the node's offset -- every access pattern below is
 // "written, workgroup barrier, read by other threads of the SAME workgroup", which global memory serves like LDS.
-// MODE 2 (a node of more than 9984 poles: the top merge beyond n = 9984): the poles and the rank-one vector live in global memory
+// MODE 2 (a node of more than 9920 poles: the top merge beyond n = 9919): the poles and the rank-one vector live in global memory
 // too (xd, xz): no dynamic LDS at all; the sequential rotation scan, when it is needed at all, then walks global memory.
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_dcl_deflate(dcl_args p, int cap) {
@@ -1850,7 +1850,15 @@ int sym_eig_large(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, d
       hipLaunchKernelGGL(k_dcl_z, dim3(nn), dim3(1024), 0, st, da);
       hipLaunchKernelGGL(k_dcl_rank, dim3((n + 63) / 64), dim3(256), 0, st, da);
       const int cap = (int)round_up((n + nn - 1) / nn + 1, 64);
-      if (cap > 9984) {      // the top merge beyond n = 9984: nothing of it in LDS
+      // MODE 1 keeps 16 bytes per pole in dynamic LDS next to the kernel's static arrays (s_scan and three ints); together they must
+      // fit what a workgroup may have on this device.  With 160 KB that ends at cap = 9920 (9984 poles: 159 744 + 4 108 bytes).
+      if (!ctx->defl1_static_known) {
+        hipFuncAttributes fa;
+        HIP_TRY(hipFuncGetAttributes(&fa, (const void*)k_dcl_deflate<1>));
+        ctx->defl1_static_lds = fa.sharedSizeBytes;
+        ctx->defl1_static_known = true;
+      }
+      if ((size_t)cap * 16 + ctx->defl1_static_lds > ctx->lds_per_block) {      // nothing of the node in LDS
         hipLaunchKernelGGL(k_dcl_deflate<2>, dim3(nn), dim3(1024), 0, st, da, cap);
       } else if (cap > 4160) {      // the top merge beyond n = 4096
         const size_t defl_lds = (size_t)cap * 16;

@@ -77,6 +77,9 @@ struct hfmi_ctx {
   hipEvent_t ev_status;
   hipEvent_t ev_side;             // small device -> host copies taken off the main stream (late QR checks, eigenvalues)
   int num_cus;
+  size_t lds_per_block;          // LDS a workgroup may have on this device (static + dynamic; hipDeviceProp_t::sharedMemPerBlock)
+  size_t defl1_static_lds;        // static LDS of k_dcl_deflate<1>, read once per context (hfmi_eig_blocked.hip)
+  bool defl1_static_known;
   void* ws[WS_NSLOTS];
   size_t ws_bytes[WS_NSLOTS];
   double* small;                  // SM_NSLOTS * SM_MAXK * SM_LD doubles

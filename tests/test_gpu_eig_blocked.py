@@ -311,14 +311,36 @@ def test_pod_from_data_8300_snapshots_matches_the_reference(ctx, golden_dir, shi
     assert np.linalg.norm(eye - phi.T @ Mphi) / np.linalg.norm(eye) < 1e-8
 
 
-@pytest.mark.parametrize("n", [8193, 8320, 9000, 12500, 16384])
+# 9920 and 9983: the ends of the range whose top merge has cap = round_up(n + 1, 64) = 9984; 16 bytes per pole plus the static LDS of
+# k_dcl_deflate<1> exceed 160 KB there, so these sizes must take k_dcl_deflate<2>
+@pytest.mark.parametrize("n", [8193, 8320, 9000, 9920, 9983, 12500, 16384])
 def test_sym_eig_blocked_beyond_8192(ctx, n):
     """8192 < n <= 16384: the first columns take full-column products (v of k_tri_b is up to 128 KB of LDS), the top merge of the divide
-    and conquer keeps everything in global memory beyond 9984 poles (k_dcl_deflate<2>).  A matrix with a KNOWN spectrum (a diagonal
+    and conquer keeps everything in global memory beyond 9920 poles (k_dcl_deflate<2>).  A matrix with a KNOWN spectrum (a diagonal
     conjugated by three Householder reflectors: O(n^2) to build, no host eigh): every eigenvalue, and residual + orthonormality of the
     64 leading eigenvectors."""
     rng = np.random.default_rng(n)
     lam = np.sort(np.concatenate([np.exp(-0.002 * np.arange(n - 40)), np.repeat([2.0, 3.0], 10), -np.linspace(0.1, 1.0, 20)]))[::-1]
+    T = np.diag(lam)
+    for _ in range(3):
+        u = rng.standard_normal(n)
+        u /= np.linalg.norm(u)
+        T -= 2.0 * np.outer(u, u @ T)
+        T -= 2.0 * np.outer(T @ u, u)
+    T = 0.5 * (T + T.T)
+    d, V = hf.sym_eig_small(T, nvec=64)
+    assert np.abs(d - lam).max() <= 2e-11 * np.abs(lam).max()
+    assert np.abs(V.T @ V - np.eye(64)).max() <= 1e-11
+    assert np.abs(T @ V - V * d[:64]).max() <= 2e-11 * np.abs(lam).max()
+
+
+@pytest.mark.parametrize("n", [8320, 16384])
+def test_sym_eig_blocked_beyond_8192_flat_spectrum(ctx, n):
+    """The same construction with a spectrum that does NOT decay: |eigenvalues| uniform in [1, 2], both signs.  With the geometric
+    spectrum above the trailing block is ~1e-7 by column 8191 and an error in a late reflector hides below the tolerance; here every
+    column carries weight.  Same three assertions, same tolerances (2e-11 max|lam|, 1e-11)."""
+    rng = np.random.default_rng(n + 1)
+    lam = np.sort(rng.uniform(1.0, 2.0, n) * np.where(rng.random(n) < 0.5, -1.0, 1.0))[::-1]
     T = np.diag(lam)
     for _ in range(3):
         u = rng.standard_normal(n)
