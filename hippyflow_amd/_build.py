@@ -14,8 +14,9 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhfmi.so")
-SOURCES = ["hfmi_api.hip", "hfmi_gemm.hip", "hfmi_gemm_nn.hip", "hfmi_misc.hip", "hfmi_small.hip", "hfmi_skinny.hip", "hfmi_comm.hip", "hfmi_eig_large.hip", "hfmi_eig_blocked.hip", "hfmi_eig_dc.hip", "hfmi_chol.hip", "hfmi_cheb.hip", "hfmi_xfer.hip", "hfmi_amg.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC] + os.environ.get("HFMI_EXTRA_HIPCC_FLAGS", "").split()
+EXPORTS = os.path.join(HERE, "libhfmi.map")      # linker version script: only hfmi_* leaves the library
+SOURCES = ["hfmi_ctx.hip", "hfmi_block.hip", "hfmi_op.hip", "hfmi_qr.hip", "hfmi_solve.hip", "hfmi_bench.hip", "hfmi_gemm.hip", "hfmi_gemm_nn.hip", "hfmi_misc.hip", "hfmi_small.hip", "hfmi_skinny.hip", "hfmi_comm.hip", "hfmi_eig_large.hip", "hfmi_eig_blocked.hip", "hfmi_eig_dc.hip", "hfmi_chol.hip", "hfmi_cheb.hip", "hfmi_xfer.hip", "hfmi_amg.hip"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + INCLUDE, "-I" + CSRC] + os.environ.get("HFMI_EXTRA_HIPCC_FLAGS", "").split()
 
 
 def _hipcc():
@@ -60,7 +61,7 @@ def build(force=False, verbose=True):
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJDIR, src.replace(".hip", ".o"))
         objs.append(o)
-        carries_tag = src == "hfmi_api.hip"
+        carries_tag = src == "hfmi_ctx.hip"          # defines hfmi_build_tag
         if force or not _newer(o, [s] + headers) or (carries_tag and tag_changed):
             jobs.append([hipcc] + FLAGS + (['-DHFMI_BUILD_TAG="%s"' % tag] if carries_tag else []) + ["-c", s, "-o", o])
 
@@ -76,8 +77,8 @@ def build(force=False, verbose=True):
         with ThreadPoolExecutor(max_workers=min(6, len(jobs))) as ex:
             list(ex.map(run, jobs))
     open(tag_file, "w").write(tag + "\n")
-    if jobs or force or not _newer(LIB, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl", "-lrt", "-lpthread"])
+    if jobs or force or not _newer(LIB, objs + [EXPORTS]):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS, "-o", LIB] + objs + ["-ldl", "-lrt", "-lpthread"])
     return LIB
 
 

@@ -7,7 +7,7 @@
 // the right-hand side in and one of the solution out.  Almost all the work is sparse products -- the smoother steps, the
 // residual, restriction R = P^T, prolongation P, A p -- and with lanes across the k columns of one row the gathers of the
 // neighbour rows are contiguous runs (hfmi_cheb.hip's header: 1.5 TB/s for the column-major one-thread-per-row SpMM of the
-// block CG against the row-major step's rate).  A column-major CG (pcg_solve, hfmi_api.hip) would transpose to row-major and
+// block CG against the row-major step's rate).  A column-major CG (csr_pcg_solve, hfmi_cheb.hip) would transpose to row-major and
 // back around every V-cycle: four extra passes per iteration on the fine level.  The per-column inner products of CG are
 // the price: they reduce over the row groups of a workgroup in LDS, then over workgroups in a fixed order (deterministic).
 //

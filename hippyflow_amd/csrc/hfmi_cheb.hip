@@ -2,7 +2,7 @@
 // hp.doublePassG(KLE_Operator, prior.M, prior.Msolver, ...), KLEProjector.py:163-164; the mass-orthogonal QR applies it
 // once per solve to an N x k block).
 //
-// Why not the block CG of hfmi_api.hip (kept: it estimates the spectrum once per matrix and is the fallback): per
+// Why not the block CG at the end of this file (kept: it estimates the spectrum once per matrix and is the fallback): per
 // iteration CG needs two global reductions -- five launches, eleven passes over N x k blocks, a host look at the
 // residual every fourth iteration -- and its SpMM with one thread per ROW gathers 8 bytes per lane from k different
 // vectors (1.5 TB/s on config 2 while the elementwise kernels beside it run at 6 TB/s out of the Infinity Cache).
@@ -19,9 +19,10 @@
 // -- the three-term form of the iteration: the residual is recomputed from b in every step (no residual or direction
 // arrays, no drift), x_{n+1} overwrites x_{n-1} in place, and a step reads b, x_n (with its neighbour rows), x_{n-1} and
 // writes x_{n+1}: FOUR passes over three N x k arrays -- 200 MB on config 2, resident in the 256 MB Infinity Cache.
-// [lmin, lmax] bracket the spectrum of D^-1 A (hfmi_api.hip: Gershgorin from above, Lanczos of a scalar CG run from
+// [lmin, lmax] bracket the spectrum of D^-1 A (cheb_estimate below: Gershgorin from above, Lanczos of a scalar CG run from
 // below); the error after n steps is at most 2 c^n / (1 + c^2n), c = (sqrt(kappa) - 1) / (sqrt(kappa) + 1).
 #include <algorithm>
+#include <cmath>
 
 #include "hfmi_internal.h"
 
@@ -231,4 +232,268 @@ int launch_rm_colsq(hfmi_ctx* ctx, const double* A, int64_t nrows, int k, double
   hipLaunchKernelGGL(k_rm_colsq, dim3(chunks), dim3(256), 256 * sizeof(double), ctx->stream, A, nrows, k, (double*)part);
   HIP_TRY(hipGetLastError());
   return launch_dots_final(ctx, (const double*)part, chunks, k, out);
+}
+
+// ------------------------------------------------------------------ host side of the sparse SPD solve
+// ---- spectrum of D^-1 A for the Chebyshev solve -------------------------------------------------------------------------
+// extreme eigenvalues of the symmetric tridiagonal matrix (a, b) by bisection on the Sturm count
+static int sturm_count(const std::vector<double>& a, const std::vector<double>& b, double x) {
+  int cnt = 0;
+  double q = a[0] - x;
+  if (q < 0) ++cnt;
+  for (size_t i = 1; i < a.size(); ++i) {
+    if (q == 0.0) q = 1e-300;
+    q = a[i] - x - b[i - 1] * b[i - 1] / q;
+    if (q < 0) ++cnt;
+  }
+  return cnt;
+}
+static void tridiag_extremes(const std::vector<double>& a, const std::vector<double>& b, double* smallest, double* largest) {
+  double lo = a[0], hi = a[0];
+  for (size_t i = 0; i < a.size(); ++i) {
+    const double rad = (i > 0 ? fabs(b[i - 1]) : 0.0) + (i + 1 < a.size() ? fabs(b[i]) : 0.0);
+    lo = std::min(lo, a[i] - rad);
+    hi = std::max(hi, a[i] + rad);
+  }
+  const int m = (int)a.size();
+  double l = lo, h = hi;
+  for (int it = 0; it < 200 && h - l > 1e-14 * std::max(fabs(l), fabs(h)); ++it) {   // smallest: first x with count >= 1
+    const double mid = 0.5 * (l + h);
+    if (sturm_count(a, b, mid) >= 1) h = mid; else l = mid;
+  }
+  *smallest = 0.5 * (l + h);
+  l = lo; h = hi;
+  for (int it = 0; it < 200 && h - l > 1e-14 * std::max(fabs(l), fabs(h)); ++it) {   // largest: last x with count < m
+    const double mid = 0.5 * (l + h);
+    if (sturm_count(a, b, mid) >= m) h = mid; else l = mid;
+  }
+  *largest = 0.5 * (l + h);
+}
+// One scalar Jacobi-CG run on a pseudo-random right-hand side, on the device, with its two inner products per iteration read
+// back: the CG coefficients are the Lanczos matrix of D^-1 A, whose extreme eigenvalues approach those of D^-1 A from inside.
+// Once per matrix (~40 iterations of one-vector kernels).
+static int cheb_estimate(hfmi_op* op) {
+  hfmi_ctx* ctx = op->ctx;
+  hfmi_csr* M = const_cast<hfmi_csr*>(op->csr);
+  const int64_t N = M->nrows;
+  M->cheb_state = -1;
+  if (!(M->gersh_lmax > 0.0)) return HFMI_OK;
+  hfmi_block R, Z, P, AP;
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_0, N, 1, &R));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_1, N, 1, &Z));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_2, N, 1, &P));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_3, N, 1, &AP));
+  void* sc = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, 4 * sizeof(double), &sc));
+  double *rz = (double*)sc, *pap = rz + 1, *rz_new = rz + 2;
+  HFMI_TRY(launch_randn(ctx, R.p, N, 1, R.ld, 0x5eedc0deull, 77u, 1.0));
+  HFMI_TRY(launch_diag_scale(ctx, Z.p, Z.ld, R.p, R.ld, M->inv_diag, N, 1));
+  HFMI_TRY(launch_copy(ctx, P.p, P.ld, Z.p, Z.ld, N, 1));
+  HFMI_TRY(launch_col_dots(ctx, R.p, R.ld, Z.p, Z.ld, N, 1, rz));
+  double h_rz = 0, h_pap = 0, h_new = 0;
+  HFMI_TRY(read_back(ctx, rz, 1, &h_rz));
+  const double rz0 = h_rz;
+  std::vector<double> alpha, beta;
+  for (int it = 0; it < 60 && h_rz > 1e-28 * rz0; ++it) {
+    HFMI_TRY(launch_csr_spmm(ctx, M, P.p, P.ld, AP.p, AP.ld, 1, false));
+    HFMI_TRY(launch_col_dots(ctx, P.p, P.ld, AP.p, AP.ld, N, 1, pap));
+    HFMI_TRY(launch_col_axpy_dev(ctx, R.p, R.ld, AP.p, AP.ld, N, 1, rz, pap, -1.0));
+    HFMI_TRY(launch_diag_scale(ctx, Z.p, Z.ld, R.p, R.ld, M->inv_diag, N, 1));
+    HFMI_TRY(launch_col_dots(ctx, R.p, R.ld, Z.p, Z.ld, N, 1, rz_new));
+    HFMI_TRY(launch_col_xpby_dev(ctx, P.p, P.ld, Z.p, Z.ld, N, 1, rz_new, rz));
+    double two[3];
+    HFMI_TRY(read_back(ctx, rz, 3, two));
+    h_pap = two[1];
+    h_new = two[2];
+    if (!(h_pap > 0.0) || !std::isfinite(h_new)) return HFMI_OK;     // not SPD: leave the Chebyshev route off
+    alpha.push_back(h_rz / h_pap);
+    beta.push_back(h_new / h_rz);
+    HIP_TRY(hipMemcpyAsync(rz, rz_new, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    h_rz = h_new;
+  }
+  const size_t m = alpha.size();
+  if (m < 3) return HFMI_OK;
+  std::vector<double> a(m), b(m > 1 ? m - 1 : 0);
+  for (size_t i = 0; i < m; ++i) {
+    a[i] = 1.0 / alpha[i] + (i > 0 ? beta[i - 1] / alpha[i - 1] : 0.0);
+    if (i + 1 < m) b[i] = sqrt(beta[i]) / alpha[i];
+  }
+  double tmin, tmax;
+  tridiag_extremes(a, b, &tmin, &tmax);
+  if (!(tmin > 0.0) || !(tmax >= tmin)) return HFMI_OK;
+  // Ritz values lie inside the spectrum: widen them; never above Gershgorin's bound
+  M->cheb_lmin = 0.9 * tmin;
+  M->cheb_lmax = std::min(M->gersh_lmax, 1.05 * tmax);
+  if (M->cheb_lmax < tmax) M->cheb_lmax = tmax * (1.0 + 1e-9);
+  M->cheb_state = 1;
+  return HFMI_OK;
+}
+
+// Y = M^-1 W by Chebyshev iteration on row-major copies (hfmi_cheb.hip); *handled = false: the caller runs the block CG
+static int cheb_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, bool* handled) {
+  hfmi_ctx* ctx = op->ctx;
+  hfmi_csr* M = const_cast<hfmi_csr*>(op->csr);
+  const int64_t N = W->N;
+  const int k = W->nvec;
+  *handled = false;
+  static const bool off = env_flag("HFMI_PCG");          // A/B switch: always the block CG
+  if (off || M->cheb_state < 0) return HFMI_OK;
+  if (M->cheb_state == 0) HFMI_TRY(cheb_estimate(op));
+  if (M->cheb_state != 1) return HFMI_OK;
+  const double lmin = M->cheb_lmin, lmax = M->cheb_lmax;
+  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
+  hfmi_block Bb, X0b, X1b;
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_0, N, k, &Bb));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_1, N, k, &X0b));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_2, N, k, &X1b));
+  double* B = Bb.p;                                                  // used as row-major N x k arrays (ld >= N: large enough)
+  double* X[2] = {X0b.p, X1b.p};
+  void* sc = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)2 * k * sizeof(double), &sc));
+  double* bb = (double*)sc;
+  double* rr = bb + k;
+  HFMI_TRY(launch_block_to_dense(ctx, W->p, W->ld, B, N, k));
+  HFMI_TRY(launch_rm_colsq(ctx, B, N, k, bb));
+  HFMI_TRY(launch_cheb_first(ctx, B, X[1], X[0], M->inv_diag, N, k, 1.0 / theta));     // x_0 = 0 in X[0], x_1 in X[1]
+  int steps = 1, cur = 1;                                            // X[cur] = x_steps, X[cur ^ 1] = x_{steps-1}
+  const bool spread = delta > 1e-12 * theta;                         // else D^-1 A is a multiple of the identity: x_1 is the answer
+  double rho = spread ? delta / theta : 0.0;                         // 1 / sigma
+  int planned = 1;
+  if (spread) {
+    const double sk = sqrt(lmax / lmin), c = (sk - 1.0) / (sk + 1.0);
+    planned = (int)ceil(log(2.0 / op->rel_tol) / -log(c)) + 1;
+  }
+  if (planned > op->max_iter || planned > 200) {
+    // a spectrum this wide needs more steps than CG's superlinear convergence would: leave this matrix to the block CG
+    M->cheb_state = -1;
+    return HFMI_OK;
+  }
+  std::vector<double> h(2 * (size_t)k);
+  int budget = planned - 1;
+  for (int round = 0; round < 4; ++round) {
+    for (int i = 0; i < budget; ++i, ++steps) {
+      const double rho_new = 1.0 / (2.0 * theta / delta - rho);
+      HFMI_TRY(launch_cheb_step(ctx, M, B, X[cur], X[cur ^ 1], k, rho_new * rho, 2.0 * rho_new / delta, false));
+      rho = rho_new;
+      cur ^= 1;
+    }
+    // the true residual b - A x into the spare array, its column norms against those of b
+    void* rs = nullptr;
+    HFMI_TRY(ctx_ws(ctx, WS_STAGE, (size_t)N * k * sizeof(double), &rs));
+    HFMI_TRY(launch_cheb_step(ctx, M, B, X[cur], (double*)rs, k, 0.0, 0.0, true));
+    HFMI_TRY(launch_rm_colsq(ctx, (const double*)rs, N, k, rr));
+    HFMI_TRY(read_back(ctx, bb, (size_t)2 * k, h.data()));
+    bool done = true, diverged = false;
+    for (int j = 0; j < k; ++j) {
+      if (!std::isfinite(h[j]))
+        HFMI_FAIL(HFMI_ERR_NUMERIC, "csr solve: non-finite right-hand side in vector %d", j);
+      // a residual that is not finite, or larger than the right-hand side it started from, means the polynomial grew: an
+      // eigenvalue of D^-1 A lies outside the bracket (Ritz values of a short CG run from one random vector can miss the top of
+      // the spectrum).  That is a failure of the ESTIMATE, not of the matrix: hand the solve to the block CG, which alone
+      // reports a matrix that is not SPD (advisor r4)
+      if (!std::isfinite(h[k + j]) || h[k + j] > h[j]) diverged = true;
+      if (!(h[k + j] <= op->rel_tol * op->rel_tol * h[j])) done = false;
+    }
+    if (diverged) break;
+    if (done) {
+      op->last_iters = steps;
+      op->last_method = 1;
+      HFMI_TRY(launch_dense_to_block(ctx, X[cur], Y->p, Y->ld, N, k));
+      *handled = true;
+      return HFMI_OK;
+    }
+    if (!spread) break;
+    budget = std::max(2, planned / 3);
+    if (steps + budget > op->max_iter) break;
+  }
+  M->cheb_state = -1;       // the bracket of the spectrum was not good enough: this matrix goes back to the block CG for good
+  return HFMI_OK;
+}
+
+// Y = M^{-1} W for an SPD CSR matrix: Jacobi-preconditioned CG run on all vectors at once (independent
+// recurrences, shared SpMM); per-vector scalars stay on the device, the host only polls convergence.
+int csr_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
+  hfmi_ctx* ctx = op->ctx;
+  hfmi_csr* M = const_cast<hfmi_csr*>(op->csr);
+  const int64_t N = W->N;
+  const int k = W->nvec;
+  if (M->nrows != N) HFMI_FAIL(HFMI_ERR_INVALID, "csr_pcg: matrix has %lld rows, block vectors have %lld", (long long)M->nrows, (long long)N);
+  if (!M->inv_diag) {
+    HIP_TRY(hipMalloc((void**)&M->inv_diag, (size_t)N * sizeof(double)));
+    HFMI_TRY(launch_csr_diag_inv(ctx, M));
+  }
+  {
+    bool handled = false;
+    HFMI_TRY(cheb_solve(op, W, Y, &handled));
+    if (handled) return HFMI_OK;
+  }
+  hfmi_block R, Z, P, AP;
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_0, N, k, &R));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_1, N, k, &Z));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_2, N, k, &P));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_KRYLOV_3, N, k, &AP));
+  void* sc = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)6 * k * sizeof(double), &sc));
+  // two (r.z, r.r) pairs: an iteration reads r.z from one and writes the new r.z and r.r into the other (r.r must follow
+  // r.z_new: launch_pcg_update fills both with one final pass); the pairs swap roles instead of being copied
+  double* rz = (double*)sc;       // r.z
+  double* rz_new = rz + 2 * k;
+  double* rr = rz_new + k;
+  double* pap = rz + 4 * k;
+  double* bb = rz + 5 * k;
+  std::vector<double> h_rr(k), h_bb(k);
+  // x0 = 0, r = b
+  HFMI_TRY(launch_fill(ctx, Y->p, N, k, Y->ld, 0.0, false));
+  HFMI_TRY(launch_copy(ctx, R.p, R.ld, W->p, W->ld, N, k));
+  HFMI_TRY(launch_col_dots(ctx, W->p, W->ld, W->p, W->ld, N, k, bb));
+  HFMI_TRY(read_back(ctx, bb, k, h_bb.data()));
+  HFMI_TRY(launch_diag_scale(ctx, Z.p, Z.ld, R.p, R.ld, M->inv_diag, N, k));
+  HFMI_TRY(launch_copy(ctx, P.p, P.ld, Z.p, Z.ld, N, k));
+  HFMI_TRY(launch_col_dots(ctx, R.p, R.ld, Z.p, Z.ld, N, k, rz));
+  int it = 0;
+  bool done = false;
+  for (; it < op->max_iter && !done; ++it) {
+    if (M->ell_w > 0) {
+      // three passes over the blocks per iteration: A p fused with p . A p; (x, r) update fused with both residual
+      // dots; the new direction with z = D^-1 r recomputed on the fly (never stored)
+      HFMI_TRY(launch_ell_spmm_dot(ctx, M, P.p, P.ld, AP.p, AP.ld, k, pap));
+      HFMI_TRY(launch_pcg_update(ctx, Y->p, Y->ld, R.p, R.ld, P.p, P.ld, AP.p, AP.ld, M->inv_diag, N, k, rz, pap, rz_new, rr));
+      HFMI_TRY(launch_pcg_direction(ctx, P.p, P.ld, R.p, R.ld, M->inv_diag, N, k, rz_new, rz));
+      double* const rr_done = rr;
+      std::swap(rz, rz_new);        // the pair just written becomes "current"
+      rr = rz_new + k;
+      if ((it & 3) == 3 || it + 1 == op->max_iter) {
+        HFMI_TRY(read_back(ctx, rr_done, k, h_rr.data()));
+        done = true;
+        for (int j = 0; j < k; ++j)
+          if (!(h_rr[j] <= op->rel_tol * op->rel_tol * h_bb[j])) done = false;
+        for (int j = 0; j < k; ++j)
+          if (!std::isfinite(h_rr[j]) || !std::isfinite(h_bb[j]))
+            HFMI_FAIL(HFMI_ERR_NUMERIC, "csr_pcg: non-finite residual in vector %d at iteration %d (matrix not SPD, or non-finite input)", j, it + 1);
+      }
+      continue;
+    }
+    HFMI_TRY(launch_csr_spmm(ctx, M, P.p, P.ld, AP.p, AP.ld, k, false));
+    HFMI_TRY(launch_col_dots(ctx, P.p, P.ld, AP.p, AP.ld, N, k, pap));
+    HFMI_TRY(launch_col_axpy_dev(ctx, Y->p, Y->ld, P.p, P.ld, N, k, rz, pap, 1.0));
+    HFMI_TRY(launch_col_axpy_dev(ctx, R.p, R.ld, AP.p, AP.ld, N, k, rz, pap, -1.0));
+    HFMI_TRY(launch_diag_scale(ctx, Z.p, Z.ld, R.p, R.ld, M->inv_diag, N, k));
+    HFMI_TRY(launch_col_dots(ctx, R.p, R.ld, Z.p, Z.ld, N, k, rz_new));
+    HFMI_TRY(launch_col_xpby_dev(ctx, P.p, P.ld, Z.p, Z.ld, N, k, rz_new, rz));
+    HIP_TRY(hipMemcpyAsync(rz, rz_new, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((it & 3) == 3 || it + 1 == op->max_iter) {
+      HFMI_TRY(launch_col_dots(ctx, R.p, R.ld, R.p, R.ld, N, k, rr));
+      HFMI_TRY(read_back(ctx, rr, k, h_rr.data()));
+      done = true;
+      for (int j = 0; j < k; ++j)
+        if (!(h_rr[j] <= op->rel_tol * op->rel_tol * h_bb[j])) done = false;
+      for (int j = 0; j < k; ++j)
+        if (!std::isfinite(h_rr[j]) || !std::isfinite(h_bb[j]))
+          HFMI_FAIL(HFMI_ERR_NUMERIC, "csr_pcg: non-finite residual in vector %d at iteration %d (matrix not SPD, or non-finite input)", j, it + 1);
+    }
+  }
+  op->last_iters = it;
+  op->last_method = 0;
+  if (!done) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "csr_pcg: no convergence to %.1e in %d iterations", op->rel_tol, op->max_iter);
+  return HFMI_OK;
 }

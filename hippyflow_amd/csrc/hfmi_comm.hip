@@ -972,7 +972,7 @@ int comm_allreduce_device(hfmi_comm* c, double* data, int64_t count, int op) {
   return comm_allreduce_device_on(c, data, count, op, nullptr);
 }
 // the same on another stream of the context (the row panels of an operator application are reduced on the auxiliary stream
-// while the next panel is being computed, hfmi_api.hip)
+// while the next panel is being computed, hfmi_op.hip)
 int comm_allreduce_device_on(hfmi_comm* c, double* data, int64_t count, int op, void* hip_stream) {
   if (!c || !data) HFMI_FAIL(HFMI_ERR_INVALID, "allreduce: null argument");
   if (op != HFMI_REDUCE_SUM && op != HFMI_REDUCE_AVG && op != HFMI_REDUCE_MAX) HFMI_FAIL(HFMI_ERR_INVALID, "allreduce: unknown operation %d", op);

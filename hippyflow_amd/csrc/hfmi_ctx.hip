@@ -1,0 +1,487 @@
+// Context of libhfmi.so (include/hfmi.h): error text, version and build tag, the context object with its storage pool,
+// workspaces, pinned staging and cached temporaries, status read-backs, timers and the profiler.  Host side only.
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <new>
+
+#include "hfmi_internal.h"
+
+// ------------------------------------------------------------------ errors
+static thread_local char g_err[1024] = "";
+void hfmi_set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
+extern "C" const char* hfmi_last_error(void) { return g_err; }
+extern "C" int hfmi_version(void) { return HFMI_VERSION; }
+#ifndef HFMI_BUILD_TAG
+#define HFMI_BUILD_TAG "untagged"
+#endif
+extern "C" const char* hfmi_build_tag(void) { return HFMI_BUILD_TAG; }
+
+extern "C" int hfmi_device_count(int* count) {
+  if (!count) HFMI_FAIL(HFMI_ERR_INVALID, "device_count: null argument");
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    n = 0;
+  }
+  *count = n;
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ device memory: pool of released block storage
+static void pool_flush(hfmi_ctx* ctx) {
+  if (ctx->pool.empty()) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  for (auto& e : ctx->pool) (void)hipFree(e.p);
+  ctx->pool.clear();
+  ctx->pool_bytes = 0;
+}
+static hipError_t ctx_malloc(hfmi_ctx* ctx, void** p, size_t bytes) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess && !ctx->pool.empty()) {      // give the pooled storage back and try once more
+    (void)hipGetLastError();
+    pool_flush(ctx);
+    e = hipMalloc(p, bytes);
+  }
+  return e;
+}
+// storage of a destroyed block: kept for reuse (same stream order as every other use of it) or freed
+void pool_release(hfmi_ctx* ctx, void* p, size_t bytes) {
+  constexpr size_t MAX_ENTRY = (size_t)2 << 30, MAX_TOTAL = (size_t)8 << 30;
+  if (bytes <= MAX_ENTRY && ctx->pool.size() < 16 && ctx->pool_bytes + bytes <= MAX_TOTAL) {
+    ctx->pool.push_back({p, bytes});
+    ctx->pool_bytes += bytes;
+    return;
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(p);
+}
+static void* pool_take(hfmi_ctx* ctx, size_t bytes) {
+  for (size_t i = ctx->pool.size(); i-- > 0;)
+    if (ctx->pool[i].bytes == bytes) {
+      void* p = ctx->pool[i].p;
+      ctx->pool_bytes -= bytes;
+      ctx->pool.erase(ctx->pool.begin() + i);
+      return p;
+    }
+  return nullptr;
+}
+
+int block_alloc(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out) {
+  if (N <= 0 || nvec <= 0) HFMI_FAIL(HFMI_ERR_INVALID, "block: N=%lld nvec=%d must be positive", (long long)N, nvec);
+  hfmi_block* b = new (std::nothrow) hfmi_block();
+  if (!b) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  b->ctx = ctx;
+  b->N = N;
+  b->nvec = nvec;
+  b->ld = round_up(N, 32);
+  b->owner = true;
+  b->p = (double*)pool_take(ctx, (size_t)b->ld * nvec * sizeof(double));
+  hipError_t e = b->p ? hipSuccess : ctx_malloc(ctx, (void**)&b->p, (size_t)b->ld * nvec * sizeof(double));
+  if (e != hipSuccess) {
+    const double gb = (double)b->ld * nvec * 8 / 1e9;
+    delete b;
+    HFMI_FAIL(HFMI_ERR_HIP, "hipMalloc of a %lld x %d block (%.2f GB) failed: %s", (long long)N, nvec, gb, hipGetErrorString(e));
+  }
+  *out = b;
+  return HFMI_OK;
+}
+
+void ctx_watch_comm(hfmi_ctx* ctx, hfmi_comm* c) {
+  if (ctx && c) ctx->watched_comms.push_back(c);
+}
+void ctx_unwatch_comm(hfmi_ctx* ctx, hfmi_comm* c) {
+  if (!ctx) return;
+  for (size_t i = 0; i < ctx->watched_comms.size(); ++i)
+    if (ctx->watched_comms[i] == c) {
+      ctx->watched_comms.erase(ctx->watched_comms.begin() + i);
+      return;
+    }
+}
+// after a host synchronisation: did a stream-ordered collective behind it give up?  (one read of pinned host memory per
+// communicator; no device call)
+int ctx_check_comm(hfmi_ctx* ctx) {
+  for (hfmi_comm* c : ctx->watched_comms) HFMI_TRY(comm_check_error(c));
+  return HFMI_OK;
+}
+
+int ctx_ws(hfmi_ctx* ctx, int slot, size_t bytes, void** out) {
+  if (bytes > ctx->ws_bytes[slot]) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // buffers other streams work in: the panel reductions' staging area (auxiliary stream), the ingest buffer
+    if (slot == WS_COMM) HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
+    if (slot == WS_INGEST) HIP_TRY(hipStreamSynchronize(ctx->ingest_stream));
+    if (ctx->ws[slot]) HIP_TRY(hipFree(ctx->ws[slot]));
+    ctx->ws[slot] = nullptr;
+    ctx->ws_bytes[slot] = 0;
+    size_t want = bytes + bytes / 4 + 4096;
+    HIP_TRY(ctx_malloc(ctx, &ctx->ws[slot], want));
+    ctx->ws_bytes[slot] = want;
+  }
+  *out = ctx->ws[slot];
+  return HFMI_OK;
+}
+int ctx_pinned(hfmi_ctx* ctx, size_t bytes, void** out) {
+  if (bytes > ctx->pinned_bytes) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->pinned) HIP_TRY(hipHostFree(ctx->pinned));
+    ctx->pinned = nullptr;
+    ctx->pinned_bytes = 0;
+    HIP_TRY(hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault));
+    ctx->pinned_bytes = bytes;
+  }
+  *out = ctx->pinned;
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ context
+extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
+  if (!out) HFMI_FAIL(HFMI_ERR_INVALID, "ctx_create: null out");
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    HFMI_FAIL(HFMI_ERR_NO_DEVICE, "no HIP device visible (libhfmi has no CPU path)");
+  }
+  if (device < 0 || device >= n) HFMI_FAIL(HFMI_ERR_INVALID, "ctx_create: device %d out of range [0,%d)", device, n);
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  hfmi_ctx* c = new (std::nothrow) hfmi_ctx();
+  if (!c) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  c->device = device;
+  c->num_cus = prop.multiProcessorCount;
+  c->lds_per_block = prop.sharedMemPerBlock;
+  c->defl1_static_lds = 0;
+  c->defl1_static_known = false;
+  c->own_stream = true;
+  c->compose_depth = 0;
+  for (int i = 0; i < WS_NSLOTS; ++i) {
+    c->ws[i] = nullptr;
+    c->ws_bytes[i] = 0;
+  }
+  c->pinned = nullptr;
+  c->pinned_bytes = 0;
+  c->pinned_cb = nullptr;
+  c->pinned_cb_bytes = 0;
+  c->xfer = nullptr;
+  c->pool_bytes = 0;
+  for (int i = 0; i < HFMI_PHASE_COUNT; ++i) c->phase_ms[i] = 0.0;
+  c->profiling = false;
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreate(&c->ev0));
+  HIP_TRY(hipEventCreate(&c->ev1));
+  HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming));
+  for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&c->ev_cb[i], hipEventDisableTiming));
+  for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreateWithFlags(&c->ev_panel[i], hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  c->ingest_stream = nullptr;
+  c->ingest_seq = 0;
+  c->late_pinned = nullptr;
+  c->nn_hook = nullptr;
+  c->nn_hook_user = nullptr;
+  c->nn_hook_panels = 0;
+  c->nn_hook_called = false;
+  c->nn_upper_hint = false;
+  HIP_TRY(hipMalloc((void**)&c->small, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double)));
+  HIP_TRY(hipMemsetAsync(c->small, 0, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double), c->stream));
+  HIP_TRY(hipMalloc((void**)&c->status_dev, 2 * sizeof(hfmi_status_words)));      // [1]: a factorisation taken on trust (qr_chol)
+  HIP_TRY(hipMemsetAsync(c->status_dev, 0, 2 * sizeof(hfmi_status_words), c->stream));
+  HIP_TRY(hipHostMalloc((void**)&c->status_host, sizeof(hfmi_status_words), hipHostMallocDefault));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *out = c;
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_ctx_destroy(hfmi_ctx* ctx) {
+  if (!ctx) return HFMI_OK;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->stream);
+  for (hfmi_comm* c : ctx->watched_comms) comm_forget_ctx(c);    // a communicator destroyed after its context must not look for it
+  ctx->watched_comms.clear();
+  for (hfmi_block* b : ctx->tmp_blocks)
+    if (b) {
+      if (b->owner && b->p) (void)hipFree(b->p);
+      delete b;
+    }
+  pool_flush(ctx);
+  for (int i = 0; i < WS_NSLOTS; ++i)
+    if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
+  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  if (ctx->pinned_cb) (void)hipHostFree(ctx->pinned_cb);
+  if (ctx->late_pinned) (void)hipHostFree(ctx->late_pinned);
+  xfer_destroy(ctx);
+  for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ctx->ev_cb[i]);
+  for (int i = 0; i < 8; ++i) (void)hipEventDestroy(ctx->ev_panel[i]);
+  (void)hipEventDestroy(ctx->ev_join);
+  if (ctx->ingest_stream) {
+    (void)hipStreamSynchronize(ctx->ingest_stream);
+    for (int i = 0; i < HFMI_INGEST_RING; ++i) (void)hipEventDestroy(ctx->ev_ingest[i]);
+    (void)hipStreamDestroy(ctx->ingest_stream);
+  }
+  (void)hipFree(ctx->small);
+  (void)hipFree(ctx->status_dev);
+  (void)hipHostFree(ctx->status_host);
+  (void)hipEventDestroy(ctx->ev0);
+  (void)hipEventDestroy(ctx->ev1);
+  (void)hipEventDestroy(ctx->ev_status);
+  (void)hipEventDestroy(ctx->ev_side);
+  (void)hipStreamDestroy(ctx->aux_stream);
+  if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+  delete ctx;
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (hip_stream == nullptr) {
+    if (!ctx->own_stream) {
+      HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+      ctx->own_stream = true;
+    }
+  } else {
+    if (ctx->own_stream) HIP_TRY(hipStreamDestroy(ctx->stream));
+    ctx->stream = (hipStream_t)hip_stream;
+    ctx->own_stream = false;
+  }
+  return HFMI_OK;
+}
+extern "C" int hfmi_ctx_get_stream(hfmi_ctx* ctx, void** hip_stream) {
+  if (!ctx || !hip_stream) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  *hip_stream = (void*)ctx->stream;
+  return HFMI_OK;
+}
+extern "C" int hfmi_ctx_synchronize(hfmi_ctx* ctx) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return ctx_check_comm(ctx);
+}
+extern "C" int hfmi_ctx_device_info(hfmi_ctx* ctx, char* name, int name_len, int* compute_units, int64_t* hbm_bytes) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+  if (name && name_len > 0) {
+    snprintf(name, name_len, "%s (%s)", prop.name, prop.gcnArchName);
+  }
+  if (compute_units) *compute_units = prop.multiProcessorCount;
+  if (hbm_bytes) *hbm_bytes = (int64_t)prop.totalGlobalMem;
+  return HFMI_OK;
+}
+extern "C" int hfmi_ctx_pci_bus_id(hfmi_ctx* ctx, char* buf, int len) {
+  if (!ctx || !buf || len < 16) HFMI_FAIL(HFMI_ERR_INVALID, "ctx_pci_bus_id: bad argument");
+  HIP_TRY(hipDeviceGetPCIBusId(buf, len, ctx->device));
+  return HFMI_OK;
+}
+extern "C" int hfmi_timer_start(hfmi_ctx* ctx) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  return HFMI_OK;
+}
+extern "C" int hfmi_timer_stop(hfmi_ctx* ctx, double* milliseconds) {
+  if (!ctx || !milliseconds) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *milliseconds = ms;
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ cached temporaries (enum hfmi_tmp_slot)
+// *out: a view of exactly nvec vectors of the slot's cached block (which may hold more and is regrown when it holds fewer)
+int ctx_tmp_view(hfmi_ctx* ctx, int idx, int64_t N, int nvec, hfmi_block* out) {
+  if ((int)ctx->tmp_blocks.size() <= idx) ctx->tmp_blocks.resize(idx + 1, nullptr);
+  hfmi_block* b = ctx->tmp_blocks[idx];
+  if (b && (b->N != N || b->nvec < nvec)) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    (void)hipFree(b->p);
+    delete b;
+    b = nullptr;
+    ctx->tmp_blocks[idx] = nullptr;
+  }
+  if (!b) {
+    HFMI_TRY(block_alloc(ctx, N, nvec, &b));
+    HIP_TRY(hipMemsetAsync(b->p, 0, (size_t)b->ld * nvec * sizeof(double), ctx->stream));
+    ctx->tmp_blocks[idx] = b;
+  }
+  *out = *b;
+  out->nvec = nvec;
+  out->owner = false;
+  return HFMI_OK;
+}
+
+// read `count` doubles of device memory back to the host (synchronises the stream)
+int read_back(hfmi_ctx* ctx, const double* dev, size_t count, double* host) {
+  void* pin = nullptr;
+  HFMI_TRY(ctx_pinned(ctx, count * sizeof(double), &pin));
+  HIP_TRY(hipMemcpyAsync(pin, dev, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HFMI_TRY(ctx_check_comm(ctx));            // what was read may have come through a collective that gave up
+  memcpy(host, pin, count * sizeof(double));
+  return HFMI_OK;
+}
+void print_status_dbg(const hfmi_status_words* out) {
+  static const bool dbg = env_flag("HFMI_DEBUG_TIMING");
+  if (dbg)
+    fprintf(stderr, "[hfmi timing] %s cycles: %lld %lld %lld %lld\n",
+            out->tick[4] == 3 ? "chol-polish(load,-,-,out)" : out->tick[4] ? "jacobi(total,phase1,phase2,sweeps)" : "chol(load,chol,inv,out)",
+            out->tick[0], out->tick[1], out->tick[2], out->tick[3]);
+  if (dbg && (!out->tick[4] || out->tick[4] == 3))
+    fprintf(stderr, "[hfmi timing]   chol status: min pivot ratio %.3e, input defect %.3e, shifted %d; blocked phases (diag, row, trailing) %lld %lld %lld\n",
+            out->min_pivot_ratio, out->gram_dev, out->shifted, out->tick[5], out->tick[6], out->tick[7]);
+}
+int read_status(hfmi_ctx* ctx, hfmi_status_words* out) {
+  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  *out = *ctx->status_host;
+  print_status_dbg(out);
+  return HFMI_OK;
+}
+// Small device -> host copies that nothing on the main stream waits for: a copy engine / blit between two dependent kernels costs
+// the main stream 5 us of copy and 10-15 us of bubbles (timeline of the shard step), on the auxiliary stream it costs nothing.
+// side_copies_begin orders the auxiliary stream behind the current point of the main stream; the copies are then enqueued on
+// ctx->aux_stream by the caller; side_copies_end leaves an event the main stream can be made to wait for before a kernel
+// overwrites the source.
+int side_copies_begin(hfmi_ctx* ctx) {
+  HIP_TRY(hipEventRecord(ctx->ev_status, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_status, 0));
+  return HFMI_OK;
+}
+int side_copies_end(hfmi_ctx* ctx) {
+  HIP_TRY(hipEventRecord(ctx->ev_side, ctx->aux_stream));
+  return HFMI_OK;
+}
+
+int g_comm_panels = -1;    // HFMI_COMM_PANELS: 0 = one all-reduce after the product, n = at most n row panels (default 4)
+// What a profiling region (hfmi_profile_begin .. _end) records.  Every record is a pair of events on the stream, and an event
+// between two dependent kernels costs 2-4 us of idle GPU: with one pair per contraction and per phase a 64-sample shard step of
+// config 4 carried ~32 of them.  Level 2 (default): contractions and phases.  Level 1: only contractions of at least
+// HFMI_PROF_MIN_GFLOP (2.0) Gflop -- what a roofline line needs -- and no phases.
+static int g_prof_level = 2;
+// HFMI_QR_TRUST_FIRST=0 / tuning key "qr_trust_first": the first Cholesky-QR pass of the Gram-form solve waits for its status words
+// (the behaviour up to round 4: one host round trip in the middle of every solve); default 1
+int g_qr_trust_first = -1;
+int api_tuning_set(const char* key, int value) {
+  if (key && !strcmp(key, "comm_panels") && value >= 0 && value <= 8) {
+    g_comm_panels = value;
+    return 1;
+  }
+  if (key && !strcmp(key, "prof_level") && (value == 1 || value == 2)) {
+    g_prof_level = value;
+    return 1;
+  }
+  if (key && !strcmp(key, "qr_trust_first") && (value == 0 || value == 1)) {
+    g_qr_trust_first = value;
+    return 1;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------ instrumentation
+int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N) {
+  if (!ctx->profiling) return -1;
+  if (g_prof_level < 2 && 2.0 * (double)N * (double)m * (double)k < 2.0e9) return -1;
+  hfmi_ctx::prof_rec r;
+  r.kind = kind;
+  r.m = m;
+  r.k = k;
+  r.N = N;
+  // algorithmic work (each operand touched once): flops 2 N m k, bytes 8 (N m + N k + m k)
+  r.flops = 2.0 * (double)N * (double)m * (double)k;
+  r.bytes = 8.0 * ((double)N * m + (double)N * k + (double)m * k);
+  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return -1;
+  (void)hipEventRecord(r.e0, ctx->stream);
+  ctx->prof.push_back(r);
+  return (int)ctx->prof.size() - 1;
+}
+int prof_stop(hfmi_ctx* ctx, int idx) {
+  if (idx >= 0) (void)hipEventRecord(ctx->prof[idx].e1, ctx->stream);
+  return HFMI_OK;
+}
+int phase_begin_on(hfmi_ctx* ctx, int phase, hipStream_t st) {
+  if (!ctx->profiling || g_prof_level < 2) return -1;
+  hfmi_ctx::phase_rec r;
+  r.phase = phase;
+  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return -1;
+  (void)hipEventRecord(r.e0, st);
+  ctx->phase_events.push_back(r);
+  return (int)ctx->phase_events.size() - 1;
+}
+void phase_end_on(hfmi_ctx* ctx, int idx, hipStream_t st) {
+  if (idx >= 0) (void)hipEventRecord(ctx->phase_events[idx].e1, st);
+}
+int phase_begin(hfmi_ctx* ctx, int phase) { return phase_begin_on(ctx, phase, ctx->stream); }
+void phase_end(hfmi_ctx* ctx, int idx) { phase_end_on(ctx, idx, ctx->stream); }
+extern "C" int hfmi_profile_phases(hfmi_ctx* ctx, double* ms_out) {
+  if (!ctx || !ms_out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  for (int i = 0; i < HFMI_PHASE_COUNT; ++i) ms_out[i] = ctx->phase_ms[i];
+  return HFMI_OK;
+}
+extern "C" int hfmi_profile_begin(hfmi_ctx* ctx) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  for (auto& r : ctx->prof) {
+    (void)hipEventDestroy(r.e0);
+    (void)hipEventDestroy(r.e1);
+  }
+  ctx->prof.clear();
+  for (auto& r : ctx->phase_events) {
+    (void)hipEventDestroy(r.e0);
+    (void)hipEventDestroy(r.e1);
+  }
+  ctx->phase_events.clear();
+  for (int i = 0; i < HFMI_PHASE_COUNT; ++i) ctx->phase_ms[i] = 0.0;
+  ctx->profiling = true;
+  return HFMI_OK;
+}
+extern "C" int hfmi_profile_end(hfmi_ctx* ctx, int max_groups, int* ngroups, int* kind, int64_t* shape, double* ms,
+                                int64_t* launches, double* flops_per_launch, double* bytes_per_launch) {
+  if (!ctx || !ngroups || !kind || !shape || !ms || !launches || !flops_per_launch || !bytes_per_launch)
+    HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  ctx->profiling = false;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  int ng = 0;
+  for (auto& r : ctx->prof) {
+    float t = 0.f;
+    const bool ok = hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess;
+    (void)hipEventDestroy(r.e0);
+    (void)hipEventDestroy(r.e1);
+    if (!ok) continue;
+    int g = 0;
+    for (; g < ng; ++g)
+      if (kind[g] == r.kind && shape[3 * g] == r.m && shape[3 * g + 1] == r.k && shape[3 * g + 2] == r.N) break;
+    if (g == ng) {
+      if (ng >= max_groups) continue;
+      kind[g] = r.kind;
+      shape[3 * g] = r.m;
+      shape[3 * g + 1] = r.k;
+      shape[3 * g + 2] = r.N;
+      ms[g] = 0.0;
+      launches[g] = 0;
+      flops_per_launch[g] = r.flops;
+      bytes_per_launch[g] = r.bytes;
+      ++ng;
+    }
+    ms[g] += t;
+    launches[g] += 1;
+  }
+  ctx->prof.clear();
+  for (auto& r : ctx->phase_events) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) ctx->phase_ms[r.phase] += t;
+    (void)hipEventDestroy(r.e0);
+    (void)hipEventDestroy(r.e1);
+  }
+  ctx->phase_events.clear();
+  *ngroups = ng;
+  return HFMI_OK;
+}

@@ -119,7 +119,7 @@ struct hfmi_ctx {
   hipStream_t ingest_stream;
   hipEvent_t ev_ingest[HFMI_INGEST_RING];
   int64_t ingest_seq;
-  void* late_pinned;              // status words / R_jj table of an orthogonalisation pass taken on trust (hfmi_api.hip)
+  void* late_pinned;              // status words / R_jj table of an orthogonalisation pass taken on trust (hfmi_qr.hip)
   std::vector<hfmi_comm*> watched_comms;   // communicators whose device-side error word the host synchronisation points check
   void* pinned_cb;
   size_t pinned_cb_bytes;
@@ -133,13 +133,47 @@ int xfer_h2d(hfmi_ctx* ctx, void* dev, const void* host, size_t bytes);   // ret
 void xfer_destroy(hfmi_ctx* ctx);
 int phase_begin(hfmi_ctx* ctx, int phase);     // returns a record index or -1 when not profiling
 void phase_end(hfmi_ctx* ctx, int idx);
+int phase_begin_on(hfmi_ctx* ctx, int phase, hipStream_t st);   // the same with the events on another stream of the context
+void phase_end_on(hfmi_ctx* ctx, int idx, hipStream_t st);
 int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N);  // returns record index or -1
 int prof_stop(hfmi_ctx* ctx, int idx);
 
 static inline double* sm_ptr(hfmi_ctx* c, int slot) { return c->small + (size_t)slot * SM_MAXK * SM_LD; }
 int ctx_ws(hfmi_ctx* ctx, int slot, size_t bytes, void** out);
 int ctx_pinned(hfmi_ctx* ctx, size_t bytes, void** out);
-int ctx_tmp_block(hfmi_ctx* ctx, int idx, int64_t N, int nvec, hfmi_block** out);
+// uninitialised storage for an N x nvec block, from the pool of released blocks or hipMalloc; pool_release gives it back
+int block_alloc(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out);
+void pool_release(hfmi_ctx* ctx, void* p, size_t bytes);
+// Cached temporaries of the context, one block per slot.  Slots of different owners may all be live at once, because the owners
+// nest: a fused solve (SOLVE, SKETCH) orthogonalises (QR) and applies operators; an application may be a composition (COMPOSE,
+// one pair per nesting depth) whose stages are sparse solves (KRYLOV) or a JJT product; ACCUM belongs to the outermost
+// accumulating apply.  No owner calls itself: the sparse solves apply no operator, compositions index their pair by depth.
+enum hfmi_tmp_slot {
+  TMP_SOLVE_Q = 0,        // double_pass_impl / single_pass_impl: iterate Q (X_0)
+  TMP_SOLVE_Y = 1,        // double_pass_impl / single_pass_impl: iterate Y (X_1)
+  TMP_SKETCH_Q = 2,       // single_pass_impl (Ybar, then Q), hfmi_sketch_eig (Q)
+  TMP_SKETCH_BQ = 3,      // single_pass_impl, hfmi_sketch_eig: B Q
+  TMP_QR_BZ = 4,          // qr_chol / qr_mgs: B Q when the caller wants no BQ
+  TMP_QR_SAVE = 5,        // borth_qr(AUTO): the input, for the Gram-Schmidt fall-back
+  TMP_KRYLOV_0 = 8,       // csr_pcg_solve and its Chebyshev route (hfmi_cheb.hip): r / row-major b
+  TMP_KRYLOV_1 = 9,       //   z / x_0
+  TMP_KRYLOV_2 = 10,      //   p / x_1
+  TMP_KRYLOV_3 = 11,      //   A p
+  TMP_JJT_H = 12,         // op_apply_raw(OP_JJT): J_i^T W
+  TMP_ACCUM = 13,         // op_apply_raw with beta != 0: the result of a solver / host operator before it is added to Y
+  TMP_COMPOSE_BASE = 14   // op_apply_raw(OP_COMPOSE3): tmp_compose_slot(depth) and the slot after it
+};
+static inline int tmp_compose_slot(int depth) { return depth == 0 ? TMP_COMPOSE_BASE : TMP_COMPOSE_BASE + 2 * depth + 2; }
+// *out: a view (by value, not owned) of exactly nvec vectors of the slot's block; the cached block may be wider
+int ctx_tmp_view(hfmi_ctx* ctx, int slot, int64_t N, int nvec, hfmi_block* out);
+int read_back(hfmi_ctx* ctx, const double* dev, size_t count, double* host);   // `count` doubles to the host; synchronises
+int read_status(hfmi_ctx* ctx, hfmi_status_words* out);                        // the status words; synchronises
+int side_copies_begin(hfmi_ctx* ctx);   // small device -> host copies on the auxiliary stream, behind this point of the main one
+int side_copies_end(hfmi_ctx* ctx);     // ... leaves ev_side for the next writer of their source to wait for
+void print_status_dbg(const hfmi_status_words* out);   // HFMI_DEBUG_TIMING=1: the section timings of the last small kernel
+// hfmi_block.hip: a host row-major (rows x cols) matrix into device memory with leading dimension ld (zero padded); shape check
+int upload_small(hfmi_ctx* ctx, const double* host, int rows, int cols, double* dev, int ld);
+int check_same_shape(const hfmi_block* a, const hfmi_block* b, const char* what);
 
 struct hfmi_csr {
   hfmi_ctx* ctx;
@@ -186,8 +220,10 @@ struct hfmi_op {
   void* post_user;
   hfmi_comm* comm;       // rank average / sum of the result block (hfmi_op_set_collective), null = none
   int comm_op;
-  bool reduced_by_panels; // the last apply already reduced its result over the ranks, panel by panel (hfmi_api.hip)
+  bool reduced_by_panels; // the last apply already reduced its result over the ranks, panel by panel (hfmi_op.hip)
 };
+// Y = M^-1 W for an SPD CSR matrix by Chebyshev iteration, or Jacobi-preconditioned block CG (hfmi_cheb.hip)
+int csr_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
 // Y = A^-1 W by AMG-preconditioned block CG (hfmi_amg.hip); Y zero-filled on error
 int amg_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
 // in-place all-reduce of `count` doubles of device memory on the communicator's context stream (hfmi_comm.hip)
@@ -222,6 +258,21 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_
 // Y (N x r) = alpha * A (N x m) * S (m x r, device row-major, ld = lds, zero padded to 16 cols) + beta * Y
 int launch_tsgemm_nn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds, int r,
                      double alpha, double beta, double* Y, int64_t ldy, int64_t N);
+
+// ------------------------------------------------------------------ QR (hfmi_qr.hip)
+// Y = A S, S upper triangular
+int launch_nn_upper(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int ld, int r, double* Y, int64_t ldy, int64_t N);
+struct qr_late_checks {     // second (and first) Cholesky-QR pass taken on trust: where its status words go for the caller to verify
+  bool used;
+  hfmi_status_words* st2;   // pinned
+  double* aux;              // pinned, SM_LD + k doubles
+  int k;
+  hfmi_status_words* st1;   // pinned: status words of the FIRST pass when that one was taken on trust as well
+  bool first_trusted;
+};
+int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_out, bool* deferred = nullptr, qr_late_checks* opt = nullptr);
+// hfmi_borth_qr with want_r (exact triangular factors in every Cholesky pass) chosen by the caller
+int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes);
 
 // ------------------------------------------------------------------ kernel launchers (hfmi_misc.hip)
 int launch_fill(hfmi_ctx* ctx, double* p, int64_t N, int nvec, int64_t ld, double value, bool include_pad);
@@ -290,7 +341,9 @@ int eig_tuning_set(const char* key, int value);   // 1 = key handled
 int chol_tuning_set(const char* key, int value);  // "chol": 0 = blocked MFMA kernel (default), 1 = column-at-a-time kernels
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol);   // hfmi_chol.hip
-int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels")
+int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first"; hfmi_ctx.hip)
+extern int g_comm_panels;      // row panels of an overlapped rank reduction (hfmi_op.hip reads HFMI_COMM_PANELS when -1)
+extern int g_qr_trust_first;   // first Cholesky-QR pass taken on trust (hfmi_qr.hip reads HFMI_QR_TRUST_FIRST when -1)
 int launch_small_set_identity(hfmi_ctx* ctx, int k, int slot);
 // slot_c (k x r, zero padded to 16 columns) = slot_a (k x k) * slot_b[:, :r]
 int launch_small_matmul(hfmi_ctx* ctx, int k, int r, int slot_a, int slot_b, int slot_c);

@@ -1,0 +1,263 @@
+// B-orthogonal thin QR of libhfmi.so (include/hfmi.h): repeated (shifted) Cholesky-QR, the reference's Gram-Schmidt rule and
+// the dispatcher between them.  Host side only; kernels live in hfmi_gemm.hip / hfmi_gemm_nn.hip / hfmi_small.hip / hfmi_chol.hip.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "hfmi_internal.h"
+
+// Y = A S with S upper triangular (R^-1 of a Cholesky-QR pass: every factorisation kernel writes its strict lower triangle as
+// zeros): the hint lets the resident-S kernel skip the structurally zero column tiles; any other route ignores it
+int launch_nn_upper(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int ld, int r, double* Y, int64_t ldy,
+                    int64_t N) {
+  ctx->nn_upper_hint = true;
+  const int s = launch_tsgemm_nn(ctx, A, lda, m, S, ld, r, 1.0, 0.0, Y, ldy, N);
+  ctx->nn_upper_hint = false;
+  return s;
+}
+
+// ------------------------------------------------------------------ QR
+// Split read-back: `begin` snapshots the status words at the current point of the main stream (event + copy on the
+// auxiliary stream), `finish` waits for that copy only -- kernels queued on the main stream in between keep running
+// while the host looks at the words and decides what to launch next.
+static int read_status_begin(hfmi_ctx* ctx) {
+  HIP_TRY(hipEventRecord(ctx->ev_status, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_status, 0));
+  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  return HFMI_OK;
+}
+static int read_status_finish(hfmi_ctx* ctx, hfmi_status_words* out) {
+  HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
+  *out = *ctx->status_host;
+  print_status_dbg(out);
+  return HFMI_OK;
+}
+// deferred (optional): if non-null and B == null, the LAST pass (the one whose input is already orthonormal to 1e-2 and
+// needs no shift) does not apply its R^-1: *deferred = true and R^-1 stays in SM_RINV for the caller to fold into
+// the small matrices downstream (Q = Q_in R^-1 is never formed: one N x k x k contraction less).
+// opt (optional, fused solves only): do not stop the stream for the decisions of the SECOND pass.  When the first pass needed no
+// shift, the second one is assumed to be the last (deferred R^-1, as above); its status words and the R_jj / ||z_j|| table are
+// copied to pinned memory in stream order and verified by the caller after the synchronisation it needs anyway for the
+// eigenvalues.  If the assumption was wrong the caller repeats the solve on the checked path.  (Two host round trips of ~60 us
+// each per solve: 1.4 % of the 64-sample shard step.)
+static_assert(sizeof(hfmi_status_words) <= 128, "two sets of status words share the first 256 bytes of the late-check buffer");
+int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_out, bool* deferred, qr_late_checks* opt) {
+  hfmi_ctx* ctx = Q->ctx;
+  const int64_t N = Q->N;
+  const int k = Q->nvec;
+  if (k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", SM_MAXK, k);
+  hfmi_block* BZ = BQ;
+  hfmi_block bz_view;
+  if (B && !BQ) {
+    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
+    BZ = &bz_view;
+  }
+  const double u = 1.1102230246251565e-16;
+  const double shift_rel = 11.0 * ((double)N * k + (double)k * (k + 1)) * u;
+  // Breakdown threshold on pivot / (original diagonal): only pivots that are round-off noise (64 k eps) trigger the
+  // shifted factorisation.  A pass with small but genuine pivots leaves a defect ~ eps / min pivot ratio, which the
+  // next pass measures (st.gram_dev) and removes -- a more cautious threshold (100 k sqrt(N) u) cost config 3 a whole
+  // extra pass (shifted first pass, cond(Q1) ~ 260) without making the result more accurate.
+  const double pivot_tol = 0.0;   // launch_chol_inv default: 64 k eps
+  int passes = 0;
+  const int max_passes = 6;
+  bool first_pass_clean = false;
+  if (g_qr_trust_first < 0) {
+    const char* e = getenv("HFMI_QR_TRUST_FIRST");
+    g_qr_trust_first = (e && e[0] == '0') ? 0 : 1;
+  }
+  const bool trust_first = g_qr_trust_first != 0;
+  for (;;) {
+    const hfmi_block* right = Q;
+    if (B) {
+      HFMI_TRY(hfmi_op_apply(B, Q, BZ, 0));
+      right = BZ;
+    }
+    HFMI_TRY(launch_tsgemm_tn(ctx, Q->p, Q->ld, k, right->p, right->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_GRAM), SM_LD, 1, 0));
+    const int rtot_mode = (passes == 0) ? 1 : 2;   // always track R = R_p ... R_1: its diagonal exposes dependent columns
+    if (deferred && !B && passes == 0 && opt && trust_first) {
+      // The first pass on trust too: its status words go to their own slot (nothing overwrites them), Q <- Q R^-1 follows at
+      // once and NO host round trip interrupts the solve -- the host runs ahead of the device from here to the final
+      // synchronisation, so the small kernels of the tail are queued back to back.  The words are read with the second
+      // pass's (below); a shifted / failed first pass sends the whole solve to the checked path (double_pass_impl).
+      hfmi_status_words* const keep = ctx->status_dev;
+      ctx->status_dev = keep + 1;
+      const int cs = launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, shift_rel, pivot_tol);
+      ctx->status_dev = keep;
+      HFMI_TRY(cs);
+      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
+      opt->first_trusted = true;
+      first_pass_clean = true;
+      ++passes;
+      continue;
+    }
+    HFMI_TRY(launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, shift_rel, pivot_tol));
+    hfmi_status_words st;
+    if (deferred && !B && passes == 1 && opt && first_pass_clean) {
+      HFMI_TRY(side_copies_begin(ctx));
+      if (opt->first_trusted)
+        HIP_TRY(hipMemcpyAsync(opt->st1, ctx->status_dev + 1, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+      HIP_TRY(hipMemcpyAsync(opt->st2, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+      HIP_TRY(hipMemcpyAsync(opt->aux, sm_ptr(ctx, SM_AUX), ((size_t)SM_LD + k) * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
+      HFMI_TRY(side_copies_end(ctx));                      // the eigensolver (next writer of the status words) waits for ev_side
+      opt->used = true;
+      opt->k = k;
+      ++passes;
+      *deferred = true;
+      if (passes_out) *passes_out = passes;
+      return HFMI_OK;                                    // the checks below are the caller's, after its own synchronisation
+    }
+    if (deferred && !B && passes >= 1) {
+      // candidate last pass: look at the status words first (the read-back is not hidden here) and stop WITHOUT
+      // applying R^-1 if this pass would have been the last one anyway
+      HFMI_TRY(read_status(ctx, &st));
+      if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
+      if (!st.shifted && st.gram_dev < 1e-2) {
+        ++passes;
+        *deferred = true;
+        break;
+      }
+      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
+    } else {
+      // snapshot the status words on the auxiliary stream and enqueue Q <- Q R^-1 BEFORE waiting for them: the host
+      // round trip then overlaps the contraction.  If the factorisation failed, R^-1 was never written by this pass
+      // and Q is about to be discarded anyway (the callers restore / recompute the block on HFMI_ERR_NUMERIC).
+      HFMI_TRY(read_status_begin(ctx));
+      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
+      HFMI_TRY(read_status_finish(ctx, &st));
+      if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
+      if (passes == 0) first_pass_clean = !st.shifted;
+    }
+    ++passes;
+    // The input of this pass had orthonormality defect st.gram_dev (column-scaled).  If it was already
+    // small and no shift was needed, the output is orthonormal to round-off: done.
+    if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
+    if (passes >= max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
+  }
+  // The reference's MGS zeroes a column whose norm drops below 10 eps of its pre-sweep norm
+  // (numerically dependent); Cholesky-QR would instead normalise round-off noise.  R_jj / ||z_j|| is that
+  // drop: hand such blocks to the Gram-Schmidt route, which reproduces the reference's behaviour.
+  {
+    std::vector<double> aux((size_t)SM_LD + k);       // [0, k): original column norms; [SM_LD, SM_LD + k): diag(R)
+    HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_AUX), (size_t)SM_LD + k, aux.data()));
+    for (int j = 0; j < k; ++j)
+      if (!(aux[SM_LD + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
+        HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
+                  aux[j] > 0 ? aux[SM_LD + j] / aux[j] : 0.0);
+  }
+  (void)want_r;
+  if (B && BQ) HFMI_TRY(hfmi_op_apply(B, Q, BQ, 0));
+  if (passes_out) *passes_out = passes;
+  return HFMI_OK;
+}
+
+// Column-by-column Gram-Schmidt with the reference's re-orthogonalisation rule (hippylib
+// MultiVector._mgs_stable / _mgs_reortho as restated in oracle/hippylib_restated.py): each sweep projects
+// column j against all previous columns at once (classical GS per sweep; with the "twice is enough"
+// repetition this is as stable as the modified variant) and repeats while 10 eps t < ||q|| < t/10.
+static int qr_mgs(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* R_host /* k*k or null */, int* passes_out) {
+  hfmi_ctx* ctx = Q->ctx;
+  const int64_t N = Q->N;
+  const int k = Q->nvec;
+  const double eps = 2.220446049250313e-16;
+  hfmi_block* BZ = BQ;
+  hfmi_block bz_view;
+  if (B && !BQ) {
+    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
+    BZ = &bz_view;
+  }
+  std::vector<double> R((size_t)k * k, 0.0), s(k);
+  void* dv = nullptr;
+  // its own slot: hfmi_op_apply(B, ...) inside the column loop may regrow WS_G (Gram-form / composed / PCG operators)
+  HFMI_TRY(ctx_ws(ctx, WS_MGS, (size_t)(k + 16) * 16 * sizeof(double), &dv));
+  double* dsmall = (double*)dv;  // device scratch: coefficient column (ld 16) / scalars
+  int total_sweeps = 0;
+  for (int j = 0; j < k; ++j) {
+    hfmi_block qj = *Q;
+    qj.p = Q->p + (int64_t)j * Q->ld;
+    qj.nvec = 1;
+    hfmi_block bqj = qj;
+    if (B) {
+      bqj = *BZ;
+      bqj.p = BZ->p + (int64_t)j * BZ->ld;
+      bqj.nvec = 1;
+      HFMI_TRY(hfmi_op_apply(B, &qj, &bqj, 0));
+    }
+    double t2 = 0.0;
+    HFMI_TRY(launch_col_dots(ctx, bqj.p, bqj.ld, qj.p, qj.ld, N, 1, dsmall));
+    HFMI_TRY(read_back(ctx, dsmall, 1, &t2));
+    double t = sqrt(std::max(t2, 0.0));
+    double tt = t;
+    bool again = true;
+    while (again) {
+      ++total_sweeps;
+      if (j > 0) {
+        // s = (B Q_prev)^T q_j
+        const double* left = B ? BZ->p : Q->p;
+        const int64_t ldl = B ? BZ->ld : Q->ld;
+        HFMI_TRY(launch_tsgemm_tn(ctx, left, ldl, j, qj.p, qj.ld, 1, N, 1.0, 0.0, dsmall, 16, 1, 0));
+        std::vector<double> tmp((size_t)j * 16);
+        HFMI_TRY(read_back(ctx, dsmall, (size_t)j * 16, tmp.data()));
+        for (int i = 0; i < j; ++i) {
+          s[i] = tmp[(size_t)i * 16];
+          R[(size_t)i * k + j] += s[i];
+        }
+        // q_j -= Q_prev s   (the device copy of s already sits in dsmall with ld 16)
+        HFMI_TRY(launch_tsgemm_nn(ctx, Q->p, Q->ld, j, dsmall, 16, 1, -1.0, 1.0, qj.p, qj.ld, N));
+      }
+      if (B) HFMI_TRY(hfmi_op_apply(B, &qj, &bqj, 0));
+      double tt2 = 0.0;
+      HFMI_TRY(launch_col_dots(ctx, bqj.p, bqj.ld, qj.p, qj.ld, N, 1, dsmall));
+      HFMI_TRY(read_back(ctx, dsmall, 1, &tt2));
+      tt = sqrt(std::max(tt2, 0.0));
+      if (tt > t * 10.0 * eps && tt < t / 10.0) {
+        again = true;
+        t = tt;
+      } else {
+        again = false;
+        if (tt < 10.0 * eps * t) tt = 0.0;
+      }
+    }
+    R[(size_t)j * k + j] = tt;
+    const double inv = (fabs(tt * eps) > 0.0) ? 1.0 / tt : 0.0;
+    HFMI_TRY(launch_scale(ctx, qj.p, qj.ld, N, 1, inv));
+    if (B) HFMI_TRY(launch_scale(ctx, bqj.p, bqj.ld, N, 1, inv));
+  }
+  if (R_host) memcpy(R_host, R.data(), (size_t)k * k * sizeof(double));
+  if (passes_out) *passes_out = total_sweeps;
+  return HFMI_OK;
+}
+
+// want_r: exact triangular factors in every Cholesky pass.  Without it a pass whose input is already orthonormal to ~1e-7
+// takes the kernel's first-order inverse square root, which left a 74-column single-pass sketch orthonormal to only ~1e-10.
+int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes) {
+  if (!Q) HFMI_FAIL(HFMI_ERR_INVALID, "null block");
+  if (BQ) HFMI_TRY(check_same_shape(Q, BQ, "borth_qr"));
+  if (BQ && !B) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: BQ requested without B");
+  hfmi_ctx* ctx = Q->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int k = Q->nvec;
+  if (method == HFMI_QR_MGS) return qr_mgs(Q, B, BQ, host_R, passes);
+  if (method != HFMI_QR_CHOL && method != HFMI_QR_AUTO) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: unknown method %d", method);
+  hfmi_block save;
+  if (method == HFMI_QR_AUTO) {  // keep the input so that a breakdown can fall back to Gram-Schmidt
+    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_SAVE, Q->N, k, &save));
+    HFMI_TRY(launch_copy(ctx, save.p, save.ld, Q->p, Q->ld, Q->N, k));
+  }
+  int s = qr_chol(Q, B, BQ, want_r, passes);
+  if (s == HFMI_ERR_NUMERIC && method == HFMI_QR_AUTO) {
+    HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, save.p, save.ld, Q->N, k));
+    return qr_mgs(Q, B, BQ, host_R, passes);
+  }
+  if (s != HFMI_OK) return s;
+  if (host_R) {
+    std::vector<double> tmp((size_t)k * SM_LD);
+    HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_RTOT), (size_t)k * SM_LD, tmp.data()));
+    for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * SM_LD, (size_t)k * sizeof(double));
+  }
+  return HFMI_OK;
+}
+extern "C" int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes) {
+  return borth_qr(Q, B, BQ, host_R, host_R != nullptr, method, passes);
+}

@@ -34,6 +34,16 @@ extern "C" {
 
 #define HFMI_VERSION 100
 
+/* Entry points are the only symbols libhfmi.so exports (it is built with -fvisibility=hidden).  Define HFMI_API before
+ * including this header to override the attribute. */
+#ifndef HFMI_API
+#if defined(__GNUC__)
+#define HFMI_API __attribute__((visibility("default")))
+#else
+#define HFMI_API
+#endif
+#endif
+
 typedef enum {
   HFMI_OK = 0,
   HFMI_ERR_INVALID = -1,      /* bad argument / shape mismatch (the reference asserts) */
@@ -57,50 +67,50 @@ typedef struct hfmi_comm hfmi_comm;
 typedef struct hfmi_amg hfmi_amg;
 
 /* ---------------------------------------------------------------- context */
-const char* hfmi_last_error(void);
-int hfmi_version(void);
-const char* hfmi_build_tag(void);   /* identity of the kernel sources (hash); keys the PMC records bench.py may use */
-int hfmi_device_count(int* count);
-int hfmi_ctx_create(int device, hfmi_ctx** out);
-int hfmi_ctx_destroy(hfmi_ctx* ctx);
+HFMI_API const char* hfmi_last_error(void);
+HFMI_API int hfmi_version(void);
+HFMI_API const char* hfmi_build_tag(void);   /* identity of the kernel sources (hash); keys the PMC records bench.py may use */
+HFMI_API int hfmi_device_count(int* count);
+HFMI_API int hfmi_ctx_create(int device, hfmi_ctx** out);
+HFMI_API int hfmi_ctx_destroy(hfmi_ctx* ctx);
 /* adopt an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = own stream */
-int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream);
-int hfmi_ctx_get_stream(hfmi_ctx* ctx, void** hip_stream);
-int hfmi_ctx_synchronize(hfmi_ctx* ctx);
-int hfmi_ctx_device_info(hfmi_ctx* ctx, char* name, int name_len, int* compute_units, int64_t* hbm_bytes);
-int hfmi_ctx_pci_bus_id(hfmi_ctx* ctx, char* buf, int len);   /* "0000:5d:00.0": keys the sysfs clock / power files bench.py reads */
+HFMI_API int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream);
+HFMI_API int hfmi_ctx_get_stream(hfmi_ctx* ctx, void** hip_stream);
+HFMI_API int hfmi_ctx_synchronize(hfmi_ctx* ctx);
+HFMI_API int hfmi_ctx_device_info(hfmi_ctx* ctx, char* name, int name_len, int* compute_units, int64_t* hbm_bytes);
+HFMI_API int hfmi_ctx_pci_bus_id(hfmi_ctx* ctx, char* buf, int len);   /* "0000:5d:00.0": keys the sysfs clock / power files bench.py reads */
 /* HIP-event timer on the context's stream (bench.py measures kernels with it) */
-int hfmi_timer_start(hfmi_ctx* ctx);
-int hfmi_timer_stop(hfmi_ctx* ctx, double* milliseconds); /* synchronises */
+HFMI_API int hfmi_timer_start(hfmi_ctx* ctx);
+HFMI_API int hfmi_timer_stop(hfmi_ctx* ctx, double* milliseconds); /* synchronises */
 
 /* ---------------------------------------------------------------- blocks
  * hippylib MultiVector(vector, nvec) and its copy constructor. */
-int hfmi_block_create(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out); /* zero-filled */
+HFMI_API int hfmi_block_create(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out); /* zero-filled */
 /* wrap device memory owned by the caller (e.g. a torch tensor): ld % 32 == 0, ld >= N,
  * dptr 128-byte aligned; rows N..ld-1 are zeroed by the call. */
-int hfmi_block_wrap(hfmi_ctx* ctx, double* dptr, int64_t N, int nvec, int64_t ld, hfmi_block** out);
+HFMI_API int hfmi_block_wrap(hfmi_ctx* ctx, double* dptr, int64_t N, int nvec, int64_t ld, hfmi_block** out);
 /* view of vectors [first, first+count) of a block (MultiVector.__getitem__) */
-int hfmi_block_view(hfmi_block* parent, int first, int count, hfmi_block** out);
-int hfmi_block_destroy(hfmi_block* b);
-int hfmi_block_info(const hfmi_block* b, int64_t* N, int* nvec, int64_t* ld, double** dptr);
-int hfmi_block_upload(hfmi_block* b, const double* host, int layout);
-int hfmi_block_download(const hfmi_block* b, double* host, int layout);
+HFMI_API int hfmi_block_view(hfmi_block* parent, int first, int count, hfmi_block** out);
+HFMI_API int hfmi_block_destroy(hfmi_block* b);
+HFMI_API int hfmi_block_info(const hfmi_block* b, int64_t* N, int* nvec, int64_t* ld, double** dptr);
+HFMI_API int hfmi_block_upload(hfmi_block* b, const double* host, int layout);
+HFMI_API int hfmi_block_download(const hfmi_block* b, double* host, int layout);
 /* streaming ingest: the reference fills its snapshot / Jacobian blocks sample by sample from host PDE solves
  * (PODProjector.py:343-357; activeSubspaceProjector.py:178-221).  hfmi_block_upload_async copies from PINNED host memory
  * (hfmi_host_alloc_pinned) on the context's ingest stream and returns at once; *ticket names the upload.
  * hfmi_ingest_wait(ticket): the pinned buffer of that upload may be overwritten (host wait).  hfmi_ingest_fence: work
  * enqueued afterwards on the compute stream sees every upload made so far (device-side wait, the host is not blocked).
  * b is normally a view (hfmi_block_view) of the vectors of one sample. */
-int hfmi_host_alloc_pinned(size_t bytes, void** out);
-int hfmi_host_free_pinned(void* p);
-int hfmi_block_upload_async(hfmi_block* b, const double* host_pinned, int layout, int64_t* ticket);
-int hfmi_ingest_wait(hfmi_ctx* ctx, int64_t ticket);
-int hfmi_ingest_fence(hfmi_ctx* ctx);
-int hfmi_block_zero(hfmi_block* b);                                 /* MultiVector.zero */
-int hfmi_block_copy(hfmi_block* dst, const hfmi_block* src);        /* copy constructor */
-int hfmi_block_scale(hfmi_block* b, double alpha);                  /* vector *= alpha */
-int hfmi_block_axpy(hfmi_block* y, double alpha, const hfmi_block* x); /* vector.axpy, all vectors */
-int hfmi_block_norms(const hfmi_block* b, double* host_norms);      /* MultiVector.norm("l2") */
+HFMI_API int hfmi_host_alloc_pinned(size_t bytes, void** out);
+HFMI_API int hfmi_host_free_pinned(void* p);
+HFMI_API int hfmi_block_upload_async(hfmi_block* b, const double* host_pinned, int layout, int64_t* ticket);
+HFMI_API int hfmi_ingest_wait(hfmi_ctx* ctx, int64_t ticket);
+HFMI_API int hfmi_ingest_fence(hfmi_ctx* ctx);
+HFMI_API int hfmi_block_zero(hfmi_block* b);                                 /* MultiVector.zero */
+HFMI_API int hfmi_block_copy(hfmi_block* dst, const hfmi_block* src);        /* copy constructor */
+HFMI_API int hfmi_block_scale(hfmi_block* b, double alpha);                  /* vector *= alpha */
+HFMI_API int hfmi_block_axpy(hfmi_block* y, double alpha, const hfmi_block* x); /* vector.axpy, all vectors */
+HFMI_API int hfmi_block_norms(const hfmi_block* b, double* host_norms);      /* MultiVector.norm("l2") */
 
 /* a1: the probe draw -- hp.parRandom.normal(sigma, Omega)
  * (activeSubspaceProjector.py:433-443,536-551; PODProjector.py:365-374;
@@ -108,24 +118,24 @@ int hfmi_block_norms(const hfmi_block* b, double* host_norms);      /* MultiVect
  * regenerates the same Omega from (seed, stream), replacing collective.bcast.
  * Rows 4g .. 4g+3 of vector j come from the counter (g, j, stream) under the key
  * seed: four 32-bit uniforms -> two radius/angle pairs (oracle/philox.py). */
-int hfmi_randn_fill(hfmi_block* b, uint64_t seed, uint32_t stream, double sigma);
+HFMI_API int hfmi_randn_fill(hfmi_block* b, uint64_t seed, uint32_t stream, double sigma);
 /* the raw 32-bit stream behind it (bit-exact parity test): out[nvec][ceil(N/4)][4] */
-int hfmi_philox_raw(hfmi_block* shape_of, uint64_t seed, uint32_t stream, uint32_t* host_out);
+HFMI_API int hfmi_philox_raw(hfmi_block* shape_of, uint64_t seed, uint32_t stream, uint32_t* host_out);
 
 /* synthetic config-2 input: C (N x N block) = Matern-3/2 covariance
  * sigma^2 (1 + a) exp(-a), a = sqrt(3) d_ij / ell, over the first N nodes of an nx x ny grid on the unit square */
-int hfmi_block_fill_matern32(hfmi_block* C, int nx, int ny, double sigma, double ell);
+HFMI_API int hfmi_block_fill_matern32(hfmi_block* C, int nx, int ny, double sigma, double ell);
 
 /* MultiVector.dot_mv / dot_v: out[i*nvecB + j] = <A_i, B_j>  (row-major nvecA x nvecB) */
-int hfmi_block_dot(const hfmi_block* A, const hfmi_block* B, double* host_out);
+HFMI_API int hfmi_block_dot(const hfmi_block* A, const hfmi_block* B, double* host_out);
 /* MvDSmatMult / MultiVector.reduce: Y = alpha * A * S + beta * Y, S host (nvecA x nvecY) row-major */
-int hfmi_block_gemm_small(const hfmi_block* A, const double* host_S, double alpha, double beta, hfmi_block* Y);
+HFMI_API int hfmi_block_gemm_small(const hfmi_block* A, const double* host_S, double alpha, double beta, hfmi_block* Y);
 
 /* ---------------------------------------------------------------- sparse
  * CSR matrix (prior.M, prior.R; PODProjectorFromData.M_csr, PODProjector.py:695-697). */
-int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* indptr,
+HFMI_API int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* indptr,
                     const int32_t* indices, const double* data, hfmi_csr** out);
-int hfmi_csr_destroy(hfmi_csr* m);
+HFMI_API int hfmi_csr_destroy(hfmi_csr* m);
 
 /* ---------------------------------------------------------------- operators
  * The reference's linear-operator protocol (mult / matMvMult / init_vector;
@@ -133,35 +143,35 @@ int hfmi_csr_destroy(hfmi_csr* m);
 
 /* a2: hp.LowRankOperator(ones/n, snapshots)  -> Y = scale * X (X^T W)
  *     (PODProjector.py:359-361).  X: block, one vector per snapshot. */
-int hfmi_op_snapshot_gram(hfmi_ctx* ctx, const hfmi_block* X, double scale, hfmi_op** out);
+HFMI_API int hfmi_op_snapshot_gram(hfmi_ctx* ctx, const hfmi_block* X, double scale, hfmi_op** out);
 /*     general diagonal: hp.LowRankOperator(d, U) -> Y = U diag(d) (U^T W)  (prior.Hlr as B / B^-1,
  *     activeSubspaceProjector.py:455-459; priorPreconditionedProjector.py:48-55).  host_d: one weight per vector of U. */
-int hfmi_op_low_rank(hfmi_ctx* ctx, const hfmi_block* U, const double* host_d, hfmi_op** out);
+HFMI_API int hfmi_op_low_rank(hfmi_ctx* ctx, const hfmi_block* U, const double* host_d, hfmi_op** out);
 /* a3: sample-averaged Jacobian Gram  Y = scale * sum_i J_i^T Gamma^{-1} J_i W
  *     (MeanJTJfromDataOperator.mult, operatorWrappers.py:95-114; JTJ summed by
  *     SummedListOperator / SeriallySampledJacobianOperator,
  *     activeSubspaceProjector.py:82-95,163-248).  J: block of ndata*q vectors
  *     (row o of sample i is vector i*q+o); gamma_inv host q x q or NULL. */
-int hfmi_op_jtj(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, const double* host_gamma_inv,
+HFMI_API int hfmi_op_jtj(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, const double* host_gamma_inv,
                 double scale, hfmi_op** out);
 /*     output-space counterpart  Y = scale * sum_i J_i J_i^T W  (JJT, jacobian.py:169-193;
  *     activeSubspaceProjector.py:625-673); acts on blocks of length q. */
-int hfmi_op_jjt(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, double scale, hfmi_op** out);
+HFMI_API int hfmi_op_jjt(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, double scale, hfmi_op** out);
 /* a4: explicit dense symmetric operator (config 2 covariance; npToDolfinOperator,
  *     operatorWrappers.py:19-52).  C: block of N vectors of length N (symmetric). */
-int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out);
+HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out);
 /* a4/a9: sparse operator  Y = M W  (prior.M.mult, prior.R.mult; hp.MatMvMult(B, decoder, encoder)) */
-int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out);
+HFMI_API int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out);
 /*     solver object for an SPD CSR matrix: Y = M^{-1} W to a relative residual rel_tol per vector
  *     (prior.Msolver behind hp.Solver2Operator, KLEProjector.py:163-164).  Jacobi-preconditioned
  *     Chebyshev iteration on a row-major copy of the block (one kernel per step, no inner products;
  *     the spectrum of D^-1 M is bracketed once per matrix: Gershgorin + the Lanczos matrix of one
  *     scalar CG run); Jacobi-preconditioned block CG when that bracket is too wide or does not
  *     deliver the tolerance. */
-int hfmi_op_csr_pcg(hfmi_ctx* ctx, const hfmi_csr* M, double rel_tol, int max_iter, hfmi_op** out);
+HFMI_API int hfmi_op_csr_pcg(hfmi_ctx* ctx, const hfmi_csr* M, double rel_tol, int max_iter, hfmi_op** out);
 /*     what the last solve of such an operator did: steps taken, method (0 block CG, 1 Chebyshev, 2 AMG-CG),
  *     and the bracket of the spectrum of D^-1 M in use (0, 0: none) */
-int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* method, double* lmin, double* lmax);
+HFMI_API int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* method, double* lmin, double* lmax);
 /*     algebraic multigrid for an SPD CSR matrix A (hippylib BiLaplacianPrior.Asolver: PETSc CG with amg_method(),
  *     rel_tol 1e-12; prior.Rsolver = A^-1 M A^-1 costs two such solves per apply, activeSubspaceProjector.py:447-453,
  *     KLEProjector.py:163-168).  The smoothed-aggregation hierarchy is built on the host (hippyflow_amd/amg.py) and
@@ -170,42 +180,42 @@ int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* method, double*
  *     add_level: P (n_fine x n_c) from the new level to the current coarsest one, R = P^T (explicit), A_c = P^T A P and
  *       its own Chebyshev interval (unused when it stays the coarsest level);
  *     set_coarse: host n x n row-major inverse of the coarsest matrix (dense solve there); completes the hierarchy. */
-int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, double lmax, int degree, hfmi_amg** out);
-int hfmi_amg_add_level(hfmi_amg* amg, const hfmi_csr* P, const hfmi_csr* R, const hfmi_csr* Ac, double lmin, double lmax);
-int hfmi_amg_set_coarse(hfmi_amg* amg, int n, const double* host_inv);
-int hfmi_amg_info(const hfmi_amg* amg, int* levels, int64_t* rows, int max_levels);
-int hfmi_amg_destroy(hfmi_amg* amg);
+HFMI_API int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, double lmax, int degree, hfmi_amg** out);
+HFMI_API int hfmi_amg_add_level(hfmi_amg* amg, const hfmi_csr* P, const hfmi_csr* R, const hfmi_csr* Ac, double lmin, double lmax);
+HFMI_API int hfmi_amg_set_coarse(hfmi_amg* amg, int n, const double* host_inv);
+HFMI_API int hfmi_amg_info(const hfmi_amg* amg, int* levels, int64_t* rows, int max_levels);
+HFMI_API int hfmi_amg_destroy(hfmi_amg* amg);
 /*     X = V B: one symmetric V-cycle on a block (the preconditioner; a test hook) */
-int hfmi_amg_vcycle(hfmi_amg* amg, const hfmi_block* B, hfmi_block* X);
+HFMI_API int hfmi_amg_vcycle(hfmi_amg* amg, const hfmi_block* B, hfmi_block* X);
 /*     solver operator Y = A^-1 W: block CG with the V-cycle as preconditioner, per-vector recurrences, until every
  *     vector's residual (the true one, checked at the end) is at most rel_tol times its right-hand side.  Errors:
  *     HFMI_ERR_NUMERIC (non-finite input, p.Ap <= 0 or r.z <= 0: not SPD), HFMI_ERR_NOT_CONVERGED (max_iter),
  *     HFMI_ERR_INVALID (shapes); Y is zero-filled on error.  hfmi_op_solver_info: method 2, lmin = lmax = 0.
  *     The operator does not own the hierarchy. */
-int hfmi_op_amg_pcg(hfmi_ctx* ctx, hfmi_amg* amg, double rel_tol, int max_iter, hfmi_op** out);
+HFMI_API int hfmi_op_amg_pcg(hfmi_ctx* ctx, hfmi_amg* amg, double rel_tol, int max_iter, hfmi_op** out);
 /*     Y = c (b (a W))  (MassPreconditionedCovarianceOperator M C M, KLEProjector.py:47-69) */
-int hfmi_op_compose3(hfmi_ctx* ctx, hfmi_op* a, hfmi_op* b, hfmi_op* c, hfmi_op** out);
+HFMI_API int hfmi_op_compose3(hfmi_ctx* ctx, hfmi_op* a, hfmi_op* b, hfmi_op* c, hfmi_op** out);
 /*     host black box (FEniCS PDE solves, sparse LU ...): W and Y in HFMI_LAYOUT_VECTORS
  *     (k, N) host arrays; return non-zero to abort.  This is how any object with the
  *     reference's mult/matMvMult protocol plugs into the device solve. */
 typedef int (*hfmi_host_apply_fn)(void* user, const double* W_host, double* Y_host, int64_t N, int k);
-int hfmi_op_host_callback(hfmi_ctx* ctx, hfmi_host_apply_fn fn, void* user, int64_t N, hfmi_op** out);
+HFMI_API int hfmi_op_host_callback(hfmi_ctx* ctx, hfmi_host_apply_fn fn, void* user, int64_t N, hfmi_op** out);
 /*     For a callback that treats the vectors independently (a sparse-LU / Krylov solve per vector: prior.Rsolver,
  *     activeSubspaceProjector.py:447-450; prior.Msolver): invoke it on slabs of `vectors` vectors.  The slabs go
  *     through pinned double buffers and the device->host copy of slab i+1 and the host->device copy of slab i-1
  *     overlap the host work on slab i.  0 (default) = one call with the whole block. */
-int hfmi_op_host_set_chunk(hfmi_op* op, int vectors);
+HFMI_API int hfmi_op_host_set_chunk(hfmi_op* op, int vectors);
 /*     average of a device operator over the ranks of a communicator is done by the
  *     caller between applies (CollectiveOperator, collectiveOperator.py:31-38): a
  *     post-apply hook called with the result block, e.g. an RCCL all-reduce. */
 typedef int (*hfmi_post_apply_fn)(void* user, hfmi_block* Y);
-int hfmi_op_set_post_apply(hfmi_op* op, hfmi_post_apply_fn fn, void* user);
+HFMI_API int hfmi_op_set_post_apply(hfmi_op* op, hfmi_post_apply_fn fn, void* user);
 /*     the same average done natively: the result block of every apply (and the k x k Rayleigh quotient of the
  *     Gram-form solves) is all-reduced over `comm` on the context's stream, no host code inside the solve.
  *     reduce_op HFMI_REDUCE_SUM | HFMI_REDUCE_AVG; comm NULL detaches. */
-int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_op);
-int hfmi_op_apply(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, int accumulate);
-int hfmi_op_destroy(hfmi_op* op);
+HFMI_API int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_op);
+HFMI_API int hfmi_op_apply(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, int accumulate);
+HFMI_API int hfmi_op_destroy(hfmi_op* op);
 
 /* ---------------------------------------------------------------- communicator
  * The reference's sample-parallel collective (hippyflow/collectives/collective.py): one process per GPU.
@@ -230,23 +240,23 @@ int hfmi_op_destroy(hfmi_op* op);
 #define HFMI_REDUCE_SUM 0
 #define HFMI_REDUCE_AVG 1
 #define HFMI_REDUCE_MAX 2
-int hfmi_comm_unique_id(void* id_out);
-int hfmi_comm_init_rank(hfmi_ctx* ctx_or_null, const void* id, int nranks, int rank, hfmi_comm** out);
-int hfmi_comm_init_from_file(hfmi_ctx* ctx_or_null, const char* path, int nranks, int rank, hfmi_comm** out);
-int hfmi_comm_info(const hfmi_comm* comm, int* nranks, int* rank, int* transport);
+HFMI_API int hfmi_comm_unique_id(void* id_out);
+HFMI_API int hfmi_comm_init_rank(hfmi_ctx* ctx_or_null, const void* id, int nranks, int rank, hfmi_comm** out);
+HFMI_API int hfmi_comm_init_from_file(hfmi_ctx* ctx_or_null, const char* path, int nranks, int rank, hfmi_comm** out);
+HFMI_API int hfmi_comm_info(const hfmi_comm* comm, int* nranks, int* rank, int* transport);
 /* one line of JSON: the transport, WHY it was chosen (e.g. "fell back from rccl: the first ncclAllReduce failed on rank 3;
  * all ranks agreed on p2p"), the RCCL library in use, every rank's PCI bus id, how the p2p path synchronises */
-int hfmi_comm_describe(const hfmi_comm* comm, char* buf, int len);
+HFMI_API int hfmi_comm_describe(const hfmi_comm* comm, char* buf, int len);
 /* the transport decision as a pure function of the table the ranks publish (test hook for the CPU suite): has_device[p],
  * rccl_ok[p], device_ids[p] for p < nranks; *transport = 0 host / 1 rccl / 2 p2p, or -1 for an inconsistent table */
-int hfmi_comm_decide_transport(int nranks, const int* has_device, const int* rccl_ok, const char* const* device_ids,
+HFMI_API int hfmi_comm_decide_transport(int nranks, const int* has_device, const int* rccl_ok, const char* const* device_ids,
                                int force_p2p, int* transport, char* reason, int reason_len);
-int hfmi_comm_barrier(hfmi_comm* comm);               /* drains the context's stream, then meets the other ranks */
-int hfmi_allreduce(hfmi_comm* comm, hfmi_block* Y, int reduce_op);           /* in place, stream-ordered */
-int hfmi_bcast(hfmi_comm* comm, hfmi_block* Y, int root);
-int hfmi_allreduce_host(hfmi_comm* comm, double* v, int64_t count, int reduce_op);   /* in place */
-int hfmi_bcast_host(hfmi_comm* comm, void* v, int64_t nbytes, int root);
-int hfmi_comm_destroy(hfmi_comm* comm);
+HFMI_API int hfmi_comm_barrier(hfmi_comm* comm);               /* drains the context's stream, then meets the other ranks */
+HFMI_API int hfmi_allreduce(hfmi_comm* comm, hfmi_block* Y, int reduce_op);           /* in place, stream-ordered */
+HFMI_API int hfmi_bcast(hfmi_comm* comm, hfmi_block* Y, int root);
+HFMI_API int hfmi_allreduce_host(hfmi_comm* comm, double* v, int64_t count, int reduce_op);   /* in place */
+HFMI_API int hfmi_bcast_host(hfmi_comm* comm, void* v, int64_t nbytes, int root);
+HFMI_API int hfmi_comm_destroy(hfmi_comm* comm);
 
 /* ---------------------------------------------------------------- QR (a7)
  * MultiVector.orthogonalize() / Borthogonalize(B): thin QR with Q^T B Q = I,
@@ -258,7 +268,7 @@ int hfmi_comm_destroy(hfmi_comm* comm);
 #define HFMI_QR_CHOL 0
 #define HFMI_QR_MGS 1
 #define HFMI_QR_AUTO 2 /* CHOL, falling back to MGS on breakdown */
-int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes);
+HFMI_API int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes);
 
 /* ---------------------------------------------------------------- Rayleigh-Ritz (a8)
  * np.linalg.eigh(T) + descending sort: symmetric k x k (host, row-major; the
@@ -276,23 +286,23 @@ int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int
  * rounds 2-4 (hfmi_eig_large.hip; up to 4096). */
 #define HFMI_EIG_SORT_ABS 1
 #define HFMI_EIG_JACOBI 2
-int hfmi_sym_eig_small(hfmi_ctx* ctx, const double* host_T, int k, int sort_by_abs, double* host_d,
+HFMI_API int hfmi_sym_eig_small(hfmi_ctx* ctx, const double* host_T, int k, int sort_by_abs, double* host_d,
                        double* host_V);
 /* The same with only the nvec leading eigenvectors (in output order) returned; host_V is k x nvec row-major.  What the
  * deterministic POD uses of la.eigh(G): U[:, :u_rank] (PODProjector.py:821-826).  Beyond 256 the back-transformation and
  * the read-back run over nvec columns instead of k. */
-int hfmi_sym_eig_leading(hfmi_ctx* ctx, const double* host_T, int k, int sort_by_abs, int nvec, double* host_d,
+HFMI_API int hfmi_sym_eig_leading(hfmi_ctx* ctx, const double* host_T, int k, int sort_by_abs, int nvec, double* host_d,
                          double* host_V);
 /* la.eigh(X^T (M X)) of the deterministic POD in one call (PODProjector.py:818-826: UtMU = u_data @ M @ u_data.T, eigh,
  * U[:, :u_rank]): the n x n Gram matrix of two blocks of n vectors is formed on the device and handed to the
  * eigensolver there; host_d receives the n eigenvalues, host_V the nvec leading eigenvectors (n x nvec row-major). */
-int hfmi_block_gram_eig(const hfmi_block* A, const hfmi_block* B, int sort_by_abs, int nvec, double* host_d,
+HFMI_API int hfmi_block_gram_eig(const hfmi_block* A, const hfmi_block* B, int sort_by_abs, int nvec, double* host_d,
                         double* host_V);
 
 /* np.linalg.svd(R) of the small factor inside hp.accuracyEnhancedSVD (activeSubspaceProjector.py:813-834,1026):
  * R (host, k x k row-major) = U diag(sigma) V^T, sigma descending; U, V row-major k x k (columns = vectors).
  * One-workgroup one-sided Jacobi in LDS (full relative accuracy of small singular values). */
-int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double* host_sigma, double* host_U, double* host_V);
+HFMI_API int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double* host_sigma, double* host_U, double* host_V);
 
 /* ---------------------------------------------------------------- full solves (a5, a6)
  * hp.doublePass(A, Omega, r, s) / hp.doublePassG(A, B, Binv, Omega, r, s):
@@ -303,9 +313,9 @@ int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double* host_sigm
  * k x k Rayleigh-Ritz problem;  bit 2 = form T = (A Q)^T Q literally (by default, for
  * operators of Gram form A = scale X^T Gamma X the same matrix is formed as scale (X Q)^T Gamma (X Q), which skips
  * the second N x k block product and shrinks the rank average of that pass to k x k). */
-int hfmi_double_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
+HFMI_API int hfmi_double_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
                      hfmi_block* U);
-int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s,
+HFMI_API int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s,
                        int flags, double* host_d, hfmi_block* U);
 
 /* hp.singlePass(A, Omega, r, s) / hp.singlePassG(A, B, Binv, Omega, r, s) (hippylib randomizedEigensolver): the same
@@ -316,46 +326,46 @@ int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* 
  * A singular or non-finite Wt (rank-deficient sketch, e.g. dependent probe vectors) is HFMI_ERR_NUMERIC, never NaN
  * eigenpairs (hippylib's np.linalg.solve raises LinAlgError there).  A rank average attached to A applies to every
  * application, as in the double pass. */
-int hfmi_single_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U);
-int hfmi_single_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
+HFMI_API int hfmi_single_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U);
+HFMI_API int hfmi_single_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
                        double* host_d, hfmi_block* U);
 /* The single-pass core on a sketch the caller already holds (the Wt / Zt / eigh steps of hp.singlePass[G]):
  * P and Y (N x k) as above, none modified; Ybar and B both NULL for the standard problem, both given for the
  * generalized one (Y = B^-1 Ybar).  Used by streamed sketches, where Y = A Omega is summed while the samples arrive. */
-int hfmi_sketch_eig(const hfmi_block* P, const hfmi_block* Y, const hfmi_block* Ybar, hfmi_op* B, int r, int flags,
+HFMI_API int hfmi_sketch_eig(const hfmi_block* P, const hfmi_block* Y, const hfmi_block* Ybar, hfmi_op* B, int r, int flags,
                     double* host_d, hfmi_block* U);
 /* np.linalg.solve(W, Z) inside hp.singlePass[G], on the device (kernel tests): W, Z, X host row-major m x m, m <= 256.
  * HFMI_ERR_NUMERIC for a singular W (min |pivot| <= m eps max |pivot|) or non-finite input. */
-int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X);
+HFMI_API int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X);
 
 /* ---------------------------------------------------------------- instrumentation
  * Kernel-level entry points used by bench.py / the parity tests:
  *   C (nvecA x nvecB, device partial-summed, returned on host) = A^T B with an explicit split count
  *   (0 = library default) and the average kernel time of `reps` back-to-back launches. */
-int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, int nsplit, int reps, double* host_C,
+HFMI_API int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, int nsplit, int reps, double* host_C,
                          double* avg_ms);
-int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfmi_block* Y, int reps, double* avg_ms);
+HFMI_API int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfmi_block* Y, int reps, double* avg_ms);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */
-int hfmi_dense_matmul(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, const double* host_A, const double* host_B, double* host_C);
+HFMI_API int hfmi_dense_matmul(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, const double* host_A, const double* host_B, double* host_C);
 /* the general fp64 MFMA product inside the whole-GPU eigensolver (trailing rank-2k updates, Q S of the merges, block reflectors of
  * the back-transformation; la.eigh(G), PODProjector.py:812-833): C (M x N) = op(A) op(B), column-major host operands with their
  * natural leading dimensions, average kernel time of `reps` launches; host_C may be null */
-int hfmi_bench_dgemm(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, int reps, const double* host_A, const double* host_B,
+HFMI_API int hfmi_bench_dgemm(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, int reps, const double* host_A, const double* host_B,
                      double* host_C, double* avg_ms);
 /* fp64 MFMA / fp64 FMA / HBM-copy micro-benchmarks (peak denominators measured in the same job) */
-int hfmi_bench_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* fma_f64_tflops, double* hbm_copy_gbs);
+HFMI_API int hfmi_bench_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* fma_f64_tflops, double* hbm_copy_gbs);
 /* the same MFMA loop with a copy kernel streaming HBM beside it on a second stream: the ceiling of the power-limited regime the
  * big contractions run in (bench.py: roofline.frac_of_in_job_loaded_peak) */
-int hfmi_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_f64_tflops, double* hbm_copy_gbs);
+HFMI_API int hfmi_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_f64_tflops, double* hbm_copy_gbs);
 /* the MFMA loop on full-mantissa Gaussian operands rotated through the registers every iteration -- alone, and beside the streaming
  * copy: the ceiling the contractions can reach on the solve's data under the power limit (SURVEY section 8d "fp64 MFMA
  * micro-benchmark run in the same job"; bench.py: roofline.frac_of_in_job_random_operand_peak[_while_streaming]) */
 /* read-only 16-byte stream over 2 GiB: the HBM rate a contraction that only reads its big operand can reach (the copy of
  * hfmi_bench_peaks also writes); bench.py: roofline.frac_of_in_job_read_peak for the HBM-bound kernel-point shapes */
-int hfmi_bench_hbm_read(hfmi_ctx* ctx, double* hbm_read_gbs);
-int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* mfma_f64_tflops_while_streaming, double* hbm_copy_gbs);
+HFMI_API int hfmi_bench_hbm_read(hfmi_ctx* ctx, double* hbm_read_gbs);
+HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* mfma_f64_tflops_while_streaming, double* hbm_copy_gbs);
 /* per-launch HIP-event timing over a region of ordinary calls (bench.py's roofline numbers come from the
  * timed region itself): between begin and end every tsgemm_tn / tsgemm_nn launch is bracketed by events on
  * the context's stream.  end() synchronises and returns one record per distinct (kernel, shape):
@@ -376,7 +386,7 @@ int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* mfma
  * least 2 Gflop only (each record is a pair of stream events, 2-4 us of idle GPU between dependent kernels: scripts/prof_level_ab.py);
  * ("comm_panels", 0..8) row panels of an operator application whose
  * rank reduction overlaps the rest of the product (0 / 1 = one all-reduce after the product; default 4). */
-int hfmi_tuning_set(const char* key, int value);
+HFMI_API int hfmi_tuning_set(const char* key, int value);
 /* phases of hfmi_double_pass[_g], accumulated between hfmi_profile_begin and hfmi_profile_end (milliseconds, summed
  * over the solves in the region; device phases by HIP events on the context's stream, the HOST_* legs by the host's
  * wall clock -- they are part of the phase that called the host operator, normally BINV) */
@@ -393,9 +403,9 @@ int hfmi_tuning_set(const char* key, int value);
 #define HFMI_PHASE_ALLREDUCE_AUX 10 /* rank reductions of row panels on the auxiliary stream, overlapped with the product that
                                      * makes the next panel; HFMI_PHASE_ALLREDUCE then holds only what the main stream waited */
 #define HFMI_PHASE_COUNT 11
-int hfmi_profile_phases(hfmi_ctx* ctx, double* ms_out /* HFMI_PHASE_COUNT */);   /* after hfmi_profile_end */
-int hfmi_profile_begin(hfmi_ctx* ctx);
-int hfmi_profile_end(hfmi_ctx* ctx, int max_groups, int* ngroups, int* kind, int64_t* shape, double* ms,
+HFMI_API int hfmi_profile_phases(hfmi_ctx* ctx, double* ms_out /* HFMI_PHASE_COUNT */);   /* after hfmi_profile_end */
+HFMI_API int hfmi_profile_begin(hfmi_ctx* ctx);
+HFMI_API int hfmi_profile_end(hfmi_ctx* ctx, int max_groups, int* ngroups, int* kind, int64_t* shape, double* ms,
                      int64_t* launches, double* flops_per_launch, double* bytes_per_launch);
 
 #ifdef __cplusplus

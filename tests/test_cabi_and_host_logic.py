@@ -18,6 +18,27 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(hfmi_[a-z0-9_]+)\s*\(", text)))
 
 
+# what the finished library defines in its dynamic symbol table besides the declared entry points: nothing (the export list
+# hippyflow_amd/libhfmi.map keeps even the toolchain's __hip_cuid_<hash> markers local); a toolchain symbol that a later
+# linker adds goes here by its exact prefix
+TOOLCHAIN_SYMBOL_PREFIXES = ()
+
+
+def _defined_dynamic_symbols(lib_path):
+    """names the library DEFINES in its dynamic symbol table (binutils nm, or llvm-readelf of the ROCm toolchain)"""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm")
+    if nm:
+        out = subprocess.run([nm, "-D", "--defined-only", lib_path], check=True, stdout=subprocess.PIPE, text=True).stdout
+        return sorted(line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip())
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    readelf = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "llvm-readelf")
+    out = subprocess.run([readelf, "--dyn-syms", "-W", lib_path], check=True, stdout=subprocess.PIPE, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    return sorted(r[7].split("@")[0] for r in rows if len(r) >= 8 and r[0].rstrip(":").isdigit() and r[6] != "UND")
+
+
 def test_library_exports_every_declared_symbol():
     lib_path = os.path.join(ROOT, "hippyflow_amd", "libhfmi.so")
     if not os.path.exists(lib_path):
@@ -33,6 +54,12 @@ def test_library_exports_every_declared_symbol():
     assert bound == set(declared), (bound ^ set(declared))
     lib.hfmi_version.restype = ctypes.c_int
     assert lib.hfmi_version() == 100
+    # ... and exports nothing else: no launcher, helper, kernel handle or template instantiation (no C++-mangled name at all)
+    defined = _defined_dynamic_symbols(lib_path)
+    assert set(declared) <= set(defined), sorted(set(declared) - set(defined))
+    extra = [s for s in defined if s not in set(declared) and not s.startswith(TOOLCHAIN_SYMBOL_PREFIXES)]
+    assert not extra, "%d undeclared symbols exported, e.g. %s" % (len(extra), extra[:8])
+    assert not [s for s in defined if s.startswith("_Z")]
 
 
 def test_no_cpu_fallback():

@@ -98,7 +98,7 @@ def test_ranks_sharing_the_gpu_p2p_transport(tmp_path, world, sync):
 
 def test_row_panel_reduction_is_bit_identical_and_overlapped():
     """Round 3: the rank reduction of an operator application is issued panel by panel on the auxiliary stream while the rest
-    of the product is computed (hfmi_api.hip panel_reduce_hook).  Same arithmetic per element: a solve with panels equals the
+    of the product is computed (hfmi_op.hip panel_reduce_hook).  Same arithmetic per element: a solve with panels equals the
     solve with ONE all-reduce after the product bit for bit, and the profile shows collective work off the main stream.
     Shape: large enough for two rounds of row tiles and a small matrix too big for the LDS-resident kernel (what config 4 is)."""
     import ctypes as C
