@@ -14,6 +14,7 @@ LAYOUT_DENSE = 1
 QR_CHOL, QR_MGS, QR_AUTO = 0, 1, 2
 UNIQUE_ID_BYTES = 256
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
+KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
 
 HOST_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int)
 POST_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
@@ -70,6 +71,7 @@ SIGNATURES = {
     "hfmi_op_jtj": [_P, _P, C.c_int, C.c_int, _P, C.c_double, _PP],
     "hfmi_op_jjt": [_P, _P, C.c_int, C.c_int, C.c_double, _PP],
     "hfmi_op_dense_sym": [_P, _P, _PP],
+    "hfmi_op_kernel_cov": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
     "hfmi_op_csr": [_P, _P, _PP],
     "hfmi_op_csr_pcg": [_P, _P, C.c_double, C.c_int, _PP],
     "hfmi_op_solver_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)],

@@ -195,7 +195,7 @@ struct hfmi_csr {
   int cheb_state;
 };
 
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG };
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV };
 
 struct hfmi_op {
   hfmi_ctx* ctx;
@@ -212,6 +212,11 @@ struct hfmi_op {
   int last_method;        // sparse solver: 0 = block CG, 1 = Chebyshev, 2 = AMG-preconditioned CG (hfmi_op_solver_info)
   hfmi_amg* amg;          // OP_AMG_PCG: the multigrid hierarchy (not owned)
   hfmi_op *a, *b, *c;
+  // OP_KERNEL_COV: the point coordinates on the device, one array of kc_N doubles per dimension (owned), and the kernel
+  double* kc_x;
+  int64_t kc_N;
+  int kc_d, kc_family;
+  double kc_sigma, kc_ell, kc_nugget;
   hfmi_host_apply_fn host_fn;
   void* host_user;
   int64_t host_N;
@@ -258,6 +263,10 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_
 // Y (N x r) = alpha * A (N x m) * S (m x r, device row-major, ld = lds, zero padded to 16 cols) + beta * Y
 int launch_tsgemm_nn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds, int r,
                      double alpha, double beta, double* Y, int64_t ldy, int64_t N);
+
+// Y (+)= C W with C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij evaluated in registers (hfmi_kcov.hip); x: d arrays of N doubles
+int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

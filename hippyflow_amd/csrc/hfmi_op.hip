@@ -85,6 +85,37 @@ extern "C" int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** o
   *out = op;
   return HFMI_OK;
 }
+extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                                  double nugget, hfmi_op** out) {
+  if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (N < 1) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: needs at least one point (N = %lld)", (long long)N);
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: points have 1, 2 or 3 coordinates, got d = %d", d);
+  if (family < HFMI_KERNEL_MATERN12 || family > HFMI_KERNEL_SQEXP) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: unknown kernel family %d", family);
+  if (!(ell > 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: correlation length must be positive");
+  if (!(nugget >= 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: nugget must not be negative");
+  hfmi_op* op = op_new(ctx, OP_KERNEL_COV);
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  // one array per coordinate on the device (the kernel reads x_c[j] for runs of consecutive j)
+  std::vector<double> soa((size_t)N * d);
+  for (int64_t i = 0; i < N; ++i)
+    for (int c = 0; c < d; ++c) soa[(size_t)c * N + i] = host_points[(size_t)i * d + c];
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&op->kc_x, soa.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(op->kc_x, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (op->kc_x) (void)hipFree(op->kc_x);
+    delete op;
+    HFMI_FAIL(HFMI_ERR_HIP, "op_kernel_cov: %s", hipGetErrorString(e));
+  }
+  op->kc_N = N;
+  op->kc_d = d;
+  op->kc_family = family;
+  op->kc_sigma = sigma;
+  op->kc_ell = ell;
+  op->kc_nugget = nugget;
+  *out = op;
+  return HFMI_OK;
+}
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
   if (!ctx || !M || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   hfmi_op* op = op_new(ctx, OP_CSR);
@@ -171,10 +202,11 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
   if (!op) return HFMI_OK;
-  if (op->gamma_inv || op->weights) {
+  if (op->gamma_inv || op->weights || op->kc_x) {
     (void)hipStreamSynchronize(op->ctx->stream);
     if (op->gamma_inv) (void)hipFree(op->gamma_inv);
     if (op->weights) (void)hipFree(op->weights);
+    if (op->kc_x) (void)hipFree(op->kc_x);
   }
   delete op;
   return HFMI_OK;
@@ -369,6 +401,13 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       if (C.N != W->N) HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld", (long long)C.N, (long long)W->N);
       // Y = C W with C symmetric: Y[t][j] = <C_t, W_j>  (column-major output)
       return launch_tsgemm_tn(ctx, C.p, C.ld, C.nvec, W->p, W->ld, k, C.N, 1.0, beta, Y->p, 1, Y->ld, 0);
+    }
+    case OP_KERNEL_COV: {
+      if (op->kc_N != W->N || op->kc_N != Y->N)
+        HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)op->kc_N, (long long)W->N, (long long)Y->N);
+      // Y (+)= C W: the kernel adds into Y itself
+      return launch_kernel_cov(ctx, op->kc_x, op->kc_N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget, W->p, W->ld,
+                               Y->p, Y->ld, k, beta != 0.0);
     }
     case OP_CSR: {
       if (op->csr->ncols != W->N || op->csr->nrows != Y->N) HFMI_FAIL(HFMI_ERR_INVALID, "csr operator / block shape mismatch");

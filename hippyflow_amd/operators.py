@@ -9,6 +9,7 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``MeanJTJfromDataOperator``                     modeling/operatorWrappers.py:55-121
 * ``MeanJJTfromDataOperator``                     JJT summed/averaged: modeling/jacobian.py:169-193, activeSubspaceProjector.py:640-645
 * ``npToDeviceOperator``                          npToDolfinOperator, modeling/operatorWrappers.py:19-52 (symmetric case)
+* ``KernelCovarianceOperator``                    the same role for a kernel covariance given by node coordinates, never assembled
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
 * ``CsrAMGSolver`` / ``BiLaplacianRsolver``       hippylib BiLaplacianPrior.Asolver (CG + AMG) and prior.Rsolver = A^-1 M A^-1
                                                   (activeSubspaceProjector.py:447-453, KLEProjector.py:163-168)
@@ -196,6 +197,67 @@ class npToDeviceOperator(DeviceOperator):
         super().__init__(ctx or block.ctx, block.size())
         self.matrix = block
         L.call("hfmi_op_dense_sym", self.ctx.handle, block.handle, C.byref(self._op))
+
+
+def _points_array(points):
+    """(N, d) C-ordered float64 array of node coordinates (a 1-D array is N points on a line)."""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim == 1:
+        pts = pts[:, None]
+    if pts.ndim != 2:
+        raise ValueError("points must be an (N, d) array, got shape %r" % (pts.shape,))
+    return L.as_f64(pts)
+
+
+def kernel_cov_host(points, family, sigma, ell, nugget=0.0, rows=None):
+    """Dense host evaluation of the covariance ``KernelCovarianceOperator`` applies: C_ij = sigma^2 phi(|x_i - x_j| / ell)
+    + nugget delta_ij (the delta is on the point INDEX), all rows or the rows ``rows``.  With r the scaled distance:
+    'matern12' exp(-r); 'matern32' (1 + a) exp(-a), a = sqrt(3) r; 'matern52' (1 + a + a^2/3) exp(-a), a = sqrt(5) r;
+    'sqexp' exp(-r^2 / 2).  What tests and users compare the device operator against."""
+    if family not in L.KERNEL_FAMILIES:
+        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+    pts = _points_array(points)
+    r = np.arange(pts.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64)
+    d2 = np.zeros((len(r), pts.shape[0]))
+    for c in range(pts.shape[1]):
+        d2 += (pts[r, c][:, None] - pts[None, :, c]) ** 2
+    dist = np.sqrt(d2)
+    if family == "matern12":
+        C = np.exp(-dist / ell)
+    elif family == "matern32":
+        a = np.sqrt(3.0) * dist / ell
+        C = (1.0 + a) * np.exp(-a)
+    elif family == "matern52":
+        a = np.sqrt(5.0) * dist / ell
+        C = (1.0 + a + a * a / 3.0) * np.exp(-a)
+    else:
+        C = np.exp(-0.5 * (dist / ell) ** 2)
+    C = sigma ** 2 * C
+    if nugget:
+        C[np.arange(len(r)), r] += nugget
+    return C
+
+
+class KernelCovarianceOperator(DeviceOperator):
+    """Kernel covariance over scattered points WITHOUT the N x N matrix: y = C x with C_ij = sigma^2 phi(|x_i - x_j| / ell)
+    + nugget delta_ij, its entries evaluated inside the apply (hfmi_kcov.hip) and fed to the fp64 matrix cores.  ``points`` are
+    the (N, d) node coordinates of the parameter's mesh or point cloud, d = 1, 2 or 3; ``family`` as in ``kernel_cov_host``.
+    A drop-in ``prior.C`` for ``KLEProjector`` (and any place an explicit covariance went through ``npToDeviceOperator``):
+    memory is 8 N d bytes, so N is bounded by time (2 N^2 k flops per apply), not by HBM."""
+
+    def __init__(self, points, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None):
+        if family not in L.KERNEL_FAMILIES:
+            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        pts = _points_array(points)
+        super().__init__(ctx, pts.shape[0])
+        self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
+        self.points = pts
+        L.call("hfmi_op_kernel_cov", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
+               self.sigma, self.ell, self.nugget, C.byref(self._op))
+
+    def to_dense(self, rows=None):
+        """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows)
 
 
 class _Csr:

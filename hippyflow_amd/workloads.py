@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib as L
 from .multivector import MultiVector, MvDSmatMult
-from .operators import CsrOperator, MeanJTJfromDataOperator, SnapshotGramOperator, npToDeviceOperator
+from .operators import CsrOperator, KernelCovarianceOperator, MeanJTJfromDataOperator, SnapshotGramOperator, npToDeviceOperator
 
 
 class Workload:
@@ -388,6 +388,27 @@ def kle_matern_workload(nx, ny, N=None, sigma=1.0, ell=0.1, ctx=None):
     matern32_covariance(wl.C, nx, ny, sigma, ell)
     wl.M = grid_mass_matrix(nx, ny)[:N, :N].tocsr()
     wl.C_operator = npToDeviceOperator(wl.C)
+    wl.M_operator = CsrOperator(wl.M, ctx=ctx)
+    return wl
+
+
+def grid_points(N, nx, ny):
+    """Coordinates (N, 2) of the first N nodes (row-major numbering) of an nx x ny grid on the unit square: the nodes
+    ``matern32_host`` and ``hfmi_block_fill_matern32`` number."""
+    idx = np.arange(int(N))
+    return np.stack([(idx % nx) / (nx - 1.0), (idx // nx) / (ny - 1.0)], axis=1)
+
+
+def kle_kernel_workload(nx, ny, N=None, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None):
+    """Config 2's recipe with the covariance matrix-free: the same grid nodes and P1 mass matrix as ``kle_matern_workload``, the
+    covariance a ``KernelCovarianceOperator`` over the node coordinates instead of an N x N block (16 N bytes instead of 8 N^2)."""
+    ctx = ctx or L.Context.default()
+    N = int(nx * ny if N is None else N)
+    wl = Workload()
+    wl.N, wl.nx, wl.ny, wl.sigma, wl.ell, wl.family, wl.nugget = N, nx, ny, sigma, ell, family, nugget
+    wl.points = grid_points(N, nx, ny)
+    wl.M = grid_mass_matrix(nx, ny)[:N, :N].tocsr()
+    wl.C_operator = KernelCovarianceOperator(wl.points, family=family, sigma=sigma, ell=ell, nugget=nugget, ctx=ctx)
     wl.M_operator = CsrOperator(wl.M, ctx=ctx)
     return wl
 

@@ -160,6 +160,19 @@ HFMI_API int hfmi_op_jjt(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, d
 /* a4: explicit dense symmetric operator (config 2 covariance; npToDolfinOperator,
  *     operatorWrappers.py:19-52).  C: block of N vectors of length N (symmetric). */
 HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out);
+/*     the same covariance without the N x N block: C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij over N points with
+ *     d = 1, 2 or 3 coordinates each (host_points: N x d row-major, copied to the device), entries evaluated inside the apply
+ *     (hfmi_kcov.hip) -- 16 N k bytes move per apply instead of 8 N^2, so N is not capped by HBM.  With r = |x_i - x_j| / ell:
+ *       HFMI_KERNEL_MATERN12  exp(-a), a = r              HFMI_KERNEL_MATERN32  (1 + a) exp(-a), a = sqrt(3) r
+ *       HFMI_KERNEL_MATERN52  (1 + a + a^2/3) exp(-a), a = sqrt(5) r              HFMI_KERNEL_SQEXP  exp(-r^2 / 2)
+ *     HFMI_ERR_INVALID: d outside 1..3, ell <= 0, nugget < 0, unknown family, N < 1; at apply, blocks of another length.
+ *     The summation order is fixed: two applies of the same input are bit-identical. */
+#define HFMI_KERNEL_MATERN12 0
+#define HFMI_KERNEL_MATERN32 1
+#define HFMI_KERNEL_MATERN52 2
+#define HFMI_KERNEL_SQEXP 3
+HFMI_API int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                       double nugget, hfmi_op** out);
 /* a4/a9: sparse operator  Y = M W  (prior.M.mult, prior.R.mult; hp.MatMvMult(B, decoder, encoder)) */
 HFMI_API int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out);
 /*     solver object for an SPD CSR matrix: Y = M^{-1} W to a relative residual rel_tol per vector
