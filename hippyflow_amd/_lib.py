@@ -115,6 +115,9 @@ SIGNATURES = {
     "hfmi_small_solve": [_P, _P, _P, C.c_int, _P],
     "hfmi_bench_tsgemm_tn": [_P, _P, C.c_int, C.c_int, _P, _D],
     "hfmi_bench_tsgemm_nn": [_P, _P, _P, C.c_int, _D],
+    "hfmi_test_tsgemm_tn": [_P, _P, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P],
+    "hfmi_plan_clear": [_P],
+    "hfmi_plan_read": [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],
     "hfmi_bench_loaded_peak": [_P, _D, _D],
     "hfmi_bench_random_peaks": [_P, _D, _D, _D],

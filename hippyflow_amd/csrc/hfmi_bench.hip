@@ -28,6 +28,26 @@ extern "C" int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, in
   }
   return HFMI_OK;
 }
+// launch_tsgemm_tn with its whole argument list on a device copy of the caller's array (the instance sweep of the tests)
+extern "C" int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, double scale, double beta, int colmajor, int ldc, int nsplit,
+                                   double* host_C) {
+  if (!A || !B || !host_C) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (A->N != B->N) HFMI_FAIL(HFMI_ERR_INVALID, "test_tsgemm_tn: vector lengths differ");
+  if (A->ctx != B->ctx) HFMI_FAIL(HFMI_ERR_INVALID, "test_tsgemm_tn: blocks of different contexts");
+  const int m = A->nvec, k = B->nvec;
+  const int fast = colmajor ? m : k, slow = colmajor ? k : m;
+  if (ldc < fast || (colmajor && ldc == 1)) HFMI_FAIL(HFMI_ERR_INVALID, "test_tsgemm_tn: ldc %d too small for %d x %d", ldc, m, k);
+  if (nsplit < 0) HFMI_FAIL(HFMI_ERR_INVALID, "test_tsgemm_tn: negative split count");
+  hfmi_ctx* ctx = A->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t count = (size_t)slow * ldc;
+  void* dev = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, count * sizeof(double), &dev));
+  HIP_TRY(hipMemcpyAsync(dev, host_C, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HFMI_TRY(launch_tsgemm_tn(ctx, A->p, A->ld, m, B->p, B->ld, k, A->N, scale, beta, (double*)dev, colmajor ? 1 : ldc, colmajor ? ldc : 1,
+                            nsplit));
+  return read_back(ctx, (const double*)dev, count, host_C);
+}
 extern "C" int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfmi_block* Y, int reps, double* avg_ms) {
   if (!A || !host_S || !Y) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   hfmi_ctx* ctx = A->ctx;

@@ -191,6 +191,7 @@ extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
   c->nn_hook_panels = 0;
   c->nn_hook_called = false;
   c->nn_upper_hint = false;
+  c->plan_count = 0;
   HIP_TRY(hipMalloc((void**)&c->small, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double)));
   HIP_TRY(hipMemsetAsync(c->small, 0, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double), c->stream));
   HIP_TRY(hipMalloc((void**)&c->status_dev, 2 * sizeof(hfmi_status_words)));      // [1]: a factorisation taken on trust (qr_chol)
@@ -237,6 +238,23 @@ extern "C" int hfmi_ctx_destroy(hfmi_ctx* ctx) {
   (void)hipStreamDestroy(ctx->aux_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_plan_clear(hfmi_ctx* ctx) {
+  if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
+  ctx->plan_count = 0;
+  return HFMI_OK;
+}
+extern "C" int hfmi_plan_read(hfmi_ctx* ctx, int max_records, int* words, int* nrecords, int* total) {
+  if (!ctx || !nrecords || (max_records > 0 && !words)) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  int64_t n = ctx->plan_count < HFMI_PLAN_RING ? ctx->plan_count : HFMI_PLAN_RING;
+  if (n > max_records) n = max_records < 0 ? 0 : max_records;
+  const int64_t first = ctx->plan_count - n;     // the n newest, oldest first
+  for (int64_t i = 0; i < n; ++i)
+    memcpy(words + i * HFMI_PLAN_WORDS, ctx->plan_ring[(first + i) % HFMI_PLAN_RING], sizeof(int) * HFMI_PLAN_WORDS);
+  *nrecords = (int)n;
+  if (total) *total = (int)(ctx->plan_count > 0x7fffffff ? 0x7fffffff : ctx->plan_count);
   return HFMI_OK;
 }
 

@@ -392,21 +392,23 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_
     if (cfast == 1 && aligned && (int64_t)fastn * slown >= 65536) {
       int64_t rowlen, prow = inner_ld, kpad = 0;
       int nrows, kreal = 0;
-      if (!tr && rs == inner_ld) {          // rows are back to back on both sides: one long row, pad columns zeroed
+      const bool long_row = !tr && rs == inner_ld;
+      if (long_row) {                       // rows are back to back on both sides: one long row, pad columns zeroed
         rowlen = (int64_t)m * inner_ld;
         nrows = 1;
         kpad = inner_ld;
         kreal = k;
       } else {
-        rowlen = fastn & ~1;                // an odd tail element goes through the scalar kernel below
+        rowlen = fastn & ~1;                // an odd fast extent: not this kernel, the scalar kernels below take the whole reduction
         nrows = slown;
         kpad = kreal = 0;
       }
-      if (rowlen == fastn || nrows == 1) {
+      if (rowlen == fastn || long_row) {    // (a single row of odd length is no long row: its last element needs the scalar kernel)
         dim3 vgrid((unsigned)((rowlen / 2 + 255) / 256), (unsigned)(nrows < 32768 ? nrows : 32768));
         hipLaunchKernelGGL(k_reduce_vec, vgrid, dim3(256), 0, ctx->stream, part, nsplit, pstride, prow, rowlen, nrows, kpad, kreal, scale,
                            beta, C, crow);
         HIP_TRY(hipGetLastError());
+        plan_record(ctx, HFMI_PLAN_REDUCE, {long_row ? HFMI_REDUCE_VEC_LONG : HFMI_REDUCE_VEC_ROWS, 0, nsplit, tr ? 1 : 0, m, k});
         return HFMI_OK;
       }
     }
@@ -421,6 +423,7 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_
       hipLaunchKernelGGL(k_reduce_flat<16>, fgrid, dim3(64, 16), 0, ctx->stream, part, nsplit, pstride, total, inner_ld, k,
                          scale, beta, C);
     HIP_TRY(hipGetLastError());
+    plan_record(ctx, HFMI_PLAN_REDUCE, {HFMI_REDUCE_FLAT, nsplit <= 32 ? 4 : 16, nsplit, 0, m, k});
     return HFMI_OK;
   }
   dim3 grid((fastn + 63) / 64, slown < 32768 ? slown : 32768);
@@ -431,6 +434,7 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_
     hipLaunchKernelGGL(k_reduce_partials<16>, grid, dim3(64, 16), 0, ctx->stream, part, nsplit, pstride, inner_ld, tr ? 1 : 0, m,
                        k, scale, beta, C, rs, cs);
   HIP_TRY(hipGetLastError());
+  plan_record(ctx, HFMI_PLAN_REDUCE, {HFMI_REDUCE_PARTIALS, nsplit <= 32 ? 4 : 16, nsplit, tr ? 1 : 0, m, k});
   return HFMI_OK;
 }
 
@@ -499,6 +503,8 @@ static int tn_launch_one(hfmi_ctx* ctx, const double* A, int64_t lda, int m, con
   hipLaunchKernelGGL(kern, dim3(nrb * nsplit + o.tail_nrb * o.tail_nsplit), dim3(WAVES * 64), shmem, ctx->stream, A, lda, m, B, ldb, k,
                      N, chunk, nrb, nsplit, out, si, sj, (int64_t)mpad * kpad, o.direct ? 1 : 0, g_probe, tail);
   HIP_TRY(hipGetLastError());
+  plan_record(ctx, HFMI_PLAN_TN, {MT, NT, WAVES, TR ? 1 : 0, R4, nrb * nsplit + o.tail_nrb * o.tail_nsplit, nrb, nsplit, o.direct ? 1 : 0,
+                                  o.tail_nrb, o.tail_nsplit});
   return HFMI_OK;
 }
 

@@ -580,6 +580,10 @@ static int nn_launch_inst(hfmi_ctx* ctx, const double* A, int64_t lda, int m, co
   }
   const int tail_tiles = ntiles - full_tiles;
   dim3 block(WAVES * 64);
+  // plan record of one launch: tile height, the split, whole and split tiles it covers, grid
+  auto rec = [&](int tt, int ms, int full, int tl) {
+    plan_record(ctx, HFMI_PLAN_NN, {tt, NT, WAVES, r4, 0, ms, full, tl, full + tl * ms});
+  };
   auto reduce_tail = [&]() -> int {
     const int64_t row0 = (int64_t)full_tiles * tile_rows;   // multiple of 64
     int64_t gx = ((N - row0 + 1) / 2 + 255) / 256;
@@ -620,15 +624,18 @@ static int nn_launch_inst(hfmi_ctx* ctx, const double* A, int64_t lda, int m, co
             hipLaunchKernelGGL(kern_h, dim3((unsigned)(2 * cnt_a)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
                                (int64_t)0, 2 * cnt_a, Y, ldy, 2 * base, 0);
             HIP_TRY(hipGetLastError());
+            rec(TH, 1, 2 * cnt_a, 0);
             HFMI_TRY(ctx->nn_hook(ctx->nn_hook_user, Y, ldy, r, (int64_t)base * tile_rows, (int64_t)cnt_a * tile_rows));
             // second half (the last half-height tile may be ragged: rows >= N are never stored), then the split tail tiles
             hipLaunchKernelGGL(kern_h, dim3((unsigned)(2 * cnt_b)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
                                (int64_t)0, 2 * cnt_b, Y, ldy, 2 * (base + cnt_a), 0);
             HIP_TRY(hipGetLastError());
+            rec(TH, 1, 2 * cnt_b, 0);
             if (tl > 0) {
               hipLaunchKernelGGL(kern, dim3((unsigned)(tl * msplit)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, out, ldo, N, tl, msplit,
                                  mchunk, pstride, 0, Y, ldy, base, full_tiles);
               HIP_TRY(hipGetLastError());
+              rec(TT, msplit, 0, tl);
               HFMI_TRY(reduce_tail());
             }
             const int64_t row0 = (int64_t)(base + cnt_a) * tile_rows;
@@ -644,6 +651,7 @@ static int nn_launch_inst(hfmi_ctx* ctx, const double* A, int64_t lda, int m, co
           hipLaunchKernelGGL(kern, dim3((unsigned)cnt), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
                              (int64_t)0, cnt, Y, ldy, base, 0);
         HIP_TRY(hipGetLastError());
+        rec(TT, msplit, cnt, msplit > 1 ? tl : 0);
         if (last && msplit > 1) HFMI_TRY(reduce_tail());
         const int64_t row0 = (int64_t)base * tile_rows;
         const int64_t row1 = last ? N : (int64_t)(base + cnt) * tile_rows;
@@ -658,6 +666,7 @@ static int nn_launch_inst(hfmi_ctx* ctx, const double* A, int64_t lda, int m, co
   hipLaunchKernelGGL(kern, grid, block, shmem, ctx->stream, A, lda, m, S, lds_, r, out, ldo, N, tail_tiles, msplit, mchunk, pstride,
                      full_tiles, Y, ldy, 0, full_tiles);
   HIP_TRY(hipGetLastError());
+  rec(TT, msplit, full_tiles, tail_tiles);
   if (msplit > 1) HFMI_TRY(reduce_tail());
   return HFMI_OK;
 }
@@ -711,6 +720,7 @@ static int nn_launch_res(hfmi_ctx* ctx, const double* A, int64_t lda, int m, con
   const int grid = ntiles < cus ? ntiles : cus;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, ntiles);
   HIP_TRY(hipGetLastError());
+  plan_record(ctx, HFMI_PLAN_NN_RES, {TT, NT, 8, r4, up ? 1 : 0, 1, ntiles, 0, grid});
   return HFMI_OK;
 }
 

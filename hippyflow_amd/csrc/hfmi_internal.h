@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -126,7 +127,19 @@ struct hfmi_ctx {
   hipEvent_t ev_cb[4];            // D2H done x2, H2D done x2
   xfer_state* xfer;               // pinned ring + host threads of the large host <-> device transfers (hfmi_xfer.hip), lazily created
   int compose_depth;              // OP_COMPOSE3 applications in progress (nested compositions use separate temporaries)
+  // plan record (hfmi_plan_clear / hfmi_plan_read, include/hfmi.h): which contraction / reduction instance every launch was
+  int plan_ring[HFMI_PLAN_RING][HFMI_PLAN_WORDS];
+  int64_t plan_count;             // launches since the last clear
 };
+// appends one record: word 0 = kind (HFMI_PLAN_*), then the fields in the order include/hfmi.h lists them
+static inline void plan_record(hfmi_ctx* ctx, int kind, std::initializer_list<int> fields) {
+  int* w = ctx->plan_ring[ctx->plan_count++ % HFMI_PLAN_RING];
+  int i = 0;
+  w[i++] = kind;
+  for (int v : fields)
+    if (i < HFMI_PLAN_WORDS) w[i++] = v;
+  while (i < HFMI_PLAN_WORDS) w[i++] = 0;
+}
 // large transfers between the caller's pageable arrays and device memory, pipelined through pinned chunks (hfmi_xfer.hip)
 int xfer_d2h(hfmi_ctx* ctx, void* host, const void* dev, size_t bytes);   // returns when the host array is complete
 int xfer_h2d(hfmi_ctx* ctx, void* dev, const void* host, size_t bytes);   // returns when the host array has been read

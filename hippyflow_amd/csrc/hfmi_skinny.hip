@@ -579,12 +579,13 @@ __global__ __launch_bounds__(SS_THREADS, 2) void k_tsgemm_ssb(const double* __re
 static bool ssb_pipe();
 template <int RT, int CTL>
 static int ssb_launch(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k, int64_t Npad,
-                      int64_t chunk, int nsplit, double* part) {
+                      int64_t chunk, int nsplit, double* part, bool swapped) {
   constexpr int NQ = (RT + CTL + 1) / 2;
   const size_t shmem = 2 * (size_t)NQ * 32 * SS_BK * sizeof(double) + (size_t)NQ * 32 * sizeof(double*);
   // pipelined stages where the fragments fit next to two register stages (measured, scripts/ss_shapes.py: n = 32 / 48 / 64 at
   // k = 138 +4 / +2.5 / +2 %; the 9 x 9 tile shape loses 10 % to the registers the carried fragments cost)
-  if (ssb_pipe() && RT * CTL <= 56) {
+  const bool pipe = ssb_pipe() && RT * CTL <= 56;
+  if (pipe) {
     auto kern = k_tsgemm_ssb<RT, CTL, NQ, true>;
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, B, ldb, k, Npad, chunk, part);
@@ -594,6 +595,7 @@ static int ssb_launch(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const 
     hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, B, ldb, k, Npad, chunk, part);
   }
   HIP_TRY(hipGetLastError());
+  plan_record(ctx, HFMI_PLAN_SSB, {RT, CTL, NQ, pipe ? 1 : 0, swapped ? 1 : 0, 0, nsplit});
   return HFMI_OK;
 }
 static int g_ss_blocked = 1;   // A/B knob "ss_blocked": 0 = round-robin kernel, 1 = blocked, 2 = blocked without the stage pipelining
@@ -602,9 +604,9 @@ static bool ssb_pipe() { return g_ss_blocked != 2; }
 // rt <= ct after the caller's role swap
 static bool ssb_has_instance(int rt, int ct) { return rt >= 2 && rt <= ct && (ct == 5 || ct == 6 || ct == 9) && rt + ct <= 18; }
 static int ssb_dispatch(hfmi_ctx* ctx, int rt, int ct, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
-                        int64_t Npad, int64_t chunk, int nsplit, double* part) {
+                        int64_t Npad, int64_t chunk, int nsplit, double* part, bool swapped) {
 #define SSB_CASE(R, Cc) \
-  if (rt == R && ct == Cc) return ssb_launch<R, Cc>(ctx, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part);
+  if (rt == R && ct == Cc) return ssb_launch<R, Cc>(ctx, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part, swapped);
   SSB_CASE(2, 5) SSB_CASE(3, 5) SSB_CASE(4, 5) SSB_CASE(5, 5)
   SSB_CASE(2, 6) SSB_CASE(3, 6) SSB_CASE(4, 6) SSB_CASE(5, 6) SSB_CASE(6, 6)
   SSB_CASE(2, 9) SSB_CASE(3, 9) SSB_CASE(4, 9) SSB_CASE(5, 9) SSB_CASE(6, 9) SSB_CASE(7, 9) SSB_CASE(8, 9) SSB_CASE(9, 9)
@@ -622,6 +624,7 @@ static int ss_launch(hfmi_ctx* ctx, const double* A, int64_t lda, int m, int rt,
   hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, rt, B, ldb, k, ct, same, Npad,
                      chunk, part);
   HIP_TRY(hipGetLastError());
+  plan_record(ctx, HFMI_PLAN_SS, {TPW, NQ, ss_pf(TPW, NQ), 0, same, nsplit});
   return HFMI_OK;
 }
 
@@ -673,9 +676,9 @@ int launch_tsgemm_ss(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const d
   }
   if (blocked) {
     if (swap)
-      HFMI_TRY(ssb_dispatch(ctx, ct, rt, B, ldb, k, A, lda, m, Npad, chunk, nsplit, part));
+      HFMI_TRY(ssb_dispatch(ctx, ct, rt, B, ldb, k, A, lda, m, Npad, chunk, nsplit, part, true));
     else
-      HFMI_TRY(ssb_dispatch(ctx, rt, ct, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part));
+      HFMI_TRY(ssb_dispatch(ctx, rt, ct, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part, false));
     prof_stop(ctx, pidx);
     // swapped roles: the partial tiles hold (A^T B)^T = B^T A, k x m with row stride mpad
     return swap ? launch_reduce_partials(ctx, part, nsplit, (int64_t)mpad * kpad, mpad, true, m, k, scale, beta, C, rs, cs)
@@ -686,11 +689,12 @@ int launch_tsgemm_ss(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const d
   if (tpw == T && nq == Q)                                                                                         \
     rc = ss_launch<T, Q>(ctx, A, lda, m, rt, B, ldb, k, ct, same ? 1 : 0, Npad, chunk, nsplit, part, shmem);      \
   else
-  // every (tiles per wave, chunks per thread) pair reachable with rt, ct <= 10 and ctot <= 288
+  // every (tiles per wave, chunks per thread) pair reachable with rt, ct <= 10 and ctot <= 288, and no other
+  // (tests/test_contraction_plan_cpu.py enumerates the rule above and compares it with this list)
   SS_CASE(1, 1) SS_CASE(1, 2) SS_CASE(1, 3) SS_CASE(1, 4) SS_CASE(1, 5) SS_CASE(2, 2) SS_CASE(2, 3) SS_CASE(2, 4)
-  SS_CASE(2, 5) SS_CASE(2, 6) SS_CASE(3, 5) SS_CASE(3, 6) SS_CASE(4, 3) SS_CASE(4, 5) SS_CASE(4, 6) SS_CASE(4, 7)
-  SS_CASE(5, 3) SS_CASE(5, 6) SS_CASE(5, 7) SS_CASE(6, 7) SS_CASE(7, 4) SS_CASE(7, 7) SS_CASE(7, 8) SS_CASE(8, 4)
-  SS_CASE(8, 8) SS_CASE(9, 9) SS_CASE(10, 9) SS_CASE(11, 5) SS_CASE(11, 9) SS_CASE(13, 5)
+  SS_CASE(2, 5) SS_CASE(2, 6) SS_CASE(3, 5) SS_CASE(3, 6) SS_CASE(4, 5) SS_CASE(4, 6) SS_CASE(4, 7)
+  SS_CASE(5, 6) SS_CASE(5, 7) SS_CASE(6, 7) SS_CASE(7, 7) SS_CASE(7, 8)
+  SS_CASE(8, 8) SS_CASE(9, 9) SS_CASE(10, 9) SS_CASE(11, 9)
   // one-operand (Gram) tile lists: rt (rt + 1) / 2 tiles, rt * 16 staged columns
   SS_CASE(3, 3) SS_CASE(4, 4) SS_CASE(5, 4) SS_CASE(6, 5) SS_CASE(7, 5)
   { hfmi_set_error("tsgemm_ss: no instance for tiles/wave=%d chunks/thread=%d", tpw, nq); }

@@ -358,6 +358,38 @@ HFMI_API int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double*
 HFMI_API int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, int nsplit, int reps, double* host_C,
                          double* avg_ms);
 HFMI_API int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfmi_block* Y, int reps, double* avg_ms);
+/* The tn product with its whole argument list, for the instance sweep of the tests: C = scale A^T B + beta C on a device copy of
+ * the caller's host array.  colmajor = 0: host_C is nvecA rows of ldc >= nvecB doubles, element (i, j) at [i ldc + j];
+ * colmajor = 1: nvecB rows of ldc >= nvecA doubles, element (i, j) at [j ldc + i] (ldc > 1: a result with both strides 1 is
+ * row-major).  The WHOLE array goes up (the beta operand and the guard columns behind the fast extent) and comes
+ * back, so the caller sees the result and everything the launch wrote next to it.  nsplit: 0 = library default. */
+HFMI_API int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, double scale, double beta, int colmajor, int ldc,
+                                 int nsplit, double* host_C);
+/* Plan record: every launch of a contraction kernel (k_tsgemm_tn, k_tsgemm_nn[_res], k_tsgemm_ss[b]) and of a partial-sum
+ * reduction behind one appends HFMI_PLAN_WORDS ints to a ring of HFMI_PLAN_RING records on the context (host side, a few stores
+ * per launch).  Word 0 is the kind, the others by kind:
+ *   TN      MT, NT, WAVES, TR, R4, grid, nrb, nsplit, direct, tail_nrb, tail_nsplit
+ *   NN      TT, NT, WAVES, R4, UPPER (0), msplit, full_tiles, tail_tiles, grid      (streaming kernel)
+ *   NN_RES  TT, NT, WAVES (8), R4, UPPER, msplit (1), full_tiles (all), tail_tiles (0), grid
+ *   SS      TPW, NQ, PF, swap (0), same, nsplit
+ *   SSB     RT, CTL, NQ, PIPE, swap, same (0), nsplit
+ *   REDUCE  route (HFMI_REDUCE_*), RY (4 | 16 split lanes; 0 for the vector kernel), nsplit, tr, m, k
+ * hfmi_plan_clear empties the ring; hfmi_plan_read copies the records appended since (oldest first, at most max_records and at
+ * most the HFMI_PLAN_RING newest) and stores how many launches there were in *total. */
+#define HFMI_PLAN_WORDS 16
+#define HFMI_PLAN_RING 256
+#define HFMI_PLAN_TN 0
+#define HFMI_PLAN_NN 1
+#define HFMI_PLAN_NN_RES 2
+#define HFMI_PLAN_SS 3
+#define HFMI_PLAN_SSB 4
+#define HFMI_PLAN_REDUCE 5
+#define HFMI_REDUCE_VEC_LONG 0    /* k_reduce_vec over the m x ld array as one long row */
+#define HFMI_REDUCE_VEC_ROWS 1    /* k_reduce_vec row by row */
+#define HFMI_REDUCE_FLAT 2        /* k_reduce_flat<RY> */
+#define HFMI_REDUCE_PARTIALS 3    /* k_reduce_partials<RY> */
+HFMI_API int hfmi_plan_clear(hfmi_ctx* ctx);
+HFMI_API int hfmi_plan_read(hfmi_ctx* ctx, int max_records, int* words /* max_records x HFMI_PLAN_WORDS */, int* nrecords, int* total);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */
