@@ -23,6 +23,7 @@ from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrO
 from .projectors import (ActiveSubspaceParameterList, ActiveSubspaceProjector, BoundaryRestrictedKLEProjector,
                          KLEParameterList, KLEProjector,
                          ParameterList, PODParameterList, PODProjector, PODProjectorFromData, weighted_l2_norm_vector)
+from .lowrank import PivotedCholesky, pivoted_cholesky
 from .randomized import (StreamedSketch, accuracyEnhancedSVD, doublePass, doublePassG, parRandom, singlePass, singlePassG,
                          small_solve, svd_small, sym_eig_small)
 from .errors import input_output_error_test, projection_error_test

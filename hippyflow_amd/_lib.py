@@ -15,6 +15,8 @@ QR_CHOL, QR_MGS, QR_AUTO = 0, 1, 2
 UNIQUE_ID_BYTES = 256
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
 KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
+PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
+PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h
 
 HOST_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int)
 POST_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
@@ -72,6 +74,11 @@ SIGNATURES = {
     "hfmi_op_jjt": [_P, _P, C.c_int, C.c_int, C.c_double, _PP],
     "hfmi_op_dense_sym": [_P, _P, _PP],
     "hfmi_op_kernel_cov": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
+    "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
+    "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    "hfmi_pchol_read": [_P, _P, _P],
+    "hfmi_pchol_factor": [_P, _PP],
+    "hfmi_pchol_destroy": [_P],
     "hfmi_op_csr": [_P, _P, _PP],
     "hfmi_op_csr_pcg": [_P, _P, C.c_double, C.c_int, _PP],
     "hfmi_op_solver_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)],

@@ -363,6 +363,7 @@ int eig_tuning_set(const char* key, int value);   // 1 = key handled
 int chol_tuning_set(const char* key, int value);  // "chol": 0 = blocked MFMA kernel (default), 1 = column-at-a-time kernels
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol);   // hfmi_chol.hip
+int pchol_tuning_set(const char* key, int value); // "pchol_grid": cap on the workgroups of the pivoted Cholesky launches (hfmi_pchol.hip)
 int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first"; hfmi_ctx.hip)
 extern int g_comm_panels;      // row panels of an overlapped rank reduction (hfmi_op.hip reads HFMI_COMM_PANELS when -1)
 extern int g_qr_trust_first;   // first Cholesky-QR pass taken on trust (hfmi_qr.hip reads HFMI_QR_TRUST_FIRST when -1)

@@ -18,23 +18,13 @@
 #include <algorithm>
 
 #include "hfmi_gemm_common.h"
+#include "hfmi_kcov_eval.h"
 
 #define KC_JC 64            // rows of W (values of j) per LDS chunk
 #define KC_JCP 66           // padded column stride of the LDS image
 #define KC_WAVES 8
 #define KC_ROWS (16 * KC_WAVES)
 #define KC_MAXT 9           // column tiles per panel: 144 columns, k = 138 is one pass
-
-struct kcov_params {
-  const double *x0, *x1, *x2;   // one coordinate array per dimension (x1, x2 alias x0 when d is smaller: never read)
-  int64_t N;
-  int d;
-  double inv_ell;
-  double ca;                // a = ca * |x_i - x_j| / ell
-  double p1, p2;            // phi = (1 + p1 a + p2 a^2) exp(-g)
-  double g1, g2;            // g = a (g1 + g2 a)
-  double sigma2, nugget;
-};
 
 template <int NT>
 __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const double* __restrict__ W, int64_t ldw, double* __restrict__ Y,
@@ -93,11 +83,7 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const dou
           const double dz = xi2 - xl[2 * KC_JC + jj];
           r2 = fma(dz, dz, r2);
         }
-        const double a = P.ca * sqrt(r2) * P.inv_ell;
-        const double poly = fma(a, fma(P.p2, a, P.p1), 1.0);
-        const double g = a * fma(P.g2, a, P.g1);
-        double v = P.sigma2 * poly * exp(-g);
-        if (gi == gj) v += P.nugget;
+        const double v = kcov_entry(P, r2, gi == gj);
         return (iv && gj < N) ? v : 0.0;
       };
       double a_next = eval(0);
@@ -139,8 +125,7 @@ static int kcov_launch(hfmi_ctx* ctx, const kcov_params& P, const double* W, int
   return HFMI_OK;
 }
 
-int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+int kcov_params_init(kcov_params* out, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget) {
   kcov_params P;
   P.x0 = x;
   P.x1 = d > 1 ? x + N : x;
@@ -158,6 +143,14 @@ int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int fami
     case HFMI_KERNEL_SQEXP: P.g1 = 0.0, P.g2 = 0.5; break;                           // exp(-r^2 / 2)
     default: HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: unknown kernel family %d", family);
   }
+  *out = P;
+  return HFMI_OK;
+}
+
+int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+  kcov_params P;
+  HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
   for (int c0 = 0; c0 < nvec; c0 += 16 * KC_MAXT) {
     const int nc = std::min(16 * KC_MAXT, nvec - c0);
     const double* Wp = W + (int64_t)c0 * ldw;

@@ -1,0 +1,29 @@
+// One entry of a kernel covariance, C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij: the parameters and the evaluation shared by
+// the matrix-free apply (hfmi_kcov.hip) and the pivoted Cholesky factorisation (hfmi_pchol.hip), so that both see the same matrix.
+#pragma once
+#include "hfmi_internal.h"
+
+struct kcov_params {
+  const double *x0, *x1, *x2;   // one coordinate array per dimension (x1, x2 alias x0 when d is smaller: never read)
+  int64_t N;
+  int d;
+  double inv_ell;
+  double ca;                // a = ca * |x_i - x_j| / ell
+  double p1, p2;            // phi = (1 + p1 a + p2 a^2) exp(-g)
+  double g1, g2;            // g = a (g1 + g2 a)
+  double sigma2, nugget;
+};
+
+// x: d arrays of N doubles on the device; HFMI_ERR_INVALID for an unknown family (hfmi_kcov.hip)
+int kcov_params_init(kcov_params* out, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget);
+
+// the entry for a point pair at squared distance r2 = |x_i - x_j|^2 (summed by the caller as dx * dx, then one fma per further coordinate);
+// same_index: i == j as point INDICES (the nugget sits on the index, not on the distance)
+__device__ __forceinline__ double kcov_entry(const kcov_params& P, double r2, bool same_index) {
+  const double a = P.ca * sqrt(r2) * P.inv_ell;
+  const double poly = fma(a, fma(P.p2, a, P.p1), 1.0);
+  const double g = a * fma(P.g2, a, P.g1);
+  double v = P.sigma2 * poly * exp(-g);
+  if (same_index) v += P.nugget;
+  return v;
+}

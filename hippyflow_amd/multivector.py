@@ -31,10 +31,11 @@ class _NullComm:
 class MultiVector:
     """hp.MultiVector(vector_like, nvec) / hp.MultiVector(other) (copy)."""
 
-    def __init__(self, v=None, nvec=None, ctx=None, _handle=None, _parent=None, _borrowed=False):
+    def __init__(self, v=None, nvec=None, ctx=None, _handle=None, _parent=None, _borrowed=False, _read_only=False):
         self.ctx = ctx or getattr(v, "ctx", None) or L.Context.default()
         self._parent = _parent          # keeps the owning block alive for views
         self._borrowed = _borrowed      # handle owned by the C side (post-apply hooks): never destroyed here
+        self._read_only = _read_only    # library-owned result (a factor): the in-place members refuse, views inherit the flag
         self._views = {}
         if _handle is not None:
             self.handle = _handle
@@ -51,6 +52,10 @@ class MultiVector:
         N, k, ld, p = C.c_int64(), C.c_int(), C.c_int64(), C.c_void_p()
         L.call("hfmi_block_info", self.handle, C.byref(N), C.byref(k), C.byref(ld), C.byref(p))
         self._N, self._k, self._ld, self._ptr = N.value, k.value, ld.value, p.value
+
+    def _writable(self, what):
+        if self._read_only:
+            raise ValueError("MultiVector.%s: this block is owned by the library and read-only (copy it with MultiVector(block))" % what)
 
     # ---- construction helpers
     @classmethod
@@ -74,6 +79,7 @@ class MultiVector:
         sample by sample): copy a PINNED host array (``pinned_empty``) into this block -- normally a ``view`` of one
         sample's vectors -- on the context's ingest stream, without blocking.  Returns a ticket: ``ctx.ingest_wait(ticket)``
         before the pinned array is overwritten, ``ctx.ingest_fence()`` before compute that reads the block is enqueued."""
+        self._writable("upload_async")
         if not isinstance(rows, np.ndarray) or rows.dtype != np.float64 or not rows.flags.c_contiguous:
             raise ValueError("upload_async: a C-contiguous float64 array from pinned_empty() is required")
         want = (self._k, self._N) if layout == "vectors" else (self._N, self._k)
@@ -111,28 +117,34 @@ class MultiVector:
         if j not in self._views:
             h = C.c_void_p()
             L.call("hfmi_block_view", self.handle, j, 1, C.byref(h))
-            self._views[j] = Vector(ctx=self.ctx, _mv=MultiVector(ctx=self.ctx, _handle=h, _parent=self))
+            self._views[j] = Vector(ctx=self.ctx, _mv=MultiVector(ctx=self.ctx, _handle=h, _parent=self, _read_only=self._read_only))
         return self._views[j]
 
     def view(self, first, count):
         h = C.c_void_p()
         L.call("hfmi_block_view", self.handle, int(first), int(count), C.byref(h))
-        return MultiVector(ctx=self.ctx, _handle=h, _parent=self)
+        return MultiVector(ctx=self.ctx, _handle=h, _parent=self, _read_only=self._read_only)
 
     def zero(self):
+        self._writable("zero")
         L.call("hfmi_block_zero", self.handle)
 
     def scale(self, alpha):
+        self._writable("scale")
         L.call("hfmi_block_scale", self.handle, float(alpha))
 
     def axpy(self, alpha, X):
+        self._writable("axpy")
         L.call("hfmi_block_axpy", self.handle, float(alpha), X.handle)
 
     def copy_from(self, X):
+        self._writable("copy_from")
         L.call("hfmi_block_copy", self.handle, X.handle)
 
     def swap(self, other):
         """MultiVector.swap: exchange storage with another block of the same shape."""
+        self._writable("swap")
+        other._writable("swap")
         if (self._N, self._k) != (other._N, other._k):
             raise ValueError("swap: shapes differ")
         for name in ("handle", "_parent", "_views", "_ptr", "_ld"):
@@ -176,6 +188,7 @@ class MultiVector:
 
     def orthogonalize(self, method=L.QR_AUTO):
         """Thin QR in place (Q^T Q = I); returns R (nvec x nvec, upper triangular)."""
+        self._writable("orthogonalize")
         R = np.zeros((self._k, self._k))
         passes = C.c_int(0)
         L.call("hfmi_borth_qr", self.handle, None, None, L.ptr(R), int(method), C.byref(passes))
@@ -185,6 +198,7 @@ class MultiVector:
     def Borthogonalize(self, B, method=L.QR_AUTO):
         """Thin QR in place in the B inner product (Q^T B Q = I); returns (BQ, R)."""
         from .operators import as_device_operator
+        self._writable("Borthogonalize")
         Bop = as_device_operator(B, self._N, self.ctx)
         BQ = MultiVector(self._N, self._k, ctx=self.ctx)
         R = np.zeros((self._k, self._k))

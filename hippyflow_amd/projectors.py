@@ -29,7 +29,9 @@ from . import _lib as L
 from .collectives import CollectiveOperator, MatrixMultCollectiveOperator, NullCollective
 from . import hostvec as H
 from .multivector import ingest_stream, MatMvMult, MultiVector, mv_to_dense
-from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, MassPreconditionedCovarianceOperator,
+from .lowrank import pivoted_cholesky
+from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, KernelCovarianceOperator,
+                        MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
                         SnapshotGramOperator, Solver2Operator, as_device_operator)
 from .randomized import doublePass, doublePassG, parRandom, singlePass, singlePassG, sym_eig_small
@@ -674,6 +676,11 @@ class KLEProjector:
 
     prior_power_iterations = 2      # orthogonality='prior': passes of the randomized generalized solve (see construct_input_subspace)
 
+    # An int routes 'mass' / 'identity' through the pivoted Cholesky factor of a KernelCovarianceOperator prior.C (lowrank.py) with
+    # max_rank = kernel_factor_rank: no apply of C, no probe block, and `kle_eigenvalue_error_bound` says how far every eigenvalue can be
+    # below the exact one.  None (the default): the randomized solve, as before.  An attribute for the same reason as above.
+    kernel_factor_rank = None
+
     def __init__(self, prior, mesh_constructor_comm=None, collective=None, parameters=None, ctx=None):
         self.prior = prior
         self.mesh_constructor_comm = mesh_constructor_comm
@@ -713,9 +720,29 @@ class KLEProjector:
         Omega.orthogonalize()
         return Omega
 
+    def _factor_subspace(self, orthogonality):
+        """(decoder, encoder) from the pivoted Cholesky factor of the kernel covariance (``kernel_factor_rank`` is set)."""
+        if orthogonality == 'prior':
+            raise ValueError("kernel_factor_rank: the factor route gives 'mass' and 'identity' orthogonality, not 'prior'")
+        if orthogonality not in ('mass', 'identity'):
+            raise ValueError(orthogonality)
+        if not isinstance(self.C, KernelCovarianceOperator):
+            raise ValueError("kernel_factor_rank: prior.C must be a KernelCovarianceOperator (got %s)" % type(self.C).__name__)
+        if not isinstance(self.M, CsrOperator):
+            raise ValueError("kernel_factor_rank: prior.M must be an assembled matrix (it is only a host operator here)")
+        M = self.M if orthogonality == 'mass' else None
+        self.kle_factor = pivoted_cholesky(self.C, int(self.kernel_factor_rank))
+        self.d_KLE, self.V_KLE, MV = self.kle_factor.eig(self.parameters['rank'], M)
+        self.kle_eigenvalue_error_bound = self.kle_factor.eigenvalue_error_bound(M)
+        self.M_orthogonal = M is not None
+        self.R_orthogonal = False
+        return self.V_KLE, (MV if M is not None else MultiVector(self.V_KLE))
+
     def construct_input_subspace(self, orthogonality='mass'):
         t0 = time.time()
         assert hasattr(self.prior, 'M')
+        if self.kernel_factor_rank is not None:
+            return self._finish_subspace(t0, *self._factor_subspace(orthogonality.lower()))
         KLE_Operator = MassPreconditionedCovarianceOperator(self.C, self.M)
         Omega = _draw_omega(self.N, self.parameters['rank'] + self.parameters['oversampling'], self.collective, self.ctx)
         if orthogonality.lower() == 'mass':
@@ -748,6 +775,9 @@ class KLEProjector:
             MatMvMult(R_op, kle_decoder, kle_encoder)                                             # :333
         else:
             raise ValueError(orthogonality)
+        return self._finish_subspace(t0, kle_decoder, kle_encoder)
+
+    def _finish_subspace(self, t0, kle_decoder, kle_encoder):
         self._subspace_construction_time = time.time() - t0
         if self.parameters['verbose'] and _is_root(self.collective):
             print('Construction of input subspace took ', self._subspace_construction_time, 's')
@@ -757,7 +787,6 @@ class KLEProjector:
             _plot_spectrum(self.parameters['output_directory'], 'KLE_eigenvalues_' + str(self.parameters['rank']), self.d_KLE,
                            r'Eigenvalues of $C$' + self.parameters['plot_label_suffix'])                              # :194-197
         return self.d_KLE, kle_decoder, kle_encoder
-
 
     def test_errors(self, ranks=[None], cut_off=1e-12, samples=None):
         """Projection-error test of the KLE basis (KLEProjector.py:202-282).  ``samples`` is a block / (n, N) array

@@ -65,6 +65,7 @@ typedef struct hfmi_csr hfmi_csr;
 typedef struct hfmi_op hfmi_op;
 typedef struct hfmi_comm hfmi_comm;
 typedef struct hfmi_amg hfmi_amg;
+typedef struct hfmi_pchol hfmi_pchol;
 
 /* ---------------------------------------------------------------- context */
 HFMI_API const char* hfmi_last_error(void);
@@ -173,6 +174,27 @@ HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out
 #define HFMI_KERNEL_SQEXP 3
 HFMI_API int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, hfmi_op** out);
+/*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
+ *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
+ *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
+ *     semidefinite, so trace[rank] bounds the error of every eigenvalue of L L^T.  With d0 = sigma^2 + nugget and kmax = min(max_rank, N):
+ *       step j: (p, dp) = the largest remaining diagonal entry, ties to the LOWEST index; stop when trace[j] <= rel_tol * trace[0]
+ *       (REL_TOL) or dp <= 4 kmax eps d0 (FLOOR: what is left is rounding); L[:,j] = (C[:,p] - L[:,:j] L[p,:j]^T) / sqrt(dp).
+ *     hfmi_pchol_create runs the factorisation (the operator's coordinates are needed only here: the factor does not depend on the
+ *     operator's lifetime).  No atomics: two factorisations of the same input are bit-identical in L, pivots and trace.
+ *     hfmi_pchol_read: the `rank` pivots and the rank + 1 traces.  hfmi_pchol_factor: the factor as a block of `rank` vectors of
+ *     length N, owned by the handle, read-only, valid until hfmi_pchol_destroy; it obeys the block storage contract (allocated like
+ *     hfmi_block_create; rows N..ld-1 are +0.0, only rows below N are written); HFMI_ERR_INVALID when rank is 0.
+ *     HFMI_ERR_INVALID: not a kernel covariance operator, max_rank < 1 or > 16384 (the largest Gram eigenproblem,
+ *     hfmi_block_gram_eig), rel_tol negative or not finite. */
+#define HFMI_PCHOL_MAX_RANK 0
+#define HFMI_PCHOL_REL_TOL 1
+#define HFMI_PCHOL_FLOOR 2
+HFMI_API int hfmi_pchol_create(hfmi_op* kernel_cov_op, int max_rank, double rel_tol, hfmi_pchol** out);
+HFMI_API int hfmi_pchol_info(const hfmi_pchol* f, int* rank, int* stop_reason, double* trace0);
+HFMI_API int hfmi_pchol_read(const hfmi_pchol* f, int64_t* host_pivots, double* host_trace);
+HFMI_API int hfmi_pchol_factor(const hfmi_pchol* f, const hfmi_block** L);
+HFMI_API int hfmi_pchol_destroy(hfmi_pchol* f);
 /* a4/a9: sparse operator  Y = M W  (prior.M.mult, prior.R.mult; hp.MatMvMult(B, decoder, encoder)) */
 HFMI_API int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out);
 /*     solver object for an SPD CSR matrix: Y = M^{-1} W to a relative residual rel_tol per vector
@@ -430,7 +452,9 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * ("prof_level", 1|2) what a profiling region records: 2 = every contraction and every phase (default), 1 = contractions of at
  * least 2 Gflop only (each record is a pair of stream events, 2-4 us of idle GPU between dependent kernels: scripts/prof_level_ab.py);
  * ("comm_panels", 0..8) row panels of an operator application whose
- * rank reduction overlaps the rest of the product (0 / 1 = one all-reduce after the product; default 4). */
+ * rank reduction overlaps the rest of the product (0 / 1 = one all-reduce after the product; default 4);
+ * ("pchol_grid", 0..65535) most workgroups per launch of hfmi_pchol_create (0 = what the device holds, default): a small value makes every
+ * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits. */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
 /* phases of hfmi_double_pass[_g], accumulated between hfmi_profile_begin and hfmi_profile_end (milliseconds, summed
  * over the solves in the region; device phases by HIP events on the context's stream, the HOST_* legs by the host's
