@@ -13,6 +13,7 @@ LAYOUT_VECTORS = 0
 LAYOUT_DENSE = 1
 QR_CHOL, QR_MGS, QR_AUTO = 0, 1, 2
 UNIQUE_ID_BYTES = 256
+WIDE_MAX_VECTORS = 2048                                # orthogonalize / Borthogonalize / doublePass[G]: HFMI_WIDE_MAXK of the library
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
 KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
@@ -123,6 +124,7 @@ SIGNATURES = {
     "hfmi_bench_tsgemm_tn": [_P, _P, C.c_int, C.c_int, _P, _D],
     "hfmi_bench_tsgemm_nn": [_P, _P, _P, C.c_int, _D],
     "hfmi_test_tsgemm_tn": [_P, _P, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P],
+    "hfmi_test_chol_wide": [_P, C.c_int, _P, C.c_double, C.c_double, _P, _P, _P],
     "hfmi_plan_clear": [_P],
     "hfmi_plan_read": [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],

@@ -186,6 +186,8 @@ extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
   c->ingest_stream = nullptr;
   c->ingest_seq = 0;
   c->late_pinned = nullptr;
+  c->wide = nullptr;
+  c->wide_cap = 0;
   c->nn_hook = nullptr;
   c->nn_hook_user = nullptr;
   c->nn_hook_panels = 0;
@@ -229,6 +231,7 @@ extern "C" int hfmi_ctx_destroy(hfmi_ctx* ctx) {
     (void)hipStreamDestroy(ctx->ingest_stream);
   }
   (void)hipFree(ctx->small);
+  if (ctx->wide) (void)hipFree(ctx->wide);
   (void)hipFree(ctx->status_dev);
   (void)hipHostFree(ctx->status_host);
   (void)hipEventDestroy(ctx->ev0);
@@ -389,6 +392,9 @@ static int g_prof_level = 2;
 // HFMI_QR_TRUST_FIRST=0 / tuning key "qr_trust_first": the first Cholesky-QR pass of the Gram-form solve waits for its status words
 // (the behaviour up to round 4: one host round trip in the middle of every solve); default 1
 int g_qr_trust_first = -1;
+// tuning key "qr_wide_min": the width from which hfmi_borth_qr takes the wide Cholesky-QR (hfmi_qr.hip); below 257 only so that the
+// wide route can be compared with the narrow one at widths both serve
+int g_qr_wide_min = SM_MAXK + 1;
 int api_tuning_set(const char* key, int value) {
   if (key && !strcmp(key, "comm_panels") && value >= 0 && value <= 8) {
     g_comm_panels = value;
@@ -400,6 +406,10 @@ int api_tuning_set(const char* key, int value) {
   }
   if (key && !strcmp(key, "qr_trust_first") && (value == 0 || value == 1)) {
     g_qr_trust_first = value;
+    return 1;
+  }
+  if (key && !strcmp(key, "qr_wide_min") && value >= 17 && value <= SM_MAXK + 1) {
+    g_qr_wide_min = value;
     return 1;
   }
   return 0;

@@ -56,6 +56,12 @@ struct hfmi_block {
 #define SM_LD 256
 enum { SM_GRAM = 0, SM_R, SM_RINV, SM_RTOT, SM_T, SM_V, SM_TMP, SM_TMP2, SM_AUX, SM_NSLOTS };
 
+// Small dense matrices of 256 < k <= HFMI_WIDE_MAXK vectors (the wide Cholesky-QR and double pass) live in a second arena that a
+// context allocates the first time a wide call arrives: row-major, ld = round_up(k, 32) for the call at hand, slots spaced by the
+// arena's capacity (hfmi_chol_wide.hip)
+#define HFMI_WIDE_MAXK 2048
+enum { WA_GRAM = 0, WA_WORK, WA_R, WA_RINV, WA_RTOT, WA_TMP, WA_T, WA_V, WA_NSLOTS };
+
 struct hfmi_status_words {  // device-resident, read back by the host after small kernels
   double min_pivot_ratio;   // min_j pivot_j / G_jj
   double gram_dev;          // || D^-1/2 G D^-1/2 - I ||_F  (orthonormality defect of the input)
@@ -84,6 +90,8 @@ struct hfmi_ctx {
   void* ws[WS_NSLOTS];
   size_t ws_bytes[WS_NSLOTS];
   double* small;                  // SM_NSLOTS * SM_MAXK * SM_LD doubles
+  double* wide;                   // wide arena: WA_NSLOTS matrices of wide_cap x wide_cap doubles + wa_tail_doubles(); null until needed
+  int wide_cap;                   // leading dimension the arena was sized for (a multiple of 32)
   hfmi_status_words* status_dev;  // device
   hfmi_status_words* status_host; // pinned
   void* pinned;                   // pinned host staging
@@ -168,6 +176,7 @@ enum hfmi_tmp_slot {
   TMP_SKETCH_BQ = 3,      // single_pass_impl, hfmi_sketch_eig: B Q
   TMP_QR_BZ = 4,          // qr_chol / qr_mgs: B Q when the caller wants no BQ
   TMP_QR_SAVE = 5,        // borth_qr(AUTO): the input, for the Gram-Schmidt fall-back
+  TMP_QR_WIDE = 6,        // qr_chol_wide: the other half of the Q <- Q R^-1 ping-pong (out of place beyond 256 columns)
   TMP_KRYLOV_0 = 8,       // csr_pcg_solve and its Chebyshev route (hfmi_cheb.hip): r / row-major b
   TMP_KRYLOV_1 = 9,       //   z / x_0
   TMP_KRYLOV_2 = 10,      //   p / x_1
@@ -292,6 +301,11 @@ struct qr_late_checks {     // second (and first) Cholesky-QR pass taken on trus
   hfmi_status_words* st1;   // pinned: status words of the FIRST pass when that one was taken on trust as well
   bool first_trusted;
 };
+// the checked Cholesky-QR loop for 256 < k <= HFMI_WIDE_MAXK (and from the tuning key "qr_wide_min" on): wide arena, Q <- Q R^-1 out of place
+int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out);
+// Y = op X in column panels of at most 256 vectors (block views): no operator kind sees a width it was not written for
+int op_apply_panels(hfmi_op* op, const hfmi_block* X, hfmi_block* Y);
+extern int g_qr_wide_min;      // width from which borth_qr takes the wide route (tuning key "qr_wide_min", 17..257; default 257)
 int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_out, bool* deferred = nullptr, qr_late_checks* opt = nullptr);
 // hfmi_borth_qr with want_r (exact triangular factors in every Cholesky pass) chosen by the caller
 int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes);
@@ -363,8 +377,16 @@ int eig_tuning_set(const char* key, int value);   // 1 = key handled
 int chol_tuning_set(const char* key, int value);  // "chol": 0 = blocked MFMA kernel (default), 1 = column-at-a-time kernels
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol);   // hfmi_chol.hip
+// ------------------------------------------------------------------ wide Cholesky + inverse (hfmi_chol_wide.hip)
+static inline double* wa_ptr(hfmi_ctx* c, int slot) { return c->wide + (size_t)slot * c->wide_cap * c->wide_cap; }
+static inline double* wa_aux(hfmi_ctx* c) { return wa_ptr(c, WA_NSLOTS); }   // [0, k): original column norms; [ld, ld + k): diag(Rtot)
+int ctx_wide(hfmi_ctx* ctx, int k);      // make the arena hold k x k matrices (allocates / regrows; zero filled)
+// The contract of launch_chol_inv on the wide arena with ld = round_up(k, 32): G = WA_GRAM -> R (WA_R), R^-1 (WA_RINV), both upper
+// with zero strict lower triangles; rtot_mode 1: Rtot (WA_RTOT) <- R, 2: Rtot <- R Rtot; the AUX table (wa_aux) and the status
+// words, which it also returns on the host (it synchronises the stream: the restart with the shifted diagonal is the host's decision)
+int launch_chol_wide(hfmi_ctx* ctx, int k, int rtot_mode, double shift_rel, double pivot_tol, hfmi_status_words* host_st);
 int pchol_tuning_set(const char* key, int value); // "pchol_grid": cap on the workgroups of the pivoted Cholesky launches (hfmi_pchol.hip)
-int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first"; hfmi_ctx.hip)
+int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first", "qr_wide_min"; hfmi_ctx.hip)
 extern int g_comm_panels;      // row panels of an overlapped rank reduction (hfmi_op.hip reads HFMI_COMM_PANELS when -1)
 extern int g_qr_trust_first;   // first Cholesky-QR pass taken on trust (hfmi_qr.hip reads HFMI_QR_TRUST_FIRST when -1)
 int launch_small_set_identity(hfmi_ctx* ctx, int k, int slot);

@@ -1,5 +1,6 @@
-// B-orthogonal thin QR of libhfmi.so (include/hfmi.h): repeated (shifted) Cholesky-QR, the reference's Gram-Schmidt rule and
-// the dispatcher between them.  Host side only; kernels live in hfmi_gemm.hip / hfmi_gemm_nn.hip / hfmi_small.hip / hfmi_chol.hip.
+// B-orthogonal thin QR of libhfmi.so (include/hfmi.h): repeated (shifted) Cholesky-QR (up to 256 vectors in the fixed small-matrix
+// arena, up to 2048 in the wide one), the reference's Gram-Schmidt rule and the dispatcher between them.  Host side only; kernels
+// live in hfmi_gemm.hip / hfmi_gemm_nn.hip / hfmi_small.hip / hfmi_chol.hip / hfmi_chol_wide.hip.
 #include <math.h>
 #include <string.h>
 
@@ -46,7 +47,9 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
   hfmi_ctx* ctx = Q->ctx;
   const int64_t N = Q->N;
   const int k = Q->nvec;
-  if (k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", SM_MAXK, k);
+  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
+  // beyond the small-matrix arena: the wide loop (always checked).  The fused solves' trusted / deferred passes stay narrow.
+  if (k > SM_MAXK || (k >= g_qr_wide_min && !deferred && !opt)) return qr_chol_wide(Q, B, BQ, passes_out);
   hfmi_block* BZ = BQ;
   hfmi_block bz_view;
   if (B && !BQ) {
@@ -152,6 +155,84 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
   return HFMI_OK;
 }
 
+int op_apply_panels(hfmi_op* op, const hfmi_block* X, hfmi_block* Y) {
+  if (X->nvec <= SM_MAXK) return hfmi_op_apply(op, X, Y, 0);
+  if (Y->nvec != X->nvec) HFMI_FAIL(HFMI_ERR_INVALID, "operator application: the blocks hold %d and %d vectors", X->nvec, Y->nvec);
+  for (int c0 = 0; c0 < X->nvec; c0 += SM_MAXK) {
+    hfmi_block xv = *X, yv = *Y;
+    xv.p = X->p + (int64_t)c0 * X->ld;
+    yv.p = Y->p + (int64_t)c0 * Y->ld;
+    xv.nvec = yv.nvec = std::min(SM_MAXK, X->nvec - c0);
+    xv.owner = yv.owner = false;
+    HFMI_TRY(hfmi_op_apply(op, &xv, &yv, 0));
+  }
+  return HFMI_OK;
+}
+
+// The checked loop of qr_chol for 256 < k <= 2048 columns (and, for tests, from the tuning key "qr_wide_min" on): Gram matrix,
+// factors and status words in the wide arena (hfmi_chol_wide.hip), one host round trip per pass, and Q <- Q R^-1 OUT of place
+// (a panel of the product reads columns of Q that an earlier panel would already have overwritten): the passes alternate between Q and a cached temporary, and an
+// odd number of passes ends with a copy back.  Rtot is always the exact product of the passes' factors.
+int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
+  hfmi_ctx* ctx = Q->ctx;
+  const int64_t N = Q->N;
+  const int k = Q->nvec;
+  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
+  HFMI_TRY(ctx_wide(ctx, k));
+  const int ld = (int)round_up(k, 32);
+  hfmi_block* BZ = BQ;
+  hfmi_block bz_view, pong;
+  if (B && !BQ) {
+    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
+    BZ = &bz_view;
+  }
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_WIDE, N, k, &pong));
+  const double u = 1.1102230246251565e-16;
+  const double shift_rel = 11.0 * ((double)N * k + (double)k * (k + 1)) * u;
+  const double pivot_tol = 0.0;   // 64 k eps, as in qr_chol
+  int passes = 0;
+  const int max_passes = 6;
+  hfmi_block* cur = Q;
+  hfmi_block* nxt = &pong;
+  for (;;) {
+    const hfmi_block* right = cur;
+    if (B) {
+      HFMI_TRY(op_apply_panels(B, cur, BZ));
+      right = BZ;
+    }
+    HFMI_TRY(launch_tsgemm_tn(ctx, cur->p, cur->ld, k, right->p, right->ld, k, N, 1.0, 0.0, wa_ptr(ctx, WA_GRAM), ld, 1, 0));
+    hfmi_status_words st;
+    HFMI_TRY(launch_chol_wide(ctx, k, passes == 0 ? 1 : 2, shift_rel, pivot_tol, &st));
+    if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
+    // Q R^-1 in column panels of 256 issued here, not inside launch_tsgemm_nn: columns r0 .. r0 + rp - 1 of the upper triangular R^-1
+    // are zero below row r0 + rp, so the panel's reduction stops there (half the work, the same bits), and the upper-triangular
+    // hint of launch_nn_upper -- which takes the small matrix's column 0 for the diagonal -- goes to the first panel only
+    for (int r0 = 0; r0 < k; r0 += SM_MAXK) {
+      const int rp = std::min(SM_MAXK, k - r0);
+      const double* S = wa_ptr(ctx, WA_RINV) + r0;
+      double* Yp = nxt->p + (int64_t)r0 * nxt->ld;
+      if (r0 == 0) HFMI_TRY(launch_nn_upper(ctx, cur->p, cur->ld, rp, S, ld, rp, Yp, nxt->ld, N));
+      else HFMI_TRY(launch_tsgemm_nn(ctx, cur->p, cur->ld, r0 + rp, S, ld, rp, 1.0, 0.0, Yp, nxt->ld, N));
+    }
+    std::swap(cur, nxt);
+    ++passes;
+    if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
+    if (passes >= max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
+  }
+  if (cur != Q) HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, cur->p, cur->ld, N, k));
+  {
+    std::vector<double> aux((size_t)ld + k);          // [0, k): original column norms; [ld, ld + k): diag(Rtot)
+    HFMI_TRY(read_back(ctx, wa_aux(ctx), (size_t)ld + k, aux.data()));
+    for (int j = 0; j < k; ++j)
+      if (!(aux[ld + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
+        HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
+                  aux[j] > 0 ? aux[ld + j] / aux[j] : 0.0);
+  }
+  if (B && BQ) HFMI_TRY(op_apply_panels(B, Q, BQ));
+  if (passes_out) *passes_out = passes;
+  return HFMI_OK;
+}
+
 // Column-by-column Gram-Schmidt with the reference's re-orthogonalisation rule (hippylib
 // MultiVector._mgs_stable / _mgs_reortho as restated in oracle/hippylib_restated.py): each sweep projects
 // column j against all previous columns at once (classical GS per sweep; with the "twice is enough"
@@ -240,6 +321,7 @@ int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool wan
   const int k = Q->nvec;
   if (method == HFMI_QR_MGS) return qr_mgs(Q, B, BQ, host_R, passes);
   if (method != HFMI_QR_CHOL && method != HFMI_QR_AUTO) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: unknown method %d", method);
+  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
   hfmi_block save;
   if (method == HFMI_QR_AUTO) {  // keep the input so that a breakdown can fall back to Gram-Schmidt
     HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_SAVE, Q->N, k, &save));
@@ -251,7 +333,12 @@ int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool wan
     return qr_mgs(Q, B, BQ, host_R, passes);
   }
   if (s != HFMI_OK) return s;
-  if (host_R) {
+  if (host_R && (k > SM_MAXK || k >= g_qr_wide_min)) {   // the wide route was taken: Rtot sits in the wide arena
+    const int ld = (int)round_up(k, 32);
+    std::vector<double> tmp((size_t)k * ld);
+    HFMI_TRY(read_back(ctx, wa_ptr(ctx, WA_RTOT), (size_t)k * ld, tmp.data()));
+    for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * ld, (size_t)k * sizeof(double));
+  } else if (host_R) {
     std::vector<double> tmp((size_t)k * SM_LD);
     HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_RTOT), (size_t)k * SM_LD, tmp.data()));
     for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * SM_LD, (size_t)k * sizeof(double));

@@ -146,6 +146,81 @@ static int op_rayleigh_quotient_gram(hfmi_op* A, const hfmi_block* Q, int slot_T
   return HFMI_OK;
 }
 
+// The double pass for 256 < k <= HFMI_WIDE_MAXK probe vectors.  The same algorithm with the small matrices in the wide arena:
+//   * A and B^-1 are applied in column panels of at most 256 vectors (op_apply_panels);
+//   * the orthogonalisation is qr_chol_wide (always checked), Gram-Schmidt with flag 2 or after HFMI_ERR_NUMERIC;
+//   * the Rayleigh quotient is ALWAYS the literal T = (A Q)^T Q -- the Gram-form shortcut and the trusted / deferred
+//     orthogonalisation passes of double_pass_impl stay narrow-only;
+//   * T goes to the whole-GPU eigensolver (sym_eig_large, device input), whose k x r eigenvectors come back through the host
+//     and are uploaded for U = Q V.
+static int double_pass_wide(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
+                            hfmi_block* U) {
+  hfmi_ctx* ctx = Omega->ctx;
+  const int64_t N = Omega->N;
+  const int k = Omega->nvec;
+  HFMI_TRY(ctx_wide(ctx, k));
+  hfmi_block Q, Y;
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Q, N, k, &Q));
+  HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Y, N, k, &Y));
+  const hfmi_block* cur = Omega;
+  auto power_iterations = [&]() -> int {
+    cur = Omega;
+    for (int it = 0; it < s; ++it) {
+      if (Binv) {
+        int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
+        HFMI_TRY(op_apply_panels(A, cur, &Y));
+        phase_end(ctx, ph);
+        ph = phase_begin(ctx, HFMI_PHASE_BINV);
+        HFMI_TRY(op_apply_panels(Binv, &Y, &Q));
+        phase_end(ctx, ph);
+        cur = &Q;
+      } else {
+        hfmi_block* dst = (cur == &Q) ? &Y : &Q;
+        const int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
+        HFMI_TRY(op_apply_panels(A, cur, dst));
+        phase_end(ctx, ph);
+        cur = dst;
+      }
+    }
+    return HFMI_OK;
+  };
+  HFMI_TRY(power_iterations());
+  hfmi_block* Qp = const_cast<hfmi_block*>(cur);
+  hfmi_block* AQ = (Qp == &Q) ? &Y : &Q;
+  int ph = phase_begin(ctx, HFMI_PHASE_QR);
+  if (flags & 2) {
+    HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
+  } else {
+    const int qs = qr_chol_wide(Qp, B, nullptr, nullptr);
+    if (qs == HFMI_ERR_NUMERIC) {     // recomputed from Omega (deterministic) and handed to the reference's Gram-Schmidt rule
+      HFMI_TRY(power_iterations());
+      HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
+    } else if (qs != HFMI_OK) {
+      return qs;
+    }
+  }
+  phase_end(ctx, ph);
+  ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
+  double* T = wa_ptr(ctx, WA_T);                       // k x k, contiguous (ld = k): what sym_eig_large reads
+  HFMI_TRY(op_apply_panels(A, Qp, AQ));
+  HFMI_TRY(launch_tsgemm_tn(ctx, AQ->p, AQ->ld, k, Qp->p, Qp->ld, k, N, 1.0, 0.0, T, k, 1, 0));
+  phase_end(ctx, ph);
+  ph = phase_begin(ctx, HFMI_PHASE_EIG);
+  std::vector<double> d(k), V((size_t)k * r);
+  const int es = sym_eig_large(ctx, nullptr, k, flags & 1, d.data(), V.data(), r, T);
+  phase_end(ctx, ph);
+  HFMI_TRY(es);
+  ph = phase_begin(ctx, HFMI_PHASE_BACK);
+  const int ldv = (int)round_up(r, 32);                // <= round_up(k, 32): fits a slot of the arena
+  HFMI_TRY(upload_small(ctx, V.data(), k, r, wa_ptr(ctx, WA_V), ldv));
+  HFMI_TRY(launch_tsgemm_nn(ctx, Qp->p, Qp->ld, k, wa_ptr(ctx, WA_V), ldv, r, 1.0, 0.0, U->p, U->ld, N));
+  phase_end(ctx, ph);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HFMI_TRY(ctx_check_comm(ctx));
+  memcpy(host_d, d.data(), (size_t)r * sizeof(double));
+  return HFMI_OK;
+}
+
 static int double_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
                             double* host_d, hfmi_block* U, bool late_checks = true) {
   if (!A || !Omega || !host_d || !U) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
@@ -156,8 +231,9 @@ static int double_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_bl
   if (k < r) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: Omega has %d vectors, need at least the rank %d", k, r);
   if (r < 1) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: rank must be positive");
   if (U->N != N || U->nvec != r) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: U must be %lld x %d", (long long)N, r);
-  if (k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: at most %d probe vectors (got %d)", SM_MAXK, k);
+  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: at most %d probe vectors (got %d)", HFMI_WIDE_MAXK, k);
   if (s < 1) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: s must be >= 1");
+  if (k > SM_MAXK) return double_pass_wide(A, B, Binv, Omega, r, s, flags, host_d, U);
   hfmi_block Q, Y;
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Q, N, k, &Q));
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Y, N, k, &Y));

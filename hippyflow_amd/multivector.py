@@ -187,7 +187,9 @@ class MultiVector:
         L.call("hfmi_block_gemm_small", self.handle, L.ptr(alpha), 1.0, 1.0, y._mv.handle)
 
     def orthogonalize(self, method=L.QR_AUTO):
-        """Thin QR in place (Q^T Q = I); returns R (nvec x nvec, upper triangular)."""
+        """Thin QR in place (Q^T Q = I); returns R (nvec x nvec, upper triangular).  Cholesky-QR (``QR_CHOL``, ``QR_AUTO``)
+        takes up to ``WIDE_MAX_VECTORS`` = 2048 vectors: beyond 256 the nvec x nvec factorisation is blocked over the whole
+        GPU and needs one more N x nvec temporary; ``QR_MGS`` has no width limit."""
         self._writable("orthogonalize")
         R = np.zeros((self._k, self._k))
         passes = C.c_int(0)
@@ -196,7 +198,8 @@ class MultiVector:
         return R
 
     def Borthogonalize(self, B, method=L.QR_AUTO):
-        """Thin QR in place in the B inner product (Q^T B Q = I); returns (BQ, R)."""
+        """Thin QR in place in the B inner product (Q^T B Q = I); returns (BQ, R).  Widths as for ``orthogonalize``; beyond
+        256 vectors B is applied in column panels of at most 256."""
         from .operators import as_device_operator
         self._writable("Borthogonalize")
         Bop = as_device_operator(B, self._N, self.ctx)

@@ -200,7 +200,9 @@ def doublePass(A, Omega, k, s=1, check=False, sort_by_abs=False, use_mgs=False, 
     """Randomized double pass for the dominant k eigenpairs of a Hermitian operator A.
     Omega: MultiVector with nvec >= k Gaussian probe vectors (not modified).
     ``literal_T=True`` forms T = (A Q)^T Q exactly as the reference does; by default the fused route forms the same
-    matrix as scale (X Q)^T Gamma (X Q) for Gram-form operators (one fewer N x k product, k x k rank average)."""
+    matrix as scale (X Q)^T Gamma (X Q) for Gram-form operators (one fewer N x k product, k x k rank average).
+    Up to ``WIDE_MAX_VECTORS`` = 2048 probe vectors.  Beyond 256 the fused route applies A in column panels of at most 256,
+    always forms the literal T, and solves the Rayleigh-Ritz problem with the whole-GPU eigensolver."""
     nvec = Omega.nvec()
     assert nvec >= k
     A_dev, coll, mpi_op = _unwrap_collective(A)
@@ -241,7 +243,8 @@ def _as_solver_operator(Binv, N, ctx, B=None):
 
 def doublePassG(A, B, Binv, Omega, k, s=1, check=False, sort_by_abs=False, use_mgs=False, fused=True, literal_T=False):
     """Randomized double pass for A u = lambda B u (B SPD), U^T B U = I.
-    ``Binv`` is a solver object (``solve(y, x)``) as in the reference, or an operator."""
+    ``Binv`` is a solver object (``solve(y, x)``) as in the reference, or an operator.
+    Up to 2048 probe vectors, as ``doublePass``; beyond 256, A, B and B^-1 are applied in column panels of at most 256."""
     nvec = Omega.nvec()
     assert nvec >= k
     N = Omega.size()

@@ -299,7 +299,10 @@ HFMI_API int hfmi_comm_destroy(hfmi_comm* comm);
  * reference's MGS Q to round-off).  B, BQ, host_R may be NULL.
  * method: HFMI_QR_CHOL = (shifted) Cholesky-QR, repeated until orthonormal;
  *         HFMI_QR_MGS  = column-by-column Gram-Schmidt with the reference's
- *         Rutishauser re-orthogonalisation test (dependent columns zeroed). */
+ *         Rutishauser re-orthogonalisation test (dependent columns zeroed).
+ * Cholesky-QR (CHOL, AUTO) takes up to 2048 vectors: up to 256 the k x k factorisation runs on one compute unit, from 257 on
+ * (tuning key "qr_wide_min") it is a blocked factorisation over the whole GPU with Q <- Q R^-1 formed out of place in a cached
+ * temporary.  MGS has no width limit. */
 #define HFMI_QR_CHOL 0
 #define HFMI_QR_MGS 1
 #define HFMI_QR_AUTO 2 /* CHOL, falling back to MGS on breakdown */
@@ -347,7 +350,10 @@ HFMI_API int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double* 
  * flags: bit 0 = sort by |d|;  bit 1 = use HFMI_QR_MGS;  bit 3 = Jacobi instead of divide and conquer for the
  * k x k Rayleigh-Ritz problem;  bit 2 = form T = (A Q)^T Q literally (by default, for
  * operators of Gram form A = scale X^T Gamma X the same matrix is formed as scale (X Q)^T Gamma (X Q), which skips
- * the second N x k block product and shrinks the rank average of that pass to k x k). */
+ * the second N x k block product and shrinks the rank average of that pass to k x k).
+ * k <= 2048.  Beyond 256 probe vectors the operators are applied in column panels of at most 256, T is always the literal
+ * (A Q)^T Q (bit 2 is implied) and the Rayleigh-Ritz problem goes to the whole-GPU eigensolver of hfmi_sym_eig_small (bit 3 is
+ * ignored). */
 HFMI_API int hfmi_double_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
                      hfmi_block* U);
 HFMI_API int hfmi_double_pass_g(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s,
@@ -385,6 +391,12 @@ HFMI_API int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfm
  * colmajor = 1: nvecB rows of ldc >= nvecA doubles, element (i, j) at [j ldc + i] (ldc > 1: a result with both strides 1 is
  * row-major).  The WHOLE array goes up (the beta operand and the guard columns behind the fast extent) and comes
  * back, so the caller sees the result and everything the launch wrote next to it.  nsplit: 0 = library default. */
+/* The k x k Cholesky factorisation with inverse behind the wide Cholesky-QR (256 < k <= 2048; any 1 <= k <= 2048 is accepted) on
+ * a host matrix (tests): G = R^T R with the library's shift / breakdown rule (shift_rel * trace(G) on the diagonal after a pivot
+ * below pivot_tol * G_jj; pivot_tol <= 0: 64 k eps).  host_G, host_R, host_Rinv: k x k row-major; host_status[4] =
+ * min pivot ratio, || D^-1/2 G D^-1/2 - I ||_F, shifted, failed (R and R^-1 are zero filled when failed). */
+HFMI_API int hfmi_test_chol_wide(hfmi_ctx* ctx, int k, const double* host_G, double shift_rel, double pivot_tol, double* host_R,
+                                 double* host_Rinv, double* host_status);
 HFMI_API int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, double scale, double beta, int colmajor, int ldc,
                                  int nsplit, double* host_C);
 /* Plan record: every launch of a contraction kernel (k_tsgemm_tn, k_tsgemm_nn[_res], k_tsgemm_ss[b]) and of a partial-sum
@@ -453,6 +465,8 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * least 2 Gflop only (each record is a pair of stream events, 2-4 us of idle GPU between dependent kernels: scripts/prof_level_ab.py);
  * ("comm_panels", 0..8) row panels of an operator application whose
  * rank reduction overlaps the rest of the product (0 / 1 = one all-reduce after the product; default 4);
+ * ("qr_wide_min", 17..257) width from which hfmi_borth_qr takes the wide Cholesky-QR (default 257; lower values let tests compare
+ * the two routes at widths both serve);
  * ("pchol_grid", 0..65535) most workgroups per launch of hfmi_pchol_create (0 = what the device holds, default): a small value makes every
  * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits. */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
