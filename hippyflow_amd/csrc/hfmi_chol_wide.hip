@@ -6,12 +6,11 @@
 //   status words: min pivot ratio, || D^-1/2 G D^-1/2 - I ||_F of the input, shifted, failed.
 // Right-looking with blocks of CW_NB = 64 columns.  Step p:
 //   k_cw_diag   one workgroup: the diagonal block S_pp = R_pp^T R_pp and W_pp = R_pp^-1 in LDS (33 KB);
-//   k_cw_gemm   the row panel R_p,c = W_pp^T S_p,c for the columns right of the block (one 64 x 64 tile per workgroup);
-//   k_cw_gemm   the trailing update S_c,c' -= R_p,c^T R_p,c', upper tiles only.
+//   cw_gemm     the row panel R_p,c = W_pp^T S_p,c for the columns right of the block (one 64 x 64 tile per workgroup);
+//   cw_gemm     the trailing update S_c,c' -= R_p,c^T R_p,c', upper tiles only.
 // Then R^-1 by block back-substitution, bottom up: X_p,c = -W_pp (R_p,> X_>,c), two products per block row, the first one cut at the
-// diagonal of the triangular factor; and Rtot as a triangular x triangular tile product.  All products are v_mfma_f64_16x16x4_f64
-// tiles (4 waves of 32 x 32) with the operands staged k-major through two LDS buffers -- the layout of k_dgemm in
-// hfmi_eig_blocked.hip, here row-major and with the triangular cuts.
+// diagonal of the triangular factor; and Rtot as a triangular x triangular tile product.  All products are the 64 x 64 tile kernel
+// k_dgemm<TA,TB,CUT> of hfmi_dgemm.hip with its triangular cuts (cw_gemm below holds the row-major / column-major transposition).
 // A pivot at round-off level (piv <= pivot_tol * (G_jj + shift)) raises a device flag that turns every later launch of the attempt
 // into a no-op; the host, which reads the status words of a pass anyway, restarts the factorisation ONCE with the diagonal
 // shifted by shift_rel * trace(G) and reports `failed` when that breaks down too.
@@ -21,13 +20,11 @@
 
 #include <vector>
 
-#include "hfmi_gemm_common.h"
+#include "hfmi_dgemm.h"
 #include "hfmi_internal.h"
 
 namespace {
 constexpr int CW_NB = 64;            // block size of the factorisation = tile of the products
-constexpr int CW_GK = 16;            // reduction depth of an LDS stage
-constexpr int CW_GLD = 80;           // LDS row stride: = 16 mod 32 doubles (the four k-rows of an MFMA operand fall into two bank halves)
 constexpr int CW_MAXBLK = HFMI_WIDE_MAXK / CW_NB;
 constexpr double CW_EPS = 2.220446049250313e-16;
 
@@ -178,111 +175,6 @@ __global__ __launch_bounds__(256) void k_cw_diag(const double* __restrict__ W, d
   if (tid == 0) ratio[j0 / CW_NB] = ratio_local;
 }
 
-// ------------------------------------------------------------------------------------------------ fp64 MFMA tile product
-// element (t, kk) of an operand tile for thread tid, slot u of 4: t = the operand's own index, kk = the reduction index
-template <bool KC>
-__device__ __forceinline__ void cw_idx(int tid, int u, int& t, int& kk) {
-  if (KC) {           // the reduction index is the contiguous one in memory
-    kk = tid & 15;
-    t = (tid >> 4) + 16 * u;
-  } else {            // the operand's own index is contiguous
-    t = tid & 63;
-    kk = (tid >> 6) + 4 * u;
-  }
-}
-template <bool KC>
-__device__ __forceinline__ void cw_load(const double* __restrict__ X, int ld, int t0, int k0, int Tdim, int Kend, int tid, double (&r)[4]) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    int t, kk;
-    cw_idx<KC>(tid, u, t, kk);
-    const bool ok = t0 + t < Tdim && k0 + kk < Kend;
-    const size_t off = KC ? (size_t)(t0 + t) * ld + (k0 + kk) : (size_t)(k0 + kk) * ld + (t0 + t);
-    r[u] = ok ? X[off] : 0.0;
-  }
-}
-template <bool KC>
-__device__ __forceinline__ void cw_store(double (*s)[CW_GLD], int tid, const double (&r)[4]) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    int t, kk;
-    cw_idx<KC>(tid, u, t, kk);
-    s[kk][t] = r[u];
-  }
-}
-// C (M x N) = alpha op(A) op(B) + beta C, everything row-major.  op(A)(i, l) = TA ? A[l * lda + i] : A[i * lda + l];
-// op(B)(l, j) = TB ? B[j * ldb + l] : B[l * ldb + j].  One 64 x 64 tile of C per workgroup (blockIdx.y: tile row ti, blockIdx.x: tile
-// column tj), 4 waves of 32 x 32.  mode bit 0: tiles below the diagonal (ti > tj) are skipped; bit 1: the reduction stops at
-// (tj + 1) * 64 (op(B) upper triangular); bit 2: it starts at ti * 64 (op(A) upper triangular).  The MFMA's first operand carries
-// the row index of C: a register then holds 16 consecutive columns of a row, and the stores are 128-byte runs.
-template <bool TA, bool TB>
-__global__ __launch_bounds__(256) void k_cw_gemm(int M, int N, int K, double alpha, const double* __restrict__ A, int lda,
-                                                 const double* __restrict__ B, int ldb, double beta, double* __restrict__ C, int ldc,
-                                                 int mode, const int* __restrict__ flags) {
-  __shared__ double s_a[2][CW_GK][CW_GLD], s_b[2][CW_GK][CW_GLD];
-  if (flags[0]) return;
-  const int ti = blockIdx.y, tj = blockIdx.x;
-  if ((mode & 1) && ti > tj) return;
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, li = l & 15, lk = l >> 4;
-  const int wm = w & 1, wn = w >> 1;
-  const int i0 = ti * CW_NB, j0 = tj * CW_NB;
-  const int klo = (mode & 4) ? min(K, ti * CW_NB) : 0;
-  const int khi = (mode & 2) ? min(K, (tj + 1) * CW_NB) : K;
-  d4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
-  const int nk = khi > klo ? (khi - klo + CW_GK - 1) / CW_GK : 0;
-  double ra[4], rb[4];
-  auto gload = [&](int kt) {
-    const int k0 = klo + kt * CW_GK;
-    cw_load<!TA>(A, lda, i0, k0, M, khi, tid, ra);
-    cw_load<TB>(B, ldb, j0, k0, N, khi, tid, rb);
-  };
-  if (nk > 0) {
-    gload(0);
-    cw_store<!TA>(s_a[0], tid, ra);
-    cw_store<TB>(s_b[0], tid, rb);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) gload(kt + 1);
-#pragma unroll
-    for (int k4 = 0; k4 < CW_GK / 4; ++k4) {
-      double af[2], bf[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) af[mi] = s_a[buf][k4 * 4 + lk][wm * 32 + mi * 16 + li];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) bf[ni] = s_b[buf][k4 * 4 + lk][wn * 32 + ni * 16 + li];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = MFMA_F64(af[mi], bf[ni], acc[mi][ni]);
-    }
-    if (kt + 1 < nk) {
-      cw_store<!TA>(s_a[buf ^ 1], tid, ra);
-      cw_store<TB>(s_b[buf ^ 1], tid, rb);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int i = i0 + wm * 32 + mi * 16 + lk + 4 * reg, j = j0 + wn * 32 + ni * 16 + li;
-        if (i < M && j < N) {
-          double* cp = C + (size_t)i * ldc + j;
-          double v = alpha * acc[mi][ni][reg];
-          if (beta != 0.0) v = fma(beta, *cp, v);
-          *cp = v;
-        }
-      }
-}
-
 // dst = upper triangle of src (k x k), zeros below the diagonal and in the pad columns k .. ld - 1
 __global__ __launch_bounds__(256) void k_cw_copy_upper(double* __restrict__ dst, const double* __restrict__ src, int ld, int k,
                                                        const int* __restrict__ flags) {
@@ -313,13 +205,28 @@ __global__ __launch_bounds__(256) void k_cw_final(const double* __restrict__ Rto
   }
 }
 
+// C (M x N) = alpha op(A) op(B) + beta C, everything row-major with one leading dimension.  op(A)(i, l) = TA ? A[l * ld + i] : A[i * ld + l];
+// op(B)(l, j) = TB ? B[j * ld + l] : B[l * ld + j].  mode bit 0: tiles below the diagonal are skipped; bit 1: the reduction stops at
+// (tile column + 1) * 64 (op(B) upper triangular); bit 2: it starts at tile row * 64 (op(A) upper triangular).
+// Runs as the column-major product C^T = op(B)^T op(A)^T of launch_dgemm: the operands and their transposition flags trade places,
+// and the cuts of gemm_desc are these three seen from the other side.  A raised break flag makes the launch a no-op.
 template <bool TA, bool TB>
 int cw_gemm(hfmi_ctx* ctx, int M, int N, int K, double alpha, const double* A, const double* B, double beta, double* C, int ld, int mode) {
-  if (M <= 0 || N <= 0) return HFMI_OK;
-  const dim3 grid((N + CW_NB - 1) / CW_NB, (M + CW_NB - 1) / CW_NB);
-  hipLaunchKernelGGL((k_cw_gemm<TA, TB>), grid, dim3(256), 0, ctx->stream, M, N, K, alpha, A, ld, B, ld, beta, C, ld, mode, wa_flags(ctx));
-  HIP_TRY(hipGetLastError());
-  return HFMI_OK;
+  gemm_desc g;
+  g.ta = TB;
+  g.tb = TA;
+  g.M = N;
+  g.N = M;
+  g.K = K;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.A = B;
+  g.B = A;
+  g.C = C;
+  g.lda = g.ldb = g.ldc = ld;
+  g.cut = mode;
+  g.skip = wa_flags(ctx);
+  return launch_dgemm(ctx, g);
 }
 }  // namespace
 

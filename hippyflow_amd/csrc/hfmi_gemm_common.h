@@ -1,4 +1,5 @@
-// Shared by the two MFMA translation units (hfmi_gemm.hip: tsgemm_tn, hfmi_gemm_nn.hip: tsgemm_nn).
+// Shared by the fp64 MFMA translation units (hfmi_gemm.hip: tsgemm_tn, hfmi_gemm_nn.hip: tsgemm_nn, hfmi_dgemm.hip: the general
+// product) and, through hfmi_dc_common.h, by the eigensolvers.
 #pragma once
 #include "hfmi_internal.h"
 

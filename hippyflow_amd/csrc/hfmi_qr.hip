@@ -34,6 +34,37 @@ static int read_status_finish(hfmi_ctx* ctx, hfmi_status_words* out) {
   print_status_dbg(out);
   return HFMI_OK;
 }
+// The rules both Cholesky-QR loops (qr_chol, qr_chol_wide) go by.
+// Breakdown threshold on pivot / (original diagonal): only pivots that are round-off noise (64 k eps) trigger the
+// shifted factorisation.  A pass with small but genuine pivots leaves a defect ~ eps / min pivot ratio, which the
+// next pass measures (st.gram_dev) and removes -- a more cautious threshold (100 k sqrt(N) u) cost config 3 a whole
+// extra pass (shifted first pass, cond(Q1) ~ 260) without making the result more accurate.
+struct chol_qr_rules {
+  double shift_rel;                // diagonal shift of a restarted factorisation, relative to trace(G)
+  double pivot_tol = 0.0;          // the factorisations' default: 64 k eps
+  int max_passes = 6;
+  chol_qr_rules(int64_t N, int k) : shift_rel(11.0 * ((double)N * k + (double)k * (k + 1)) * 1.1102230246251565e-16) {}
+};
+// The reference's MGS zeroes a column whose norm drops below 10 eps of its pre-sweep norm
+// (numerically dependent); Cholesky-QR would instead normalise round-off noise.  R_jj / ||z_j|| is that
+// drop: hand such blocks to the Gram-Schmidt route, which reproduces the reference's behaviour.
+// aux_dev: [0, k): original column norms; [ld, ld + k): diag(Rtot)
+static int check_dependent(hfmi_ctx* ctx, const double* aux_dev, int ld, int k) {
+  std::vector<double> aux((size_t)ld + k);
+  HFMI_TRY(read_back(ctx, aux_dev, (size_t)ld + k, aux.data()));
+  for (int j = 0; j < k; ++j)
+    if (!(aux[ld + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
+      HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
+                aux[j] > 0 ? aux[ld + j] / aux[j] : 0.0);
+  return HFMI_OK;
+}
+// host_R (k x k row-major) <- the k x k matrix at dev (row-major, ld)
+static int read_r(hfmi_ctx* ctx, const double* dev, int ld, int k, double* host_R) {
+  std::vector<double> tmp((size_t)k * ld);
+  HFMI_TRY(read_back(ctx, dev, (size_t)k * ld, tmp.data()));
+  for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * ld, (size_t)k * sizeof(double));
+  return HFMI_OK;
+}
 // deferred (optional): if non-null and B == null, the LAST pass (the one whose input is already orthonormal to 1e-2 and
 // needs no shift) does not apply its R^-1: *deferred = true and R^-1 stays in SM_RINV for the caller to fold into
 // the small matrices downstream (Q = Q_in R^-1 is never formed: one N x k x k contraction less).
@@ -56,15 +87,8 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
     HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
     BZ = &bz_view;
   }
-  const double u = 1.1102230246251565e-16;
-  const double shift_rel = 11.0 * ((double)N * k + (double)k * (k + 1)) * u;
-  // Breakdown threshold on pivot / (original diagonal): only pivots that are round-off noise (64 k eps) trigger the
-  // shifted factorisation.  A pass with small but genuine pivots leaves a defect ~ eps / min pivot ratio, which the
-  // next pass measures (st.gram_dev) and removes -- a more cautious threshold (100 k sqrt(N) u) cost config 3 a whole
-  // extra pass (shifted first pass, cond(Q1) ~ 260) without making the result more accurate.
-  const double pivot_tol = 0.0;   // launch_chol_inv default: 64 k eps
+  const chol_qr_rules rules(N, k);
   int passes = 0;
-  const int max_passes = 6;
   bool first_pass_clean = false;
   if (g_qr_trust_first < 0) {
     const char* e = getenv("HFMI_QR_TRUST_FIRST");
@@ -86,7 +110,7 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
       // pass's (below); a shifted / failed first pass sends the whole solve to the checked path (double_pass_impl).
       hfmi_status_words* const keep = ctx->status_dev;
       ctx->status_dev = keep + 1;
-      const int cs = launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, shift_rel, pivot_tol);
+      const int cs = launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, rules.shift_rel, rules.pivot_tol);
       ctx->status_dev = keep;
       HFMI_TRY(cs);
       HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
@@ -95,7 +119,7 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
       ++passes;
       continue;
     }
-    HFMI_TRY(launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, shift_rel, pivot_tol));
+    HFMI_TRY(launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, rules.shift_rel, rules.pivot_tol));
     hfmi_status_words st;
     if (deferred && !B && passes == 1 && opt && first_pass_clean) {
       HFMI_TRY(side_copies_begin(ctx));
@@ -136,19 +160,9 @@ int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_
     // The input of this pass had orthonormality defect st.gram_dev (column-scaled).  If it was already
     // small and no shift was needed, the output is orthonormal to round-off: done.
     if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
-    if (passes >= max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
+    if (passes >= rules.max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
   }
-  // The reference's MGS zeroes a column whose norm drops below 10 eps of its pre-sweep norm
-  // (numerically dependent); Cholesky-QR would instead normalise round-off noise.  R_jj / ||z_j|| is that
-  // drop: hand such blocks to the Gram-Schmidt route, which reproduces the reference's behaviour.
-  {
-    std::vector<double> aux((size_t)SM_LD + k);       // [0, k): original column norms; [SM_LD, SM_LD + k): diag(R)
-    HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_AUX), (size_t)SM_LD + k, aux.data()));
-    for (int j = 0; j < k; ++j)
-      if (!(aux[SM_LD + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
-        HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
-                  aux[j] > 0 ? aux[SM_LD + j] / aux[j] : 0.0);
-  }
+  HFMI_TRY(check_dependent(ctx, sm_ptr(ctx, SM_AUX), SM_LD, k));
   (void)want_r;
   if (B && BQ) HFMI_TRY(hfmi_op_apply(B, Q, BQ, 0));
   if (passes_out) *passes_out = passes;
@@ -187,11 +201,8 @@ int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
     BZ = &bz_view;
   }
   HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_WIDE, N, k, &pong));
-  const double u = 1.1102230246251565e-16;
-  const double shift_rel = 11.0 * ((double)N * k + (double)k * (k + 1)) * u;
-  const double pivot_tol = 0.0;   // 64 k eps, as in qr_chol
+  const chol_qr_rules rules(N, k);
   int passes = 0;
-  const int max_passes = 6;
   hfmi_block* cur = Q;
   hfmi_block* nxt = &pong;
   for (;;) {
@@ -202,7 +213,7 @@ int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
     }
     HFMI_TRY(launch_tsgemm_tn(ctx, cur->p, cur->ld, k, right->p, right->ld, k, N, 1.0, 0.0, wa_ptr(ctx, WA_GRAM), ld, 1, 0));
     hfmi_status_words st;
-    HFMI_TRY(launch_chol_wide(ctx, k, passes == 0 ? 1 : 2, shift_rel, pivot_tol, &st));
+    HFMI_TRY(launch_chol_wide(ctx, k, passes == 0 ? 1 : 2, rules.shift_rel, rules.pivot_tol, &st));
     if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
     // Q R^-1 in column panels of 256 issued here, not inside launch_tsgemm_nn: columns r0 .. r0 + rp - 1 of the upper triangular R^-1
     // are zero below row r0 + rp, so the panel's reduction stops there (half the work, the same bits), and the upper-triangular
@@ -217,17 +228,10 @@ int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
     std::swap(cur, nxt);
     ++passes;
     if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
-    if (passes >= max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
+    if (passes >= rules.max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
   }
   if (cur != Q) HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, cur->p, cur->ld, N, k));
-  {
-    std::vector<double> aux((size_t)ld + k);          // [0, k): original column norms; [ld, ld + k): diag(Rtot)
-    HFMI_TRY(read_back(ctx, wa_aux(ctx), (size_t)ld + k, aux.data()));
-    for (int j = 0; j < k; ++j)
-      if (!(aux[ld + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
-        HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
-                  aux[j] > 0 ? aux[ld + j] / aux[j] : 0.0);
-  }
+  HFMI_TRY(check_dependent(ctx, wa_aux(ctx), ld, k));
   if (B && BQ) HFMI_TRY(op_apply_panels(B, Q, BQ));
   if (passes_out) *passes_out = passes;
   return HFMI_OK;
@@ -333,17 +337,9 @@ int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool wan
     return qr_mgs(Q, B, BQ, host_R, passes);
   }
   if (s != HFMI_OK) return s;
-  if (host_R && (k > SM_MAXK || k >= g_qr_wide_min)) {   // the wide route was taken: Rtot sits in the wide arena
-    const int ld = (int)round_up(k, 32);
-    std::vector<double> tmp((size_t)k * ld);
-    HFMI_TRY(read_back(ctx, wa_ptr(ctx, WA_RTOT), (size_t)k * ld, tmp.data()));
-    for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * ld, (size_t)k * sizeof(double));
-  } else if (host_R) {
-    std::vector<double> tmp((size_t)k * SM_LD);
-    HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_RTOT), (size_t)k * SM_LD, tmp.data()));
-    for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * SM_LD, (size_t)k * sizeof(double));
-  }
-  return HFMI_OK;
+  if (!host_R) return HFMI_OK;
+  if (k > SM_MAXK || k >= g_qr_wide_min) return read_r(ctx, wa_ptr(ctx, WA_RTOT), (int)round_up(k, 32), k, host_R);   // the wide route was taken
+  return read_r(ctx, sm_ptr(ctx, SM_RTOT), SM_LD, k, host_R);
 }
 extern "C" int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes) {
   return borth_qr(Q, B, BQ, host_R, host_R != nullptr, method, passes);

@@ -1,4 +1,4 @@
-"""TFLOP/s of the eigensolver's general fp64 MFMA product (k_dgemm_p / k_dgemm, hfmi_eig_blocked.hip) on the shapes the solver runs:
+"""TFLOP/s of the eigensolver's general fp64 MFMA product (k_dgemm_p / k_dgemm, hfmi_dgemm.hip) on the shapes the solver runs:
 python scripts/dgemm_rate.py [--old]   (--old: HFMI_EIG_GEMM=0, the 64 x 64 kernel of round 5 everywhere)."""
 import os
 import sys

@@ -399,10 +399,12 @@ def test_sym_eig_blocked_ab_knobs_give_the_same_spectrum(ctx, tmp_path, env):
 
 
 @pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True), (True, True)])
-@pytest.mark.parametrize("M,N,K", [(1536, 2048, 200), (1111, 1793, 77), (256, 8192, 1030), (2050, 2050, 128), (300, 200, 64)])
+@pytest.mark.parametrize("M,N,K", [(1536, 2048, 200), (1111, 1793, 77), (256, 8192, 1030), (2050, 2050, 128), (300, 200, 64),
+                                   (64, 64, 16), (65, 63, 17), (1, 130, 3), (130, 1, 67)])
 def test_dgemm_of_the_eigensolver_matches_numpy(ctx, ta, tb, M, N, K):
     """The general fp64 MFMA product behind the trailing updates, the merges and the block reflectors (software-pipelined 128 x 128 /
-    64 x 128 tiles where they fill the chip, the 64 x 64 kernel otherwise; odd sizes take the 8-byte load path and the edge guards)
+    64 x 128 tiles where they fill the chip, the 64 x 64 kernel otherwise -- the wide Cholesky runs on that one too; odd sizes take the
+    8-byte load path and the edge guards; the small shapes straddle the 64-tile edges, the 16-deep stage and the 4-deep MFMA step)
     against numpy, to a few ulps of the accumulated magnitude."""
     rng = np.random.default_rng(M + 3 * N + 7 * K + ta + 2 * tb)
     A = rng.standard_normal((K, M) if ta else (M, K))

@@ -45,7 +45,7 @@ def dev_chol_wide(ctx, G, shift_rel, pivot_tol=0.0):
     return R, X, {"min_pivot_ratio": st[0], "gram_dev": st[1], "shifted": int(st[2]), "failed": int(st[3])}
 
 
-@pytest.mark.parametrize("k", [257, 300, 511, 512, 513, 1000, 2048])
+@pytest.mark.parametrize("k", [65, 129, 130, 257, 300, 511, 512, 513, 1000, 2048])
 def test_chol_wide_against_lapack_and_the_twin(ctx, k):
     G = gram_with_condition(k, 1e4, seed=k)
     shift_rel = qr_shift_rel(2 * k, k)
