@@ -16,6 +16,7 @@ UNIQUE_ID_BYTES = 256
 WIDE_MAX_VECTORS = 2048                                # orthogonalize / Borthogonalize / doublePass[G]: HFMI_WIDE_MAXK of the library
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
 KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
+KERNEL_NO_DIAGONAL = -1                                # HFMI_KERNEL_NO_DIAGONAL: no target of a cross-covariance is a source
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
 PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h
 
@@ -75,6 +76,8 @@ SIGNATURES = {
     "hfmi_op_jjt": [_P, _P, C.c_int, C.c_int, C.c_double, _PP],
     "hfmi_op_dense_sym": [_P, _P, _PP],
     "hfmi_op_kernel_cov": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
+    "hfmi_op_kernel_cross_cov": [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_rows": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64, _PP],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

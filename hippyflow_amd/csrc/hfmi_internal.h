@@ -217,7 +217,7 @@ struct hfmi_csr {
   int cheb_state;
 };
 
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV };
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS };
 
 struct hfmi_op {
   hfmi_ctx* ctx;
@@ -239,6 +239,12 @@ struct hfmi_op {
   int64_t kc_N;
   int kc_d, kc_family;
   double kc_sigma, kc_ell, kc_nugget;
+  // OP_KERNEL_CROSS: K(T, S) with S in kc_x (kc_N points).  kc_slab: T = S[kc_diag : kc_diag + kc_M], Y is addressed at row kc_diag and
+  // an overwriting apply zeroes its other rows (hfmi_op_kernel_cov_rows).  Otherwise T is kc_t (owned, one array of kc_M doubles per
+  // dimension) and Y has kc_M rows; kc_diag: target i is source i + kc_diag, HFMI_KERNEL_NO_DIAGONAL for none (hfmi_op_kernel_cross_cov).
+  double* kc_t;
+  int64_t kc_M, kc_diag;
+  bool kc_slab;
   hfmi_host_apply_fn host_fn;
   void* host_user;
   int64_t host_N;
@@ -289,6 +295,11 @@ int launch_tsgemm_nn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const d
 // Y (+)= C W with C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij evaluated in registers (hfmi_kcov.hip); x: d arrays of N doubles
 int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
                       const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
+// Y (M rows) (+)= K W (N rows), K_ij = sigma^2 phi(|t_i - x_j| / ell) + nugget [j == i + diag_offset] (diag_offset < 0: no nugget); t: d
+// arrays of M doubles, tstride apart.  Same per-row summation order as launch_kernel_cov.  M = 0: nothing is launched.
+int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
+                            int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
+                            int64_t ldy, int nvec, int accumulate);
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

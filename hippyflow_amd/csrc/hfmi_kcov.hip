@@ -15,6 +15,13 @@
 // LDS image of a chunk: [column][66] doubles (64 rows + 2 of padding).  A column's stride is 132 dwords = 4 (mod 64 banks), so the 16
 // columns x 2 k-rows a half-wave reads as its B fragment fall on 32 different bank pairs, and the staging stores (lanes along the rows of
 // one column) are contiguous.
+//
+// Rectangular form (the kcov_cross_params instances; hfmi_op_kernel_cross_cov, hfmi_op_kernel_cov_rows):  Y (M rows) (+)= K W (N rows),
+// K_ij = sigma^2 phi(|t_i - s_j| / ell) + nugget [j == i + diag_offset].  Same layout and the same sweep over ALL sources, with the row
+// coordinates read from a second point set t (M targets) and the nugget on the source index i + diag_offset.  A row's sum does not depend
+// on the tile, wave or lane row that holds it, so with t = s[row0 : row0 + M] and diag_offset = row0 the result is the same bits as rows
+// row0 .. row0 + M - 1 of the square apply: a row slab per rank, summed over the ranks, IS the square apply.  The square instances take
+// kcov_params as before: neither their arguments nor their registers know of the second set.
 #include <algorithm>
 
 #include "hfmi_gemm_common.h"
@@ -26,23 +33,38 @@
 #define KC_ROWS (16 * KC_WAVES)
 #define KC_MAXT 9           // column tiles per panel: 144 columns, k = 138 is one pass
 
-template <int NT>
-__global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const double* __restrict__ W, int64_t ldw, double* __restrict__ Y,
+// what differs between the two argument types: the number of rows, their coordinates, and the source index a row's nugget sits on
+__device__ __forceinline__ int64_t kcov_targets(const kcov_params& P) { return P.N; }
+__device__ __forceinline__ int64_t kcov_targets(const kcov_cross_params& P) { return P.M; }
+__device__ __forceinline__ const double* kcov_t0(const kcov_params& P) { return P.x0; }
+__device__ __forceinline__ const double* kcov_t1(const kcov_params& P) { return P.x1; }
+__device__ __forceinline__ const double* kcov_t2(const kcov_params& P) { return P.x2; }
+__device__ __forceinline__ const double* kcov_t0(const kcov_cross_params& P) { return P.t0; }
+__device__ __forceinline__ const double* kcov_t1(const kcov_cross_params& P) { return P.t1; }
+__device__ __forceinline__ const double* kcov_t2(const kcov_cross_params& P) { return P.t2; }
+__device__ __forceinline__ int64_t kcov_diag_source(const kcov_params&, int64_t gi) { return gi; }
+__device__ __forceinline__ int64_t kcov_diag_source(const kcov_cross_params& P, int64_t gi) { return P.diag_offset >= 0 ? gi + P.diag_offset : -1; }
+
+template <int NT, class PT>      // PT: kcov_params (square) or kcov_cross_params (rectangular)
+__global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(PT P, const double* __restrict__ W, int64_t ldw, double* __restrict__ Y,
                                                         int64_t ldy, int ncols, int accumulate) {
   __shared__ double wl[16 * NT * KC_JCP];
   __shared__ double xl[3 * KC_JC];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int64_t N = P.N;
+  const int64_t N = P.N;                       // sources: rows of W
+  const int64_t M = kcov_targets(P);           // targets: rows of Y
   const int d = P.d;
-  const int64_t ntiles = (N + KC_ROWS - 1) / KC_ROWS;
+  const int64_t ntiles = (M + KC_ROWS - 1) / KC_ROWS;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t row0 = tile * KC_ROWS + wave * 16;
     const int64_t gi = row0 + lr;
-    const bool iv = gi < N;
-    const double xi0 = iv ? P.x0[gi] : 0.0;
-    const double xi1 = (iv && d > 1) ? P.x1[gi] : 0.0;
-    const double xi2 = (iv && d > 2) ? P.x2[gi] : 0.0;
+    const bool iv = gi < M;
+    // the source index the nugget of row gi sits on: gi itself for the square operator, none (-1) for disjoint point sets
+    const int64_t gd = kcov_diag_source(P, gi);
+    const double xi0 = iv ? kcov_t0(P)[gi] : 0.0;
+    const double xi1 = (iv && d > 1) ? kcov_t1(P)[gi] : 0.0;
+    const double xi2 = (iv && d > 2) ? kcov_t2(P)[gi] : 0.0;
     d4 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
@@ -69,7 +91,7 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const dou
       if (j0 + KC_JC < N) fetch(j0 + KC_JC);
       const int64_t left = N - j0;
       const int nslab = left >= KC_JC ? KC_JC / 4 : (int)((left + 3) / 4);
-      // one entry of C per lane: row gi, column j0 + 4 s + lk
+      // one entry of K per lane: row gi, column j0 + 4 s + lk
       auto eval = [&](int s) -> double {
         const int jj = 4 * s + lk;
         const int64_t gj = j0 + jj;
@@ -83,7 +105,7 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const dou
           const double dz = xi2 - xl[2 * KC_JC + jj];
           r2 = fma(dz, dz, r2);
         }
-        const double v = kcov_entry(P, r2, gi == gj);
+        const double v = kcov_entry(P, r2, gd == gj);
         return (iv && gj < N) ? v : 0.0;
       };
       double a_next = eval(0);
@@ -106,21 +128,21 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(kcov_params P, const dou
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t row = row0 + lk + 4 * r;
-          if (row < N) yc[row] = accumulate ? yc[row] + acc[t][r] : acc[t][r];
+          if (row < M) yc[row] = accumulate ? yc[row] + acc[t][r] : acc[t][r];
         }
       }
     }
   }
 }
 
-template <int NT>
-static int kcov_launch(hfmi_ctx* ctx, const kcov_params& P, const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate) {
+template <int NT, class PT>
+static int kcov_launch(hfmi_ctx* ctx, const PT& P, int64_t M, const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate) {
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kcov<NT>, 64 * KC_WAVES, 0));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kcov<NT, PT>, 64 * KC_WAVES, 0));
   if (per_cu < 1) per_cu = 1;
-  const int64_t ntiles = (P.N + KC_ROWS - 1) / KC_ROWS;
+  const int64_t ntiles = (M + KC_ROWS - 1) / KC_ROWS;
   const int64_t grid = std::min<int64_t>(ntiles, (int64_t)per_cu * ctx->num_cus);
-  hipLaunchKernelGGL(k_kcov<NT>, dim3((unsigned)grid), dim3(64 * KC_WAVES), 0, ctx->stream, P, W, ldw, Y, ldy, ncols, accumulate);
+  hipLaunchKernelGGL((k_kcov<NT, PT>), dim3((unsigned)grid), dim3(64 * KC_WAVES), 0, ctx->stream, P, W, ldw, Y, ldy, ncols, accumulate);
   HIP_TRY(hipGetLastError());
   return HFMI_OK;
 }
@@ -147,25 +169,48 @@ int kcov_params_init(kcov_params* out, const double* x, int64_t N, int d, int fa
   return HFMI_OK;
 }
 
-int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
-  kcov_params P;
-  HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
+// panels of at most 144 columns, one instance per number of column tiles
+template <class PT>
+static int kcov_panels(hfmi_ctx* ctx, const PT& P, int64_t M, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
   for (int c0 = 0; c0 < nvec; c0 += 16 * KC_MAXT) {
     const int nc = std::min(16 * KC_MAXT, nvec - c0);
     const double* Wp = W + (int64_t)c0 * ldw;
     double* Yp = Y + (int64_t)c0 * ldy;
     switch ((nc + 15) / 16) {
-      case 1: HFMI_TRY(kcov_launch<1>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 2: HFMI_TRY(kcov_launch<2>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 3: HFMI_TRY(kcov_launch<3>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 4: HFMI_TRY(kcov_launch<4>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 5: HFMI_TRY(kcov_launch<5>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 6: HFMI_TRY(kcov_launch<6>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 7: HFMI_TRY(kcov_launch<7>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      case 8: HFMI_TRY(kcov_launch<8>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
-      default: HFMI_TRY(kcov_launch<9>(ctx, P, Wp, ldw, Yp, ldy, nc, accumulate)); break;
+      case 1: HFMI_TRY((kcov_launch<1, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 2: HFMI_TRY((kcov_launch<2, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 3: HFMI_TRY((kcov_launch<3, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 4: HFMI_TRY((kcov_launch<4, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 5: HFMI_TRY((kcov_launch<5, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 6: HFMI_TRY((kcov_launch<6, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 7: HFMI_TRY((kcov_launch<7, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      case 8: HFMI_TRY((kcov_launch<8, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
+      default: HFMI_TRY((kcov_launch<9, PT>(ctx, P, M, Wp, ldw, Yp, ldy, nc, accumulate))); break;
     }
   }
   return HFMI_OK;
+}
+
+int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+  kcov_params P;
+  HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
+  return kcov_panels(ctx, P, N, W, ldw, Y, ldy, nvec, accumulate);
+}
+
+int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
+                            int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
+                            int64_t ldy, int nvec, int accumulate) {
+  if (M < 1) return HFMI_OK;      // an empty slab: no row of Y is this operator's
+  if (diag_offset >= 0 && diag_offset + M > N)
+    HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: targets %lld .. %lld are not sources (N = %lld)", (long long)diag_offset,
+              (long long)(diag_offset + M - 1), (long long)N);
+  kcov_cross_params P;
+  HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
+  P.t0 = t;
+  P.t1 = d > 1 ? t + tstride : t;
+  P.t2 = d > 2 ? t + 2 * tstride : t;
+  P.M = M;
+  P.diag_offset = diag_offset >= 0 ? diag_offset : -1;
+  return kcov_panels(ctx, P, M, W, ldw, Y, ldy, nvec, accumulate);
 }

@@ -1,5 +1,6 @@
 // One entry of a kernel covariance, C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij: the parameters and the evaluation shared by
-// the matrix-free apply (hfmi_kcov.hip) and the pivoted Cholesky factorisation (hfmi_pchol.hip), so that both see the same matrix.
+// the matrix-free apply (hfmi_kcov.hip) and the pivoted Cholesky factorisation (hfmi_pchol.hip), so that both see the same matrix.  The
+// rectangular apply K(T, S) reads its rows' coordinates from a second point set (kcov_cross_params) and puts the nugget on source i + diag_offset.
 #pragma once
 #include "hfmi_internal.h"
 
@@ -12,6 +13,14 @@ struct kcov_params {
   double p1, p2;            // phi = (1 + p1 a + p2 a^2) exp(-g)
   double g1, g2;            // g = a (g1 + g2 a)
   double sigma2, nugget;
+};
+
+// what the rectangular apply K(T, S) adds: the rows' (targets') coordinates.  A type of its own, so that the square instances of k_kcov
+// and the factorisation's kernels take the argument block they always took and compile to the code they always were.
+struct kcov_cross_params : kcov_params {
+  const double *t0, *t1, *t2;   // target coordinates, M per array (t1, t2 alias t0 when d is smaller: never read)
+  int64_t M;
+  int64_t diag_offset;          // target i is source i + diag_offset; -1: no target is a source (no nugget anywhere)
 };
 
 // x: d arrays of N doubles on the device; HFMI_ERR_INVALID for an unknown family (hfmi_kcov.hip)

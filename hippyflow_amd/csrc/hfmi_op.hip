@@ -85,27 +85,39 @@ extern "C" int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** o
   *out = op;
   return HFMI_OK;
 }
-extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
-                                  double nugget, hfmi_op** out) {
-  if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  if (N < 1) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: needs at least one point (N = %lld)", (long long)N);
-  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: points have 1, 2 or 3 coordinates, got d = %d", d);
-  if (family < HFMI_KERNEL_MATERN12 || family > HFMI_KERNEL_SQEXP) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: unknown kernel family %d", family);
-  if (!(ell > 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: correlation length must be positive");
-  if (!(nugget >= 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: nugget must not be negative");
-  hfmi_op* op = op_new(ctx, OP_KERNEL_COV);
-  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  // one array per coordinate on the device (the kernel reads x_c[j] for runs of consecutive j)
-  std::vector<double> soa((size_t)N * d);
-  for (int64_t i = 0; i < N; ++i)
-    for (int c = 0; c < d; ++c) soa[(size_t)c * N + i] = host_points[(size_t)i * d + c];
+// the checks every kernel covariance constructor shares
+static int kcov_check(const char* who, int64_t N, int d, int family, double ell, double nugget) {
+  if (N < 1) HFMI_FAIL(HFMI_ERR_INVALID, "%s: needs at least one point (N = %lld)", who, (long long)N);
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "%s: points have 1, 2 or 3 coordinates, got d = %d", who, d);
+  if (family < HFMI_KERNEL_MATERN12 || family > HFMI_KERNEL_SQEXP) HFMI_FAIL(HFMI_ERR_INVALID, "%s: unknown kernel family %d", who, family);
+  if (!(ell > 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "%s: correlation length must be positive", who);
+  if (!(nugget >= 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "%s: nugget must not be negative", who);
+  return HFMI_OK;
+}
+// host points (n x d row-major) -> one array per coordinate on the device (the kernel reads x_c[j] for runs of consecutive j)
+static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t n, int d, double** out) {
+  std::vector<double> soa((size_t)n * d);
+  for (int64_t i = 0; i < n; ++i)
+    for (int c = 0; c < d; ++c) soa[(size_t)c * n + i] = host_points[(size_t)i * d + c];
+  double* x = nullptr;
   hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&op->kc_x, soa.size() * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(op->kc_x, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&x, soa.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(x, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (op->kc_x) (void)hipFree(op->kc_x);
+    if (x) (void)hipFree(x);
+    HFMI_FAIL(HFMI_ERR_HIP, "kernel covariance points: %s", hipGetErrorString(e));
+  }
+  *out = x;
+  return HFMI_OK;
+}
+static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                       double nugget, hfmi_op** out) {
+  hfmi_op* op = op_new(ctx, kind);
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  const int s = kcov_upload_points(ctx, host_points, N, d, &op->kc_x);
+  if (s != HFMI_OK) {
     delete op;
-    HFMI_FAIL(HFMI_ERR_HIP, "op_kernel_cov: %s", hipGetErrorString(e));
+    return s;
   }
   op->kc_N = N;
   op->kc_d = d;
@@ -113,6 +125,51 @@ extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int6
   op->kc_sigma = sigma;
   op->kc_ell = ell;
   op->kc_nugget = nugget;
+  *out = op;
+  return HFMI_OK;
+}
+extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                                  double nugget, hfmi_op** out) {
+  if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  HFMI_TRY(kcov_check("kernel_cov", N, d, family, ell, nugget));
+  return kcov_op_new(ctx, OP_KERNEL_COV, host_points, N, d, family, sigma, ell, nugget, out);
+}
+extern "C" int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                        int family, double sigma, double ell, double nugget, int64_t diag_offset, hfmi_op** out) {
+  if (!ctx || !host_targets || !host_sources || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  HFMI_TRY(kcov_check("kernel_cross_cov", N, d, family, ell, nugget));
+  if (M < 1) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: needs at least one target (M = %lld)", (long long)M);
+  if (diag_offset == HFMI_KERNEL_NO_DIAGONAL) {
+    if (nugget != 0.0) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: a nugget needs targets that are sources (diag_offset >= 0)");
+  } else if (diag_offset < 0 || diag_offset > N - M) {
+    HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: diag_offset = %lld with M = %lld targets does not lie inside the N = %lld sources",
+              (long long)diag_offset, (long long)M, (long long)N);
+  }
+  hfmi_op* op = nullptr;
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &op));
+  const int s = kcov_upload_points(ctx, host_targets, M, d, &op->kc_t);
+  if (s != HFMI_OK) {
+    (void)hfmi_op_destroy(op);
+    return s;
+  }
+  op->kc_M = M;
+  op->kc_diag = diag_offset;
+  op->kc_slab = false;
+  *out = op;
+  return HFMI_OK;
+}
+extern "C" int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                                       double nugget, int64_t row0, int64_t nrows, hfmi_op** out) {
+  if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  HFMI_TRY(kcov_check("kernel_cov_rows", N, d, family, ell, nugget));
+  if (row0 < 0 || nrows < 0 || row0 > N - nrows)
+    HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_rows: rows %lld .. %lld + %lld do not lie inside 0 .. N = %lld", (long long)row0, (long long)row0,
+              (long long)nrows, (long long)N);
+  hfmi_op* op = nullptr;
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_points, N, d, family, sigma, ell, nugget, &op));
+  op->kc_M = nrows;
+  op->kc_diag = row0;
+  op->kc_slab = true;
   *out = op;
   return HFMI_OK;
 }
@@ -202,11 +259,12 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
   if (!op) return HFMI_OK;
-  if (op->gamma_inv || op->weights || op->kc_x) {
+  if (op->gamma_inv || op->weights || op->kc_x || op->kc_t) {
     (void)hipStreamSynchronize(op->ctx->stream);
     if (op->gamma_inv) (void)hipFree(op->gamma_inv);
     if (op->weights) (void)hipFree(op->weights);
     if (op->kc_x) (void)hipFree(op->kc_x);
+    if (op->kc_t) (void)hipFree(op->kc_t);
   }
   delete op;
   return HFMI_OK;
@@ -408,6 +466,29 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       // Y (+)= C W: the kernel adds into Y itself
       return launch_kernel_cov(ctx, op->kc_x, op->kc_N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget, W->p, W->ld,
                                Y->p, Y->ld, k, beta != 0.0);
+    }
+    case OP_KERNEL_CROSS: {
+      const int64_t N = op->kc_N, M = op->kc_M;
+      const int acc = beta != 0.0;
+      if (!op->kc_slab) {
+        if (N != W->N || M != Y->N)
+          HFMI_FAIL(HFMI_ERR_INVALID, "operator maps vectors of length %lld to length %lld, got %lld -> %lld", (long long)N, (long long)M,
+                    (long long)W->N, (long long)Y->N);
+        return launch_kernel_cross_cov(ctx, op->kc_x, N, op->kc_t, M, M, op->kc_diag, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell,
+                                       op->kc_nugget, W->p, W->ld, Y->p, Y->ld, k, acc);
+      }
+      if (N != W->N || N != Y->N)
+        HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)N, (long long)W->N, (long long)Y->N);
+      // rows row0 .. row0 + M - 1 of C W; an overwriting apply leaves +0.0 in the other rows below N (the rows from N on are zero already)
+      const int64_t row0 = op->kc_diag, row1 = row0 + M;
+      if (!acc) {
+        if (row0 > 0)
+          HIP_TRY(hipMemset2DAsync(Y->p, (size_t)Y->ld * sizeof(double), 0, (size_t)row0 * sizeof(double), (size_t)k, ctx->stream));
+        if (row1 < N)
+          HIP_TRY(hipMemset2DAsync(Y->p + row1, (size_t)Y->ld * sizeof(double), 0, (size_t)(N - row1) * sizeof(double), (size_t)k, ctx->stream));
+      }
+      return launch_kernel_cross_cov(ctx, op->kc_x, N, op->kc_x + row0, M, N, row0, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell,
+                                     op->kc_nugget, W->p, W->ld, Y->p + row0, Y->ld, k, acc);
     }
     case OP_CSR: {
       if (op->csr->ncols != W->N || op->csr->nrows != Y->N) HFMI_FAIL(HFMI_ERR_INVALID, "csr operator / block shape mismatch");

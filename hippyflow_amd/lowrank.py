@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib as L
 from .multivector import MatMvMult, MultiVector, MvDSmatMult
-from .operators import CsrOperator, KernelCovarianceOperator, as_device_operator
+from .operators import CsrOperator, KernelCovarianceOperator, KernelCrossCovarianceOperator, as_device_operator
 
 
 class _Factorisation:
@@ -53,6 +53,8 @@ class PivotedCholesky:
         L.call("hfmi_pchol_read", self.handle, L.ptr(self.pivots), L.ptr(self.trace))
         self.N = op.shape[0]
         self._L = None
+        self._kernel = (op.points, op.family, op.sigma, op.ell)     # what extend() evaluates K(., X_P) with
+        self._LP_invT = None
 
     @property
     def L(self):
@@ -115,6 +117,30 @@ class PivotedCholesky:
         X = MultiVector(self.N, int(n), ctx=self.ctx)
         MvDSmatMult(self.L, xi.to_dense(), X)
         return X, xi
+
+
+    def extend(self, points):
+        """The factor at other points: ``L* = K(points, X_P) L_P^-T`` with ``X_P`` the pivot points and ``L_P = L[pivots, :]`` (rank x
+        rank, lower triangular in pivot order, inverted on the host).  A ``MultiVector`` of ``rank`` vectors with one row per point;
+        at the operator's own points it reproduces ``L``.  No nugget enters: a nugget belongs to the point it sits on."""
+        from scipy.linalg import solve_triangular
+        if self.rank < 1:
+            raise ValueError("extend: the factor has rank 0")
+        pts, family, sigma, ell = self._kernel
+        if self._LP_invT is None:
+            LP = self.L.to_dense()[self.pivots, :]
+            self._LP_invT = np.ascontiguousarray(solve_triangular(LP, np.eye(self.rank), lower=True).T)
+        cross = KernelCrossCovarianceOperator(points, pts[self.pivots], family, sigma, ell, ctx=self.ctx)
+        out = MultiVector(cross.shape[0], self.rank, ctx=self.ctx)
+        cross.matMvMult(MultiVector.from_dense(self._LP_invT, ctx=self.ctx), out)
+        return out
+
+    def sample_at(self, points, xi):
+        """``L* xi``: the draws ``sample`` returned as ``L xi``, evaluated at ``points`` (``xi``: its rank x n block)."""
+        Ls = self.extend(points)
+        X = MultiVector(Ls.size(), xi.nvec(), ctx=self.ctx)
+        MvDSmatMult(Ls, xi.to_dense(), X)
+        return X
 
 
 def pivoted_cholesky(op, max_rank, rel_tol=0.0):

@@ -10,6 +10,8 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``MeanJJTfromDataOperator``                     JJT summed/averaged: modeling/jacobian.py:169-193, activeSubspaceProjector.py:640-645
 * ``npToDeviceOperator``                          npToDolfinOperator, modeling/operatorWrappers.py:19-52 (symmetric case)
 * ``KernelCovarianceOperator``                    the same role for a kernel covariance given by node coordinates, never assembled
+* ``KernelCrossCovarianceOperator``               K(T, S) between two point sets (Nystrom extension); ``KernelCovarianceOperator.rows`` /
+                                                  ``.sharded``: a row slab of C per rank, completed by the collective's SUM
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
 * ``CsrAMGSolver`` / ``BiLaplacianRsolver``       hippylib BiLaplacianPrior.Asolver (CG + AMG) and prior.Rsolver = A^-1 M A^-1
                                                   (activeSubspaceProjector.py:447-453, KLEProjector.py:163-168)
@@ -258,6 +260,200 @@ class KernelCovarianceOperator(DeviceOperator):
     def to_dense(self, rows=None):
         """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
         return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows)
+
+    def rows(self, row0, row1):
+        """Rows ``row0 .. row1 - 1`` of this operator as an operator N -> N (``KernelCovarianceRowsOperator``)."""
+        return KernelCovarianceRowsOperator(self.points, self.family, self.sigma, self.ell, self.nugget, row0, row1, ctx=self.ctx)
+
+    def sharded(self, collective):
+        """An operator N -> N that equals C on every rank of ``collective``: this rank's row slab (``shard_rows``) with the collective's
+        SUM attached for the object's lifetime -- a ``NativeCollective`` through ``hfmi_op_set_collective`` (the all-reduce is enqueued by
+        the C apply itself), any other collective as a post-apply hook; ``NullCollective`` or one rank attaches nothing.  Each rank
+        does 2 N^2 k / size flops; the slabs' rows are the bits of the full apply and the other rows are zeros, so the result is the
+        full apply bit for bit.  Use it wherever C goes (doublePass, MassPreconditionedCovarianceOperator, singlePass,
+        StreamedSketch); accumulating into it is the library's "ambiguous" error."""
+        size, rank = int(collective.size()), int(collective.rank())
+        op = self.rows(*shard_rows(self.shape[0], size, rank))
+        if size > 1 and not _is_null_collective(collective):
+            op._attach_sum(collective)
+        return op
+
+
+def _is_null_collective(collective):
+    from .collectives import NullCollective
+    return isinstance(collective, NullCollective)
+
+
+def shard_rows(N, size, rank):
+    """Contiguous rows ``(row0, row1)`` of rank ``rank`` when ``N`` rows are dealt to ``size`` ranks: the first ``N % size`` ranks get one
+    row more; ranges are empty when there are more ranks than rows."""
+    N, size, rank = int(N), int(size), int(rank)
+    if N < 0 or size < 1 or not 0 <= rank < size:
+        raise ValueError("shard_rows: N = %d, size = %d, rank = %d" % (N, size, rank))
+    q, rem = divmod(N, size)
+    row0 = rank * q + min(rank, rem)
+    return row0, row0 + q + (1 if rank < rem else 0)
+
+
+def kernel_cross_cov_host(targets, sources, family, sigma, ell, nugget=0.0, diag_offset=None):
+    """Dense host evaluation of what ``KernelCrossCovarianceOperator`` applies: the (M, N) matrix K_ij = sigma^2 phi(|t_i - s_j| / ell)
+    + nugget [j == i + diag_offset], ``family`` as in ``kernel_cov_host``.  ``diag_offset`` None: no target is a source (and the nugget
+    must be 0).  With ``targets = points[r0:r1]``, ``sources = points`` and ``diag_offset = r0`` it is
+    ``kernel_cov_host(points, ..., rows=range(r0, r1))``."""
+    if family not in L.KERNEL_FAMILIES:
+        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+    tg, src = _points_array(targets), _points_array(sources)
+    _check_cross(tg, src, nugget, diag_offset)
+    d2 = np.zeros((tg.shape[0], src.shape[0]))
+    for c in range(src.shape[1]):
+        d2 += (tg[:, c][:, None] - src[None, :, c]) ** 2
+    dist = np.sqrt(d2)
+    if family == "matern12":
+        K = np.exp(-dist / ell)
+    elif family == "matern32":
+        a = np.sqrt(3.0) * dist / ell
+        K = (1.0 + a) * np.exp(-a)
+    elif family == "matern52":
+        a = np.sqrt(5.0) * dist / ell
+        K = (1.0 + a + a * a / 3.0) * np.exp(-a)
+    else:
+        K = np.exp(-0.5 * (dist / ell) ** 2)
+    K = sigma ** 2 * K
+    if nugget:
+        i = np.arange(tg.shape[0])
+        K[i, i + int(diag_offset)] += nugget
+    return K
+
+
+def _check_cross(tg, src, nugget, diag_offset):
+    """The argument rules of hfmi_op_kernel_cross_cov that need no device."""
+    M, N = tg.shape[0], src.shape[0]
+    if tg.shape[1] != src.shape[1]:
+        raise ValueError("targets have %d coordinates, sources %d" % (tg.shape[1], src.shape[1]))
+    if M < 1 or N < 1:
+        raise ValueError("a cross-covariance needs at least one target and one source (M = %d, N = %d)" % (M, N))
+    if diag_offset is None:
+        if nugget:
+            raise ValueError("a nugget needs targets that are sources: pass diag_offset")
+    elif int(diag_offset) < 0 or int(diag_offset) + M > N:
+        raise ValueError("diag_offset = %d with %d targets does not lie inside the %d sources" % (diag_offset, M, N))
+
+
+class KernelCrossCovarianceOperator(DeviceOperator):
+    """Rectangular cross-covariance K(T, S) between M ``targets`` and N ``sources`` without the M x N matrix: y = K x maps length N to
+    length M, K_ij = sigma^2 phi(|t_i - s_j| / ell) + nugget [j == i + diag_offset], by the kernel of ``KernelCovarianceOperator`` with a
+    second coordinate set (hfmi_kcov.hip).  ``diag_offset``: target i IS source i + diag_offset (the nugget sits on the index); None: no
+    target is a source, and the nugget must be 0.  What the Nystrom extension of a KLE or of a pivoted Cholesky factor applies
+    (``nystrom_extend``, ``KLEProjector.extend``, ``PivotedCholesky.extend``)."""
+
+    def __init__(self, targets, sources, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, diag_offset=None, ctx=None):
+        if family not in L.KERNEL_FAMILIES:
+            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        tg, src = _points_array(targets), _points_array(sources)
+        _check_cross(tg, src, nugget, diag_offset)
+        super().__init__(ctx, tg.shape[0], src.shape[0])
+        self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
+        self.targets, self.sources = tg, src
+        self.diag_offset = None if diag_offset is None else int(diag_offset)
+        L.call("hfmi_op_kernel_cross_cov", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
+               L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget,
+               L.KERNEL_NO_DIAGONAL if diag_offset is None else self.diag_offset, C.byref(self._op))
+
+    def to_dense(self):
+        """The same matrix on the host (``kernel_cross_cov_host``)."""
+        return kernel_cross_cov_host(self.targets, self.sources, self.family, self.sigma, self.ell, self.nugget, self.diag_offset)
+
+    def transpose(self):
+        """K(S, T), the operator with the two point sets swapped; only without a diagonal."""
+        if self.diag_offset is not None:
+            raise ValueError("transpose: only for a cross-covariance without a diagonal (diag_offset is %d)" % self.diag_offset)
+        return KernelCrossCovarianceOperator(self.sources, self.targets, self.family, self.sigma, self.ell, ctx=self.ctx)
+
+    def transpmult(self, x, y):
+        raise NotImplementedError("KernelCrossCovarianceOperator: apply transpose() for K^T")
+
+
+class KernelCovarianceRowsOperator(DeviceOperator):
+    """Rows ``row0 .. row1 - 1`` of a ``KernelCovarianceOperator`` as an operator N -> N (hfmi_op_kernel_cov_rows): those rows of y are
+    the rows of C x, bit for bit; an overwriting apply leaves the other rows +0.0, an accumulating one leaves them alone.  An empty
+    range is valid.  Made by ``KernelCovarianceOperator.rows`` / ``.sharded``."""
+
+    def __init__(self, points, family, sigma, ell, nugget, row0, row1, ctx=None):
+        if family not in L.KERNEL_FAMILIES:
+            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        pts = _points_array(points)
+        row0, row1 = int(row0), int(row1)
+        if not 0 <= row0 <= row1 <= pts.shape[0]:
+            raise ValueError("rows %d .. %d do not lie inside 0 .. %d" % (row0, row1, pts.shape[0]))
+        super().__init__(ctx, pts.shape[0])
+        self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
+        self.points, self.row0, self.row1 = pts, row0, row1
+        self.collective = None
+        self._hook = self._hook_error = None
+        L.call("hfmi_op_kernel_cov_rows", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
+               self.sigma, self.ell, self.nugget, row0, row1 - row0, C.byref(self._op))
+
+    def to_dense(self):
+        """The N x N matrix this operator applies: the slab's rows of C, zeros elsewhere (before any rank sum)."""
+        out = np.zeros((self.points.shape[0],) * 2)
+        if self.row1 > self.row0:
+            out[self.row0:self.row1] = kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget,
+                                                       rows=np.arange(self.row0, self.row1))
+        return out
+
+    def _attach_sum(self, collective):
+        """The rank SUM of every result block, for this object's lifetime."""
+        from .collectives import NativeCollective
+        self.collective = collective                    # the communicator outlives the operator that points at it
+        if isinstance(collective, NativeCollective):
+            L.call("hfmi_op_set_collective", self._op, collective._comm, L.REDUCE_SUM)
+            return
+
+        def _cb(user, block_handle):
+            try:
+                collective.allReduce(MultiVector(ctx=self.ctx, _handle=C.c_void_p(block_handle), _borrowed=True), "sum")
+                return 0
+            except Exception as exc:  # never let an exception cross the C boundary
+                self._hook_error = exc
+                return 1
+
+        self._hook = L.POST_APPLY_FN(_cb)
+        L.call("hfmi_op_set_post_apply", self._op, self._hook, None)
+
+    def _raise_pending(self):
+        if self._hook_error is not None:
+            exc, self._hook_error = self._hook_error, None
+            raise exc
+
+    def matMvMult(self, X, Y, accumulate=False):
+        try:
+            super().matMvMult(X, Y, accumulate)
+        except L.HfmiError:
+            self._raise_pending()
+            raise
+
+    def mult(self, x, y):
+        try:
+            super().mult(x, y)
+        except L.HfmiError:
+            self._raise_pending()
+            raise
+
+
+def nystrom_extend(cross_op, encoder, d):
+    """Nystrom extension of eigenpairs to the targets of ``cross_op``: K(T, S) . encoder . diag(1 / d), a ``MultiVector`` of M rows.
+    ``encoder``: the block the eigenvectors are applied through on the sources (M V for an M-orthonormal KLE, V for an orthonormal one);
+    ``d``: its eigenvalues, one per vector, none zero."""
+    d = np.asarray(d, dtype=np.float64).ravel()
+    if d.size != encoder.nvec():
+        raise ValueError("nystrom_extend: %d eigenvalues for %d vectors" % (d.size, encoder.nvec()))
+    if np.any(d == 0.0):
+        raise ZeroDivisionError("nystrom_extend: zero eigenvalue")
+    out = MultiVector(cross_op.shape[0], encoder.nvec(), ctx=cross_op.ctx)
+    cross_op.matMvMult(encoder, out)
+    for j in range(out.nvec()):
+        out.view(j, 1).scale(1.0 / d[j])
+    return out
 
 
 class _Csr:

@@ -31,6 +31,7 @@ from . import hostvec as H
 from .multivector import ingest_stream, MatMvMult, MultiVector, mv_to_dense
 from .lowrank import pivoted_cholesky
 from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, KernelCovarianceOperator,
+                        KernelCrossCovarianceOperator, nystrom_extend,
                         MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
                         SnapshotGramOperator, Solver2Operator, as_device_operator)
@@ -681,6 +682,11 @@ class KLEProjector:
     # below the exact one.  None (the default): the randomized solve, as before.  An attribute for the same reason as above.
     kernel_factor_rank = None
 
+    # True: with more than one rank in `collective` and a KernelCovarianceOperator prior.C, the randomized route applies
+    # `C.sharded(collective)` -- every rank evaluates its row slab of C and the collective's SUM completes the block (same bits as the
+    # unsharded apply, 1 / size of its flops).  M, Msolver and the probe block stay replicated.  An attribute for the same reason as above.
+    shard_kernel_covariance = False
+
     def __init__(self, prior, mesh_constructor_comm=None, collective=None, parameters=None, ctx=None):
         self.prior = prior
         self.mesh_constructor_comm = mesh_constructor_comm
@@ -702,6 +708,27 @@ class KLEProjector:
         self.V_KLE = None
         self.M_orthogonal = None
         self.R_orthogonal = False
+        self._kle_encoder = None
+
+    def _covariance(self):
+        """prior.C as the randomized route applies it: its row-sharded form when ``shard_kernel_covariance`` asks for it."""
+        if self.shard_kernel_covariance and self.collective.size() > 1 and isinstance(self.C, KernelCovarianceOperator):
+            return self.C.sharded(self.collective)
+        return self.C
+
+    def extend(self, points):
+        """The decoder's columns at other ``points`` (an (M, d) array): the Nystrom extension K(points, X) . encoder . diag(1 / d_KLE)
+        of the KLE computed by ``construct_input_subspace('mass' | 'identity')`` from a ``KernelCovarianceOperator`` prior.C.  A
+        ``MultiVector`` of M rows; at the projector's own nodes (and without a nugget) it reproduces the decoder to the accuracy of the
+        eigensolve.  ValueError for 'prior' orthogonality, a covariance that is not a kernel, or before the subspace exists."""
+        if not isinstance(self.C, KernelCovarianceOperator):
+            raise ValueError("extend: prior.C must be a KernelCovarianceOperator (got %s)" % type(self.C).__name__)
+        if self.R_orthogonal:
+            raise ValueError("extend: the Nystrom extension is for 'mass' and 'identity' orthogonality, not 'prior'")
+        if self._kle_encoder is None or self.d_KLE is None:
+            raise ValueError("extend: call construct_input_subspace('mass' | 'identity') first")
+        cross = KernelCrossCovarianceOperator(points, self.C.points, self.C.family, self.C.sigma, self.C.ell, ctx=self.ctx)
+        return nystrom_extend(cross, self._kle_encoder, self.d_KLE)
 
     def _Msolver(self):
         """M^-1 for the M-orthogonal double pass.  With M in HBM as CSR the solve is a device Jacobi-PCG to 1e-13 (tighter
@@ -743,7 +770,8 @@ class KLEProjector:
         assert hasattr(self.prior, 'M')
         if self.kernel_factor_rank is not None:
             return self._finish_subspace(t0, *self._factor_subspace(orthogonality.lower()))
-        KLE_Operator = MassPreconditionedCovarianceOperator(self.C, self.M)
+        C_op = self._covariance()
+        KLE_Operator = MassPreconditionedCovarianceOperator(C_op, self.M)
         Omega = _draw_omega(self.N, self.parameters['rank'] + self.parameters['oversampling'], self.collective, self.ctx)
         if orthogonality.lower() == 'mass':
             self.d_KLE, self.V_KLE = _randomized(self, True)(KLE_Operator, self.M, self._Msolver(), Omega, self.parameters['rank'], s=1)
@@ -752,7 +780,7 @@ class KLEProjector:
             kle_encoder = MultiVector(kle_decoder)
             MatMvMult(self.M, kle_decoder, kle_encoder)
         elif orthogonality.lower() == 'identity':
-            self.d_KLE, self.V_KLE = _randomized(self, False)(self.C, Omega, self.parameters['rank'], s=1)
+            self.d_KLE, self.V_KLE = _randomized(self, False)(C_op, Omega, self.parameters['rank'], s=1)
             self.M_orthogonal = False
             kle_decoder = self.V_KLE
             kle_encoder = MultiVector(kle_decoder)
@@ -778,6 +806,7 @@ class KLEProjector:
         return self._finish_subspace(t0, kle_decoder, kle_encoder)
 
     def _finish_subspace(self, t0, kle_decoder, kle_encoder):
+        self._kle_encoder = kle_encoder
         self._subspace_construction_time = time.time() - t0
         if self.parameters['verbose'] and _is_root(self.collective):
             print('Construction of input subspace took ', self._subspace_construction_time, 's')

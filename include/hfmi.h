@@ -174,6 +174,26 @@ HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out
 #define HFMI_KERNEL_SQEXP 3
 HFMI_API int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, hfmi_op** out);
+/*     the rectangular cross-covariance between two point sets, by the same kernel: K_ij = sigma^2 phi(|t_i - s_j| / ell)
+ *     + nugget [j == i + diag_offset] over M targets t and N sources s (both row-major x d on the host, copied to the device).  It acts
+ *     on blocks of length N and gives blocks of length M: the Nystrom extension of a KLE, or of a pivoted Cholesky factor, to other
+ *     points.  The nugget sits on the point INDEX: target i is source i + diag_offset; HFMI_KERNEL_NO_DIAGONAL says that no target is a
+ *     source, and then the nugget must be 0.  Coincident points with different indices get no nugget.
+ *     HFMI_ERR_INVALID: as hfmi_op_kernel_cov, M < 1, a diag_offset other than HFMI_KERNEL_NO_DIAGONAL that is negative or has
+ *     diag_offset + M > N, a non-zero nugget without a diagonal; at apply, blocks of other lengths.
+ *     Every row is summed over the sources in the order hfmi_op_kernel_cov uses: two applies are bit-identical. */
+#define HFMI_KERNEL_NO_DIAGONAL (-1)
+HFMI_API int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                       int family, double sigma, double ell, double nugget, int64_t diag_offset, hfmi_op** out);
+/*     a row slab of hfmi_op_kernel_cov's matrix as an operator on blocks of length N: rows row0 .. row0 + nrows - 1 of Y = C W, computed as
+ *     the cross-covariance with targets s[row0 : row0 + nrows] (read in place, no second copy) and diag_offset = row0.  An overwriting
+ *     apply writes +0.0 to the other rows below N, an accumulating one leaves them alone; nrows = 0 is valid (all zeros / a no-op).
+ *     With one slab per rank and hfmi_op_set_collective(op, comm, HFMI_REDUCE_SUM) every rank holds C W after 2 N^2 k / P flops.
+ *     HFMI_ERR_INVALID: as hfmi_op_kernel_cov, row0 < 0, nrows < 0, row0 + nrows > N; at apply, blocks of another length.
+ *     A slab's rows are the same bits as those rows of hfmi_op_kernel_cov's apply, and adding zeros is exact: the slabs of a partition
+ *     of 0 .. N, summed in any order, reproduce the square apply bit for bit. */
+HFMI_API int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                       double nugget, int64_t row0, int64_t nrows, hfmi_op** out);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
