@@ -130,6 +130,8 @@ SIGNATURES = {
     "hfmi_test_chol_wide": [_P, C.c_int, _P, C.c_double, C.c_double, _P, _P, _P],
     "hfmi_plan_clear": [_P],
     "hfmi_plan_read": [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "hfmi_plan_predict": [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                          C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],
     "hfmi_bench_loaded_peak": [_P, _D, _D],
     "hfmi_bench_random_peaks": [_P, _D, _D, _D],

@@ -261,6 +261,49 @@ extern "C" int hfmi_plan_read(hfmi_ctx* ctx, int max_records, int* words, int* n
   return HFMI_OK;
 }
 
+// the records a launch of that shape would append, from the planners the launchers call (hfmi_tsgemm_plan.h); no device involved
+extern "C" int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale, double beta, int64_t rs, int64_t cs, int nsplit_req,
+                                 int flags, int num_cus, int hook_panels, int max_records, int* words, int64_t* hook_rows, int* nrecords) {
+  if (!nrecords || (max_records > 0 && !words)) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (m <= 0 || k <= 0 || N <= 0 || hook_panels < 0 || hook_panels > NN_MAX_PANELS) HFMI_FAIL(HFMI_ERR_INVALID, "plan_predict: bad shape");
+  const tsgemm_knobs& kn = tsgemm_knobs_ref();
+  int n = 0, spill[HFMI_PLAN_WORDS];
+  auto slot = [&](int64_t row0, int64_t rows) {
+    const bool fits = n < max_records;
+    if (fits && hook_rows) hook_rows[2 * n] = row0, hook_rows[2 * n + 1] = rows;
+    return fits ? words + (size_t)HFMI_PLAN_WORDS * n++ : (++n, spill);
+  };
+  auto reduce = [&](const reduce_call& c) { reduce_plan_words(reduce_plan_make(c, rs, cs, !(flags & HFMI_PREDICT_UNALIGNED)), slot(0, 0)); };
+  if (kind == HFMI_PREDICT_TN) {
+    for (int k0 = 0; k0 < k; k0 += 256) {
+      const tn_plan p = tn_plan_make(m, k - k0 < 256 ? k - k0 : 256, N, scale, beta, rs, cs, flags & HFMI_PREDICT_ALIASED, nsplit_req, kn, num_cus);
+      if (!p.has_instance) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: no instance for MT=%d NT=%d WAVES=%d", p.mt, p.nt, p.waves);
+      tn_plan_words(p, slot(0, 0));
+      for (int i = 0; i < p.nred; ++i) reduce(p.red[i]);
+    }
+  } else if (kind == HFMI_PREDICT_SS) {
+    const bool same = flags & HFMI_PREDICT_SAME;
+    if (!ss_applicable(m, k, same)) HFMI_FAIL(HFMI_ERR_INVALID, "plan_predict: not a skinny x skinny shape");
+    const ss_plan p = ss_plan_make(m, k, N, same, nsplit_req, kn, num_cus);
+    if (!p.has_instance) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_ss: no instance for tiles/wave=%d chunks/thread=%d", p.tpw, p.nq);
+    ss_plan_words(p, slot(0, 0));
+    reduce(p.red);
+  } else if (kind == HFMI_PREDICT_NN) {
+    for (int r0 = 0; r0 < k; r0 += 256) {
+      const int rp = k - r0 < 256 ? k - r0 : 256;
+      const nn_plan p = nn_plan_make(m, rp, N, flags & HFMI_PREDICT_UPPER, hook_panels, kn, num_cus);
+      if (!p.has_instance) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_nn: panel too wide (%d)", rp);
+      if (p.res) nn_res_plan_words(p, slot(0, 0));
+      for (int i = 0; i < p.nlaunch; ++i) nn_launch_words(p, p.launch[i], slot(p.launch[i].hook_row0, p.launch[i].hook_rows));
+    }
+  } else {
+    HFMI_FAIL(HFMI_ERR_INVALID, "plan_predict: unknown kind %d", kind);
+  }
+  *nrecords = n;
+  if (n > max_records) HFMI_FAIL(HFMI_ERR_INVALID, "plan_predict: %d records, room for %d", n, max_records);
+  return HFMI_OK;
+}
+
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
   if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;

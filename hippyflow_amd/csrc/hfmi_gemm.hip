@@ -25,7 +25,6 @@
 // =====================================================================================
 // tsgemm_tn
 // =====================================================================================
-constexpr int TN_BK = 32;   // reduction indices per LDS stage
 // the streamed operand is read once by one workgroup: -DHFMI_TN_NT marks its loads non-temporal (A/B build, scripts/build_variant.sh)
 #ifdef HFMI_TN_NT
 #define TN_LOAD_A(p) __builtin_nontemporal_load(p)
@@ -382,333 +381,108 @@ __global__ __launch_bounds__(256) void k_reduce_vec(const double* __restrict__ p
   }
 }
 
-int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_t pstride, int inner_ld, bool tr, int m,
-                           int k, double scale, double beta, double* C, int64_t rs, int64_t cs) {
-  const int fastn = tr ? m : k, slown = tr ? k : m;
-  {
-    // vector path: fast axis contiguous and even-strided on both sides, pointers 16-byte aligned, enough work to matter
-    const int64_t cfast = tr ? rs : cs, crow = tr ? cs : rs;
-    const bool aligned = (((uintptr_t)part | (uintptr_t)C) & 15) == 0 && pstride % 2 == 0 && inner_ld % 2 == 0 && crow % 2 == 0;
-    if (cfast == 1 && aligned && (int64_t)fastn * slown >= 65536) {
-      int64_t rowlen, prow = inner_ld, kpad = 0;
-      int nrows, kreal = 0;
-      const bool long_row = !tr && rs == inner_ld;
-      if (long_row) {                       // rows are back to back on both sides: one long row, pad columns zeroed
-        rowlen = (int64_t)m * inner_ld;
-        nrows = 1;
-        kpad = inner_ld;
-        kreal = k;
-      } else {
-        rowlen = fastn & ~1;                // an odd fast extent: not this kernel, the scalar kernels below take the whole reduction
-        nrows = slown;
-        kpad = kreal = 0;
-      }
-      if (rowlen == fastn || long_row) {    // (a single row of odd length is no long row: its last element needs the scalar kernel)
-        dim3 vgrid((unsigned)((rowlen / 2 + 255) / 256), (unsigned)(nrows < 32768 ? nrows : 32768));
-        hipLaunchKernelGGL(k_reduce_vec, vgrid, dim3(256), 0, ctx->stream, part, nsplit, pstride, prow, rowlen, nrows, kpad, kreal, scale,
-                           beta, C, crow);
-        HIP_TRY(hipGetLastError());
-        plan_record(ctx, HFMI_PLAN_REDUCE, {long_row ? HFMI_REDUCE_VEC_LONG : HFMI_REDUCE_VEC_ROWS, 0, nsplit, tr ? 1 : 0, m, k});
-        return HFMI_OK;
-      }
-    }
+int launch_reduce_partials(hfmi_ctx* ctx, const double* part, const reduce_call& c, double scale, double beta, double* C, int64_t rs,
+                           int64_t cs) {
+  const reduce_plan p = reduce_plan_make(c, rs, cs, (((uintptr_t)part | (uintptr_t)C) & 15) == 0);
+  const dim3 grid(p.gx, p.gy);
+  switch (p.route) {
+    case HFMI_REDUCE_VEC_LONG:
+    case HFMI_REDUCE_VEC_ROWS:
+      hipLaunchKernelGGL(k_reduce_vec, grid, dim3(256), 0, ctx->stream, part, p.nsplit, c.pstride, (int64_t)c.inner_ld, p.rowlen, p.nrows,
+                         p.kpad, p.kreal, scale, beta, C, p.crow);
+      break;
+    case HFMI_REDUCE_FLAT:
+      hipLaunchKernelGGL(p.ry == 4 ? k_reduce_flat<4> : k_reduce_flat<16>, grid, dim3(64, p.ry), 0, ctx->stream, part, p.nsplit, c.pstride,
+                         p.rowlen, c.inner_ld, p.k, scale, beta, C);
+      break;
+    default:
+      hipLaunchKernelGGL(p.ry == 4 ? k_reduce_partials<4> : k_reduce_partials<16>, grid, dim3(64, p.ry), 0, ctx->stream, part, p.nsplit,
+                         c.pstride, c.inner_ld, p.tr, p.m, p.k, scale, beta, C, rs, cs);
   }
-  if (!tr && cs == 1 && rs == inner_ld && (int64_t)m * inner_ld >= 65536) {
-    const int64_t total = (int64_t)m * inner_ld;
-    dim3 fgrid((unsigned)((total + 63) / 64));
-    if (nsplit <= 32)
-      hipLaunchKernelGGL(k_reduce_flat<4>, fgrid, dim3(64, 4), 0, ctx->stream, part, nsplit, pstride, total, inner_ld, k, scale,
-                         beta, C);
-    else
-      hipLaunchKernelGGL(k_reduce_flat<16>, fgrid, dim3(64, 16), 0, ctx->stream, part, nsplit, pstride, total, inner_ld, k,
-                         scale, beta, C);
-    HIP_TRY(hipGetLastError());
-    plan_record(ctx, HFMI_PLAN_REDUCE, {HFMI_REDUCE_FLAT, nsplit <= 32 ? 4 : 16, nsplit, 0, m, k});
-    return HFMI_OK;
-  }
-  dim3 grid((fastn + 63) / 64, slown < 32768 ? slown : 32768);
-  if (nsplit <= 32)
-    hipLaunchKernelGGL(k_reduce_partials<4>, grid, dim3(64, 4), 0, ctx->stream, part, nsplit, pstride, inner_ld, tr ? 1 : 0, m,
-                       k, scale, beta, C, rs, cs);
-  else
-    hipLaunchKernelGGL(k_reduce_partials<16>, grid, dim3(64, 16), 0, ctx->stream, part, nsplit, pstride, inner_ld, tr ? 1 : 0, m,
-                       k, scale, beta, C, rs, cs);
   HIP_TRY(hipGetLastError());
-  plan_record(ctx, HFMI_PLAN_REDUCE, {HFMI_REDUCE_PARTIALS, nsplit <= 32 ? 4 : 16, nsplit, tr ? 1 : 0, m, k});
+  reduce_plan_words(p, plan_slot(ctx));
   return HFMI_OK;
 }
 
-#include <stdlib.h>
-#include <string.h>
-// Tuning knobs of the MFMA kernels (A/B measurements: environment HFMI_GEMM_WAVES, or
-// hfmi_tuning_set at run time).
-//   waves: 8 = two waves per SIMD with <= 16 accumulator tiles each; 4 = one wave per SIMD with <= 32 tiles
-//   rem4 : compute a last column tile of <= 12 columns with 4x4x4 MFMAs (1, default) or as a full 16-column tile (0)
-static int g_waves = 0, g_rem4 = 1, g_probe = 0, g_tn_mt = 0;
-// where a launch writes: split partials (the reduce kernel sums them) or, for one split with nothing to scale, C itself
-struct TnOut {
-  bool direct;
-  double* C;
-  int64_t rs, cs;
-  // tail plan (tn_panel): row blocks beyond the whole rounds, their split and their compact partial buffer
-  int tail_nrb, tail_nsplit;
-  int64_t tail_chunk;
-  double* tail_part;
-  int tail_mpad;
-};
-static int g_ss = 1;                                 // route skinny x skinny contractions to tsgemm_ss (hfmi_skinny.hip)
-static int g_tn_hybrid = 1;                          // tsgemm_tn: whole rounds of row blocks coarsely split + a finely split tail (A/B: "tn_hybrid")
-static void tuning_init() {
-  if (g_waves) return;
-  const char* e = getenv("HFMI_GEMM_WAVES");
-  g_waves = (e && atoi(e) == 4) ? 4 : (e && atoi(e) == 44) ? 44 : 8;   // measured: 8 waves is best or equal on every shape (scripts/gemm_ab.py)
-}
-static int gemm_waves() {
-  tuning_init();
-  return g_waves;
-}
+// Tuning knobs (A/B measurements): the contractions' live in tsgemm_knobs (hfmi_tsgemm_plan.h), the other subsystems keep their own
 extern "C" int hfmi_tuning_set(const char* key, int value) {
-  tuning_init();
-  if (key && !strcmp(key, "waves") && (value == 4 || value == 8 || value == 44)) g_waves = value;
-  else if (key && !strcmp(key, "rem4") && (value == 0 || value == 1)) { g_rem4 = value; nn_tuning_set(key, value); }
-  else if (key && nn_tuning_set(key, value)) {}
+  if (key && tsgemm_knob_set(key, value)) {}
   else if (key && eig_tuning_set(key, value)) {}
   else if (key && chol_tuning_set(key, value)) {}
   else if (key && api_tuning_set(key, value)) {}
   else if (key && pchol_tuning_set(key, value)) {}
-  else if (key && !strcmp(key, "ss") && (value == 0 || value == 1)) g_ss = value;
-  else if (key && !strcmp(key, "probe")) g_probe = value;
-  else if (key && !strcmp(key, "tn_hybrid") && (value == 0 || value == 1)) g_tn_hybrid = value;
-  else if (key && !strcmp(key, "tn_mt") && value >= 0 && value <= 8) g_tn_mt = value;   // A/B: wave tile height of tsgemm_tn (0 = automatic)
-  else if (key && !strcmp(key, "ss_percu") && value >= 1 && value <= 4) tsgemm_ss_set_percu(value);
-  else if (key && !strcmp(key, "ss_blocked") && value >= 0 && value <= 2) tsgemm_ss_set_blocked(value);
   else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
   return HFMI_OK;
 }
-// tallest wave tile (in 16-row MFMA tiles) for a panel of nt column tiles
-static inline int tn_mt_max(int nt, int waves) {
-  static const int t4[17] = {0, 8, 8, 8, 8, 6, 5, 4, 4, 3, 3, 2, 2, 2, 2, 2, 2};
-  static const int t8[17] = {0, 5, 5, 5, 4, 3, 3, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1};   // A/B (r01e): <3,6> and <2,9> beat <2,6> / <1,9>; <4,5> does not beat <3,5>
-  return waves == 4 ? t4[nt] : t8[nt];
-}
 
-template <int MT, int NT, int WAVES, bool TR, int R4>
-static int tn_launch_one(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k, int64_t N,
-                         int64_t chunk, int nrb, int nsplit, double* part, int mpad, int kpad, const TnOut& o) {
-  const size_t shmem = (size_t)2 * NT * 16 * (TN_BK + 2) * sizeof(double);
-  auto kern = k_tsgemm_tn<MT, NT, TR, WAVES, R4>;
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  double* out = o.direct ? o.C : part;
-  const int64_t si = o.direct ? o.rs : (TR ? 1 : kpad), sj = o.direct ? o.cs : (TR ? mpad : 1);
-  TnTail tail = {o.tail_nrb, o.tail_nsplit, o.tail_chunk, o.tail_part, TR ? 1 : kpad, TR ? o.tail_mpad : 1, (int64_t)o.tail_mpad * kpad};
-  hipLaunchKernelGGL(kern, dim3(nrb * nsplit + o.tail_nrb * o.tail_nsplit), dim3(WAVES * 64), shmem, ctx->stream, A, lda, m, B, ldb, k,
-                     N, chunk, nrb, nsplit, out, si, sj, (int64_t)mpad * kpad, o.direct ? 1 : 0, g_probe, tail);
-  HIP_TRY(hipGetLastError());
-  plan_record(ctx, HFMI_PLAN_TN, {MT, NT, WAVES, TR ? 1 : 0, R4, nrb * nsplit + o.tail_nrb * o.tail_nsplit, nrb, nsplit, o.direct ? 1 : 0,
-                                  o.tail_nrb, o.tail_nsplit});
-  return HFMI_OK;
-}
-
-// r4: number of 4-column groups the last column tile is computed in (0 = as a full 16-column tile)
+// the instance <MT, NT, TR, WAVES, R4> of a plan; null: not compiled
+typedef void (*tn_kernel_t)(const double*, int64_t, int, const double*, int64_t, int, int64_t, int64_t, int, int, double*, int64_t, int64_t,
+                            int64_t, int, int, TnTail);
 template <int MT, int NT, int WAVES>
-static int tn_launch_inst(hfmi_ctx* ctx, bool tr, int r4, const double* A, int64_t lda, int m, const double* B, int64_t ldb,
-                          int k, int64_t N, int64_t chunk, int nrb, int nsplit, double* part, int mpad, int kpad,
-                          const TnOut& o) {
-#define TN_R4(R)                                                                                                          \
-  case R:                                                                                                                 \
-    if (tr) return tn_launch_one<MT, NT, WAVES, true, R>(ctx, A, lda, m, B, ldb, k, N, chunk, nrb, nsplit, part, mpad, kpad, o); \
-    return tn_launch_one<MT, NT, WAVES, false, R>(ctx, A, lda, m, B, ldb, k, N, chunk, nrb, nsplit, part, mpad, kpad, o);
+static tn_kernel_t tn_kernel_r4(bool tr, int r4) {
+#define TN_R4(R) \
+  case R:        \
+    return tr ? k_tsgemm_tn<MT, NT, true, WAVES, R> : k_tsgemm_tn<MT, NT, false, WAVES, R>;
   if constexpr (WAVES == 8) {
     switch (r4) { TN_R4(1) TN_R4(2) TN_R4(3) }
   }
   switch (0) { TN_R4(0) }
 #undef TN_R4
-  return HFMI_OK;
+  return nullptr;
 }
-
 template <int NT, int WAVES>
-static int tn_dispatch_mt(hfmi_ctx* ctx, int mt, bool tr, int r4, const double* A, int64_t lda, int m, const double* B,
-                          int64_t ldb, int k, int64_t N, int64_t chunk, int nrb, int nsplit, double* part, int mpad,
-                          int kpad, const TnOut& o) {
-  constexpr int LIM = (WAVES == 8) ? 20 : 32;
-#define TN_CASE(M)                                                                                                 \
-  case M:                                                                                                          \
-    if constexpr (M * NT <= LIM)                                                                                   \
-      return tn_launch_inst<M, NT, WAVES>(ctx, tr, r4, A, lda, m, B, ldb, k, N, chunk, nrb, nsplit, part, mpad, kpad, o); \
+static tn_kernel_t tn_kernel_mt(int mt, bool tr, int r4) {
+#define TN_CASE(M) \
+  case M:          \
+    if constexpr (M * NT <= tn_mt_limit(WAVES)) return tn_kernel_r4<M, NT, WAVES>(tr, r4); \
     break;
-  switch (mt) {
-    TN_CASE(1) TN_CASE(2) TN_CASE(3) TN_CASE(4) TN_CASE(5) TN_CASE(6) TN_CASE(8)
-  }
+  switch (mt) { HFMI_TN_MT_CASES(TN_CASE) }
 #undef TN_CASE
-  HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: no instance for MT=%d NT=%d WAVES=%d", mt, NT, WAVES);
+  return nullptr;
+}
+static tn_kernel_t tn_kernel(const tn_plan& p) {
+#define TN_NT(NTV) \
+  case NTV:        \
+    return p.waves == 8 ? tn_kernel_mt<NTV, 8>(p.mt, p.tr, p.r4) : tn_kernel_mt<NTV, 4>(p.mt, p.tr, 0);
+  switch (p.nt) { HFMI_TN_NT_CASES(TN_NT) }
+#undef TN_NT
+  return nullptr;
 }
 
 // one panel of at most 256 columns of B
 static int tn_panel(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
                     int64_t N, double scale, double beta, double* C, int64_t rs, int64_t cs, int nsplit_req) {
-  const int nt = (k + 15) / 16;
-  const int kpad = nt * 16;
-  const int64_t Npad = round_up(N, TN_BK);
-  if (lda % 32 != 0 || ldb % 32 != 0 || lda < Npad || ldb < Npad)
+  const tsgemm_knobs& kn = tsgemm_knobs_ref();
+  const tn_plan p = tn_plan_make(m, k, N, scale, beta, rs, cs, C == A || C == B, nsplit_req, kn, ctx->num_cus);
+  if (lda % 32 != 0 || ldb % 32 != 0 || lda < p.Npad || ldb < p.Npad)
     HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: leading dimensions must be multiples of 32 and >= round_up(N,32)");
-  const bool tr = (rs == 1 && cs != 1);  // column-major output: coalesce along i
-  // wave tile height: as tall as the accumulator budget allows, but no taller than the problem needs
-  // waves: 8 = one 8-wave workgroup per CU (two waves per SIMD); 4 = one 4-wave workgroup with big tiles;
-  // 44 = 4-wave workgroups with the small (two-per-SIMD) tiles, TWO workgroups per CU: their stage barriers are not
-  // synchronised with each other, so one workgroup's MFMAs cover the other's barrier / staging bubbles
-  const int wcfg = (nt > 11) ? 4 : gemm_waves();   // very wide panels: the 2-waves/SIMD register budget is too tight
-  const bool small4 = wcfg == 44;
-  const int waves = small4 ? 4 : wcfg;
-  const int row_tiles = (m + 15) / 16;
-  int mt = tn_mt_max(nt, small4 ? 8 : waves);
-  const int need = (row_tiles + waves - 1) / waves;
-  if (need < mt) mt = need;
-  if (g_tn_mt > 0 && g_tn_mt < mt) mt = g_tn_mt;
-  if (mt == 7) mt = 6;
-  if (mt < 1) mt = 1;
-  const int rows_per_block = 16 * waves * mt;
-  const int nrb = (m + rows_per_block - 1) / rows_per_block;
-  const int mpad = nrb * rows_per_block;
-  // split the long axis so that the grid fills the chip in (nearly) whole rounds of CUs
-  const int cus = (ctx->num_cus > 0 ? ctx->num_cus : 256) * (small4 ? 2 : 1);   // resident workgroup slots
-  int nsplit = nsplit_req;
-  if (nsplit <= 0) {
-    const int64_t stages = Npad / TN_BK;
-    int best = 1;
-    double best_cost = 1e300;
-    for (int ns = 1; ns <= 128; ++ns) {
-      if (ns > 1 && stages / ns < 16) break;
-      const int64_t blocks = (int64_t)nrb * ns;
-      const int64_t rounds = (blocks + cus - 1) / cus;
-      const double eff = (double)blocks / (double)(rounds * cus);
-      const double part_ratio = 2.0 * ns * (double)mpad * kpad / ((double)N * (m + k));
-      const double cost = 1.0 / eff + part_ratio;
-      if (cost < best_cost - 1e-12) {
-        best_cost = cost;
-        best = ns;
-      }
-    }
-    nsplit = best;
-  }
-  const int64_t stage_len = TN_BK;
-  // Hybrid plan: when the row blocks make at least one whole round of the CUs, the rounds that ARE whole need no fine split at
-  // all (ns_full = 1 or 2: their partial traffic is a single slice or none) and only the blocks beyond them are split finely
-  // enough to fill one more round for 1 / ns_tail of a block's time.  m = 1e5 (config 2): 261 blocks = 256 whole + 5 x 51 instead
-  // of 261 x 19 (the uniform plan's best: 3 % quantisation loss, 1.5 GB of partials written and read back, a 0.3 ms reduction);
-  // m = 51200 (config 4): 128 x 2 + 6 x 42 instead of 134 x 21 (0.7 GB of partials, 0.12 ms).
-  const bool can_direct = (scale == 1.0 && beta == 0.0 && C != A && C != B);
-  int ns_full = 0, nrb_full = 0, ns_tail = 0;
-  if (nsplit_req <= 0 && g_tn_hybrid) {
-    const int64_t stages = Npad / TN_BK;
-    const double ideal = (double)nrb / cus;
-    const double part_unit = 2.0 * (double)rows_per_block * kpad / ((double)N * (m + k));   // one slice of one row block
-    double uniform_cost;
-    {
-      const int64_t blocks = (int64_t)nrb * nsplit;
-      const int64_t rounds = (blocks + cus - 1) / cus;
-      uniform_cost = (double)(rounds * cus) / (double)blocks + part_unit * nsplit * nrb;
-    }
-    double best_cost = uniform_cost;
-    static const int cand[] = {1, 2, 3, 4, 6, 8};
-    for (int ci = 0; ci < 6; ++ci) {
-      const int nsf = cand[ci];
-      if (nsf > 1 && stages / nsf < 16) break;
-      const int64_t R = ((int64_t)nrb * nsf) / cus;            // whole rounds of full-region workgroups
-      if (R < 1 || (R * cus) % nsf != 0) continue;
-      const int nf = (int)(R * cus / nsf);
-      const int nt_blocks = nrb - nf;
-      if (nt_blocks <= 0) continue;                             // the uniform plan already is this one
-      int nst = cus / nt_blocks;
-      if (nst > stages / 16) nst = (int)(stages / 16);
-      if (nst > 128) nst = 128;
-      if (nst < 1) nst = 1;
-      const int64_t tail_rounds = ((int64_t)nt_blocks * nst + cus - 1) / cus;
-      const double time = (double)R / nsf + (double)tail_rounds / nst;
-      const double parts = part_unit * ((nsf == 1 && can_direct ? 0.0 : (double)nsf * nf) + (double)nst * nt_blocks);
-      const double cost = time / ideal + parts;
-      if (cost < best_cost - 1e-9) {
-        best_cost = cost;
-        ns_full = nsf;
-        nrb_full = nf;
-        ns_tail = nst;
-      }
-    }
-  }
-  const int rem = k - (nt - 1) * 16;
-  const int r4 = (g_rem4 && waves == 8 && rem <= 12) ? (rem + 3) / 4 : 0;
-  if (ns_full > 0) {
-    const int nrb_t = nrb - nrb_full;
-    const int mpad_f = nrb_full * rows_per_block, mpad_t = nrb_t * rows_per_block;
-    int64_t chunk_f = round_up((Npad + ns_full - 1) / ns_full, stage_len);
-    ns_full = (int)((Npad + chunk_f - 1) / chunk_f);
-    int64_t chunk_t = round_up((Npad + ns_tail - 1) / ns_tail, stage_len);
-    ns_tail = (int)((Npad + chunk_t - 1) / chunk_t);
-    const bool direct_f = ns_full == 1 && can_direct;
-    const size_t full_doubles = direct_f ? 0 : (size_t)ns_full * mpad_f * kpad;
-    void* partv = nullptr;
-    HFMI_TRY(ctx_ws(ctx, WS_PART, (full_doubles + (size_t)ns_tail * mpad_t * kpad) * sizeof(double), &partv));
-    double* part_f = (double*)partv;
-    double* part_t = part_f + full_doubles;
-    const TnOut o = {direct_f, C, rs, cs, nrb_t, ns_tail, chunk_t, part_t, mpad_t};
-    const int pidx = prof_start(ctx, 0, m, k, N);
-#define TN_NT(NTV)                                                                                                       \
-  case NTV:                                                                                                              \
-    if (waves == 8)                                                                                                      \
-      HFMI_TRY((tn_dispatch_mt<NTV, 8>(ctx, mt, tr, r4, A, lda, m, B, ldb, k, Npad, chunk_f, nrb_full, ns_full, part_f, mpad_f, kpad, o))); \
-    else                                                                                                                 \
-      HFMI_TRY((tn_dispatch_mt<NTV, 4>(ctx, mt, tr, 0, A, lda, m, B, ldb, k, Npad, chunk_f, nrb_full, ns_full, part_f, mpad_f, kpad, o))); \
-    break;
-    switch (nt) {
-      TN_NT(1) TN_NT(2) TN_NT(3) TN_NT(4) TN_NT(5) TN_NT(6) TN_NT(7) TN_NT(8) TN_NT(9) TN_NT(10) TN_NT(11) TN_NT(12)
-      TN_NT(13) TN_NT(14) TN_NT(15) TN_NT(16)
-      default:
-        HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: panel too wide (%d)", k);
-    }
-#undef TN_NT
-    prof_stop(ctx, pidx);
-    const int m_full = mpad_f;                        // every row of the whole rounds is a real row (only the last block is ragged)
-    if (!direct_f)
-      HFMI_TRY(launch_reduce_partials(ctx, part_f, ns_full, (int64_t)mpad_f * kpad, tr ? mpad_f : kpad, tr, m_full, k, scale, beta, C,
-                                      rs, cs));
-    return launch_reduce_partials(ctx, part_t, ns_tail, (int64_t)mpad_t * kpad, tr ? mpad_t : kpad, tr, m - m_full, k, scale, beta,
-                                  C + (int64_t)m_full * rs, rs, cs);
-  }
-  int64_t chunk = round_up((Npad + nsplit - 1) / nsplit, stage_len);
-  if (chunk < stage_len) chunk = stage_len;
-  nsplit = (int)((Npad + chunk - 1) / chunk);
-  if (nsplit < 1) nsplit = 1;
+  const tn_kernel_t kern = p.has_instance ? tn_kernel(p) : nullptr;
+  if (!kern) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: no instance for MT=%d NT=%d WAVES=%d", p.mt, p.nt, p.waves);
   void* partv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_PART, (size_t)nsplit * mpad * kpad * sizeof(double), &partv));
+  HFMI_TRY(ctx_ws(ctx, WS_PART, p.ws_bytes, &partv));
   double* part = (double*)partv;
+  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+  // where the launch writes: split partials (the reduce kernel sums them) or, for one split with nothing to scale, C itself
+  const int64_t psi = p.tr ? 1 : p.kpad;
+  const TnTail tail = {p.tail_nrb, p.tail_nsplit, p.tail_chunk, p.tail_nrb ? part + p.tail_off : nullptr, psi, p.tr ? p.tail_mpad : 1,
+                       (int64_t)p.tail_mpad * p.kpad};
   // algorithmic work of this launch: flops 2 N m k, bytes 8 (N m + N k + m k)
-  // columns of the last tile: up to 12 are done as 1..3 groups of 4 with the 4x4x4 MFMA (16 instead of 64 cycles each)
-  const bool direct = (nsplit == 1 && can_direct);   // blocks never overlap partially
-  const TnOut o = {direct, C, rs, cs, 0, 0, 0, nullptr, 0};
   const int pidx = prof_start(ctx, 0, m, k, N);
-#define TN_NT(NTV)                                                                                                       \
-  case NTV:                                                                                                              \
-    if (waves == 8)                                                                                                      \
-      HFMI_TRY((tn_dispatch_mt<NTV, 8>(ctx, mt, tr, r4, A, lda, m, B, ldb, k, Npad, chunk, nrb, nsplit, part, mpad, kpad, o))); \
-    else                                                                                                                 \
-      HFMI_TRY((tn_dispatch_mt<NTV, 4>(ctx, mt, tr, 0, A, lda, m, B, ldb, k, Npad, chunk, nrb, nsplit, part, mpad, kpad, o))); \
-    break;
-  switch (nt) {
-    TN_NT(1) TN_NT(2) TN_NT(3) TN_NT(4) TN_NT(5) TN_NT(6) TN_NT(7) TN_NT(8) TN_NT(9) TN_NT(10) TN_NT(11) TN_NT(12)
-    TN_NT(13) TN_NT(14) TN_NT(15) TN_NT(16)
-    default:
-      HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_tn: panel too wide (%d)", k);
-  }
-#undef TN_NT
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.waves * 64), p.shmem, ctx->stream, A, lda, m, B, ldb, k, p.Npad, p.chunk, p.nrb, p.nsplit,
+                     p.direct ? C : part, p.direct ? rs : psi, p.direct ? cs : (int64_t)(p.tr ? p.mpad : 1), (int64_t)p.mpad * p.kpad,
+                     p.direct ? 1 : 0, kn.probe, tail);
+  HIP_TRY(hipGetLastError());
+  tn_plan_words(p, plan_slot(ctx));
   prof_stop(ctx, pidx);
-  if (direct) return HFMI_OK;
-  return launch_reduce_partials(ctx, part, nsplit, (int64_t)mpad * kpad, tr ? mpad : kpad, tr, m, k, scale, beta, C, rs,
-                                cs);
+  for (int i = 0; i < p.nred; ++i)
+    HFMI_TRY(launch_reduce_partials(ctx, part + p.red[i].part_off, p.red[i], scale, beta, C + p.red[i].c_off, rs, cs));
+  return HFMI_OK;
 }
 
 int launch_tsgemm_tn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
                      int64_t N, double scale, double beta, double* C, int64_t rs, int64_t cs, int nsplit_req) {
   if (m <= 0 || k <= 0 || N <= 0) return HFMI_OK;
-  if (g_ss && tsgemm_ss_applicable(m, k, A == B && lda == ldb && m == k))
+  if (tsgemm_knobs_ref().ss && ss_applicable(m, k, A == B && lda == ldb && m == k))
     return launch_tsgemm_ss(ctx, A, lda, m, B, ldb, k, N, scale, beta, C, rs, cs, nsplit_req);
   for (int k0 = 0; k0 < k; k0 += 256) {
     const int kp = (k - k0 < 256) ? (k - k0) : 256;
@@ -717,4 +491,3 @@ int launch_tsgemm_tn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const d
   }
   return HFMI_OK;
 }
-

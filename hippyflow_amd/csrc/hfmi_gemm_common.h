@@ -18,6 +18,3 @@ __device__ __forceinline__ int xcd_remap(int lin, int total) {
   const int fl = total >> 3, rem = total & 7;
   return xcd * fl + (xcd < rem ? xcd : rem) + slot;
 }
-
-// tuning knobs of tsgemm_nn (set through hfmi_tuning_set, hfmi_gemm.hip)
-int nn_tuning_set(const char* key, int value);   // 1 = key handled

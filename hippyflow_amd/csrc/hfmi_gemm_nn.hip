@@ -2,34 +2,10 @@
 // Fragment maps and the overall design are described at the top of hfmi_gemm.hip; this half lives in its own
 // translation unit so that the two instance families compile in parallel.
 #include "hfmi_gemm_common.h"
-#include <string.h>
-
-static int g_nn_waves = 0;    // 0 = auto (4 for <= 6 column tiles, else 8)
-static int g_nn_hybrid = 1;   // split only the row tiles beyond the last full round of CUs
-static int g_nn_tt = 0;       // A/B: force the nn wave-tile height (1 = tallest, 2, 3 = next smaller)
-static int g_rem4 = 1;        // last column tile of <= 12 columns in 4-column groups (4x4x4 MFMA)
-static int g_nn_res = 1;      // small matrix resident in LDS + persistent workgroups when it fits
-static int g_nn_halve_last = 0;   // overlapped rank reduction: last round of a 2-3 round product as two launches of half-height tiles
-                                  // (off: on one GPU the shorter tiles cost more than the smaller exposed panel saves, profiles/r04i_halve_last_ab.txt)
-static int g_nn_upper = 1;    // Q R^-1: skip the structurally zero column tiles of the upper-triangular small matrix (A/B: "nn_upper")
-static int g_nn_res_tt = 0;   // 0: tile height of nn_res by the round count (below); 1: always the table's; 2: always one less (A/B)
-int nn_tuning_set(const char* key, int value) {
-  if (!strcmp(key, "rem4") && (value == 0 || value == 1)) g_rem4 = value;
-  else if (!strcmp(key, "nn_waves") && (value == 0 || value == 4 || value == 8)) g_nn_waves = value;
-  else if (!strcmp(key, "nn_tt") && value >= 0 && value <= 3) g_nn_tt = value;
-  else if (!strcmp(key, "nn_hybrid") && (value == 0 || value == 1)) g_nn_hybrid = value;
-  else if (!strcmp(key, "nn_res") && (value == 0 || value == 1)) g_nn_res = value;
-  else if (!strcmp(key, "nn_halve_last") && (value == 0 || value == 1)) g_nn_halve_last = value;
-  else if (!strcmp(key, "nn_res_tt") && value >= 0 && value <= 2) g_nn_res_tt = value;
-  else if (!strcmp(key, "nn_upper") && (value == 0 || value == 1)) g_nn_upper = value;
-  else return 0;
-  return 1;
-}
 
 // =====================================================================================
 // tsgemm_nn
 // =====================================================================================
-constexpr int NN_KC = 32;  // reduction indices per LDS stage (8 MFMA k-steps)
 #ifdef HFMI_NN_NT
 #define NN_LOAD_A(p) __builtin_nontemporal_load(p)
 #else
@@ -494,280 +470,94 @@ __global__ void k_reduce_nn(const double* __restrict__ part, int msplit, int64_t
   }
 }
 
-// Launch plan of tsgemm_nn for a tile of `tile_rows` rows: how many ways to split the reduction axis m so that the
-// grid fills the 256 CUs in (nearly) whole rounds.  Time model (the kernel is MFMA bound, the split partials only
-// cost their own HBM round trip in k_reduce_nn): t = flops / (eff * rate) + (msplit + 1) * N * r * 8 / hbm.
-static double nn_plan(hfmi_ctx* ctx, int tile_rows, int m, int r, int64_t N, double rate_factor, int* msplit_out) {
-  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  const int64_t ntiles = (N + tile_rows - 1) / tile_rows;
-  const int stages = (m + NN_KC - 1) / NN_KC;
-  const double flops = 2.0 * (double)ntiles * tile_rows * (double)m * (double)(((r + 15) / 16) * 16);
-  const double rate = 60e12 * rate_factor, hbm = 4.0e12;
-  int best = 1;
-  double best_t = 1e300;
-  for (int ns = 1; ns <= 64; ++ns) {
-    if (ns > 1 && stages / ns < 8) break;
-    const int64_t blocks = ntiles * ns;
-    const int64_t rounds = (blocks + cus - 1) / cus;
-    const double eff = (double)blocks / (double)(rounds * cus);
-    const double t = flops / (eff * rate) + (ns > 1 ? (ns + 1.0) * (double)N * r * 8.0 / hbm + 3e-6 : 0.0);
-    if (t < best_t - 1e-12) {
-      best_t = t;
-      best = ns;
-    }
-  }
-  *msplit_out = best;
-  return best_t;
-}
-
+// the kernels of a plan: the instance itself and, for the streaming kernel at an even tile height, the one of half the height (same
+// signature); false: not compiled
+typedef void (*nn_kernel_t)(const double*, int64_t, int, const double*, int, int, double*, int64_t, int64_t, int, int, int, int64_t, int,
+                            double*, int64_t, int, int);
+typedef void (*nn_res_kernel_t)(const double*, int64_t, int, const double*, int, int, double*, int64_t, int64_t, int);
 template <int TT, int NT, int WAVES>
-static int nn_launch_inst(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds_, int r,
-                          double* Y, int64_t ldy, int64_t N, int msplit, bool tail_split = false) {
-  constexpr int SLD = NT * 16 + ((NT % 2 == 0) ? 16 : 0);
-  const size_t shmem = (size_t)2 * NN_KC * SLD * sizeof(double);
-  // columns of the last tile: up to 12 are done as 1..3 groups of 4 with the 4x4x4 MFMA
-  const int rem = r - (NT - 1) * 16;
-  const int r4 = (g_rem4 && rem <= 12) ? (rem + 3) / 4 : 0;
-  auto kern = r4 == 1 ? k_tsgemm_nn<TT, NT, WAVES, 1> : r4 == 2 ? k_tsgemm_nn<TT, NT, WAVES, 2>
-            : r4 == 3 ? k_tsgemm_nn<TT, NT, WAVES, 3> : k_tsgemm_nn<TT, NT, WAVES, 0>;
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  const int tile_rows = 16 * TT * WAVES;
-  const int ntiles = (int)((N + tile_rows - 1) / tile_rows);
-  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  // msplit > 1 means the plan found the row tiles badly quantised over the CUs.  With at least one full round of
-  // tiles, only the tiles beyond the last full round are split (see the kernel); otherwise every tile is.
-  int full_tiles = 0;
-  if ((msplit > 1 || tail_split) && ntiles >= cus && g_nn_hybrid) {
-    full_tiles = ntiles / cus * cus;
-    const int tail = ntiles - full_tiles;
-    if (tail == 0) {
-      msplit = 1;
-    } else {
-      const int stages = (m + NN_KC - 1) / NN_KC;
-      // split the tail tiles ms ways so that their pieces fill whole rounds of CUs: the tail then costs
-      // ceil(tail ms / cus) / ms of a round instead of a whole one (config 3: 162 tail tiles, ms = 3 -> 486 pieces = 2 rounds
-      // of a third each = 0.67 of a round; unsplit it was the 8th round of 7.63).  A few tail tiles: one round of short pieces.
-      int ms = cus / tail;
-      if (ms < 2) {
-        double best = 1.0;
-        ms = 1;
-        for (int c = 2; c <= 8; ++c) {
-          const double cost = (double)((tail * c + cus - 1) / cus) / c + 0.01 * c;     // + the partials' round trip
-          if (cost < best - 1e-9) {
-            best = cost;
-            ms = c;
-          }
-        }
-      }
-      if (ms > stages / 4) ms = stages / 4;                 // at least four LDS stages per workgroup
-      if (ms < 1) ms = 1;
-      msplit = ms;
-      if (msplit == 1) full_tiles = 0;                      // nothing to split: plain launch
-    }
-  }
-  int mchunk = (int)round_up((m + msplit - 1) / msplit, NN_KC);
-  msplit = (m + mchunk - 1) / mchunk;
-  double* out = Y;
-  int64_t ldo = ldy, pstride = 0;
-  if (msplit > 1) {
-    ldo = round_up(N, 32);
-    pstride = ldo * r;
-    void* pv = nullptr;
-    HFMI_TRY(ctx_ws(ctx, WS_PART, (size_t)msplit * pstride * sizeof(double), &pv));
-    out = (double*)pv;
-  } else {
-    full_tiles = 0;
-  }
-  const int tail_tiles = ntiles - full_tiles;
-  dim3 block(WAVES * 64);
-  // plan record of one launch: tile height, the split, whole and split tiles it covers, grid
-  auto rec = [&](int tt, int ms, int full, int tl) {
-    plan_record(ctx, HFMI_PLAN_NN, {tt, NT, WAVES, r4, 0, ms, full, tl, full + tl * ms});
-  };
-  auto reduce_tail = [&]() -> int {
-    const int64_t row0 = (int64_t)full_tiles * tile_rows;   // multiple of 64
-    int64_t gx = ((N - row0 + 1) / 2 + 255) / 256;
-    if (gx > 2048) gx = 2048;
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(k_reduce_nn, dim3((unsigned)gx, (unsigned)r), dim3(256), 0, ctx->stream, (const double*)out, msplit,
-                       pstride, ldo, Y, ldy, row0, N, r);
-    HIP_TRY(hipGetLastError());
-    return HFMI_OK;
-  };
-  // Row panels for an overlapped rank reduction (ctx->nn_hook, set by hfmi_op_apply): whole rounds of tiles per launch, the
-  // hook is told which rows are final after each.  Tiles keep the plan of the single launch, so the results are the same bits.
-  // A round's tiles finish together, so with R rounds the last panel is 1/R of the block and its reduction is exposed.  When
-  // every round already is its own panel and one more panel is allowed, the LAST round is issued as two launches of tiles of
-  // HALF the height (same reduction order per row: still the same bits): its first half is final -- and on its way through the
-  // fabric -- while the second half is computed, and only a quarter of a two-round product is left exposed.
-  if (ctx->nn_hook) {
-    const int whole_cnt = msplit > 1 ? full_tiles : ntiles;          // tiles computed in one piece
-    const int rounds = whole_cnt / cus;
-    if (rounds >= 2) {
-      int panels = rounds < ctx->nn_hook_panels ? rounds : ctx->nn_hook_panels;
-      if (panels < 1) panels = 1;
-      constexpr int TH = TT / 2;
-      static const int env_halve = getenv("HFMI_NN_HALVE_LAST") ? atoi(getenv("HFMI_NN_HALVE_LAST")) : -1;   // A/B switch: 1 on, 0 off
-      const bool halve = (env_halve >= 0 ? env_halve != 0 : g_nn_halve_last != 0) && (TT % 2 == 0) && TH >= 1 && panels == rounds && panels + 1 <= ctx->nn_hook_panels && panels + 1 <= 8;
-      int base = 0;
-      for (int p = 0; p < panels; ++p) {
-        const bool last = p == panels - 1;
-        const int cnt = last ? whole_cnt - base : (rounds / panels + (p < rounds % panels ? 1 : 0)) * cus;
-        const int tl = (last && msplit > 1) ? tail_tiles : 0;
-        if (last && halve) {
-          if constexpr (TT % 2 == 0 && TT >= 2) {
-            auto kern_h = r4 == 1 ? k_tsgemm_nn<TH, NT, WAVES, 1> : r4 == 2 ? k_tsgemm_nn<TH, NT, WAVES, 2>
-                        : r4 == 3 ? k_tsgemm_nn<TH, NT, WAVES, 3> : k_tsgemm_nn<TH, NT, WAVES, 0>;
-            HIP_TRY(hipFuncSetAttribute((const void*)kern_h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            const int cnt_a = cnt / 2, cnt_b = cnt - cnt_a;          // in tiles of the full height
-            // first half of the round: 2 cnt_a half-height tiles starting at half-tile 2 base
-            hipLaunchKernelGGL(kern_h, dim3((unsigned)(2 * cnt_a)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
-                               (int64_t)0, 2 * cnt_a, Y, ldy, 2 * base, 0);
-            HIP_TRY(hipGetLastError());
-            rec(TH, 1, 2 * cnt_a, 0);
-            HFMI_TRY(ctx->nn_hook(ctx->nn_hook_user, Y, ldy, r, (int64_t)base * tile_rows, (int64_t)cnt_a * tile_rows));
-            // second half (the last half-height tile may be ragged: rows >= N are never stored), then the split tail tiles
-            hipLaunchKernelGGL(kern_h, dim3((unsigned)(2 * cnt_b)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
-                               (int64_t)0, 2 * cnt_b, Y, ldy, 2 * (base + cnt_a), 0);
-            HIP_TRY(hipGetLastError());
-            rec(TH, 1, 2 * cnt_b, 0);
-            if (tl > 0) {
-              hipLaunchKernelGGL(kern, dim3((unsigned)(tl * msplit)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, out, ldo, N, tl, msplit,
-                                 mchunk, pstride, 0, Y, ldy, base, full_tiles);
-              HIP_TRY(hipGetLastError());
-              rec(TT, msplit, 0, tl);
-              HFMI_TRY(reduce_tail());
-            }
-            const int64_t row0 = (int64_t)(base + cnt_a) * tile_rows;
-            HFMI_TRY(ctx->nn_hook(ctx->nn_hook_user, Y, ldy, r, row0, N - row0));
-          }
-          base += cnt;
-          continue;
-        }
-        if (msplit > 1)
-          hipLaunchKernelGGL(kern, dim3((unsigned)(cnt + tl * msplit)), block, shmem, ctx->stream, A, lda, m, S, lds_, r, out, ldo, N,
-                             tl > 0 ? tl : 1, msplit, mchunk, pstride, cnt, Y, ldy, base, full_tiles);
-        else
-          hipLaunchKernelGGL(kern, dim3((unsigned)cnt), block, shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, 1, 1, mchunk,
-                             (int64_t)0, cnt, Y, ldy, base, 0);
-        HIP_TRY(hipGetLastError());
-        rec(TT, msplit, cnt, msplit > 1 ? tl : 0);
-        if (last && msplit > 1) HFMI_TRY(reduce_tail());
-        const int64_t row0 = (int64_t)base * tile_rows;
-        const int64_t row1 = last ? N : (int64_t)(base + cnt) * tile_rows;
-        HFMI_TRY(ctx->nn_hook(ctx->nn_hook_user, Y, ldy, r, row0, row1 - row0));
-        base += cnt;
-      }
-      ctx->nn_hook_called = true;
-      return HFMI_OK;
-    }
-  }
-  dim3 grid((unsigned)(full_tiles + tail_tiles * msplit));
-  hipLaunchKernelGGL(kern, grid, block, shmem, ctx->stream, A, lda, m, S, lds_, r, out, ldo, N, tail_tiles, msplit, mchunk, pstride,
-                     full_tiles, Y, ldy, 0, full_tiles);
-  HIP_TRY(hipGetLastError());
-  rec(TT, msplit, full_tiles, tail_tiles);
-  if (msplit > 1) HFMI_TRY(reduce_tail());
-  return HFMI_OK;
+static nn_kernel_t nn_kernel_r4(int r4) {
+  return r4 == 1 ? k_tsgemm_nn<TT, NT, WAVES, 1> : r4 == 2 ? k_tsgemm_nn<TT, NT, WAVES, 2>
+       : r4 == 3 ? k_tsgemm_nn<TT, NT, WAVES, 3> : k_tsgemm_nn<TT, NT, WAVES, 0>;
 }
-
-// one-wave-per-SIMD variants: the tile height is chosen among TMAX, TMAX-1, TMAX-2 (16-row tiles per wave) together
-// with the reduction split, by the time model above -- a slightly shorter tile often fills the last round of CUs
-template <int NT, int TMAX>
-static int nn_launch_w4(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds_, int r, double* Y,
-                        int64_t ldy, int64_t N) {
-  constexpr int T1 = TMAX > 1 ? TMAX - 1 : 1, T2 = TMAX > 2 ? TMAX - 2 : 1;
-  int ms0 = 1, ms1 = 1, ms2 = 1;
-  const double c0 = nn_plan(ctx, 64 * TMAX, m, r, N, 1.0, &ms0);
-  const double c1 = (T1 != TMAX) ? nn_plan(ctx, 64 * T1, m, r, N, 0.98, &ms1) : 1e300;
-  const double c2 = (T2 != T1) ? nn_plan(ctx, 64 * T2, m, r, N, 0.96, &ms2) : 1e300;
-  // With at least one full round of the tallest tiles the quantisation is handled by splitting only the tail tiles
-  // (nn_launch_inst), so the tallest tile -- the best MFMA-to-LDS ratio -- is taken (A/B r01e: config 4 nn 56.5 -> 59.7 TF)
-  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  if (g_nn_hybrid && g_nn_tt == 0 && (N + 64 * TMAX - 1) / (64 * TMAX) >= cus && m >= 16 * NN_KC)
-    return nn_launch_inst<TMAX, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, 1, true);
-  if (g_nn_tt == 1) return nn_launch_inst<TMAX, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms0);
-  if (g_nn_tt == 2) return nn_launch_inst<T1, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms1);
-  if (g_nn_tt == 3) return nn_launch_inst<T2, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms2);
-  if (c0 <= c1 && c0 <= c2) return nn_launch_inst<TMAX, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms0);
-  if (c1 <= c2) return nn_launch_inst<T1, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms1);
-  return nn_launch_inst<T2, NT, 4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms2);
+template <int TT, int NT, int WAVES>
+static bool nn_kernels_tt(int r4, nn_kernel_t* full, nn_kernel_t* half) {
+  *full = nn_kernel_r4<TT, NT, WAVES>(r4);
+  if constexpr (TT % 2 == 0) *half = nn_kernel_r4<TT / 2, NT, WAVES>(r4);
+  return true;
 }
-
-template <int NT, int TT>
-static int nn_launch_w8(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds_, int r, double* Y,
-                        int64_t ldy, int64_t N) {
-  int ms = 1;
-  nn_plan(ctx, 128 * TT, m, r, N, 1.0, &ms);
-  return nn_launch_inst<TT, NT, 8>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, ms);
+static bool nn_kernels(const nn_plan& p, nn_kernel_t* full, nn_kernel_t* half) {
+#define NN_CASE(NTV, TT4, TT8)                                                                                       \
+  case NTV:                                                                                                          \
+    if (p.waves == 8) return p.tt == TT8 && nn_kernels_tt<TT8, NTV, 8>(p.r4, full, half);                            \
+    if (p.tt == TT4) return nn_kernels_tt<TT4, NTV, 4>(p.r4, full, half);                                            \
+    if (p.tt == nn_tt_lower(TT4, 1)) return nn_kernels_tt<nn_tt_lower(TT4, 1), NTV, 4>(p.r4, full, half);            \
+    return p.tt == nn_tt_lower(TT4, 2) && nn_kernels_tt<nn_tt_lower(TT4, 2), NTV, 4>(p.r4, full, half);
+  switch (p.nt) { HFMI_NN_CASES(NN_CASE) }
+#undef NN_CASE
+  return false;
 }
-
+template <int TT, int NT, bool UP>
+static nn_res_kernel_t nn_res_kernel_r4(int r4) {
+  return r4 == 1 ? k_tsgemm_nn_res<TT, NT, 1, UP> : r4 == 2 ? k_tsgemm_nn_res<TT, NT, 2, UP>
+       : r4 == 3 ? k_tsgemm_nn_res<TT, NT, 3, UP> : k_tsgemm_nn_res<TT, NT, 0, UP>;
+}
 template <int TT, int NT>
-static int nn_launch_res(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds_, int r, double* Y,
-                         int64_t ldy, int64_t N, size_t shmem) {
-  const int rem = r - (NT - 1) * 16;
-  const int r4 = (g_rem4 && rem <= 12) ? (rem + 3) / 4 : 0;
-  static const bool env_off = getenv("HFMI_NN_UPPER") && atoi(getenv("HFMI_NN_UPPER")) == 0;   // A/B switch
-  const bool up = ctx->nn_upper_hint && g_nn_upper && !env_off;
-  auto kern = up ? (r4 == 1 ? k_tsgemm_nn_res<TT, NT, 1, true> : r4 == 2 ? k_tsgemm_nn_res<TT, NT, 2, true>
-                    : r4 == 3 ? k_tsgemm_nn_res<TT, NT, 3, true> : k_tsgemm_nn_res<TT, NT, 0, true>)
-                 : (r4 == 1 ? k_tsgemm_nn_res<TT, NT, 1, false> : r4 == 2 ? k_tsgemm_nn_res<TT, NT, 2, false>
-                    : r4 == 3 ? k_tsgemm_nn_res<TT, NT, 3, false> : k_tsgemm_nn_res<TT, NT, 0, false>);
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  const int tile_rows = 16 * TT * 8;
-  const int ntiles = (int)((N + tile_rows - 1) / tile_rows);
-  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  const int grid = ntiles < cus ? ntiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, ntiles);
-  HIP_TRY(hipGetLastError());
-  plan_record(ctx, HFMI_PLAN_NN_RES, {TT, NT, 8, r4, up ? 1 : 0, 1, ntiles, 0, grid});
-  return HFMI_OK;
+static nn_res_kernel_t nn_res_kernel_tt(int r4, bool up) {
+  return up ? nn_res_kernel_r4<TT, NT, true>(r4) : nn_res_kernel_r4<TT, NT, false>(r4);
+}
+static nn_res_kernel_t nn_res_kernel(const nn_plan& p) {
+#define NN_RES(NTV, TTV) \
+  case NTV:              \
+    return p.tt == TTV ? nn_res_kernel_tt<TTV, NTV>(p.r4, p.upper) : nn_res_kernel_tt<nn_tt_lower(TTV, 1), NTV>(p.r4, p.upper);
+  switch (p.nt) { HFMI_NN_RES_CASES(NN_RES) }
+#undef NN_RES
+  return nullptr;
 }
 
+// one panel of at most 256 columns: plan (hfmi_tsgemm_plan.h), then every launch of its list with the partial-sum reduction and the
+// row-panel hook of an overlapped rank reduction (ctx->nn_hook, set by hfmi_op_apply) behind it where the plan says so
 static int nn_panel(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds_, int r, double* Y,
                     int64_t ldy, int64_t N) {
-  const int nt = (r + 15) / 16;
-  // S whole in LDS (one workgroup per CU): [round_up(m, 4)][SLD] doubles.  In-place products (Y == A: Q <- Q R^-1) are
-  // fine: a workgroup reads the rows of a tile completely before it stores them, and tiles do not overlap.
-  if (g_nn_res && nt <= 10 && N >= 4096) {
-    const int sld = nt * 16 + ((nt % 2 == 0) ? 16 : 0);
-    const size_t shmem = (size_t)((m + 3) & ~3) * sld * sizeof(double);
-    if (shmem <= 160 * 1024) {
-      // Tile height: the persistent workgroups take whole tiles of 128 TT rows in turn, so the product costs
-      // ceil(tiles / CUs) rounds of TT units each.  N = 2e5 with TT = 3 is 521 tiles = 2.03 rounds -> 3 rounds (9 units) where
-      // TT = 2 needs 4 rounds of 2 (8 units): the shorter tile is taken when it saves more than the ~5 % its worse
-      // MFMA-to-LDS ratio costs.
-      const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-      auto units = [&](int tt) {
-        const int64_t tiles = (N + 128 * tt - 1) / (128 * tt);
-        return (double)((tiles + cus - 1) / cus) * tt;
-      };
-#define NN_RES(NTV, TTV)                                                                                      \
-  case NTV: {                                                                                                 \
-    constexpr int TL = TTV > 1 ? TTV - 1 : 1;                                                                 \
-    const bool lower = g_nn_res_tt == 2 || (g_nn_res_tt == 0 && TL != TTV && units(TL) * 1.05 < units(TTV)); \
-    if (lower) return nn_launch_res<TL, NTV>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, shmem);                   \
-    return nn_launch_res<TTV, NTV>(ctx, A, lda, m, S, lds_, r, Y, ldy, N, shmem);                             \
+  const int hook_panels = !ctx->nn_hook ? 0 : ctx->nn_hook_panels > 1 ? ctx->nn_hook_panels : 1;
+  const nn_plan p = nn_plan_make(m, r, N, ctx->nn_upper_hint, hook_panels, tsgemm_knobs_ref(), ctx->num_cus);
+  if (!p.has_instance) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_nn: panel too wide (%d)", r);
+  if (p.res) {
+    const nn_res_kernel_t kern = nn_res_kernel(p);
+    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.shmem, ctx->stream, A, lda, m, S, lds_, r, Y, ldy, N, p.ntiles);
+    HIP_TRY(hipGetLastError());
+    nn_res_plan_words(p, plan_slot(ctx));
+    return HFMI_OK;
   }
-      switch (nt) {
-        NN_RES(1, 4) NN_RES(2, 4) NN_RES(3, 4) NN_RES(4, 4) NN_RES(5, 3) NN_RES(6, 2) NN_RES(7, 2) NN_RES(8, 2) NN_RES(9, 2)
-        NN_RES(10, 1)
-      }
-#undef NN_RES
+  nn_kernel_t full = nullptr, half = nullptr;
+  if (!nn_kernels(p, &full, &half)) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_nn: no instance for TT=%d NT=%d WAVES=%d", p.tt, p.nt, p.waves);
+  double* part = nullptr;
+  if (p.msplit > 1) {
+    void* pv = nullptr;
+    HFMI_TRY(ctx_ws(ctx, WS_PART, p.ws_bytes, &pv));
+    part = (double*)pv;
+  }
+  HIP_TRY(hipFuncSetAttribute((const void*)full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+  if (p.halved) HIP_TRY(hipFuncSetAttribute((const void*)half, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+  for (int i = 0; i < p.nlaunch; ++i) {
+    const nn_launch& l = p.launch[i];
+    const nn_kernel_t kern = l.half ? half : full;
+    const bool split = l.msplit > 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(p.waves * 64), p.shmem, ctx->stream, A, lda, m, S, lds_, r, split ? part : Y,
+                       split ? p.ldo : ldy, N, l.tail_tiles, l.msplit, p.mchunk, split ? p.pstride : (int64_t)0, l.full_tiles, Y, ldy,
+                       l.full_base, l.tail_base);
+    HIP_TRY(hipGetLastError());
+    nn_launch_words(p, l, plan_slot(ctx));
+    if (l.reduce) {
+      hipLaunchKernelGGL(k_reduce_nn, dim3(p.reduce_gx, (unsigned)r), dim3(256), 0, ctx->stream, (const double*)part, p.msplit, p.pstride,
+                         p.ldo, Y, ldy, p.reduce_row0, N, r);
+      HIP_TRY(hipGetLastError());
     }
+    if (l.hook_rows > 0) HFMI_TRY(ctx->nn_hook(ctx->nn_hook_user, Y, ldy, r, l.hook_row0, l.hook_rows));
   }
-  const int waves = g_nn_waves ? g_nn_waves : (nt >= 7 ? 8 : 4);   // A/B (scripts/nn_waves_ab.py, r01g): one wave per SIMD wins up to 6 column tiles
-#define NN_CASE(NTV, TT4, TT8)                                                             \
-  case NTV:                                                                                \
-    if (waves == 8) return nn_launch_w8<NTV, TT8>(ctx, A, lda, m, S, lds_, r, Y, ldy, N);  \
-    return nn_launch_w4<NTV, TT4>(ctx, A, lda, m, S, lds_, r, Y, ldy, N);
-  switch (nt) {
-    NN_CASE(1, 8, 8) NN_CASE(2, 8, 8) NN_CASE(3, 8, 5) NN_CASE(4, 8, 4) NN_CASE(5, 6, 3) NN_CASE(6, 5, 2)
-    NN_CASE(7, 4, 2) NN_CASE(8, 4, 2) NN_CASE(9, 3, 2) NN_CASE(10, 3, 1) NN_CASE(11, 2, 1) NN_CASE(12, 2, 1)
-    NN_CASE(13, 2, 1) NN_CASE(14, 2, 1) NN_CASE(15, 2, 1) NN_CASE(16, 2, 1)
-  }
-#undef NN_CASE
-  HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_nn: panel too wide (%d)", r);
+  if (p.hooked) ctx->nn_hook_called = true;
+  return HFMI_OK;
 }
 
 __global__ void k_small_scale_copy(double* __restrict__ dst, const double* __restrict__ src, int rows, int cols, int ld,

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hfmi.h"
+#include "hfmi_tsgemm_plan.h"
 
 // ------------------------------------------------------------------ errors
 void hfmi_set_error(const char* fmt, ...);
@@ -139,15 +140,8 @@ struct hfmi_ctx {
   int plan_ring[HFMI_PLAN_RING][HFMI_PLAN_WORDS];
   int64_t plan_count;             // launches since the last clear
 };
-// appends one record: word 0 = kind (HFMI_PLAN_*), then the fields in the order include/hfmi.h lists them
-static inline void plan_record(hfmi_ctx* ctx, int kind, std::initializer_list<int> fields) {
-  int* w = ctx->plan_ring[ctx->plan_count++ % HFMI_PLAN_RING];
-  int i = 0;
-  w[i++] = kind;
-  for (int v : fields)
-    if (i < HFMI_PLAN_WORDS) w[i++] = v;
-  while (i < HFMI_PLAN_WORDS) w[i++] = 0;
-}
+// the slot of the next record, to be filled by one of the *_plan_words helpers (hfmi_tsgemm_plan.h)
+static inline int* plan_slot(hfmi_ctx* ctx) { return ctx->plan_ring[ctx->plan_count++ % HFMI_PLAN_RING]; }
 // large transfers between the caller's pageable arrays and device memory, pipelined through pinned chunks (hfmi_xfer.hip)
 int xfer_d2h(hfmi_ctx* ctx, void* host, const void* dev, size_t bytes);   // returns when the host array is complete
 int xfer_h2d(hfmi_ctx* ctx, void* dev, const void* host, size_t bytes);   // returns when the host array has been read
@@ -280,14 +274,11 @@ int ctx_check_comm(hfmi_ctx* ctx);        // comm_check_error over the watched c
 int launch_tsgemm_tn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
                      int64_t N, double scale, double beta, double* C, int64_t rs, int64_t cs, int nsplit_req);
 // skinny x skinny variant (hfmi_skinny.hip): both operands staged through LDS, m, k <= 160 and m + k <= 288 columns
-bool tsgemm_ss_applicable(int m, int k, bool same);
-void tsgemm_ss_set_percu(int v);
-void tsgemm_ss_set_blocked(int v);
 int launch_tsgemm_ss(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
                      int64_t N, double scale, double beta, double* C, int64_t rs, int64_t cs, int nsplit_req);
-// C[i*rs + j*cs] = scale * sum_sp part[sp][..] + beta * C, fixed summation order
-int launch_reduce_partials(hfmi_ctx* ctx, const double* part, int nsplit, int64_t pstride, int inner_ld, bool tr, int m,
-                           int k, double scale, double beta, double* C, int64_t rs, int64_t cs);
+// C[i*rs + j*cs] = scale * sum_sp part[sp][..] + beta * C, fixed summation order (part and C: where the call's slices and result start)
+int launch_reduce_partials(hfmi_ctx* ctx, const double* part, const reduce_call& c, double scale, double beta, double* C, int64_t rs,
+                           int64_t cs);
 // Y (N x r) = alpha * A (N x m) * S (m x r, device row-major, ld = lds, zero padded to 16 cols) + beta * Y
 int launch_tsgemm_nn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int lds, int r,
                      double alpha, double beta, double* Y, int64_t ldy, int64_t N);

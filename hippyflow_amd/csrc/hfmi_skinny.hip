@@ -49,7 +49,6 @@ typedef const __attribute__((address_space(1))) double* gdptr;
 #ifndef SS_PROBE
 #define SS_PROBE 0
 #endif
-constexpr int SS_BK = 32;  // reduction indices per stage (16 chunks of 16 bytes per column)
 constexpr int SS_THREADS = 512;
 
 // One 32-row stage of MFMAs for a wave that owns NT tiles.  The A/B fragments of step i+1 are read from LDS
@@ -576,130 +575,51 @@ __global__ __launch_bounds__(SS_THREADS, 2) void k_tsgemm_ssb(const double* __re
 #undef SSB_RUN
 }
 
-static bool ssb_pipe();
-template <int RT, int CTL>
-static int ssb_launch(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k, int64_t Npad,
-                      int64_t chunk, int nsplit, double* part, bool swapped) {
-  constexpr int NQ = (RT + CTL + 1) / 2;
-  const size_t shmem = 2 * (size_t)NQ * 32 * SS_BK * sizeof(double) + (size_t)NQ * 32 * sizeof(double*);
-  // pipelined stages where the fragments fit next to two register stages (measured, scripts/ss_shapes.py: n = 32 / 48 / 64 at
-  // k = 138 +4 / +2.5 / +2 %; the 9 x 9 tile shape loses 10 % to the registers the carried fragments cost)
-  const bool pipe = ssb_pipe() && RT * CTL <= 56;
-  if (pipe) {
-    auto kern = k_tsgemm_ssb<RT, CTL, NQ, true>;
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, B, ldb, k, Npad, chunk, part);
-  } else {
-    auto kern = k_tsgemm_ssb<RT, CTL, NQ, false>;
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, B, ldb, k, Npad, chunk, part);
-  }
-  HIP_TRY(hipGetLastError());
-  plan_record(ctx, HFMI_PLAN_SSB, {RT, CTL, NQ, pipe ? 1 : 0, swapped ? 1 : 0, 0, nsplit});
-  return HFMI_OK;
+// the instance of a plan; null: not compiled
+typedef void (*ss_kernel_t)(const double*, int64_t, int, int, const double*, int64_t, int, int, int, int64_t, int64_t, double*);
+typedef void (*ssb_kernel_t)(const double*, int64_t, int, const double*, int64_t, int, int64_t, int64_t, double*);
+static ss_kernel_t ss_kernel(const ss_plan& p) {
+#define SS_CASE(T, Q) \
+  if (p.tpw == T && p.nq == Q) return k_tsgemm_ss<T, Q, ss_pf(T, Q)>;
+  HFMI_SS_CASES(SS_CASE)
+#undef SS_CASE
+  return nullptr;
 }
-static int g_ss_blocked = 1;   // A/B knob "ss_blocked": 0 = round-robin kernel, 1 = blocked, 2 = blocked without the stage pipelining
-void tsgemm_ss_set_blocked(int v) { g_ss_blocked = v; }
-static bool ssb_pipe() { return g_ss_blocked != 2; }
-// rt <= ct after the caller's role swap
-static bool ssb_has_instance(int rt, int ct) { return rt >= 2 && rt <= ct && (ct == 5 || ct == 6 || ct == 9) && rt + ct <= 18; }
-static int ssb_dispatch(hfmi_ctx* ctx, int rt, int ct, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
-                        int64_t Npad, int64_t chunk, int nsplit, double* part, bool swapped) {
+static ssb_kernel_t ssb_kernel(const ss_plan& p) {
 #define SSB_CASE(R, Cc) \
-  if (rt == R && ct == Cc) return ssb_launch<R, Cc>(ctx, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part, swapped);
-  SSB_CASE(2, 5) SSB_CASE(3, 5) SSB_CASE(4, 5) SSB_CASE(5, 5)
-  SSB_CASE(2, 6) SSB_CASE(3, 6) SSB_CASE(4, 6) SSB_CASE(5, 6) SSB_CASE(6, 6)
-  SSB_CASE(2, 9) SSB_CASE(3, 9) SSB_CASE(4, 9) SSB_CASE(5, 9) SSB_CASE(6, 9) SSB_CASE(7, 9) SSB_CASE(8, 9) SSB_CASE(9, 9)
+  if (p.rt == R && p.ct == Cc) return p.pipe ? k_tsgemm_ssb<R, Cc, (R + Cc + 1) / 2, true> : k_tsgemm_ssb<R, Cc, (R + Cc + 1) / 2, false>;
+  HFMI_SSB_CASES(SSB_CASE)
 #undef SSB_CASE
-  HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_ssb: no instance for %d x %d tiles", rt, ct);
-}
-
-constexpr int ss_pf(int tpw, int nq) { return (tpw <= 4 && nq <= 6) ? 2 : 1; }
-
-template <int TPW, int NQ>
-static int ss_launch(hfmi_ctx* ctx, const double* A, int64_t lda, int m, int rt, const double* B, int64_t ldb, int k,
-                     int ct, int same, int64_t Npad, int64_t chunk, int nsplit, double* part, size_t shmem) {
-  auto kern = k_tsgemm_ss<TPW, NQ, ss_pf(TPW, NQ)>;
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(kern, dim3(nsplit), dim3(SS_THREADS), shmem, ctx->stream, A, lda, m, rt, B, ldb, k, ct, same, Npad,
-                     chunk, part);
-  HIP_TRY(hipGetLastError());
-  plan_record(ctx, HFMI_PLAN_SS, {TPW, NQ, ss_pf(TPW, NQ), 0, same, nsplit});
-  return HFMI_OK;
-}
-
-static int g_ss_percu = 2;  // cap on resident workgroups per CU used to size the grid (A/B knob "ss_percu")
-void tsgemm_ss_set_percu(int v) { g_ss_percu = v < 1 ? 1 : v; }
-
-bool tsgemm_ss_applicable(int m, int k, bool same) {
-  const int rt = (m + 15) / 16, ct = (k + 15) / 16;
-  if (rt < 1 || ct < 1 || rt > 10 || ct > 10) return false;
-  const int ctot = same ? rt * 16 : (rt + ct) * 16;
-  return ctot <= 288;
+  return nullptr;
 }
 
 int launch_tsgemm_ss(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* B, int64_t ldb, int k,
                      int64_t N, double scale, double beta, double* C, int64_t rs, int64_t cs, int nsplit_req) {
   const bool same = (A == B && lda == ldb && m == k);
-  const int rt = (m + 15) / 16, ct = (k + 15) / 16;
-  const int ctot = same ? rt * 16 : (rt + ct) * 16;
-  const int64_t Npad = round_up(N, SS_BK);
-  if (lda % 32 != 0 || ldb % 32 != 0 || lda < Npad || ldb < Npad)
+  const ss_plan p = ss_plan_make(m, k, N, same, nsplit_req, tsgemm_knobs_ref(), ctx->num_cus);
+  if (lda % 32 != 0 || ldb % 32 != 0 || lda < p.Npad || ldb < p.Npad)
     HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_ss: leading dimensions must be multiples of 32 and >= round_up(N,32)");
-  const bool swap = !same && rt > ct;                      // the blocked variant wants rt <= ct: exchange the operand roles
-  const bool blocked = !same && g_ss_blocked && ssb_has_instance(swap ? ct : rt, swap ? rt : ct);
-  const int tpw = ((same ? rt * (rt + 1) / 2 : rt * ct) + 7) / 8;
-  const int nq = (ctot + 31) / 32;  // staged columns are padded to 32 (one 16-byte chunk per thread per 32 columns)
-  // unpadded stage buffers: one for the HBM-bound variants (PF = 2), two plus the column pointer table otherwise
-  const size_t stage_bytes = (size_t)nq * 32 * SS_BK * sizeof(double);
-  const size_t shmem = (ss_pf(tpw, nq) == 2 && !blocked) ? stage_bytes : 2 * stage_bytes + (size_t)nq * 32 * sizeof(double*);
-  // workgroups resident per CU: LDS (160 KB) and registers (TPW <= 4 compiles for 4 waves per SIMD = 2 workgroups)
-  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  int per_cu = (int)((160 * 1024) / shmem);
-  const int reg_cap = (tpw <= 4 && !blocked) ? g_ss_percu : 1;
-  if (per_cu > reg_cap) per_cu = reg_cap;
-  if (per_cu < 1) per_cu = 1;
-  const int64_t stages = Npad / SS_BK;
-  int nsplit = nsplit_req > 0 ? nsplit_req : cus * per_cu;
-  if (nsplit > stages / 2) nsplit = (int)(stages / 2);
-  if (nsplit < 1) nsplit = 1;
-  int64_t chunk = round_up((Npad + nsplit - 1) / nsplit, SS_BK);
-  nsplit = (int)((Npad + chunk - 1) / chunk);
-  const int mpad = rt * 16, kpad = ct * 16;
+  const ss_kernel_t kern = p.blocked ? nullptr : ss_kernel(p);
+  const ssb_kernel_t kern_b = p.blocked ? ssb_kernel(p) : nullptr;
+  if (!kern && !kern_b) HFMI_FAIL(HFMI_ERR_INVALID, "tsgemm_ss: no instance for tiles/wave=%d chunks/thread=%d", p.tpw, p.nq);
   void* partv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_PART, (size_t)nsplit * mpad * kpad * sizeof(double), &partv));
+  HFMI_TRY(ctx_ws(ctx, WS_PART, p.ws_bytes, &partv));
   double* part = (double*)partv;
   const int pidx = prof_start(ctx, 0, m, k, N);
   if (same && pidx >= 0) {   // symmetric output from ONE operand: algorithmic work N k (k + 1) flops, 8 (N k + k^2) bytes
     ctx->prof[pidx].flops = (double)N * k * (k + 1);
     ctx->prof[pidx].bytes = 8.0 * ((double)N * k + (double)k * k);
   }
-  if (blocked) {
-    if (swap)
-      HFMI_TRY(ssb_dispatch(ctx, ct, rt, B, ldb, k, A, lda, m, Npad, chunk, nsplit, part, true));
-    else
-      HFMI_TRY(ssb_dispatch(ctx, rt, ct, A, lda, m, B, ldb, k, Npad, chunk, nsplit, part, false));
-    prof_stop(ctx, pidx);
-    // swapped roles: the partial tiles hold (A^T B)^T = B^T A, k x m with row stride mpad
-    return swap ? launch_reduce_partials(ctx, part, nsplit, (int64_t)mpad * kpad, mpad, true, m, k, scale, beta, C, rs, cs)
-                : launch_reduce_partials(ctx, part, nsplit, (int64_t)mpad * kpad, kpad, false, m, k, scale, beta, C, rs, cs);
-  }
-  int rc = HFMI_ERR_INVALID;
-#define SS_CASE(T, Q)                                                                                              \
-  if (tpw == T && nq == Q)                                                                                         \
-    rc = ss_launch<T, Q>(ctx, A, lda, m, rt, B, ldb, k, ct, same ? 1 : 0, Npad, chunk, nsplit, part, shmem);      \
+  HIP_TRY(hipFuncSetAttribute(p.blocked ? (const void*)kern_b : (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+  if (!p.blocked)
+    hipLaunchKernelGGL(kern, dim3(p.nsplit), dim3(SS_THREADS), p.shmem, ctx->stream, A, lda, m, p.swap ? p.ct : p.rt, B, ldb, k,
+                       p.swap ? p.rt : p.ct, same ? 1 : 0, p.Npad, p.chunk, part);
+  else if (p.swap)
+    hipLaunchKernelGGL(kern_b, dim3(p.nsplit), dim3(SS_THREADS), p.shmem, ctx->stream, B, ldb, k, A, lda, m, p.Npad, p.chunk, part);
   else
-  // every (tiles per wave, chunks per thread) pair reachable with rt, ct <= 10 and ctot <= 288, and no other
-  // (tests/test_contraction_plan_cpu.py enumerates the rule above and compares it with this list)
-  SS_CASE(1, 1) SS_CASE(1, 2) SS_CASE(1, 3) SS_CASE(1, 4) SS_CASE(1, 5) SS_CASE(2, 2) SS_CASE(2, 3) SS_CASE(2, 4)
-  SS_CASE(2, 5) SS_CASE(2, 6) SS_CASE(3, 5) SS_CASE(3, 6) SS_CASE(4, 5) SS_CASE(4, 6) SS_CASE(4, 7)
-  SS_CASE(5, 6) SS_CASE(5, 7) SS_CASE(6, 7) SS_CASE(7, 7) SS_CASE(7, 8)
-  SS_CASE(8, 8) SS_CASE(9, 9) SS_CASE(10, 9) SS_CASE(11, 9)
-  // one-operand (Gram) tile lists: rt (rt + 1) / 2 tiles, rt * 16 staged columns
-  SS_CASE(3, 3) SS_CASE(4, 4) SS_CASE(5, 4) SS_CASE(6, 5) SS_CASE(7, 5)
-  { hfmi_set_error("tsgemm_ss: no instance for tiles/wave=%d chunks/thread=%d", tpw, nq); }
-#undef SS_CASE
-  HFMI_TRY(rc);
+    hipLaunchKernelGGL(kern_b, dim3(p.nsplit), dim3(SS_THREADS), p.shmem, ctx->stream, A, lda, m, B, ldb, k, p.Npad, p.chunk, part);
+  HIP_TRY(hipGetLastError());
+  ss_plan_words(p, plan_slot(ctx));
   prof_stop(ctx, pidx);
-  return launch_reduce_partials(ctx, part, nsplit, (int64_t)mpad * kpad, kpad, false, m, k, scale, beta, C, rs, cs);
+  return launch_reduce_partials(ctx, part, p.red, scale, beta, C, rs, cs);
 }

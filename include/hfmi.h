@@ -444,6 +444,22 @@ HFMI_API int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, doubl
 #define HFMI_REDUCE_PARTIALS 3    /* k_reduce_partials<RY> */
 HFMI_API int hfmi_plan_clear(hfmi_ctx* ctx);
 HFMI_API int hfmi_plan_read(hfmi_ctx* ctx, int max_records, int* words /* max_records x HFMI_PLAN_WORDS */, int* nrecords, int* total);
+/* The records a contraction of that shape would append, computed on the host by the planners the launchers call: no context and no
+ * device.  kind TN: the m x k result of tsgemm_tn over the long axis N (its own kernels, in column panels of 256; the skinny route
+ * is kind SS), addressed as C[i rs + j cs], with nsplit_req > 0 forcing the split; NN: Y (N x k) = A (N x m) S, hook_panels = most
+ * row panels of an overlapped rank reduction (0: none, at most 8); SS: tsgemm_ss for m, k the shapes it accepts.  flags describe
+ * what the dispatchers read off their pointers.  The knobs are the process's (hfmi_tuning_set), num_cus <= 0 stands for 256.
+ * hook_rows (optional, 2 x max_records): first row and row count the row-panel hook is called with behind each record (0, 0: no
+ * call).  *nrecords is the number of records of the plan; more than max_records is an error. */
+#define HFMI_PREDICT_TN 0
+#define HFMI_PREDICT_NN 1
+#define HFMI_PREDICT_SS 2
+#define HFMI_PREDICT_SAME 1        /* SS: one operand against itself */
+#define HFMI_PREDICT_ALIASED 2     /* TN: C is one of the operands */
+#define HFMI_PREDICT_UNALIGNED 4   /* TN, SS: C or the workspace is not 16-byte aligned */
+#define HFMI_PREDICT_UPPER 8       /* NN: the caller marks the small matrix upper triangular (Q R^-1 of the QR) */
+HFMI_API int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale, double beta, int64_t rs, int64_t cs, int nsplit_req,
+                               int flags, int num_cus, int hook_panels, int max_records, int* words, int64_t* hook_rows, int* nrecords);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */

@@ -1,9 +1,10 @@
-"""Plain-Python twin of the deterministic part of the three contraction dispatchers of libhfmi: ``tn_panel``
-(hippyflow_amd/csrc/hfmi_gemm.hip), ``nn_panel`` (hfmi_gemm_nn.hip) and ``launch_tsgemm_ss`` (hfmi_skinny.hip), and of
-``launch_reduce_partials``.  Given a shape, the tuning knobs and the CU count it returns the plan records (include/hfmi.h,
-``hfmi_plan_read``) the library must append; it also enumerates every instance a dispatcher can reach and generates the case
-lists of tests/test_gpu_contraction_instances.py.  Test infrastructure only: a new instance, table entry or knob has to be
-restated here, or tests/test_contraction_plan_cpu.py fails.
+"""Plain-Python twin of the planners of the three contraction dispatchers of libhfmi (hippyflow_amd/csrc/hfmi_tsgemm_plan.h:
+``tn_plan_make`` behind ``tn_panel``, ``nn_plan_make`` behind ``nn_panel``, ``ss_plan_make`` behind ``launch_tsgemm_ss``, and
+``reduce_plan_make`` behind ``launch_reduce_partials``).  Given a shape, the tuning knobs and the CU count it returns the plan records
+(include/hfmi.h, ``hfmi_plan_read`` / ``hfmi_plan_predict``) the library must append, for nn also the rows handed to the row-panel
+hook behind each launch; it also enumerates every instance a dispatcher can reach and generates the case lists of
+tests/test_gpu_contraction_instances.py.  Test infrastructure only: a new instance, table entry, rule or knob has to be restated
+here, or tests/test_contraction_plan_cpu.py fails.
 
 The cost models are restated operation by operation in the same order, so that the floating-point comparisons fall the same way."""
 
@@ -21,7 +22,7 @@ FIELDS = {
 VEC_LONG, VEC_ROWS, FLAT, PARTIALS = range(4)
 
 DEFAULT_KNOBS = {"waves": 8, "rem4": 1, "ss": 1, "tn_hybrid": 1, "tn_mt": 0, "ss_percu": 2, "ss_blocked": 1, "nn_waves": 0,
-                 "nn_tt": 0, "nn_hybrid": 1, "nn_res": 1, "nn_res_tt": 0, "nn_upper": 1, "probe": 0}
+                 "nn_tt": 0, "nn_hybrid": 1, "nn_res": 1, "nn_res_tt": 0, "nn_upper": 1, "nn_halve_last": 0, "probe": 0}
 
 
 def knobs(**kw):
@@ -97,8 +98,9 @@ def tn_tile(m, k, kn):
     return mode, waves, max(mt, 1)
 
 
-def tn_plan(m, k, N, kn, num_cus, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req=0):
-    """records of one tn_panel call (k <= 256); C is addressed as C[i rs + j cs]"""
+def tn_plan(m, k, N, kn, num_cus, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req=0, aliased=False, ptrs_aligned=True):
+    """records of one tn_panel call (k <= 256); C is addressed as C[i rs + j cs]; aliased: C is one of the operands; ptrs_aligned:
+    C and the workspace are 16-byte aligned"""
     rs = k if rs is None else rs
     assert 1 <= k <= 256
     nt = (k + 15) // 16
@@ -126,7 +128,7 @@ def tn_plan(m, k, N, kn, num_cus, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req
             if cost < best_cost - 1e-12:
                 best_cost, best = cost, ns
         nsplit = best
-    can_direct = scale == 1.0 and beta == 0.0
+    can_direct = scale == 1.0 and beta == 0.0 and not aliased
     ns_full = nrb_full = ns_tail = 0
     if nsplit_req <= 0 and kn["tn_hybrid"]:
         ideal = float(nrb) / cus
@@ -164,15 +166,15 @@ def tn_plan(m, k, N, kn, num_cus, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req
         direct_f = ns_full == 1 and can_direct
         out = [record(TN, mt, nt, waves, tr, r4, nrb_full * ns_full + nrb_t * ns_tail, nrb_full, ns_full, direct_f, nrb_t, ns_tail)]
         if not direct_f:
-            out.append(reduce_plan(ns_full, mpad_f * kpad, mpad_f if tr else kpad, tr, mpad_f, k, rs, cs))
-        out.append(reduce_plan(ns_tail, mpad_t * kpad, mpad_t if tr else kpad, tr, m - mpad_f, k, rs, cs))
+            out.append(reduce_plan(ns_full, mpad_f * kpad, mpad_f if tr else kpad, tr, mpad_f, k, rs, cs, ptrs_aligned))
+        out.append(reduce_plan(ns_tail, mpad_t * kpad, mpad_t if tr else kpad, tr, m - mpad_f, k, rs, cs, ptrs_aligned))
         return out
     chunk = max(round_up((Npad + nsplit - 1) // nsplit, TN_BK), TN_BK)
     nsplit = max((Npad + chunk - 1) // chunk, 1)
     direct = nsplit == 1 and can_direct
     out = [record(TN, mt, nt, waves, tr, r4, nrb * nsplit, nrb, nsplit, direct, 0, 0)]
     if not direct:
-        out.append(reduce_plan(nsplit, mpad * kpad, mpad if tr else kpad, tr, m, k, rs, cs))
+        out.append(reduce_plan(nsplit, mpad * kpad, mpad if tr else kpad, tr, m, k, rs, cs, ptrs_aligned))
     return out
 
 
@@ -238,8 +240,14 @@ def nn_cost(num_cus, tile_rows, m, r, N, rate_factor):
     return best_t, best
 
 
-def nn_inst(tt, nt, waves, m, r, N, msplit, kn, num_cus, tail_split=False):
-    """nn_launch_inst without a row-panel hook"""
+NN_MAX_PANELS = 8
+
+
+def nn_inst(tt, nt, waves, m, r, N, msplit, kn, num_cus, tail_split=False, hook_panels=0):
+    """nn_plan_stream: the launches of the streaming kernel as (record, hook_row0, hook_rows); hook_rows = 0: no hook call.  One
+    launch without a row-panel hook; with one (hook_panels > 0) and at least two rounds of whole tiles, whole rounds per panel, the
+    last round as two launches of half the tile height where the halve knob, an even TT and the panel budget allow, and the split
+    tail tiles with or behind the last panel"""
     r4 = r4_class(r, nt, kn["rem4"])
     tile_rows = 16 * tt * waves
     ntiles = (N + tile_rows - 1) // tile_rows
@@ -268,15 +276,45 @@ def nn_inst(tt, nt, waves, m, r, N, msplit, kn, num_cus, tail_split=False):
     if msplit <= 1:
         full_tiles = 0
     tail_tiles = ntiles - full_tiles
-    return record(NN, tt, nt, waves, r4, 0, msplit, full_tiles, tail_tiles, full_tiles + tail_tiles * msplit)
+
+    def rec(t, ms, full, tl):
+        return record(NN, t, nt, waves, r4, 0, ms, full, tl, full + tl * ms)
+
+    whole_cnt = full_tiles if msplit > 1 else ntiles
+    rounds = whole_cnt // cus
+    if hook_panels <= 0 or rounds < 2:
+        return [(rec(tt, msplit, full_tiles, tail_tiles), 0, 0)]
+    hook_panels = min(hook_panels, NN_MAX_PANELS)
+    panels = min(rounds, hook_panels)
+    halve = bool(kn["nn_halve_last"]) and tt % 2 == 0 and panels == rounds and panels + 1 <= hook_panels
+    out = []
+    base = 0
+    for p in range(panels):
+        last = p == panels - 1
+        cnt = whole_cnt - base if last else (rounds // panels + (1 if p < rounds % panels else 0)) * cus
+        tl = tail_tiles if (last and msplit > 1) else 0
+        row0 = base * tile_rows
+        if last and halve:
+            cnt_a = cnt // 2
+            cnt_b = cnt - cnt_a
+            row1 = (base + cnt_a) * tile_rows
+            out.append((rec(tt // 2, 1, 2 * cnt_a, 0), row0, row1 - row0))
+            out.append((rec(tt // 2, 1, 2 * cnt_b, 0), 0, 0) if tl > 0 else (rec(tt // 2, 1, 2 * cnt_b, 0), row1, N - row1))
+            if tl > 0:
+                out.append((rec(tt, msplit, 0, tl), row1, N - row1))
+        else:
+            row1 = N if last else (base + cnt) * tile_rows
+            out.append((rec(tt, msplit, cnt, tl if msplit > 1 else 0), row0, row1 - row0))
+        base += cnt
+    return out
 
 
-def nn_plan(m, r, N, kn, num_cus, upper_hint=False):
-    """record of one nn_panel call (r <= 256)"""
+def nn_launches(m, r, N, kn, num_cus, upper_hint=False, hook_panels=0):
+    """launches of one nn_panel call (r <= 256) as (record, hook_row0, hook_rows)"""
     assert 1 <= r <= 256
     nt = (r + 15) // 16
     cus = num_cus if num_cus > 0 else 256
-    if kn["nn_res"] and nt <= 10 and N >= 4096:
+    if kn["nn_res"] and nt in NN_RES_TT and N >= 4096:
         sld = nt * 16 + (16 if nt % 2 == 0 else 0)
         if ((m + 3) & ~3) * sld * 8 <= NN_RES_LDS:
             def units(tt):
@@ -288,29 +326,37 @@ def nn_plan(m, r, N, kn, num_cus, upper_hint=False):
             tt = tl if lower else ttv
             ntiles = (N + 128 * tt - 1) // (128 * tt)
             up = bool(upper_hint and kn["nn_upper"])
-            return record(NN_RES, tt, nt, 8, r4_class(r, nt, kn["rem4"]), up, 1, ntiles, 0, min(ntiles, cus))
+            return [(record(NN_RES, tt, nt, 8, r4_class(r, nt, kn["rem4"]), up, 1, ntiles, 0, min(ntiles, cus)), 0, 0)]
     waves = kn["nn_waves"] if kn["nn_waves"] else (8 if nt >= 7 else 4)
     tt4, tt8 = NN_CASE[nt]
     if waves == 8:
-        return nn_inst(tt8, nt, 8, m, r, N, nn_cost(num_cus, 128 * tt8, m, r, N, 1.0)[1], kn, num_cus)
+        return nn_inst(tt8, nt, 8, m, r, N, nn_cost(num_cus, 128 * tt8, m, r, N, 1.0)[1], kn, num_cus, hook_panels=hook_panels)
     t1 = tt4 - 1 if tt4 > 1 else 1
     t2 = tt4 - 2 if tt4 > 2 else 1
     c0, ms0 = nn_cost(num_cus, 64 * tt4, m, r, N, 1.0)
     c1, ms1 = nn_cost(num_cus, 64 * t1, m, r, N, 0.98) if t1 != tt4 else (1e300, 1)
     c2, ms2 = nn_cost(num_cus, 64 * t2, m, r, N, 0.96) if t2 != t1 else (1e300, 1)
     if kn["nn_hybrid"] and kn["nn_tt"] == 0 and (N + 64 * tt4 - 1) // (64 * tt4) >= cus and m >= 16 * NN_KC:
-        return nn_inst(tt4, nt, 4, m, r, N, 1, kn, num_cus, tail_split=True)
+        return nn_inst(tt4, nt, 4, m, r, N, 1, kn, num_cus, tail_split=True, hook_panels=hook_panels)
     if kn["nn_tt"] == 1:
-        return nn_inst(tt4, nt, 4, m, r, N, ms0, kn, num_cus)
-    if kn["nn_tt"] == 2:
-        return nn_inst(t1, nt, 4, m, r, N, ms1, kn, num_cus)
-    if kn["nn_tt"] == 3:
-        return nn_inst(t2, nt, 4, m, r, N, ms2, kn, num_cus)
-    if c0 <= c1 and c0 <= c2:
-        return nn_inst(tt4, nt, 4, m, r, N, ms0, kn, num_cus)
-    if c1 <= c2:
-        return nn_inst(t1, nt, 4, m, r, N, ms1, kn, num_cus)
-    return nn_inst(t2, nt, 4, m, r, N, ms2, kn, num_cus)
+        tt, ms = tt4, ms0
+    elif kn["nn_tt"] == 2:
+        tt, ms = t1, ms1
+    elif kn["nn_tt"] == 3:
+        tt, ms = t2, ms2
+    elif c0 <= c1 and c0 <= c2:
+        tt, ms = tt4, ms0
+    elif c1 <= c2:
+        tt, ms = t1, ms1
+    else:
+        tt, ms = t2, ms2
+    return nn_inst(tt, nt, 4, m, r, N, ms, kn, num_cus, hook_panels=hook_panels)
+
+
+def nn_plan(m, r, N, kn, num_cus, upper_hint=False):
+    """record of one nn_panel call (r <= 256) without a row-panel hook"""
+    (rec, _, _), = nn_launches(m, r, N, kn, num_cus, upper_hint)
+    return rec
 
 
 def nn_stream_reachable():
@@ -383,7 +429,7 @@ def ss_select(rt, ct, same, blocked_knob):
     return ("ss", tpw, (ctot + 31) // 32)
 
 
-def ss_plan(m, k, N, kn, num_cus, same=False, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req=0):
+def ss_plan(m, k, N, kn, num_cus, same=False, scale=1.0, beta=0.0, rs=None, cs=1, nsplit_req=0, ptrs_aligned=True):
     rs = k if rs is None else rs
     assert ss_applicable(m, k, same)
     rt, ct = (m + 15) // 16, (k + 15) // 16
@@ -409,11 +455,11 @@ def ss_plan(m, k, N, kn, num_cus, same=False, scale=1.0, beta=0.0, rs=None, cs=1
         _, a, b, swap = sel
         pipe = kn["ss_blocked"] != 2 and a * b <= 56
         launch = record(SSB, a, b, (a + b + 1) // 2, pipe, swap, 0, nsplit)
-        red = reduce_plan(nsplit, mpad * kpad, mpad if swap else kpad, bool(swap), m, k, rs, cs)
+        red = reduce_plan(nsplit, mpad * kpad, mpad if swap else kpad, bool(swap), m, k, rs, cs, ptrs_aligned)
         return [launch, red]
     if (tpw, nq) not in SS_CASES:
         raise LookupError("tsgemm_ss: no instance for tiles/wave=%d chunks/thread=%d" % (tpw, nq))
-    return [record(SS, tpw, nq, ss_pf(tpw, nq), 0, same, nsplit), reduce_plan(nsplit, mpad * kpad, kpad, False, m, k, rs, cs)]
+    return [record(SS, tpw, nq, ss_pf(tpw, nq), 0, same, nsplit), reduce_plan(nsplit, mpad * kpad, kpad, False, m, k, rs, cs, ptrs_aligned)]
 
 
 def ss_tile_shapes():

@@ -2,12 +2,15 @@
 (all a one-GPU box can offer: RCCL refuses two ranks on one device) and the p2p transport with 2 and 4 ranks sharing
 the GPU, both through the same C entry points the multi-GPU run uses."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import contraction_plan_twin as twin  # noqa: E402
 WORKER = os.path.join(ROOT, "tests", "helpers", "gpu_comm_worker.py")
 WORKER2 = os.path.join(ROOT, "tests", "helpers", "gpu_comm_worker2.py")
 
@@ -113,21 +116,49 @@ def test_row_panel_reduction_is_bit_identical_and_overlapped():
     hf.parRandom.normal(1.0, Omega)
     A = hf.CollectiveOperator(wl.operator, coll, mpi_op="avg")
     ctx = hf.Context.default()
+    cus = ctx.device_info()["compute_units"]
+
+    def streamed_launches():
+        """the plan records (include/hfmi.h) of the streaming nn kernel since the last clear, Y = X G of the operator among them"""
+        words = (C.c_int * (256 * twin.PLAN_WORDS))()
+        n = C.c_int(0)
+        L.call("hfmi_plan_read", ctx.handle, 256, words, C.byref(n), None)
+        flat = list(words)
+        recs = [twin.decode(flat[i * twin.PLAN_WORDS:(i + 1) * twin.PLAN_WORDS]) for i in range(n.value)]
+        return [rec for rec in recs if rec["kind"] == "nn"]
+
+    def applications(got, want):
+        """how often the launch list `want` occurs in `got` (the solve has other streamed products, of other shapes)"""
+        return sum(1 for i in range(len(got)) if got[i:i + len(want)] == want)
+
+    def predicted(panels, halve):
+        kn = twin.knobs(nn_halve_last=halve)
+        return [rec for rec, _, _ in twin.nn_launches(ns * q, k, N, kn, cus, hook_panels=panels if panels > 1 else 0)]
+
     out = {}
     for panels in (0, 4):
         L.call("hfmi_tuning_set", b"comm_panels", panels)
+        L.call("hfmi_plan_clear", ctx.handle)
         ctx.profile_begin()
         d, U = hf.doublePass(A, Omega, r, s=1)
         ctx.profile_end()
         out[panels] = (d, U.to_dense(), ctx.profile_phases())
+        # the launches are the twin's row panels: whole rounds of tiles per launch, the split tail tiles with the last one
+        want = predicted(panels, 0)
+        assert len(want) == (1 if panels == 0 or N < 2 * cus * 512 else 2) and applications(streamed_launches(), want) >= 1, (panels, streamed_launches(), want)
     # the opt-in half-height last round (one more, smaller, panel; profiles/archive/r04i_halve_last_ab.txt): still the same bits
     L.call("hfmi_tuning_set", b"comm_panels", 4)
     L.call("hfmi_tuning_set", b"nn_halve_last", 1)
+    L.call("hfmi_plan_clear", ctx.handle)
     ctx.profile_begin()
     d_h, U_h = hf.doublePass(A, Omega, r, s=1)
     ctx.profile_end()
     halved_phases = ctx.profile_phases()
     L.call("hfmi_tuning_set", b"nn_halve_last", 0)
+    want = predicted(4, 1)
+    assert applications(streamed_launches(), want) >= 1, (streamed_launches(), want)
+    if N >= 2 * cus * 512:        # first round, the two halves of the last round at half the tile height, the split tail
+        assert [rec["TT"] for rec in want] == [8, 4, 4, 8] and want[-1]["full_tiles"] == 0 and want[-1]["msplit"] > 1
     np.testing.assert_array_equal(d_h, out[4][0])
     np.testing.assert_array_equal(U_h.to_dense(), out[4][1])
     assert 0.0 < halved_phases["allreduce"] < out[4][2]["allreduce"]          # a smaller last panel is left exposed
