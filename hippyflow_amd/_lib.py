@@ -132,6 +132,8 @@ SIGNATURES = {
     "hfmi_plan_read": [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hfmi_plan_predict": [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                           C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)],
+    "hfmi_eig_plan_predict": [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                              C.POINTER(C.c_int64)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],
     "hfmi_bench_loaded_peak": [_P, _D, _D],
     "hfmi_bench_random_peaks": [_P, _D, _D, _D],

@@ -6,6 +6,7 @@
 
 #include <new>
 
+#include "hfmi_eig_plan.h"
 #include "hfmi_internal.h"
 
 // ------------------------------------------------------------------ errors
@@ -301,6 +302,44 @@ extern "C" int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale
   }
   *nrecords = n;
   if (n > max_records) HFMI_FAIL(HFMI_ERR_INVALID, "plan_predict: %d records, room for %d", n, max_records);
+  return HFMI_OK;
+}
+
+// the plan of the whole-GPU eigensolver for n, from the planner and the walk the driver runs (hfmi_eig_plan.h); no device involved
+static_assert(EIG_NREGIONS == HFMI_EIG_PLAN_REGIONS && EIG_NINST == HFMI_EIG_PLAN_INSTANCES && EB_MAX_LEVELS == HFMI_EIG_PLAN_LEVELS,
+              "include/hfmi.h sizes the outputs of hfmi_eig_plan_predict");
+extern "C" int hfmi_eig_plan_predict(int n, int nvec, int64_t lds_per_block, int64_t defl1_static_lds, int64_t* scalars, int64_t* regions,
+                                     int64_t* levels, int64_t* walk) {
+  if (!scalars || !regions || !levels || !walk) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (n < 1 || n > EB_MAXN || lds_per_block < 0 || defl1_static_lds < 0) HFMI_FAIL(HFMI_ERR_INVALID, "eig_plan_predict: bad argument");
+  if (nvec < 0 || nvec > n) nvec = n;
+  const eig_knobs& kn = eig_knobs_ref();
+  const eig_plan p = eig_plan_make(n, nvec, kn, (size_t)lds_per_block, (size_t)defl1_static_lds);
+  memset(scalars, 0, sizeof(int64_t) * HFMI_EIG_PLAN_SCALARS);
+  memset(regions, 0, sizeof(int64_t) * 4 * HFMI_EIG_PLAN_REGIONS);
+  memset(levels, 0, sizeof(int64_t) * 4 * HFMI_EIG_PLAN_LEVELS);
+  memset(walk, 0, sizeof(int64_t) * 4 * HFMI_EIG_PLAN_INSTANCES);
+  scalars[0] = p.blocked;
+  if (!p.blocked) return HFMI_OK;
+  eig_walk_summary w;
+  (void)eig_tri_walk(p, w);
+  const int64_t sc[HFMI_EIG_PLAN_SCALARS] = {1, p.nr, p.ld, p.npad, p.WY, p.nblk, p.npanels, p.Lf, (int64_t)p.vlen, (int64_t)p.bytes,
+                                             p.tri_b_lds_attr, w.j_unb, w.panel_cols, w.panel_ends, w.mirrors, w.lower_updates, w.tails,
+                                             w.max_ntiles, w.max_npvy_all, w.max_nb, w.max_ga, kn.sym_min, kn.unb_max, kn.leaf_max};
+  memcpy(scalars, sc, sizeof(sc));
+  for (int i = 0; i < EIG_NREGIONS; ++i) {
+    const eig_region& r = p.region[i];
+    const int64_t v[4] = {r.elem, (int64_t)r.count, (int64_t)r.offset, (int64_t)r.bytes()};
+    memcpy(regions + 4 * i, v, sizeof(v));
+  }
+  for (int L = 0; L < p.Lf; ++L) {
+    const int64_t v[4] = {p.level[L].cap, p.level[L].mode, p.level[L].lds, p.level[L].raise};
+    memcpy(levels + 4 * L, v, sizeof(v));
+  }
+  for (int i = 0; i < EIG_NINST; ++i) {
+    const int64_t v[4] = {w.launches[i], w.max_npn[i], w.max_npvy[i], w.max_lds[i]};
+    memcpy(walk + 4 * i, v, sizeof(v));
+  }
   return HFMI_OK;
 }
 

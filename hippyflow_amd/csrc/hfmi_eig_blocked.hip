@@ -21,6 +21,11 @@
 //      triangular factors, Y = V T, then per panel Z <- Z - Y (V^T Z): two MFMA products.
 //   4. eigenvalues sorted on the host (n numbers), eigenvectors permuted + transposed to the row-major output on the device.
 //
+// This unit holds the kernels and, at its end, the driver: sym_eig_large checks its arguments, asks hfmi_eig_plan.h for the plan
+// (route, geometry, workspace regions, kernel instances, deflation modes; the launch sequence of the tridiagonalisation is
+// eig_tri_walk there), allocates by the plan's region table and runs one function per phase.  The plan is host-only code:
+// hfmi_eig_plan_predict (include/hfmi.h) evaluates it without a device and tests/test_eig_plan_cpu.py sweeps every n.
+//
 // Every reduction has a fixed order: results are bit-reproducible from run to run.  tests/helpers/eig_blocked_twin.py is the numpy
 // twin (same recurrences, same tearing); tests/test_eig_blocked_twin.py pins it against numpy.linalg.eigh on the CPU.
 #include <math.h>
@@ -34,14 +39,14 @@
 
 #include "hfmi_dc_common.h"
 #include "hfmi_dgemm.h"
+#include "hfmi_eig_plan.h"
 
 int launch_dc_leaves(hfmi_ctx* ctx, int n, int Lf, const double* dvec, const double* evec, double* Dout, double* Qbig, int64_t ldq,
                      int* fail);
 int sym_eig_large_jacobi(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, double* host_d, double* host_V);
 
 namespace {
-constexpr int EB_NB = 64;          // panel width of the tridiagonalisation and of the block reflectors
-constexpr int EB_MAXN = HFMI_EIG_MAXN;      // 16384: v of k_tri_b lives in LDS (128 KB of 160)
+static_assert(EB_MAXN == HFMI_EIG_MAXN, "hfmi_eig_plan.h states the largest eigenproblem a second time");
 
 // ------------------------------------------------------------------------------------------------ load: symmetrise, scale
 // raw: the caller's n x n row-major matrix.  A (column-major, ld) = (raw + raw^T) / 2; per-tile max |entry| -> pmax
@@ -373,7 +378,7 @@ __global__ __launch_bounds__(512) void k_tri_b(tri_args p) {
 // one per slot, which the next k_tri_a<true> adds in a fixed order -- bit-reproducible.  The last 2 jj workgroups are the panel's columns of V and
 // W (V^T v, W^T v): one column per workgroup, an eighth of the rows per wave.  v is not staged: tiles need 2 x 128 entries, taken
 // from column j of the reduced matrix with the reflector's scaling (same arithmetic in every workgroup).
-constexpr int TS = 128;
+constexpr int TS = EB_TS;
 template <int CB>
 __global__ __launch_bounds__(512) void k_tri_bs(tri_args p, int ntiles) {
   __shared__ double s_vi[TS], s_vj[TS];
@@ -506,7 +511,7 @@ __global__ __launch_bounds__(512) void k_tri_bs(tri_args p, int ntiles) {
 // -- v, w and v_new live in LDS (24 bytes per row), the first column of a wave is requested before anything else.  The matrix is
 // read AND written once per column (the panel algorithm reads half of it and writes it once per 64 columns), which is why this
 // path stops at EB_UNB_CAP rows: below it the trailing block sits in the caches and the column time is latency, not bytes.
-constexpr int EB_UNB_CAP = 2304;      // rows of LDS vectors: (cap + 63 + 127 rounded to 128) * 24 bytes <= 64 KB
+// (EB_UNB_CAP = 2304 rows of LDS vectors, hfmi_eig_plan.h: (cap + 63 + 127 rounded to 128) * 24 bytes <= 64 KB)
 template <int UNR>       // 16-byte loads per lane that cover one column: (ld - rs) / 2 <= 64 UNR pairs
 __global__ __launch_bounds__(512) void k_tri_u(tri_args p, const double* __restrict__ yprev, double* __restrict__ ynew, int has_prev) {
   constexpr int CB = UNR / 4;         // rows per thread of the whole-vector part: (ld - rs) <= 512 CB
@@ -1076,18 +1081,20 @@ __global__ __launch_bounds__(256) void k_mirror_lower(double* __restrict__ A, in
   }
 }
 
+
+// ------------------------------------------------------------------------------------------------ the driver
+// hfmi_eig_plan.h decides (route, geometry, workspace table, kernel instances, deflation modes, the launch sequence of the
+// tridiagonalisation); everything below allocates and launches what the plan says, one function per phase.
 struct phase_clock {
   hfmi_ctx* ctx;
   bool on;
   std::chrono::steady_clock::time_point t0;
   double ms[8];
-  int cur;
-  explicit phase_clock(hfmi_ctx* c) : ctx(c), on(env_flag("HFMI_EIG_LARGE_TIMING")), cur(0) {
-    memset(ms, 0, sizeof(ms));
-    if (on) {
-      (void)hipStreamSynchronize(ctx->stream);
-      t0 = std::chrono::steady_clock::now();
-    }
+  explicit phase_clock(hfmi_ctx* c) : ctx(c), on(eig_knobs_ref().timing) { memset(ms, 0, sizeof(ms)); }
+  void start() {
+    if (!on) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    t0 = std::chrono::steady_clock::now();
   }
   void mark(int slot) {
     if (!on) return;
@@ -1096,7 +1103,317 @@ struct phase_clock {
     ms[slot] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     t0 = t1;
   }
+  void print(int n) const {
+    if (on)
+      fprintf(stderr, "[hfmi eig n=%d] ms: workspace + fills %.3f | upload %.3f | load %.3f | tridiagonalisation %.3f | leaves %.3f | merges %.3f | back-transformation %.3f | output %.3f\n",
+              n, ms[6], ms[7], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+  }
 };
+
+static_assert(sizeof(dcl_node) == EB_NODE_BYTES, "hfmi_eig_plan.h sizes the node records");
+using eig_elem_D = double;
+using eig_elem_I = int;
+using eig_elem_B = unsigned char;
+using eig_elem_N = dcl_node;
+struct eig_ws {      // the regions of the plan's table, as pointers
+#define X(name, T, count) eig_elem_##T* name;
+  HFMI_EIG_REGIONS(X)
+#undef X
+};
+struct eig_run {
+  hfmi_ctx* ctx;
+  hipStream_t st;
+  eig_plan p;
+  eig_ws w;
+  phase_clock clk;
+  double *Dcur, *Dnext, *Qcur, *Qnext;      // eigenvalues / eigenvectors of the tridiagonal matrix: current and scratch
+  eig_run(hfmi_ctx* c, const eig_plan& plan) : ctx(c), st(c->stream), p(plan), clk(c) {}
+};
+
+// op(A) op(B) with the plain BLAS argument list; batches, the second operand pair and the cuts are set by the caller
+gemm_desc gemm(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
+               double* C, int64_t ldc) {
+  gemm_desc g;
+  g.ta = ta, g.tb = tb, g.M = M, g.N = N, g.K = K, g.alpha = alpha, g.beta = beta;
+  g.A = A, g.lda = lda, g.B = B, g.ldb = ldb, g.C = C, g.ldc = ldc;
+  return g;
+}
+gemm_desc batched(gemm_desc g, int batch, int64_t sA, int64_t sB, int64_t sC) {
+  g.batch = batch, g.sA = sA, g.sB = sB, g.sC = sC;
+  return g;
+}
+
+int eig_allocate(eig_run& r) {
+  void* base = nullptr;
+  HFMI_TRY(ctx_ws(r.ctx, WS_STAGE, r.p.bytes, &base));
+  int i = 0;
+#define X(name, T, count) r.w.name = (eig_elem_##T*)((char*)base + r.p.region[i++].offset);
+  HFMI_EIG_REGIONS(X)
+#undef X
+  r.clk.start();
+  return HFMI_OK;
+}
+
+// ---- fills, upload, load: A (column-major, ld) = the symmetric part of the input, scaled to max |entry| in [1, 2)
+int eig_load(eig_run& r, const double* host_T, const double* dev_T) {
+  const eig_plan& p = r.p;
+  const eig_ws& w = r.w;
+  const int n = p.n;
+  hipStream_t st = r.st;
+  int* sexp_dev = w.fail + 1;
+  const double* raw = dev_T ? dev_T : w.Qg;
+  HIP_TRY(hipMemsetAsync(w.A, 0, p.mat * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(w.Vh, 0, p.mat * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(w.Q1, 0, 2 * p.mat * sizeof(double), st));          // Q1 and Q2 are adjacent
+  HIP_TRY(hipMemsetAsync(w.Wp, 0, (size_t)p.ld * EB_NB * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(w.colbuf, 0, 16 * p.vlen * sizeof(double), st));    // the vectors (tau beyond n - 3 must read 0)
+  HIP_TRY(hipMemsetAsync(w.fail, 0, 16 * sizeof(int), st));
+  r.clk.mark(6);
+  if (!dev_T) HFMI_TRY(xfer_h2d(r.ctx, w.Qg, host_T, (size_t)n * n * sizeof(double)));      // (the fills above run while the host side is read)
+  r.clk.mark(7);
+  const int nt = (n + 31) / 32;
+  hipLaunchKernelGGL(k_sym_load, dim3(nt, nt), dim3(256), 0, st, raw, n, w.A, p.ld, w.pmax);
+  hipLaunchKernelGGL(k_scale_exp, dim3(1), dim3(1024), 0, st, w.pmax, nt * nt, sexp_dev);
+  hipLaunchKernelGGL(k_scale_apply, dim3(n), dim3(256), 0, st, w.A, p.ld, n, sexp_dev);
+  HIP_TRY(hipGetLastError());
+  r.clk.mark(0);
+  return HFMI_OK;
+}
+
+// ---- tridiagonalisation: the visitor of eig_tri_walk that launches
+using tri_kernel = void (*)(tri_args);
+tri_kernel tri_b_kernel(int inst) {
+  switch (inst) {
+    case EIG_K_TRI_B_4_8: return k_tri_b<4, 8>;
+    case EIG_K_TRI_B_8_8: return k_tri_b<8, 8>;
+    case EIG_K_TRI_B_8_16: return k_tri_b<8, 16>;
+    default: return k_tri_b<8, 32>;
+  }
+}
+struct tri_launcher {
+  eig_run& r;
+  tri_args ta;
+  explicit tri_launcher(eig_run& run) : r(run) {
+    const eig_ws& w = r.w;
+    ta.n = r.p.n, ta.j = 0, ta.jj = 0, ta.p0 = 0, ta.mode = 0;
+    ta.nr = r.p.nr;
+    ta.ld = r.p.ld;
+    ta.A = w.A, ta.Vh = w.Vh, ta.W = w.Wp;
+    ta.colbuf = w.colbuf, ta.ybuf = w.ybuf;
+    ta.x1 = w.x1, ta.x2 = w.x2;
+    ta.pvy = w.pvy, ta.npvy = 0;
+    ta.pn = w.pn, ta.npn = 0;
+    ta.dvec = w.dvec, ta.evec = w.evec, ta.tauv = w.tauv;
+    ta.part = w.Qg;                      // free between the load and the merges: nb <= 64 partial vectors of ld doubles
+    ta.nb = 0;
+  }
+  void tri_a(bool slots, int grid) {
+    if (slots) hipLaunchKernelGGL(k_tri_a<true>, dim3(grid), dim3(64 * TA_WAVES), 0, r.st, ta);
+    else hipLaunchKernelGGL(k_tri_a<false>, dim3(grid), dim3(64 * TA_WAVES), 0, r.st, ta);
+  }
+  int column(const eig_tri_col& c) {
+    ta.p0 = c.p0, ta.j = c.j, ta.jj = c.jj, ta.mode = 3;
+    ta.npn = c.ga;
+    tri_a(c.prev_slots, c.ga);
+    if (eig_inst_is_bs(c.inst)) ta.nb = c.nb;
+    switch (c.inst) {
+      case EIG_K_TRI_BS_8: hipLaunchKernelGGL(k_tri_bs<8>, dim3(c.grid), dim3(512), 0, r.st, ta, c.ntiles); break;
+      case EIG_K_TRI_BS_16: hipLaunchKernelGGL(k_tri_bs<16>, dim3(c.grid), dim3(512), 0, r.st, ta, c.ntiles); break;
+      case EIG_K_TRI_BS_32: hipLaunchKernelGGL(k_tri_bs<32>, dim3(c.grid), dim3(512), 0, r.st, ta, c.ntiles); break;
+      default: hipLaunchKernelGGL(tri_b_kernel(c.inst), dim3(c.grid), dim3(512), c.lds, r.st, ta);
+    }
+    ta.npvy = c.npvy;
+    return HFMI_OK;
+  }
+  int panel_end(const eig_tri_end& e) {
+    const eig_ws& w = r.w;
+    const int n = r.p.n, t0 = e.t0;
+    const int64_t ld = r.p.ld;
+    ta.j = t0, ta.jj = e.ncols, ta.mode = 1;
+    tri_a(e.prev_slots, (n - t0 + 63) / 64);
+    HIP_TRY(hipGetLastError());
+    // A[t0:, t0:] -= V W^T + W V^T
+    const double *V = w.Vh + (size_t)e.p0 * ld + t0, *W = w.Wp + t0;
+    gemm_desc g = gemm(false, true, n - t0, n - t0, e.ncols, -1.0, V, ld, W, ld, 1.0, w.A + (size_t)t0 * ld + t0, ld);
+    g.K2 = e.ncols, g.A2 = W, g.B2 = V;
+    g.lower = e.lower;
+    return launch_dgemm(r.ctx, g);
+  }
+  int mirror(int t0) {
+    const int nt = (r.p.n - t0 + 31) / 32;
+    hipLaunchKernelGGL(k_mirror_lower, dim3(nt, nt), dim3(256), 0, r.st, r.w.A, r.p.ld, r.p.n, t0);
+    return HFMI_OK;
+  }
+  int tail_column(const eig_tri_ucol& u) {
+    double* yb[2] = {r.w.ybuf, r.w.colbuf};      // y of the last step / of this step (the panel kernels' colbuf is free here)
+    const double* yp = yb[u.ybuf];
+    double* yn = yb[u.ybuf ^ 1];
+    ta.j = u.j;
+    switch (u.inst) {
+      case EIG_K_TRI_U_4: hipLaunchKernelGGL(k_tri_u<4>, dim3(u.grid), dim3(512), u.lds, r.st, ta, yp, yn, u.has_prev); break;
+      case EIG_K_TRI_U_8: hipLaunchKernelGGL(k_tri_u<8>, dim3(u.grid), dim3(512), u.lds, r.st, ta, yp, yn, u.has_prev); break;
+      case EIG_K_TRI_U_16: hipLaunchKernelGGL(k_tri_u<16>, dim3(u.grid), dim3(512), u.lds, r.st, ta, yp, yn, u.has_prev); break;
+      default: hipLaunchKernelGGL(k_tri_u<20>, dim3(u.grid), dim3(512), u.lds, r.st, ta, yp, yn, u.has_prev);
+    }
+    return HFMI_OK;
+  }
+  int tail() {
+    hipLaunchKernelGGL(k_tri_tail, dim3(1), dim3(64), 0, r.st, r.w.A, r.p.ld, r.p.n, r.w.dvec, r.w.evec);
+    return HFMI_OK;
+  }
+};
+int eig_tridiagonalise(eig_run& r) {
+  if (r.p.tri_b_lds_attr)
+    HIP_TRY(hipFuncSetAttribute((const void*)tri_b_kernel(r.p.tri_b), hipFuncAttributeMaxDynamicSharedMemorySize, r.p.tri_b_lds_attr));
+  HFMI_TRY(eig_tri_walk(r.p, tri_launcher(r)));
+  HIP_TRY(hipGetLastError());
+  r.clk.mark(1);
+  return HFMI_OK;
+}
+
+// ---- divide and conquer: the leaves, then the merges level by level
+int eig_deflate(eig_run& r, const dcl_args& da, int nn, const eig_level& lv) {
+  using defl_kernel = void (*)(dcl_args, int);
+  const defl_kernel k = lv.mode == 2 ? k_dcl_deflate<2> : lv.mode == 1 ? k_dcl_deflate<1> : k_dcl_deflate<0>;
+  if (lv.raise) HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lv.lds));
+  hipLaunchKernelGGL(k, dim3(nn), dim3(1024), lv.lds, r.st, da, lv.cap);
+  return HFMI_OK;
+}
+int eig_divide_and_conquer(eig_run& r) {
+  const eig_ws& w = r.w;
+  const int n = r.p.n;
+  const int64_t ld = r.p.ld;
+  hipStream_t st = r.st;
+  HFMI_TRY(launch_dc_leaves(r.ctx, n, r.p.Lf, w.dvec, w.evec, w.D0, w.Q1, ld, w.fail));
+  r.clk.mark(2);
+  r.Dcur = w.D0, r.Dnext = w.D1, r.Qcur = w.Q1, r.Qnext = w.Q2;
+  void* pin = nullptr;
+  HFMI_TRY(ctx_pinned(r.ctx, EB_NODES * sizeof(dcl_node), &pin));
+  dcl_node* hnodes = (dcl_node*)pin;
+  dcl_args da;
+  da.n = n, da.ld = ld;
+  da.evec = w.evec, da.Qg = w.Qg, da.S = w.A;
+  da.Zv = w.Zv, da.Ds = w.Ds, da.Zs = w.Zs, da.dl = w.dl, da.wv = w.wvv, da.tauS = w.tauS, da.zhat = w.zhat, da.rc = w.rc, da.rs = w.rs;
+  da.Col = w.Col, da.Live = w.Live, da.Ks = w.Ks, da.Src = w.Src, da.orgv = w.orgv, da.ra = w.ra, da.rb = w.rb;
+  da.xkp = w.xkp, da.xli = w.xli, da.xkept = w.xkept, da.xlv = w.xlv, da.xd = w.xd, da.xz = w.xz;
+  da.nodes = w.nodes, da.fail = w.fail;
+  for (int L = r.p.Lf - 1; L >= 0; --L) {
+    const int nn = 1 << L;
+    da.L = L;
+    da.D = r.Dcur, da.Dnew = r.Dnext, da.Q = r.Qcur, da.Qout = r.Qnext;
+    hipLaunchKernelGGL(k_dcl_z, dim3(nn), dim3(1024), 0, st, da);
+    hipLaunchKernelGGL(k_dcl_rank, dim3((n + 63) / 64), dim3(256), 0, st, da);
+    HFMI_TRY(eig_deflate(r, da, nn, r.p.level[L]));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hnodes, w.nodes, (size_t)nn * sizeof(dcl_node), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(r.ctx->ev_side, st));
+    hipLaunchKernelGGL(k_dcl_rot, dim3((n + 255) / 256), dim3(256), 0, st, da);
+    hipLaunchKernelGGL(k_dcl_secular, dim3((n + 3) / 4), dim3(256), 0, st, da);
+    hipLaunchKernelGGL(k_dcl_zhat, dim3((n + 3) / 4), dim3(256), 0, st, da);
+    hipLaunchKernelGGL(k_dcl_svec, dim3((n + 3) / 4), dim3(256), 0, st, da);
+    hipLaunchKernelGGL(k_dcl_gather, dim3(n), dim3(256), 0, st, da);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventSynchronize(r.ctx->ev_side));
+    for (int i = 0; i < nn; ++i) {      // Q <- Q S of every node, on its kept columns
+      const dcl_node& nd = hnodes[i];
+      if (nd.K <= 0) continue;
+      const size_t o = (size_t)nd.lo * ld + nd.lo;
+      HFMI_TRY(launch_dgemm(r.ctx, gemm(false, false, nd.hi - nd.lo, nd.K, nd.K, 1.0, w.Qg + o, ld, w.A + o, ld, 0.0, r.Qnext + o, ld)));
+    }
+    std::swap(r.Dcur, r.Dnext);
+    std::swap(r.Qcur, r.Qnext);
+  }
+  r.clk.mark(3);
+  return HFMI_OK;
+}
+
+// ---- eigenvalues to the host, output order; the wanted eigenvectors of the tridiagonal matrix, in that order, into the other Q
+// buffer: everything after this works on nvec columns
+int eig_values_and_order(eig_run& r, int sort_by_abs, double* host_d) {
+  const int n = r.p.n, nv = r.p.nvec;
+  hipStream_t st = r.st;
+  std::vector<double> lam(n);
+  int hfail[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(lam.data(), r.Dcur, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hfail, r.w.fail, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (hfail[2]) HFMI_FAIL(HFMI_ERR_NUMERIC, "sym_eig (n=%d): the matrix has non-finite entries", n);
+  if (hfail[0]) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "sym_eig (n=%d): a secular equation did not converge", n);
+  std::vector<int> perm(n);
+  std::iota(perm.begin(), perm.end(), 0);
+  std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return sort_by_abs ? fabs(lam[x]) > fabs(lam[y]) : lam[x] > lam[y]; });
+  for (int jx = 0; jx < n; ++jx) host_d[jx] = ldexp(lam[perm[jx]], hfail[1]);
+  if (nv == 0) return HFMI_OK;
+  HIP_TRY(hipMemcpyAsync(r.w.order, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_pick_columns, dim3(nv), dim3(256), 0, st, r.Qcur, r.Qnext, r.p.ld, n, r.w.order);
+  HIP_TRY(hipGetLastError());
+  std::swap(r.Qcur, r.Qnext);
+  return HFMI_OK;
+}
+
+// ---- back-transformation: Z <- (I - V_0 T_0 V_0^T) ... (I - V_last T_last V_last^T) Z with block reflectors of WY = 256 | 512
+// columns (four panels): 64-column products V^T Z would be 64 tiles on 256 compute units.  The triangular factor of a block is
+// assembled from those of its panels: [V_a V_b] has T = [[T_a, -T_a (V_a^T V_b) T_b], [0, T_b]] (twice: 64 -> 128 -> 256).
+int eig_back_transform(eig_run& r) {
+  const eig_ws& w = r.w;
+  const int n = r.p.n, nv = r.p.nvec, WY = r.p.WY, nblk = r.p.nblk;
+  const int64_t ld = r.p.ld, sWY = (int64_t)WY * WY, sV = (int64_t)WY * ld;
+  double *Z = r.Qcur, *Y = w.A;
+  // Gram matrices of all blocks
+  HFMI_TRY(launch_dgemm(r.ctx, batched(gemm(true, false, WY, WY, n, 1.0, w.Vh, ld, w.Vh, ld, 0.0, w.Gm, WY), nblk, sV, sV, sWY)));
+  HIP_TRY(hipMemsetAsync(w.Tf, 0, (size_t)nblk * sWY * sizeof(double), r.st));
+  hipLaunchKernelGGL(k_larft, dim3(r.p.npanels), dim3(64), 0, r.st, w.Gm, w.tauv, w.Tf, WY);
+  HIP_TRY(hipGetLastError());
+  for (int wd = EB_NB; wd < WY; wd *= 2) {              // merge neighbours of width wd into width 2 wd
+    for (int a0 = 0; a0 + 2 * wd <= WY; a0 += 2 * wd) {
+      const size_t offTa = (size_t)a0 * (WY + 1), offTb = (size_t)(a0 + wd) * (WY + 1);
+      const size_t offX = (size_t)a0 + (size_t)(a0 + wd) * WY;          // rows of a, columns of b
+      // tmp = (V_a^T V_b) T_b, then T_ab = -T_a tmp
+      HFMI_TRY(launch_dgemm(r.ctx, batched(gemm(false, false, wd, wd, wd, 1.0, w.Gm + offX, WY, w.Tf + offTb, WY, 0.0, w.Tt + offX, WY), nblk, sWY, sWY, sWY)));
+      HFMI_TRY(launch_dgemm(r.ctx, batched(gemm(false, false, wd, wd, wd, -1.0, w.Tf + offTa, WY, w.Tt + offX, WY, 0.0, w.Tf + offX, WY), nblk, sWY, sWY, sWY)));
+    }
+  }
+  // Y = V T, every block
+  HFMI_TRY(launch_dgemm(r.ctx, batched(gemm(false, false, n, WY, WY, 1.0, w.Vh, ld, w.Tf, WY, 0.0, Y, ld), nblk, sV, sWY, sV)));
+  for (int bi = nblk - 1; bi >= 0; --bi) {
+    // rows from p0 on: row p0 of the block's reflectors (and of Y = V T) is zero -- column p0 + c starts at row p0 + c + 1 --
+    // so the products are the same as from p0 + 1, and every operand keeps its 16-byte alignment
+    const int p0 = bi * WY, r0 = p0;
+    if (p0 >= n - 2) continue;
+    // W1 = V^T Z (rows r0 ..), then Z -= Y W1
+    HFMI_TRY(launch_dgemm(r.ctx, gemm(true, false, WY, nv, n - r0, 1.0, w.Vh + (size_t)p0 * ld + r0, ld, Z + r0, ld, 0.0, w.W1, WY)));
+    HFMI_TRY(launch_dgemm(r.ctx, gemm(false, false, n - r0, nv, WY, -1.0, Y + (size_t)p0 * ld + r0, ld, w.W1, WY, 1.0, Z + r0, ld)));
+  }
+  r.clk.mark(4);
+  return HFMI_OK;
+}
+
+// ---- output: the eigenvectors transposed to row-major n x nvec, then to the host
+int eig_output(eig_run& r, double* host_V) {
+  const int n = r.p.n, nv = r.p.nvec;
+  double* out = r.Qnext;
+  hipLaunchKernelGGL(k_out, dim3((n + 31) / 32, (nv + 31) / 32), dim3(256), 0, r.st, r.Qcur, r.p.ld, n, nv, out);
+  HIP_TRY(hipGetLastError());
+  HFMI_TRY(xfer_d2h(r.ctx, host_V, out, (size_t)n * nv * sizeof(double)));
+  r.clk.mark(5);
+  return HFMI_OK;
+}
+
+// n < 3 or HFMI_EIG_LARGE=jacobi: the Jacobi of hfmi_eig_large.hip, which takes a host matrix and returns every eigenvector
+int eig_jacobi_route(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, double* host_d, double* host_V, int nvec, const double* dev_T) {
+  std::vector<double> staged;
+  if (dev_T) {
+    staged.resize((size_t)n * n);
+    HIP_TRY(hipMemcpyAsync(staged.data(), dev_T, staged.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    host_T = staged.data();
+  }
+  if (nvec == n || !host_V) return sym_eig_large_jacobi(ctx, host_T, n, sort_by_abs, host_d, host_V);
+  std::vector<double> full((size_t)n * n);
+  HFMI_TRY(sym_eig_large_jacobi(ctx, host_T, n, sort_by_abs, host_d, full.data()));
+  for (int i = 0; i < n; ++i) memcpy(host_V + (size_t)i * nvec, full.data() + (size_t)i * n, (size_t)nvec * sizeof(double));
+  return HFMI_OK;
+}
 }  // namespace
 
 // host_T: n x n row-major symmetric (the symmetric part is used); host_d: n eigenvalues descending (by |d| if
@@ -1110,524 +1427,23 @@ int sym_eig_large(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, d
   sort_by_abs &= 1;      // the callers hand over their whole flags word (bit 1 = HFMI_EIG_JACOBI selects a method, not an order)
   if (nvec < 0 || nvec > n) nvec = n;
   if (!host_V) nvec = 0;
-  static const bool jacobi_env = [] {
-    const char* e = getenv("HFMI_EIG_LARGE");
-    return e && !strcmp(e, "jacobi");
-  }();
-  const bool jacobi = jacobi_env && n <= 4096;      // (the A/B route of round 4 stops there)
-  std::vector<double> staged;
-  if ((jacobi || n < 3) && dev_T) {      // the Jacobi route takes a host matrix
-    staged.resize((size_t)n * n);
-    HIP_TRY(hipMemcpyAsync(staged.data(), dev_T, staged.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    host_T = staged.data();
+  if (!ctx->defl1_static_known) {      // static LDS of k_dcl_deflate<1>: the plan's MODE threshold counts it
+    hipFuncAttributes fa;
+    HIP_TRY(hipFuncGetAttributes(&fa, (const void*)k_dcl_deflate<1>));
+    ctx->defl1_static_lds = fa.sharedSizeBytes;
+    ctx->defl1_static_known = true;
   }
-  if (jacobi || n < 3) {
-    if (nvec == n || !host_V) return sym_eig_large_jacobi(ctx, host_T, n, sort_by_abs, host_d, host_V);
-    std::vector<double> full((size_t)n * n);
-    HFMI_TRY(sym_eig_large_jacobi(ctx, host_T, n, sort_by_abs, host_d, full.data()));
-    for (int i = 0; i < n; ++i) memcpy(host_V + (size_t)i * nvec, full.data() + (size_t)i * n, (size_t)nvec * sizeof(double));
-    return HFMI_OK;
+  eig_run r(ctx, eig_plan_make(n, nvec, eig_knobs_ref(), ctx->lds_per_block, ctx->defl1_static_lds));
+  if (!r.p.blocked) return eig_jacobi_route(ctx, host_T, n, sort_by_abs, host_d, host_V, nvec, dev_T);
+  HFMI_TRY(eig_allocate(r));
+  HFMI_TRY(eig_load(r, host_T, dev_T));
+  HFMI_TRY(eig_tridiagonalise(r));
+  HFMI_TRY(eig_divide_and_conquer(r));
+  HFMI_TRY(eig_values_and_order(r, sort_by_abs, host_d));
+  if (nvec > 0) {
+    HFMI_TRY(eig_back_transform(r));
+    HFMI_TRY(eig_output(r, host_V));
+    r.clk.print(n);
   }
-  const int NB = EB_NB;
-  // width of a block reflector of the back-transformation: V^T Z is a WY x nv product over WY / 64 row tiles -- 512 columns from
-  // n = 2048 on keep 8 row tiles x nv / 128 column tiles of the pipelined kernel on the chip where 256 would leave half of it idle
-  // (back-transformation at n = 2048 / 4096: 1.9 -> 1.6 / 6.5 -> 4.7 ms; profiles/r06_eig_large.txt)
-  static const int wy_env = [] {
-    const char* e = getenv("HFMI_EIG_WY");
-    const int v = e ? atoi(e) : 0;
-    return (v == 256 || v == 512) ? v : 0;
-  }();
-  const int WY = wy_env ? wy_env : (n >= 2048 ? 512 : 256);
-  // rows of a column: n rounded up to 128.  Leading dimension: the same, except where that is a power of two (n = 4096, 8192,
-  // 16384): consecutive columns of a 128 x 128 tile or of a wave's column set then sit a power of two apart and crowd the same
-  // HBM channels -- the tile pattern of the lower-triangle products read 6.25 TB/s at ld = 8192 and 6.9-7.0 at 8336 / 8720, 5.5
-  // against 6.0-6.2 at n = 4096 (scripts/tile_stride_probe.hip, profiles/r06_tile_stride_probe.txt); 144 = 9 cache lines
-  static const bool ld_pad = !env_flag("HFMI_EIG_NO_LD_PAD");
-  const int nr = (int)round_up(n, 128);
-  const int64_t ld = nr + ((ld_pad && nr >= 4096 && (nr & (nr - 1)) == 0) ? 144 : 0);
-  const int npad = (int)round_up(n, WY), npanels = npad / NB, nblk = npad / WY;
-  const size_t mat = (size_t)ld * npad;
-  const size_t vlen = (size_t)npad + 128;
-  // ---- workspace
-  const size_t n_mats = 5;
-  const size_t d_count = n_mats * mat + (size_t)ld * NB + (size_t)WY * npad + 3 * (size_t)nblk * WY * WY + 18 * vlen + 2 * 64 + EB_MAXN / 64 + 2112 +
-                         (size_t)(npad / 32 + 1) * (npad / 32 + 1);
-  const size_t i_count = 11 * vlen + 64;
-  const size_t bytes = d_count * sizeof(double) + i_count * sizeof(int) + 64 * sizeof(dcl_node) + 256;
-  void* wv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_STAGE, bytes, &wv));
-  double* dp = (double*)wv;
-  auto take = [&](size_t count) {
-    double* r = dp;
-    dp += count;
-    return r;
-  };
-  double* A = take(mat);        // the matrix; later S of the merges, then Y = V T of the back-transformation
-  double* Vh = take(mat);
-  double* Q1 = take(mat);
-  double* Q2 = take(mat);
-  double* Qg = take(mat);       // raw upload first, gathered columns of the merges, nothing afterwards
-  double* Wp = take((size_t)ld * NB);
-  double* W1 = take((size_t)WY * npad);
-  double* Gm = take((size_t)nblk * WY * WY);
-  double* Tf = take((size_t)nblk * WY * WY);
-  double* Tt = take((size_t)nblk * WY * WY);      // products in flight while the triangular factors are merged
-  double* colbuf = take(vlen);
-  double* ybuf = take(vlen);
-  double* dvec = take(vlen);
-  double* evec = take(vlen);
-  double* tauv = take(vlen);
-  double* D0 = take(vlen);
-  double* D1 = take(vlen);
-  double* Zv = take(vlen);
-  double* Ds = take(vlen);
-  double* Zs = take(vlen);
-  double* dl = take(vlen);
-  double* wvv = take(vlen);
-  double* tauS = take(vlen);
-  double* zhat = take(vlen);
-  double* rc = take(vlen);
-  double* rs = take(vlen);
-  double* xd = take(vlen);
-  double* xz = take(vlen);
-  double* x1 = take(64);
-  double* x2 = take(64);
-  double* pn = take(EB_MAXN / 64);  // one partial norm per 64 rows
-  double* pvy = take(2112);         // partial sums of v . y: <= 512 workgroups of k_tri_b, <= 2080 tiles of k_tri_bs
-  double* pmax = take((size_t)(npad / 32 + 1) * (npad / 32 + 1));
-  int* ip = (int*)dp;
-  auto take_i = [&](size_t count) {
-    int* r = ip;
-    ip += count;
-    return r;
-  };
-  int* Col = take_i(vlen);
-  int* Live = take_i(vlen);
-  int* Ks = take_i(vlen);
-  int* Src = take_i(vlen);
-  int* orgv = take_i(vlen);
-  int* ra = take_i(vlen);
-  int* rb = take_i(vlen);
-  int* order = take_i(vlen);
-  int* xkp = take_i(vlen);
-  int* xli = take_i(vlen);
-  unsigned char* xkept = (unsigned char*)take_i(vlen / 2);
-  unsigned char* xlv = (unsigned char*)take_i(vlen / 2);
-  int* fail = take_i(16);
-  int* sexp_dev = fail + 1;
-  dcl_node* nodes = (dcl_node*)round_up((int64_t)(uintptr_t)(ip + 48), 16);
-  hipStream_t st = ctx->stream;
-  phase_clock clk(ctx);
-
-  // ---- load
-  const double* raw = dev_T ? dev_T : Qg;
-  HIP_TRY(hipMemsetAsync(A, 0, mat * sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(Vh, 0, mat * sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(Q1, 0, 2 * mat * sizeof(double), st));          // Q1 and Q2 are adjacent
-  HIP_TRY(hipMemsetAsync(Wp, 0, (size_t)ld * NB * sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(colbuf, 0, 16 * vlen * sizeof(double), st));    // the vectors (tau beyond n - 3 must read 0)
-  HIP_TRY(hipMemsetAsync(fail, 0, 16 * sizeof(int), st));
-  clk.mark(6);
-  if (!dev_T) HFMI_TRY(xfer_h2d(ctx, Qg, host_T, (size_t)n * n * sizeof(double)));      // (the fills above run while the host side is read)
-  clk.mark(7);
-  {
-    const int nt = (n + 31) / 32;
-    hipLaunchKernelGGL(k_sym_load, dim3(nt, nt), dim3(256), 0, st, raw, n, A, ld, pmax);
-    hipLaunchKernelGGL(k_scale_exp, dim3(1), dim3(1024), 0, st, pmax, nt * nt, sexp_dev);
-    hipLaunchKernelGGL(k_scale_apply, dim3(n), dim3(256), 0, st, A, ld, n, sexp_dev);
-    HIP_TRY(hipGetLastError());
-  }
-  clk.mark(0);
-
-  // ---- tridiagonalisation
-  {
-    static const int tri_unr = [] {      // HFMI_EIG_TRI_UNR = 4 | 8: 16-byte loads in flight per lane of k_tri_b (A/B)
-      const char* e = getenv("HFMI_EIG_TRI_UNR");
-      return (e && atoi(e) == 4) ? 4 : 8;
-    }();
-    static const int sym_min = [] {      // HFMI_EIG_SYM_MIN: trailing blocks from this size on take the lower-triangle products (0: never)
-      const char* e = getenv("HFMI_EIG_SYM_MIN");
-      const int v = e ? atoi(e) : 3072;
-      return v <= 0 ? (1 << 30) : std::max(v, 256);
-    }();
-    tri_args ta;
-    ta.part = Qg;                        // free between the load and the merges: nb <= 64 partial vectors of ld doubles
-    ta.nb = 0;
-    ta.n = n;
-    ta.nr = nr;
-    ta.ld = ld;
-    ta.A = A;
-    ta.Vh = Vh;
-    ta.W = Wp;
-    ta.colbuf = colbuf;
-    ta.ybuf = ybuf;
-    ta.x1 = x1;
-    ta.x2 = x2;
-    ta.pvy = pvy;
-    ta.pn = pn;
-    ta.dvec = dvec;
-    ta.evec = evec;
-    ta.tauv = tauv;
-    ta.npvy = 0;
-    ta.npn = 0;
-    bool prev_slots = false;             // the last column's products were left in slots by k_tri_bs
-    if (n > 8192)      // v of the first columns is 128 KB (of 160)
-      HIP_TRY(hipFuncSetAttribute((const void*)k_tri_b<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(nr * sizeof(double))));
-    else if (n > 4096)      // v of the first columns is 64 KB: beyond what a kernel gets without asking
-      HIP_TRY(hipFuncSetAttribute((const void*)k_tri_b<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(nr * sizeof(double))));
-    // the lower-triangle products serve trailing blocks of sym_min ... 8192 rows (64 slots of 128 rows, 2080 tiles); the first columns of a
-    // larger matrix take the full-column products
-    auto uses_bs = [&](int j) { return n - j - 1 >= sym_min && (nr - ((j + 1) & ~(TS - 1))) / TS <= 64; };
-    static const int unb_max = [] {      // HFMI_EIG_UNB_MAX: trailing blocks of at most this many rows take one launch per column (0: never)
-      const char* e = getenv("HFMI_EIG_UNB_MAX");
-      const int v = e ? atoi(e) : 2048;
-      return std::max(0, std::min(v, EB_UNB_CAP));
-    }();
-    int j_unb = -1;                      // first column of the unblocked tail
-    bool upper_valid = true;             // the upper triangle of the trailing block is up to date
-    static const bool lower_updates = !env_flag("HFMI_EIG_FULL_UPDATE");     // A/B: every rank-2k update over the full block
-    auto make_upper_valid = [&](int t0) {
-      if (upper_valid) return;
-      const int nt = (n - t0 + 31) / 32;
-      hipLaunchKernelGGL(k_mirror_lower, dim3(nt, nt), dim3(256), 0, st, A, ld, n, t0);
-      upper_valid = true;
-    };
-    for (int p0 = 0; p0 < n - 2; p0 += NB) {
-      if (n - p0 <= unb_max) {
-        j_unb = p0;
-        make_upper_valid(p0);
-        break;
-      }
-      const int ncols = std::min(NB, n - 2 - p0);
-      ta.p0 = p0;
-      for (int jj = 0; jj < ncols; ++jj) {
-        const int j = p0 + jj;
-        ta.j = j;
-        ta.jj = jj;
-        ta.mode = 3;
-        const int ga = (n - j + 63) / 64;
-        ta.npn = ga;
-        if (prev_slots) hipLaunchKernelGGL(k_tri_a<true>, dim3(ga), dim3(64 * TA_WAVES), 0, st, ta);
-        else hipLaunchKernelGGL(k_tri_a<false>, dim3(ga), dim3(64 * TA_WAVES), 0, st, ta);
-        const int nc = (n - j - 1) + 2 * jj;
-        const int gb = std::max(1, std::min(512, (nc + 7) / 8));
-        const int rs0 = (j + 1) & ~63;
-        const size_t v_lds = (size_t)(nr - rs0) * sizeof(double);
-        if (uses_bs(j)) {
-          // large trailing block: the lower triangle only (k_tri_bs); the next k_tri_a adds the partial vectors
-          const int rs2 = (j + 1) & ~(TS - 1);
-          const int nb = (nr - rs2) / TS, ntiles = nb * (nb + 1) / 2;
-          ta.nb = nb;
-          // CB / 8 partial norms per lane, one per 64 rows from j: beyond n = 8192 the column below j can span 129 of them (j = n - 8193
-          // when n is a multiple of 128), which k_tri_bs<16> would drop
-          if (n > 8192) hipLaunchKernelGGL(k_tri_bs<32>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
-          else if (n > 4096) hipLaunchKernelGGL(k_tri_bs<16>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
-          else hipLaunchKernelGGL(k_tri_bs<8>, dim3(ntiles + 2 * jj), dim3(512), 0, st, ta, ntiles);
-          ta.npvy = ntiles;
-          prev_slots = true;
-        } else {
-          if (n > 8192) hipLaunchKernelGGL((k_tri_b<8, 32>), dim3(gb), dim3(512), v_lds, st, ta);
-          else if (n > 4096) hipLaunchKernelGGL((k_tri_b<8, 16>), dim3(gb), dim3(512), v_lds, st, ta);
-          else if (tri_unr == 8) hipLaunchKernelGGL((k_tri_b<8, 8>), dim3(gb), dim3(512), v_lds, st, ta);
-          else hipLaunchKernelGGL((k_tri_b<4, 8>), dim3(gb), dim3(512), v_lds, st, ta);
-          ta.npvy = gb;
-          prev_slots = false;
-        }
-      }
-      const int t0 = p0 + ncols;
-      ta.j = t0;
-      ta.jj = ncols;
-      ta.mode = 1;
-      if (prev_slots) hipLaunchKernelGGL(k_tri_a<true>, dim3((n - t0 + 63) / 64), dim3(64 * TA_WAVES), 0, st, ta);
-      else hipLaunchKernelGGL(k_tri_a<false>, dim3((n - t0 + 63) / 64), dim3(64 * TA_WAVES), 0, st, ta);
-      HIP_TRY(hipGetLastError());
-      // A[t0:, t0:] -= V W^T + W V^T
-      gemm_desc g;
-      g.ta = false;
-      g.tb = true;
-      g.M = g.N = n - t0;
-      g.K = g.K2 = ncols;
-      g.alpha = -1.0;
-      g.beta = 1.0;
-      g.A = Vh + (size_t)p0 * ld + t0;
-      g.B = Wp + t0;
-      g.A2 = Wp + t0;
-      g.B2 = Vh + (size_t)p0 * ld + t0;
-      g.lda = g.ldb = ld;
-      g.C = A + (size_t)t0 * ld + t0;
-      g.ldc = ld;
-      // every column of the NEXT panel takes the lower-triangle products (and there is a next panel): the tiles above the diagonal are
-      // not read again until the full-column / unblocked columns begin -- they are skipped and mirrored back once, there
-      const bool next_all_lower = uses_bs(t0) && uses_bs(t0 + NB - 1) && n - t0 > unb_max;
-      g.lower = (lower_updates && (next_all_lower || !upper_valid)) ? 1 + (t0 & 127) : 0;
-      HFMI_TRY(launch_dgemm(ctx, g));
-      if (g.lower) upper_valid = false;
-      if (!next_all_lower) make_upper_valid(t0);
-    }
-    make_upper_valid(0);
-    if (j_unb < 0) {
-      hipLaunchKernelGGL(k_tri_tail, dim3(1), dim3(64), 0, st, A, ld, n, dvec, evec);
-    } else {
-      // the matrix is fully updated at a panel boundary: nothing is pending at column j_unb.  Steps j_unb .. n - 1: step j applies
-      // reflector j - 1 and forms reflector j; the last two steps only collect d and e of the final 2 x 2 block.
-      double* yb[2] = {ybuf, colbuf};      // y of the last step / of this step (the panel kernels' colbuf is free here)
-      for (int j = j_unb; j < n; ++j) {
-        ta.j = j;
-        const int rs0 = j & ~63, L = nr - rs0, nA = n - j - 1;
-        const int g = std::max(1, std::min(512, (nA + 7) / 8));
-        const size_t lds = (size_t)3 * L * sizeof(double);
-        const int has_prev = j > j_unb ? 1 : 0;
-        const double* yp = yb[(j - j_unb) & 1];
-        double* yn = yb[(j - j_unb + 1) & 1];
-        if (L <= 512) hipLaunchKernelGGL(k_tri_u<4>, dim3(g), dim3(512), lds, st, ta, yp, yn, has_prev);
-        else if (L <= 1024) hipLaunchKernelGGL(k_tri_u<8>, dim3(g), dim3(512), lds, st, ta, yp, yn, has_prev);
-        else if (L <= 2048) hipLaunchKernelGGL(k_tri_u<16>, dim3(g), dim3(512), lds, st, ta, yp, yn, has_prev);
-        else hipLaunchKernelGGL(k_tri_u<20>, dim3(g), dim3(512), lds, st, ta, yp, yn, has_prev);
-      }
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  clk.mark(1);
-
-  // ---- divide and conquer
-  static const int leaf_max = [] {      // HFMI_EIG_LEAF = 64 ... 256: largest leaf handed to the one-workgroup solver (A/B)
-    const char* e = getenv("HFMI_EIG_LEAF");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 64 && v <= 256) ? v : 128;      // 128: n = 512 / 1024 5.65 / 11.5 ms against 6.06 / 11.9 with 256-row leaves, equal beyond
-  }();
-  int Lf = 0;
-  // at most 128 leaves: the merges' node records (device workspace and pinned copy) hold 64 nodes; leaves stay <= 256 rows up to EB_MAXN
-  while (((n + (1 << Lf) - 1) >> Lf) > leaf_max && Lf < 7) ++Lf;
-  HFMI_TRY(launch_dc_leaves(ctx, n, Lf, dvec, evec, D0, Q1, ld, fail));
-  clk.mark(2);
-  double *Dcur = D0, *Dnext = D1, *Qcur = Q1, *Qnext = Q2;
-  {
-    void* pin = nullptr;
-    HFMI_TRY(ctx_pinned(ctx, 64 * sizeof(dcl_node), &pin));
-    dcl_node* hnodes = (dcl_node*)pin;
-    dcl_args da;
-    da.n = n;
-    da.ld = ld;
-    da.evec = evec;
-    da.Qg = Qg;
-    da.S = A;
-    da.Zv = Zv;
-    da.Ds = Ds;
-    da.Zs = Zs;
-    da.dl = dl;
-    da.wv = wvv;
-    da.tauS = tauS;
-    da.zhat = zhat;
-    da.rc = rc;
-    da.rs = rs;
-    da.Col = Col;
-    da.Live = Live;
-    da.Ks = Ks;
-    da.Src = Src;
-    da.orgv = orgv;
-    da.ra = ra;
-    da.rb = rb;
-    da.xkp = xkp;
-    da.xli = xli;
-    da.xkept = xkept;
-    da.xlv = xlv;
-    da.xd = xd;
-    da.xz = xz;
-    da.nodes = nodes;
-    da.fail = fail;
-    for (int L = Lf - 1; L >= 0; --L) {
-      const int nn = 1 << L;
-      da.L = L;
-      da.D = Dcur;
-      da.Dnew = Dnext;
-      da.Q = Qcur;
-      da.Qout = Qnext;
-      hipLaunchKernelGGL(k_dcl_z, dim3(nn), dim3(1024), 0, st, da);
-      hipLaunchKernelGGL(k_dcl_rank, dim3((n + 63) / 64), dim3(256), 0, st, da);
-      const int cap = (int)round_up((n + nn - 1) / nn + 1, 64);
-      // MODE 1 keeps 16 bytes per pole in dynamic LDS next to the kernel's static arrays (s_scan and three ints); together they must
-      // fit what a workgroup may have on this device.  With 160 KB that ends at cap = 9920 (9984 poles: 159 744 + 4 108 bytes).
-      if (!ctx->defl1_static_known) {
-        hipFuncAttributes fa;
-        HIP_TRY(hipFuncGetAttributes(&fa, (const void*)k_dcl_deflate<1>));
-        ctx->defl1_static_lds = fa.sharedSizeBytes;
-        ctx->defl1_static_known = true;
-      }
-      if ((size_t)cap * 16 + ctx->defl1_static_lds > ctx->lds_per_block) {      // nothing of the node in LDS
-        hipLaunchKernelGGL(k_dcl_deflate<2>, dim3(nn), dim3(1024), 0, st, da, cap);
-      } else if (cap > 4160) {      // the top merge beyond n = 4096
-        const size_t defl_lds = (size_t)cap * 16;
-        HIP_TRY(hipFuncSetAttribute((const void*)k_dcl_deflate<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)defl_lds));
-        hipLaunchKernelGGL(k_dcl_deflate<1>, dim3(nn), dim3(1024), defl_lds, st, da, cap);
-      } else {
-        const size_t defl_lds = (size_t)cap * 30;
-        HIP_TRY(hipFuncSetAttribute((const void*)k_dcl_deflate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)defl_lds));
-        hipLaunchKernelGGL(k_dcl_deflate<0>, dim3(nn), dim3(1024), defl_lds, st, da, cap);
-      }
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(hnodes, nodes, (size_t)nn * sizeof(dcl_node), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipEventRecord(ctx->ev_side, st));
-      hipLaunchKernelGGL(k_dcl_rot, dim3((n + 255) / 256), dim3(256), 0, st, da);
-      hipLaunchKernelGGL(k_dcl_secular, dim3((n + 3) / 4), dim3(256), 0, st, da);
-      hipLaunchKernelGGL(k_dcl_zhat, dim3((n + 3) / 4), dim3(256), 0, st, da);
-      hipLaunchKernelGGL(k_dcl_svec, dim3((n + 3) / 4), dim3(256), 0, st, da);
-      hipLaunchKernelGGL(k_dcl_gather, dim3(n), dim3(256), 0, st, da);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventSynchronize(ctx->ev_side));
-      for (int i = 0; i < nn; ++i) {
-        const dcl_node& nd = hnodes[i];
-        if (nd.K <= 0) continue;
-        gemm_desc g;
-        g.ta = g.tb = false;
-        g.M = nd.hi - nd.lo;
-        g.N = g.K = nd.K;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.A = Qg + (size_t)nd.lo * ld + nd.lo;
-        g.B = A + (size_t)nd.lo * ld + nd.lo;
-        g.lda = g.ldb = ld;
-        g.C = Qnext + (size_t)nd.lo * ld + nd.lo;
-        g.ldc = ld;
-        HFMI_TRY(launch_dgemm(ctx, g));
-      }
-      std::swap(Dcur, Dnext);
-      std::swap(Qcur, Qnext);
-    }
-  }
-  clk.mark(3);
-
-  // ---- eigenvalues to the host, output order
-  std::vector<double> lam(n);
-  int hfail[3] = {0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(lam.data(), Dcur, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hfail, fail, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (hfail[2]) HFMI_FAIL(HFMI_ERR_NUMERIC, "sym_eig (n=%d): the matrix has non-finite entries", n);
-  if (hfail[0]) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "sym_eig (n=%d): a secular equation did not converge", n);
-  std::vector<int> perm(n);
-  std::iota(perm.begin(), perm.end(), 0);
-  std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return sort_by_abs ? fabs(lam[x]) > fabs(lam[y]) : lam[x] > lam[y]; });
-  for (int jx = 0; jx < n; ++jx) host_d[jx] = ldexp(lam[perm[jx]], hfail[1]);
-  if (!host_V || nvec == 0) return HFMI_OK;
-  const int nv = nvec;
-  // the wanted eigenvectors of the tridiagonal matrix, in output order, into the other Q buffer: everything below works on nv columns
-  HIP_TRY(hipMemcpyAsync(order, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_pick_columns, dim3(nv), dim3(256), 0, st, Qcur, Qnext, ld, n, order);
-  HIP_TRY(hipGetLastError());
-  std::swap(Qcur, Qnext);
-
-  // ---- back-transformation: Z <- (I - V_0 T_0 V_0^T) ... (I - V_last T_last V_last^T) Z with block reflectors of WY = 256 | 512
-  // columns (four panels): 64-column products V^T Z would be 64 tiles on 256 compute units.  The triangular factor of a block is
-  // assembled from those of its panels: [V_a V_b] has T = [[T_a, -T_a (V_a^T V_b) T_b], [0, T_b]] (twice: 64 -> 128 -> 256).
-  {
-    double* Z = Qcur;
-    double* Y = A;
-    const int64_t sWY = (int64_t)WY * WY;
-    gemm_desc g;
-    g.ta = true;                 // Gram matrices of all blocks
-    g.tb = false;
-    g.M = g.N = WY;
-    g.K = n;
-    g.alpha = 1.0;
-    g.beta = 0.0;
-    g.A = g.B = Vh;
-    g.lda = g.ldb = ld;
-    g.C = Gm;
-    g.ldc = WY;
-    g.batch = nblk;
-    g.sA = g.sB = (int64_t)WY * ld;
-    g.sC = sWY;
-    HFMI_TRY(launch_dgemm(ctx, g));
-    HIP_TRY(hipMemsetAsync(Tf, 0, (size_t)nblk * sWY * sizeof(double), st));
-    hipLaunchKernelGGL(k_larft, dim3(npanels), dim3(64), 0, st, Gm, tauv, Tf, WY);
-    HIP_TRY(hipGetLastError());
-    for (int w = NB; w < WY; w *= 2) {              // merge neighbours of width w into width 2 w
-      for (int a0 = 0; a0 + 2 * w <= WY; a0 += 2 * w) {
-        const size_t offTa = (size_t)a0 * (WY + 1), offTb = (size_t)(a0 + w) * (WY + 1);
-        const size_t offX = (size_t)a0 + (size_t)(a0 + w) * WY;          // rows of a, columns of b
-        gemm_desc m1;            // tmp = (V_a^T V_b) T_b
-        m1.ta = m1.tb = false;
-        m1.M = m1.N = m1.K = w;
-        m1.alpha = 1.0;
-        m1.beta = 0.0;
-        m1.A = Gm + offX;
-        m1.lda = WY;
-        m1.B = Tf + offTb;
-        m1.ldb = WY;
-        m1.C = Tt + offX;
-        m1.ldc = WY;
-        m1.batch = nblk;
-        m1.sA = m1.sB = m1.sC = sWY;
-        HFMI_TRY(launch_dgemm(ctx, m1));
-        gemm_desc m2 = m1;       // T_ab = -T_a tmp
-        m2.alpha = -1.0;
-        m2.A = Tf + offTa;
-        m2.B = Tt + offX;
-        m2.C = Tf + offX;
-        HFMI_TRY(launch_dgemm(ctx, m2));
-      }
-    }
-    gemm_desc gy;                // Y = V T, every block
-    gy.ta = gy.tb = false;
-    gy.M = n;
-    gy.N = gy.K = WY;
-    gy.alpha = 1.0;
-    gy.beta = 0.0;
-    gy.A = Vh;
-    gy.lda = ld;
-    gy.B = Tf;
-    gy.ldb = WY;
-    gy.C = Y;
-    gy.ldc = ld;
-    gy.batch = nblk;
-    gy.sA = gy.sC = (int64_t)WY * ld;
-    gy.sB = sWY;
-    HFMI_TRY(launch_dgemm(ctx, gy));
-    for (int bi = nblk - 1; bi >= 0; --bi) {
-      // rows from p0 on: row p0 of the block's reflectors (and of Y = V T) is zero -- column p0 + c starts at row p0 + c + 1 --
-      // so the products are the same as from p0 + 1, and every operand keeps its 16-byte alignment
-      const int p0 = bi * WY, r0 = p0;
-      if (p0 >= n - 2) continue;
-      gemm_desc g1;              // W1 = V^T Z   (rows r0 ..)
-      g1.ta = true;
-      g1.tb = false;
-      g1.M = WY;
-      g1.N = nv;
-      g1.K = n - r0;
-      g1.alpha = 1.0;
-      g1.beta = 0.0;
-      g1.A = Vh + (size_t)p0 * ld + r0;
-      g1.lda = ld;
-      g1.B = Z + r0;
-      g1.ldb = ld;
-      g1.C = W1;
-      g1.ldc = WY;
-      HFMI_TRY(launch_dgemm(ctx, g1));
-      gemm_desc g2;              // Z -= Y W1
-      g2.ta = g2.tb = false;
-      g2.M = n - r0;
-      g2.N = nv;
-      g2.K = WY;
-      g2.alpha = -1.0;
-      g2.beta = 1.0;
-      g2.A = Y + (size_t)p0 * ld + r0;
-      g2.lda = ld;
-      g2.B = W1;
-      g2.ldb = WY;
-      g2.C = Z + r0;
-      g2.ldc = ld;
-      HFMI_TRY(launch_dgemm(ctx, g2));
-    }
-    clk.mark(4);
-    double* out = Qnext;
-    hipLaunchKernelGGL(k_out, dim3((n + 31) / 32, (nv + 31) / 32), dim3(256), 0, st, Z, ld, n, nv, out);
-    HIP_TRY(hipGetLastError());
-    HFMI_TRY(xfer_d2h(ctx, host_V, out, (size_t)n * nv * sizeof(double)));
-    clk.mark(5);
-  }
-  if (clk.on)
-    fprintf(stderr, "[hfmi eig n=%d] ms: workspace + fills %.3f | upload %.3f | load %.3f | tridiagonalisation %.3f | leaves %.3f | merges %.3f | back-transformation %.3f | output %.3f\n",
-            n, clk.ms[6], clk.ms[7], clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5]);
   return HFMI_OK;
 }

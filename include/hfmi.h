@@ -460,6 +460,35 @@ HFMI_API int hfmi_plan_read(hfmi_ctx* ctx, int max_records, int* words /* max_re
 #define HFMI_PREDICT_UPPER 8       /* NN: the caller marks the small matrix upper triangular (Q R^-1 of the QR) */
 HFMI_API int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale, double beta, int64_t rs, int64_t cs, int nsplit_req,
                                int flags, int num_cus, int hook_panels, int max_records, int* words, int64_t* hook_rows, int* nrecords);
+/* The launch plan of the whole-GPU symmetric eigensolver (hfmi_sym_eig_small / _leading, hfmi_block_gram_eig for 256 < n <= 16384) for
+ * an n x n matrix of which nvec eigenvectors are wanted, computed on the host by the planner and the launch walk the solver itself
+ * runs: no context and no device.  lds_per_block: LDS a workgroup may have on the device (static + dynamic; 163840 on an MI355X);
+ * defl1_static_lds: static LDS of the solver's deflation kernel (4108).  The knobs are the process's (the HFMI_EIG_* environment
+ * switches, read once).  Every output is zero-filled first.
+ * scalars[HFMI_EIG_PLAN_SCALARS]:
+ *    0 route: 1 = the blocked solver, 0 = n < 3 or the Jacobi route (nothing else is filled then)
+ *    1 nr (rows of a column: n rounded up to 128)    2 ld (leading dimension)    3 npad (n rounded up to WY)
+ *    4 WY (columns of a block reflector)    5 nblk (block reflectors)    6 npanels (64-column panels)    7 Lf (merge levels; 2^Lf leaves)
+ *    8 vlen (elements of a workspace vector)    9 bytes of the workspace
+ *   10 bytes the dynamic-LDS attribute of k_tri_b is raised to (0: not raised)
+ *   11 j_unb: first column of the unblocked tail (-1: none)    12 panel columns    13 panel ends (rank-2k updates)
+ *   14 mirror launches (k_mirror_lower)    15 rank-2k updates cut to the lower triangle    16 k_tri_tail launches
+ *   17 largest ntiles of a k_tri_bs launch    18 largest npvy (partial sums of v . y a column leaves)
+ *   19 largest nb (128-row slots of k_tri_bs)    20 largest npn (partial norms a column leaves)
+ *   21, 22, 23 the knobs sym_min, unb_max, leaf_max as clamped
+ * regions[4 x HFMI_EIG_PLAN_REGIONS], in layout order (the names: HFMI_EIG_REGIONS of csrc/hfmi_eig_plan.h):
+ *   element (0 double, 1 int, 2 byte, 3 node record), count, byte offset, bytes
+ * levels[4 x HFMI_EIG_PLAN_LEVELS], entry L < Lf = the merge level of 2^L nodes:
+ *   cap (poles the deflation kernel is sized for), MODE (0 / 1 / 2), dynamic LDS bytes, 1 = the dynamic-LDS attribute is raised to them
+ * walk[4 x HFMI_EIG_PLAN_INSTANCES], one entry per kernel instance of the tridiagonalisation, in the order k_tri_a<false>, <true>,
+ * k_tri_b<4,8>, <8,8>, <8,16>, <8,32>, k_tri_bs<8>, <16>, <32>, k_tri_u<4>, <8>, <16>, <20>:
+ *   launches, largest npn it is handed (k_tri_b, k_tri_bs), largest npvy it is handed (k_tri_a), largest dynamic LDS bytes */
+#define HFMI_EIG_PLAN_SCALARS 24
+#define HFMI_EIG_PLAN_REGIONS 47
+#define HFMI_EIG_PLAN_LEVELS 7
+#define HFMI_EIG_PLAN_INSTANCES 13
+HFMI_API int hfmi_eig_plan_predict(int n, int nvec, int64_t lds_per_block, int64_t defl1_static_lds, int64_t* scalars, int64_t* regions,
+                                   int64_t* levels, int64_t* walk);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */
