@@ -140,6 +140,8 @@ SIGNATURES = {
     "hfmi_bench_hbm_read": [_P, _D],
     "hfmi_dense_matmul": [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D],
     "hfmi_bench_dgemm": [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D, _D],
+    "hfmi_dgemm_route_predict": [C.c_int] * 7 + [C.c_int64] * 4 + [C.c_int] * 7 + [C.POINTER(C.c_int)],
+    "hfmi_test_dgemm": [_P, C.POINTER(C.c_int64), C.c_double, C.c_double, _D, _D, _D, _D, _D, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hfmi_profile_begin": [_P],
     "hfmi_profile_phases": [_P, _D],
     "hfmi_tuning_set": [C.c_char_p, C.c_int],
@@ -373,6 +375,38 @@ class Context:
         call("hfmi_bench_dgemm", self.handle, M, N, K, int(ta), int(tb), int(reps), A.ctypes.data_as(_D), B.ctypes.data_as(_D),
              Cm.ctypes.data_as(_D) if want_c else None, C.byref(ms))
         return Cm, ms.value
+
+    def test_dgemm(self, desc, A, B, C0, A2=None, B2=None):
+        """One launch of the general fp64 MFMA product with its whole descriptor (hfmi_test_dgemm).  ``desc``: ta, tb, M, N, K, alpha,
+        beta, lda, ldb, ldc and optionally K2, batch, sA, sB, sC, lower, cut, skip (0 none, 1 flag down, 2 flag up), off_A, off_B,
+        off_A2, off_B2, off_C (element offsets of the operands inside their arrays).  A, B, A2, B2, C0: flat float64 arrays, the
+        whole allocations.  Returns (the whole C allocation after the launch, route dict, status of the launch)."""
+        import numpy as np
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (A, B, A2, B2)]
+        out = np.array(C0, dtype=np.float64, order="C").ravel()      # a copy: the caller's prefill stays
+        g = lambda key: int(desc.get(key, 0))
+        dims = [g("ta"), g("tb"), g("M"), g("N"), g("K"), g("K2"), int(desc.get("batch", 1)), g("lda"), g("ldb"), g("ldc"), g("sA"), g("sB"),
+                g("sC"), g("lower"), g("cut"), g("skip")]
+        for a, key in zip(arrs, ("off_A", "off_B", "off_A2", "off_B2")):
+            dims += [0 if a is None else a.size, g(key)]
+        dims += [out.size, g("off_C")]
+        route, status = (C.c_int * 8)(), C.c_int(0)
+        call("hfmi_test_dgemm", self.handle, (C.c_int64 * 26)(*dims), float(desc["alpha"]), float(desc["beta"]),
+             *[None if a is None else a.ctypes.data_as(_D) for a in arrs], out.ctypes.data_as(_D), route, C.byref(status))
+        names = ("kernel", "vec", "gx", "gy", "gz", "error")
+        return out, {k: route[i] for i, k in enumerate(names)}, status.value
+
+    @staticmethod
+    def dgemm_route_predict(desc, pipelined=1):
+        """The route of that descriptor without a device (hfmi_dgemm_route_predict): the keys of ``test_dgemm`` plus align_A,
+        align_B, align_A2, align_B2 (bytes modulo 16; default: 8 for an odd offset) and has_skip (default: skip != 0)."""
+        g = lambda key: int(desc.get(key, 0))
+        al = lambda x: int(desc.get("align_" + x, 8 * (g("off_" + x) & 1)))
+        route = (C.c_int * 8)()
+        call("hfmi_dgemm_route_predict", g("M"), g("N"), g("K"), g("K2"), int(desc.get("batch", 1)), g("ta"), g("tb"), g("lda"), g("ldb"),
+             g("sA"), g("sB"), al("A"), al("B"), al("A2"), al("B2"), g("cut"), int(desc.get("has_skip", g("skip") != 0)), int(pipelined), route)
+        names = ("kernel", "vec", "gx", "gy", "gz", "error")
+        return {k: route[i] for i, k in enumerate(names)}
 
     def bench_hbm_read(self):
         a = C.c_double(0)

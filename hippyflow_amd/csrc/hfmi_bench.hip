@@ -1,6 +1,7 @@
 // Micro-benchmark entry points of libhfmi.so (include/hfmi.h) behind bench.py and the parity tests.  Host side only.
 #include <string.h>
 
+#include "hfmi_dgemm.h"
 #include "hfmi_internal.h"
 
 extern "C" int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, int nsplit, int reps, double* host_C, double* avg_ms) {
@@ -47,6 +48,112 @@ extern "C" int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, dou
   HFMI_TRY(launch_tsgemm_tn(ctx, A->p, A->ld, m, B->p, B->ld, k, A->N, scale, beta, (double*)dev, colmajor ? 1 : ldc, colmajor ? ldc : 1,
                             nsplit));
   return read_back(ctx, (const double*)dev, count, host_C);
+}
+static void dgemm_route_words(const gemm_route& r, int* route) {
+  const int w[HFMI_DGEMM_ROUTE_WORDS] = {r.kernel, r.vec, r.gx, r.gy, r.gz, r.error, 0, 0};
+  memcpy(route, w, sizeof(w));
+}
+// the route launch_dgemm would take, from the function it calls (hfmi_dgemm.h); no device involved.  The pointers of the descriptor
+// carry the alignments only and are never dereferenced.
+extern "C" int hfmi_dgemm_route_predict(int M, int N, int K, int K2, int batch, int ta, int tb, int64_t lda, int64_t ldb, int64_t sA, int64_t sB,
+                                        int align_A, int align_B, int align_A2, int align_B2, int cut, int has_skip, int pipelined, int* route) {
+  if (!route) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  static const int flag = 0;
+  auto at = [](int align) { return (const double*)(uintptr_t)(4096 + (align & 15)); };
+  gemm_desc g;
+  g.ta = ta != 0;
+  g.tb = tb != 0;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.alpha = 1.0;
+  g.beta = 0.0;
+  g.A = at(align_A);
+  g.B = at(align_B);
+  g.lda = lda;
+  g.ldb = ldb;
+  g.C = nullptr;
+  g.ldc = M;
+  g.K2 = K2;
+  g.A2 = at(align_A2);
+  g.B2 = at(align_B2);
+  g.batch = batch;
+  g.sA = sA;
+  g.sB = sB;
+  g.cut = cut;
+  g.skip = has_skip ? &flag : nullptr;
+  dgemm_route_words(dgemm_route_make(g, pipelined), route);
+  return HFMI_OK;
+}
+// launch_dgemm with its whole descriptor on device copies of the caller's arrays (the descriptor sweep of the tests)
+extern "C" int hfmi_test_dgemm(hfmi_ctx* ctx, const int64_t* dims, double alpha, double beta, const double* host_A, const double* host_B,
+                               const double* host_A2, const double* host_B2, double* host_C, int* route, int* launch_status) {
+  if (!ctx || !dims || !host_A || !host_B || !host_C || !route || !launch_status) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  const int64_t* d = dims;
+  const bool ta = d[0] != 0, tb = d[1] != 0;
+  const int64_t M = d[2], N = d[3], K = d[4], K2 = d[5], batch = d[6], lda = d[7], ldb = d[8], ldc = d[9], sA = d[10], sB = d[11], sC = d[12];
+  const int64_t skip_mode = d[15];
+  const int64_t n[5] = {d[16], d[18], d[20], d[22], d[24]}, off[5] = {d[17], d[19], d[21], d[23], d[25]};
+  const double* host[5] = {host_A, host_B, host_A2, host_B2, host_C};
+  for (int i = 0; i < HFMI_TEST_DGEMM_DIMS; ++i)
+    if (d[i] < 0 || d[i] > ((int64_t)1 << 40)) HFMI_FAIL(HFMI_ERR_INVALID, "test_dgemm: dims[%d] = %lld out of range", i, (long long)d[i]);
+  if (M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff || K2 > 0x7fffffff || batch < 1 || batch > 65535 || skip_mode > 2 || n[4] < 1)
+    HFMI_FAIL(HFMI_ERR_INVALID, "test_dgemm: bad shape");
+  if ((n[2] > 0 && !host_A2) || (n[3] > 0 && !host_B2)) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  // buffer sizes: the last element a kernel may touch of an operand of `rows` x `cols` (every batch member) lies inside its array
+  auto fits = [&](int64_t rows, int64_t cols, int64_t ld, int64_t stride, int which) {
+    if (rows <= 0 || cols <= 0) return off[which] <= n[which];
+    const double last = (double)off[which] + (double)(batch - 1) * (double)stride + (double)(cols - 1) * (double)ld + (double)rows;
+    return last <= (double)n[which];
+  };
+  const bool okA = fits(ta ? K : M, ta ? M : K, lda, sA, 0), okB = fits(tb ? N : K, tb ? K : N, ldb, sB, 1);
+  const bool okA2 = K2 == 0 || fits(ta ? K2 : M, ta ? M : K2, lda, sA, 2), okB2 = K2 == 0 || fits(tb ? N : K2, tb ? K2 : N, ldb, sB, 3);
+  if (!okA || !okB || !okA2 || !okB2 || !fits(M, N, ldc, sC, 4)) HFMI_FAIL(HFMI_ERR_INVALID, "test_dgemm: an operand does not fit its array");
+  HIP_TRY(hipSetDevice(ctx->device));
+  // one allocation: the five arrays on 16-byte boundaries, the flag behind them
+  int64_t base[6], total = 0;
+  for (int i = 0; i < 5; ++i) {
+    base[i] = total;
+    total += round_up(n[i], 2);
+  }
+  base[5] = total;
+  void* wv = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_STAGE, (size_t)(total + 2) * sizeof(double), &wv));
+  double* dev = (double*)wv;
+  hipStream_t st = ctx->stream;
+  for (int i = 0; i < 5; ++i)
+    if (n[i] > 0) HIP_TRY(hipMemcpyAsync(dev + base[i], host[i], (size_t)n[i] * sizeof(double), hipMemcpyHostToDevice, st));
+  int* flag = (int*)(dev + base[5]);
+  const int up = skip_mode == 2 ? 1 : 0;
+  HIP_TRY(hipMemcpyAsync(flag, &up, sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));       // (`up` is a local)
+  gemm_desc g;
+  g.ta = ta;
+  g.tb = tb;
+  g.M = (int)M;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.A = dev + base[0] + off[0];
+  g.B = dev + base[1] + off[1];
+  g.lda = lda;
+  g.ldb = ldb;
+  g.C = dev + base[4] + off[4];
+  g.ldc = ldc;
+  g.K2 = (int)K2;
+  g.A2 = n[2] > 0 ? dev + base[2] + off[2] : nullptr;
+  g.B2 = n[3] > 0 ? dev + base[3] + off[3] : nullptr;
+  g.batch = (int)batch;
+  g.sA = sA;
+  g.sB = sB;
+  g.sC = sC;
+  g.lower = (int)d[13];
+  g.cut = (int)d[14];
+  g.skip = skip_mode ? flag : nullptr;
+  dgemm_route_words(dgemm_route_make(g, dgemm_pipelined_switch()), route);
+  *launch_status = launch_dgemm(ctx, g);
+  return read_back(ctx, dev + base[4], (size_t)n[4], host_C);
 }
 extern "C" int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfmi_block* Y, int reps, double* avg_ms) {
   if (!A || !host_S || !Y) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_p(int M, int N, int K, double 
 }
 
 template <bool TA, bool TB, int BM>
-int launch_dgemm_p(hfmi_ctx* ctx, const gemm_desc& g, int vec) {
+int launch_dgemm_p(hfmi_ctx* ctx, const gemm_desc& g, const gemm_route& r) {
   typedef pstage<TA, BM> SA;
   typedef pstage<!TB, 128> SB;
   const size_t lds = (size_t)2 * (SA::DOUBLES + SB::DOUBLES) * sizeof(double);
@@ -324,45 +324,39 @@ int launch_dgemm_p(hfmi_ctx* ctx, const gemm_desc& g, int vec) {
     HIP_TRY(hipFuncSetAttribute((const void*)k_dgemm_p<TA, TB, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  const dim3 grid((g.M + BM - 1) / BM, (g.N + 127) / 128, g.batch), block(256);
+  const dim3 grid(r.gx, r.gy, r.gz), block(256);
   hipLaunchKernelGGL((k_dgemm_p<TA, TB, BM>), grid, block, lds, ctx->stream, g.M, g.N, g.K, g.alpha, g.A, g.lda, g.B, g.ldb, g.K2, g.A2, g.B2,
-                     g.beta, g.C, g.ldc, g.sA, g.sB, g.sC, vec, g.lower);
+                     g.beta, g.C, g.ldc, g.sA, g.sB, g.sC, r.vec, g.lower);
   HIP_TRY(hipGetLastError());
   return HFMI_OK;
 }
 }  // namespace
 
-// One rule: a descriptor with a cut or a skip flag always runs the 64 x 64 kernel, never the pipelined one (its clients rely on the
-// tile size of the cuts and on the bits of that kernel).
-int launch_dgemm(hfmi_ctx* ctx, const gemm_desc& g) {
-  if (g.M <= 0 || g.N <= 0) return HFMI_OK;
-  // k_dgemm does not move A2 / B2 by the batch index (k_dgemm_p does): a second product takes no batch, whichever kernel would run.
-  // (The eleven scalar instructions of that offset in k_dgemm's prologue move its main loop by 44 bytes and cost the small TN products
-  // of the eigensolver 2 %: docs/measurements.md, dgemm-rate section.  No caller combines the two.)
-  if (g.K2 > 0 && g.batch > 1) HFMI_FAIL(HFMI_ERR_INVALID, "dgemm: a second product (K2=%d) takes no batch (%d)", g.K2, g.batch);
-  const bool cut = g.cut != 0 || g.skip != nullptr;
-  if (cut && (g.K2 > 0 || g.ta)) HFMI_FAIL(HFMI_ERR_INVALID, "dgemm: a cut product takes one untransposed A (ta=%d, K2=%d)", (int)g.ta, g.K2);
+int dgemm_pipelined_switch() {
   static const int pipelined = [] {      // HFMI_EIG_GEMM = 0: the 64 x 64 kernel of round 5 everywhere (A/B)
     const char* e = getenv("HFMI_EIG_GEMM");
     return e ? atoi(e) : 1;
   }();
-  // the pipelined kernel where its tiles fill the chip: 128 x 128 from 192 tiles on, 64 x 128 from 192 of those; the 64 x 64 kernel below
-  // for the small products (panel factors, merges of small nodes)
-  const int64_t t128 = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
-  const int64_t t64 = (int64_t)((g.M + 63) / 64) * ((g.N + 127) / 128) * g.batch;
-  if (!cut && pipelined && (t128 >= 192 || t64 >= 192) && g.K + g.K2 >= 32) {
-    auto even = [](int64_t v) { return (v & 1) == 0; };
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    const int vec = even(g.lda) && even(g.ldb) && even(g.sA) && even(g.sB) && al16(g.A) && al16(g.B) && (g.K2 == 0 || (al16(g.A2) && al16(g.B2)));
-    const bool big = t128 >= 192;
-#define EB_GEMM_P(TAV, TBV) (big ? launch_dgemm_p<TAV, TBV, 128>(ctx, g, vec) : launch_dgemm_p<TAV, TBV, 64>(ctx, g, vec))
+  return pipelined;
+}
+
+// The decision is dgemm_route_make's (hfmi_dgemm.h); this launches what it says.
+int launch_dgemm(hfmi_ctx* ctx, const gemm_desc& g) {
+  const gemm_route r = dgemm_route_make(g, dgemm_pipelined_switch());
+  if (r.error == HFMI_DGEMM_ERR_K2_BATCH) HFMI_FAIL(HFMI_ERR_INVALID, "dgemm: a second product (K2=%d) takes no batch (%d)", g.K2, g.batch);
+  if (r.error == HFMI_DGEMM_ERR_CUT) HFMI_FAIL(HFMI_ERR_INVALID, "dgemm: a cut product takes one untransposed A (ta=%d, K2=%d)", (int)g.ta, g.K2);
+  if (r.kernel == HFMI_DGEMM_NONE) return HFMI_OK;
+  if (r.kernel == HFMI_DGEMM_P128 || r.kernel == HFMI_DGEMM_P64) {
+    const bool big = r.kernel == HFMI_DGEMM_P128;
+#define EB_GEMM_P(TAV, TBV) (big ? launch_dgemm_p<TAV, TBV, 128>(ctx, g, r) : launch_dgemm_p<TAV, TBV, 64>(ctx, g, r))
     if (!g.ta && !g.tb) return EB_GEMM_P(false, false);
     if (g.ta && !g.tb) return EB_GEMM_P(true, false);
     if (!g.ta && g.tb) return EB_GEMM_P(false, true);
     return EB_GEMM_P(true, true);
 #undef EB_GEMM_P
   }
-  const dim3 grid((g.M + GT - 1) / GT, (g.N + GT - 1) / GT, g.batch), block(256);
+  const bool cut = r.kernel == HFMI_DGEMM_K64_CUT;
+  const dim3 grid(r.gx, r.gy, r.gz), block(256);
 #define EB_GEMM(TAV, TBV, CUTV)                                                                                                           \
   hipLaunchKernelGGL((k_dgemm<TAV, TBV, CUTV>), grid, block, 0, ctx->stream, g.M, g.N, g.K, g.alpha, g.A, g.lda, g.B, g.ldb, g.K2, g.A2, \
                      g.B2, g.beta, g.C, g.ldc, g.sA, g.sB, g.sC, g.cut, g.skip)

@@ -498,6 +498,39 @@ HFMI_API int hfmi_dense_matmul(hfmi_ctx* ctx, int M, int N, int K, int ta, int t
  * natural leading dimensions, average kernel time of `reps` launches; host_C may be null */
 HFMI_API int hfmi_bench_dgemm(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, int reps, const double* host_A, const double* host_B,
                      double* host_C, double* avg_ms);
+/* What the general fp64 MFMA product does with a descriptor (csrc/hfmi_dgemm.h: gemm_desc, dgemm_route_make), computed on the host by
+ * the function the launcher itself calls: no context and no device.  C (M x N) = alpha (op(A) op(B) + op(A2) op(B2)) + beta C with
+ * reduction lengths K, K2, `batch` products with element strides sA, sB, leading dimensions lda, ldb; align_X = byte address of X
+ * modulo 16 (0 or 8; A2 / B2 only count when K2 > 0); cut = the three triangular-cut bits; has_skip != 0: a device skip flag is
+ * passed; pipelined = the process switch HFMI_EIG_GEMM (1 when unset, 0: the 64 x 64 kernel everywhere).
+ * route[HFMI_DGEMM_ROUTE_WORDS]: kernel (HFMI_DGEMM_*), vec (pipelined kernels: 1 = 16-byte loads for interior tiles, else 0),
+ * grid x, y, z, error (HFMI_DGEMM_ERR_*: the launcher returns HFMI_ERR_INVALID and launches nothing), two spare words (0).
+ * kernel HFMI_DGEMM_NONE with error 0: M <= 0 or N <= 0, a no-op. */
+#define HFMI_DGEMM_ROUTE_WORDS 8
+#define HFMI_DGEMM_NONE (-1)
+#define HFMI_DGEMM_K64 0          /* k_dgemm<TA, TB, false>: 64 x 64 tiles */
+#define HFMI_DGEMM_K64_CUT 1      /* k_dgemm<false, TB, true>: triangular cuts and the skip flag */
+#define HFMI_DGEMM_P128 2         /* k_dgemm_p<TA, TB, 128>: pipelined, 128 x 128 tiles */
+#define HFMI_DGEMM_P64 3          /* k_dgemm_p<TA, TB, 64>: pipelined, 64 x 128 tiles */
+#define HFMI_DGEMM_ERR_NONE 0
+#define HFMI_DGEMM_ERR_K2_BATCH 1 /* a second product (K2 > 0) with batch > 1 */
+#define HFMI_DGEMM_ERR_CUT 2      /* a cut or a skip flag with a transposed A or a second product */
+HFMI_API int hfmi_dgemm_route_predict(int M, int N, int K, int K2, int batch, int ta, int tb, int64_t lda, int64_t ldb, int64_t sA, int64_t sB,
+                                      int align_A, int align_B, int align_A2, int align_B2, int cut, int has_skip, int pipelined, int* route);
+/* launch_dgemm with its whole descriptor, for the descriptor sweep of the tests.  Each host array X of n_X doubles (A, B, C; A2, B2 may
+ * be null with n = 0) is uploaded to a 16-byte aligned device base and the descriptor's pointer is base + off_X, so an odd offset
+ * makes an operand 8-byte but not 16-byte aligned.  dims[HFMI_TEST_DGEMM_DIMS], in this order:
+ *    0 ta  1 tb  2 M  3 N  4 K  5 K2  6 batch  7 lda  8 ldb  9 ldc  10 sA  11 sB  12 sC  13 lower  14 cut
+ *   15 skip: 0 = no flag, 1 = a device flag that is down, 2 = a device flag that is up
+ *   16 n_A  17 off_A  18 n_B  19 off_B  20 n_A2  21 off_A2  22 n_B2  23 off_B2  24 n_C  25 off_C
+ * The descriptor is filled verbatim and launch_dgemm is called once; nothing is validated beyond null pointers and that every operand
+ * as described lies inside its array.  *launch_status = what launch_dgemm returned (HFMI_ERR_INVALID for its two refusals: the
+ * text is in hfmi_last_error); the WHOLE host_C array comes back in either case -- pad rows of ldc, gaps between batch members, the
+ * guard doubles before off_C and behind the last column -- so the caller can compare what must stay untouched bit for bit.
+ * route[HFMI_DGEMM_ROUTE_WORDS]: the route of the launch that ran, as hfmi_dgemm_route_predict writes it. */
+#define HFMI_TEST_DGEMM_DIMS 26
+HFMI_API int hfmi_test_dgemm(hfmi_ctx* ctx, const int64_t* dims, double alpha, double beta, const double* host_A, const double* host_B,
+                             const double* host_A2, const double* host_B2, double* host_C, int* route, int* launch_status);
 /* fp64 MFMA / fp64 FMA / HBM-copy micro-benchmarks (peak denominators measured in the same job) */
 HFMI_API int hfmi_bench_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, double* fma_f64_tflops, double* hbm_copy_gbs);
 /* the same MFMA loop with a copy kernel streaming HBM beside it on a second stream: the ceiling of the power-limited regime the
