@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hfmi.h"
+#include "hfmi_qr_rules.h"
 #include "hfmi_tsgemm_plan.h"
 
 // ------------------------------------------------------------------ errors
@@ -295,20 +296,29 @@ int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const dou
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular
 int launch_nn_upper(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const double* S, int ld, int r, double* Y, int64_t ldy, int64_t N);
-struct qr_late_checks {     // second (and first) Cholesky-QR pass taken on trust: where its status words go for the caller to verify
-  bool used;
-  hfmi_status_words* st2;   // pinned
-  double* aux;              // pinned, SM_LD + k doubles
-  int k;
-  hfmi_status_words* st1;   // pinned: status words of the FIRST pass when that one was taken on trust as well
-  bool first_trusted;
+// Pinned home of what a Cholesky-QR pass taken on trust reports, for the caller to judge after the synchronisation it needs anyway
+// (ctx->late_pinned, made by ctx_late_pinned).  The single pass parks the status words of its LU solve in the first slot.
+struct qr_late_buffer {
+  alignas(128) hfmi_status_words st2;   // the second pass's status words
+  alignas(128) hfmi_status_words st1;   // the first pass's, when that one was taken on trust as well
+  double aux[SM_LD + SM_MAXK];          // SM_AUX: [0, k) original column norms; [SM_LD, SM_LD + k) diag(Rtot)
 };
-// the checked Cholesky-QR loop for 256 < k <= HFMI_WIDE_MAXK (and from the tuning key "qr_wide_min" on): wide arena, Q <- Q R^-1 out of place
-int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out);
+static_assert(sizeof(hfmi_status_words) <= 128 && sizeof(qr_late_buffer) == 256 + sizeof(double) * (SM_LD + SM_MAXK),
+              "two sets of status words share the first 256 bytes of the late-check buffer");
+int ctx_late_pinned(hfmi_ctx* ctx, qr_late_buffer** out);
 // Y = op X in column panels of at most 256 vectors (block views): no operator kind sees a width it was not written for
 int op_apply_panels(hfmi_op* op, const hfmi_block* X, hfmi_block* Y);
-extern int g_qr_wide_min;      // width from which borth_qr takes the wide route (tuning key "qr_wide_min", 17..257; default 257)
-int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_out, bool* deferred = nullptr, qr_late_checks* opt = nullptr);
+extern int g_qr_wide_min;      // width from which a checked qr_chol takes the wide route (tuning key "qr_wide_min", 17..257; default 257)
+struct qr_result {             // where qr_chol left things
+  int passes = 0;
+  bool deferred = false;       // the last pass was not applied: Q stands for Q R^-1 with R^-1 in SM_RINV
+  bool wide = false;           // the wide arena holds Rtot (WA_RTOT, ld = round_up(k, 32)), not SM_RTOT
+  bool late = false;           // the second pass was taken on trust: ctx->late_pinned holds what qr_late_stands judges ...
+  bool first_trusted = false;  // ... and the first one too
+};
+// repeated Cholesky-QR by the rules of hfmi_qr_rules.h; want_r: exact triangular factors in every pass (see borth_qr)
+int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, qr_policy policy, qr_result* res);
+bool qr_late_stands(const qr_late_buffer* late, int k, bool first_trusted);   // the late verdict (qr_late_verdict) on the buffer
 // hfmi_borth_qr with want_r (exact triangular factors in every Cholesky pass) chosen by the caller
 int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes);
 

@@ -34,28 +34,14 @@ static int read_status_finish(hfmi_ctx* ctx, hfmi_status_words* out) {
   print_status_dbg(out);
   return HFMI_OK;
 }
-// The rules both Cholesky-QR loops (qr_chol, qr_chol_wide) go by.
-// Breakdown threshold on pivot / (original diagonal): only pivots that are round-off noise (64 k eps) trigger the
-// shifted factorisation.  A pass with small but genuine pivots leaves a defect ~ eps / min pivot ratio, which the
-// next pass measures (st.gram_dev) and removes -- a more cautious threshold (100 k sqrt(N) u) cost config 3 a whole
-// extra pass (shifted first pass, cond(Q1) ~ 260) without making the result more accurate.
-struct chol_qr_rules {
-  double shift_rel;                // diagonal shift of a restarted factorisation, relative to trace(G)
-  double pivot_tol = 0.0;          // the factorisations' default: 64 k eps
-  int max_passes = 6;
-  chol_qr_rules(int64_t N, int k) : shift_rel(11.0 * ((double)N * k + (double)k * (k + 1)) * 1.1102230246251565e-16) {}
-};
-// The reference's MGS zeroes a column whose norm drops below 10 eps of its pre-sweep norm
-// (numerically dependent); Cholesky-QR would instead normalise round-off noise.  R_jj / ||z_j|| is that
-// drop: hand such blocks to the Gram-Schmidt route, which reproduces the reference's behaviour.
 // aux_dev: [0, k): original column norms; [ld, ld + k): diag(Rtot)
 static int check_dependent(hfmi_ctx* ctx, const double* aux_dev, int ld, int k) {
   std::vector<double> aux((size_t)ld + k);
   HFMI_TRY(read_back(ctx, aux_dev, (size_t)ld + k, aux.data()));
-  for (int j = 0; j < k; ++j)
-    if (!(aux[ld + j] > 100.0 * 2.220446049250313e-16 * aux[j]))
-      HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
-                aux[j] > 0 ? aux[ld + j] / aux[j] : 0.0);
+  const int j = qr_first_dependent(aux.data(), aux.data() + ld, k);
+  if (j >= 0)
+    HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: vector %d is numerically dependent on its predecessors (R_jj/||z_j|| = %.2e)", j,
+              aux[j] > 0 ? aux[ld + j] / aux[j] : 0.0);
   return HFMI_OK;
 }
 // host_R (k x k row-major) <- the k x k matrix at dev (row-major, ld)
@@ -65,108 +51,33 @@ static int read_r(hfmi_ctx* ctx, const double* dev, int ld, int k, double* host_
   for (int i = 0; i < k; ++i) memcpy(host_R + (size_t)i * k, tmp.data() + (size_t)i * ld, (size_t)k * sizeof(double));
   return HFMI_OK;
 }
-// deferred (optional): if non-null and B == null, the LAST pass (the one whose input is already orthonormal to 1e-2 and
-// needs no shift) does not apply its R^-1: *deferred = true and R^-1 stays in SM_RINV for the caller to fold into
-// the small matrices downstream (Q = Q_in R^-1 is never formed: one N x k x k contraction less).
-// opt (optional, fused solves only): do not stop the stream for the decisions of the SECOND pass.  When the first pass needed no
-// shift, the second one is assumed to be the last (deferred R^-1, as above); its status words and the R_jj / ||z_j|| table are
-// copied to pinned memory in stream order and verified by the caller after the synchronisation it needs anyway for the
-// eigenvalues.  If the assumption was wrong the caller repeats the solve on the checked path.  (Two host round trips of ~60 us
-// each per solve: 1.4 % of the 64-sample shard step.)
-static_assert(sizeof(hfmi_status_words) <= 128, "two sets of status words share the first 256 bytes of the late-check buffer");
-int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, int* passes_out, bool* deferred, qr_late_checks* opt) {
-  hfmi_ctx* ctx = Q->ctx;
-  const int64_t N = Q->N;
-  const int k = Q->nvec;
-  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
-  // beyond the small-matrix arena: the wide loop (always checked).  The fused solves' trusted / deferred passes stay narrow.
-  if (k > SM_MAXK || (k >= g_qr_wide_min && !deferred && !opt)) return qr_chol_wide(Q, B, BQ, passes_out);
-  hfmi_block* BZ = BQ;
-  hfmi_block bz_view;
-  if (B && !BQ) {
-    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
-    BZ = &bz_view;
-  }
-  const chol_qr_rules rules(N, k);
-  int passes = 0;
-  bool first_pass_clean = false;
-  if (g_qr_trust_first < 0) {
-    const char* e = getenv("HFMI_QR_TRUST_FIRST");
-    g_qr_trust_first = (e && e[0] == '0') ? 0 : 1;
-  }
-  const bool trust_first = g_qr_trust_first != 0;
-  for (;;) {
-    const hfmi_block* right = Q;
-    if (B) {
-      HFMI_TRY(hfmi_op_apply(B, Q, BZ, 0));
-      right = BZ;
-    }
-    HFMI_TRY(launch_tsgemm_tn(ctx, Q->p, Q->ld, k, right->p, right->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_GRAM), SM_LD, 1, 0));
-    const int rtot_mode = (passes == 0) ? 1 : 2;   // always track R = R_p ... R_1: its diagonal exposes dependent columns
-    if (deferred && !B && passes == 0 && opt && trust_first) {
-      // The first pass on trust too: its status words go to their own slot (nothing overwrites them), Q <- Q R^-1 follows at
-      // once and NO host round trip interrupts the solve -- the host runs ahead of the device from here to the final
-      // synchronisation, so the small kernels of the tail are queued back to back.  The words are read with the second
-      // pass's (below); a shifted / failed first pass sends the whole solve to the checked path (double_pass_impl).
-      hfmi_status_words* const keep = ctx->status_dev;
-      ctx->status_dev = keep + 1;
-      const int cs = launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, rules.shift_rel, rules.pivot_tol);
-      ctx->status_dev = keep;
-      HFMI_TRY(cs);
-      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
-      opt->first_trusted = true;
-      first_pass_clean = true;
-      ++passes;
-      continue;
-    }
-    HFMI_TRY(launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, rtot_mode, want_r ? 1 : 0, rules.shift_rel, rules.pivot_tol));
-    hfmi_status_words st;
-    if (deferred && !B && passes == 1 && opt && first_pass_clean) {
-      HFMI_TRY(side_copies_begin(ctx));
-      if (opt->first_trusted)
-        HIP_TRY(hipMemcpyAsync(opt->st1, ctx->status_dev + 1, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
-      HIP_TRY(hipMemcpyAsync(opt->st2, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
-      HIP_TRY(hipMemcpyAsync(opt->aux, sm_ptr(ctx, SM_AUX), ((size_t)SM_LD + k) * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
-      HFMI_TRY(side_copies_end(ctx));                      // the eigensolver (next writer of the status words) waits for ev_side
-      opt->used = true;
-      opt->k = k;
-      ++passes;
-      *deferred = true;
-      if (passes_out) *passes_out = passes;
-      return HFMI_OK;                                    // the checks below are the caller's, after its own synchronisation
-    }
-    if (deferred && !B && passes >= 1) {
-      // candidate last pass: look at the status words first (the read-back is not hidden here) and stop WITHOUT
-      // applying R^-1 if this pass would have been the last one anyway
-      HFMI_TRY(read_status(ctx, &st));
-      if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
-      if (!st.shifted && st.gram_dev < 1e-2) {
-        ++passes;
-        *deferred = true;
-        break;
-      }
-      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
-    } else {
-      // snapshot the status words on the auxiliary stream and enqueue Q <- Q R^-1 BEFORE waiting for them: the host
-      // round trip then overlaps the contraction.  If the factorisation failed, R^-1 was never written by this pass
-      // and Q is about to be discarded anyway (the callers restore / recompute the block on HFMI_ERR_NUMERIC).
-      HFMI_TRY(read_status_begin(ctx));
-      HFMI_TRY(launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N));
-      HFMI_TRY(read_status_finish(ctx, &st));
-      if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
-      if (passes == 0) first_pass_clean = !st.shifted;
-    }
-    ++passes;
-    // The input of this pass had orthonormality defect st.gram_dev (column-scaled).  If it was already
-    // small and no shift was needed, the output is orthonormal to round-off: done.
-    if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
-    if (passes >= rules.max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
-  }
-  HFMI_TRY(check_dependent(ctx, sm_ptr(ctx, SM_AUX), SM_LD, k));
-  (void)want_r;
-  if (B && BQ) HFMI_TRY(hfmi_op_apply(B, Q, BQ, 0));
-  if (passes_out) *passes_out = passes;
+static qr_status status_triple(const hfmi_status_words& w) { return {w.failed, w.shifted, w.gram_dev}; }
+// the two failing verdicts of pass number `pass` (0-based) as errors
+static int qr_fail(qr_next next, int pass, double gram_dev) {
+  if (next == QR_FAIL_NOT_PD) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", pass + 1);
+  HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", pass + 1, gram_dev);
+}
+
+int ctx_late_pinned(hfmi_ctx* ctx, qr_late_buffer** out) {
+  if (!ctx->late_pinned) HIP_TRY(hipHostMalloc(&ctx->late_pinned, sizeof(qr_late_buffer), hipHostMallocDefault));
+  *out = (qr_late_buffer*)ctx->late_pinned;
   return HFMI_OK;
+}
+// A second pass on trust: its status words (and those of a trusted first pass) and the R_jj / ||z_j|| table leave for pinned memory
+// in stream order; the eigensolver (next writer of the status words) waits for ev_side.  The caller verifies them (qr_late_stands)
+// after the synchronisation it needs anyway for the eigenvalues and repeats the solve on the checked path if the trust was misplaced.
+// (Two host round trips of ~60 us each per solve: 1.4 % of the 64-sample shard step.)
+static int late_copies(hfmi_ctx* ctx, qr_late_buffer* late, int k, bool first_trusted) {
+  HFMI_TRY(side_copies_begin(ctx));
+  if (first_trusted)
+    HIP_TRY(hipMemcpyAsync(&late->st1, ctx->status_dev + 1, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HIP_TRY(hipMemcpyAsync(&late->st2, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HIP_TRY(hipMemcpyAsync(late->aux, sm_ptr(ctx, SM_AUX), ((size_t)SM_LD + k) * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
+  return side_copies_end(ctx);
+}
+bool qr_late_stands(const qr_late_buffer* late, int k, bool first_trusted) {
+  const qr_status st1 = status_triple(late->st1);
+  return qr_late_verdict(status_triple(late->st2), first_trusted ? &st1 : nullptr, late->aux, late->aux + SM_LD, k);
 }
 
 int op_apply_panels(hfmi_op* op, const hfmi_block* X, hfmi_block* Y) {
@@ -183,15 +94,15 @@ int op_apply_panels(hfmi_op* op, const hfmi_block* X, hfmi_block* Y) {
   return HFMI_OK;
 }
 
-// The checked loop of qr_chol for 256 < k <= 2048 columns (and, for tests, from the tuning key "qr_wide_min" on): Gram matrix,
-// factors and status words in the wide arena (hfmi_chol_wide.hip), one host round trip per pass, and Q <- Q R^-1 OUT of place
-// (a panel of the product reads columns of Q that an earlier panel would already have overwritten): the passes alternate between Q and a cached temporary, and an
-// odd number of passes ends with a copy back.  Rtot is always the exact product of the passes' factors.
-int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
+// The checked loop for 256 < k <= 2048 columns (and, for tests, from the tuning key "qr_wide_min" on): Gram matrix, factors and
+// status words in the wide arena (hfmi_chol_wide.hip), one host round trip per pass (inside launch_chol_wide: nothing is applied
+// after a failed factorisation), and Q <- Q R^-1 OUT of place (a panel of the product reads columns of Q that an earlier panel would
+// already have overwritten): the passes alternate between Q and a cached temporary, and an odd number of passes ends with a copy
+// back.  Rtot is always the exact product of the passes' factors.
+static int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, qr_result* res) {
   hfmi_ctx* ctx = Q->ctx;
   const int64_t N = Q->N;
   const int k = Q->nvec;
-  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
   HFMI_TRY(ctx_wide(ctx, k));
   const int ld = (int)round_up(k, 32);
   hfmi_block* BZ = BQ;
@@ -202,19 +113,19 @@ int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
   }
   HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_WIDE, N, k, &pong));
   const chol_qr_rules rules(N, k);
-  int passes = 0;
   hfmi_block* cur = Q;
   hfmi_block* nxt = &pong;
-  for (;;) {
+  for (int pass = 0;; ++pass) {
     const hfmi_block* right = cur;
     if (B) {
       HFMI_TRY(op_apply_panels(B, cur, BZ));
       right = BZ;
     }
     HFMI_TRY(launch_tsgemm_tn(ctx, cur->p, cur->ld, k, right->p, right->ld, k, N, 1.0, 0.0, wa_ptr(ctx, WA_GRAM), ld, 1, 0));
-    hfmi_status_words st;
-    HFMI_TRY(launch_chol_wide(ctx, k, passes == 0 ? 1 : 2, rules.shift_rel, rules.pivot_tol, &st));
-    if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: Gram matrix not positive definite even after shifting (pass %d)", passes + 1);
+    hfmi_status_words w;
+    HFMI_TRY(launch_chol_wide(ctx, k, pass == 0 ? 1 : 2, rules.shift_rel, rules.pivot_tol, &w));
+    const qr_next next = qr_verdict(qr_issue_checked(), pass, status_triple(w), rules.max_passes);
+    if (next == QR_FAIL_NOT_PD) return qr_fail(next, pass, w.gram_dev);
     // Q R^-1 in column panels of 256 issued here, not inside launch_tsgemm_nn: columns r0 .. r0 + rp - 1 of the upper triangular R^-1
     // are zero below row r0 + rp, so the panel's reduction stops there (half the work, the same bits), and the upper-triangular
     // hint of launch_nn_upper -- which takes the small matrix's column 0 for the diagonal -- goes to the first panel only
@@ -226,14 +137,89 @@ int qr_chol_wide(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, int* passes_out) {
       else HFMI_TRY(launch_tsgemm_nn(ctx, cur->p, cur->ld, r0 + rp, S, ld, rp, 1.0, 0.0, Yp, nxt->ld, N));
     }
     std::swap(cur, nxt);
-    ++passes;
-    if (passes >= 2 && !st.shifted && st.gram_dev < 1e-2) break;
-    if (passes >= rules.max_passes) HFMI_FAIL(HFMI_ERR_NUMERIC, "borth_qr: no convergence in %d Cholesky-QR passes (defect %.2e)", passes, st.gram_dev);
+    res->passes = pass + 1;
+    if (next == QR_FAIL_MAX_PASSES) return qr_fail(next, pass, w.gram_dev);
+    if (next == QR_DONE) break;
   }
   if (cur != Q) HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, cur->p, cur->ld, N, k));
   HFMI_TRY(check_dependent(ctx, wa_aux(ctx), ld, k));
   if (B && BQ) HFMI_TRY(op_apply_panels(B, Q, BQ));
-  if (passes_out) *passes_out = passes;
+  return HFMI_OK;
+}
+
+static bool qr_trust_first_knob() {    // tuning key "qr_trust_first", else HFMI_QR_TRUST_FIRST, else on
+  if (g_qr_trust_first < 0) {
+    const char* e = getenv("HFMI_QR_TRUST_FIRST");
+    g_qr_trust_first = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_qr_trust_first != 0;
+}
+// Repeated Cholesky-QR of Q in place, in the fixed arena unless the route says wide.  Every pass: Gram matrix, factorisation (always
+// tracking Rtot = R_p ... R_1: its diagonal exposes dependent columns), then what the rules say about issuing it and about its words.
+int qr_chol(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, bool want_r, qr_policy policy, qr_result* res) {
+  hfmi_ctx* ctx = Q->ctx;
+  const int64_t N = Q->N;
+  const int k = Q->nvec;
+  *res = qr_result();
+  if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "borth_qr: at most %d vectors (got %d)", HFMI_WIDE_MAXK, k);
+  res->wide = qr_route_wide(k, g_qr_wide_min, policy);
+  if (res->wide) return qr_chol_wide(Q, B, BQ, res);
+  hfmi_block* BZ = BQ;
+  hfmi_block bz_view;
+  if (B && !BQ) {
+    HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_BZ, N, k, &bz_view));
+    BZ = &bz_view;
+  }
+  const chol_qr_rules rules(N, k);
+  const bool trust_first = qr_trust_first_knob();
+  qr_late_buffer* late = nullptr;
+  if (policy == QR_TRUSTED && !B) HFMI_TRY(ctx_late_pinned(ctx, &late));
+  const auto apply_rinv = [&] { return launch_nn_upper(ctx, Q->p, Q->ld, k, sm_ptr(ctx, SM_RINV), SM_LD, k, Q->p, Q->ld, N); };
+  bool first_clean = false;
+  for (int pass = 0;; ++pass) {
+    const hfmi_block* right = Q;
+    if (B) {
+      HFMI_TRY(hfmi_op_apply(B, Q, BZ, 0));
+      right = BZ;
+    }
+    HFMI_TRY(launch_tsgemm_tn(ctx, Q->p, Q->ld, k, right->p, right->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_GRAM), SM_LD, 1, 0));
+    const qr_issue how = qr_issue_of(policy, B != nullptr, trust_first, pass, first_clean);
+    hfmi_status_words* const keep = ctx->status_dev;
+    if (how == QR_TRUST_FIRST) ctx->status_dev = keep + 1;   // its own slot: nothing overwrites the words before they are read
+    const int cs = launch_chol_inv(ctx, k, SM_GRAM, SM_R, SM_RINV, SM_RTOT, pass == 0 ? 1 : 2, want_r ? 1 : 0, rules.shift_rel, rules.pivot_tol);
+    ctx->status_dev = keep;
+    HFMI_TRY(cs);
+    hfmi_status_words w = {};
+    switch (how) {
+      case QR_TRUST_FIRST:       // no host round trip interrupts the solve: the host runs ahead of the device from here to the final
+        HFMI_TRY(apply_rinv());  // synchronisation, so the small kernels of the tail are queued back to back
+        res->first_trusted = true;
+        break;
+      case QR_TRUST_SECOND:
+        HFMI_TRY(late_copies(ctx, late, k, res->first_trusted));
+        res->late = true;
+        break;
+      case QR_READ_THEN_APPLY:   // the read-back is not hidden here; R^-1 is applied below, if another pass follows
+        HFMI_TRY(read_status(ctx, &w));
+        break;
+      case QR_APPLY_THEN_READ:   // if the factorisation failed, R^-1 was never written by this pass and Q is about to be discarded
+        HFMI_TRY(read_status_begin(ctx));   // anyway (the callers restore / recompute the block on HFMI_ERR_NUMERIC)
+        HFMI_TRY(apply_rinv());
+        HFMI_TRY(read_status_finish(ctx, &w));
+        break;
+    }
+    const qr_status st = status_triple(w);
+    const qr_next next = qr_verdict(how, pass, st, rules.max_passes);
+    if (how == QR_READ_THEN_APPLY && (next == QR_AGAIN || next == QR_FAIL_MAX_PASSES)) HFMI_TRY(apply_rinv());
+    if (pass == 0) first_clean = qr_first_clean(how, st);
+    res->passes = pass + 1;
+    if (next == QR_FAIL_NOT_PD || next == QR_FAIL_MAX_PASSES) return qr_fail(next, pass, st.gram_dev);
+    res->deferred = next == QR_DONE_DEFERRED;
+    if (next != QR_AGAIN) break;
+  }
+  if (res->late) return HFMI_OK;                         // the checks below are the caller's, after its own synchronisation
+  HFMI_TRY(check_dependent(ctx, sm_ptr(ctx, SM_AUX), SM_LD, k));
+  if (B && BQ) HFMI_TRY(hfmi_op_apply(B, Q, BQ, 0));
   return HFMI_OK;
 }
 
@@ -331,16 +317,38 @@ int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool wan
     HFMI_TRY(ctx_tmp_view(ctx, TMP_QR_SAVE, Q->N, k, &save));
     HFMI_TRY(launch_copy(ctx, save.p, save.ld, Q->p, Q->ld, Q->N, k));
   }
-  int s = qr_chol(Q, B, BQ, want_r, passes);
+  qr_result res;
+  const int s = qr_chol(Q, B, BQ, want_r, QR_CHECKED, &res);
   if (s == HFMI_ERR_NUMERIC && method == HFMI_QR_AUTO) {
     HFMI_TRY(launch_copy(ctx, Q->p, Q->ld, save.p, save.ld, Q->N, k));
     return qr_mgs(Q, B, BQ, host_R, passes);
   }
   if (s != HFMI_OK) return s;
+  if (passes) *passes = res.passes;
   if (!host_R) return HFMI_OK;
-  if (k > SM_MAXK || k >= g_qr_wide_min) return read_r(ctx, wa_ptr(ctx, WA_RTOT), (int)round_up(k, 32), k, host_R);   // the wide route was taken
+  if (res.wide) return read_r(ctx, wa_ptr(ctx, WA_RTOT), (int)round_up(k, 32), k, host_R);
   return read_r(ctx, sm_ptr(ctx, SM_RTOT), SM_LD, k, host_R);
 }
 extern "C" int hfmi_borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, int method, int* passes) {
   return borth_qr(Q, B, BQ, host_R, host_R != nullptr, method, passes);
+}
+
+// the rules as the loops above ask them, for given values (hfmi_qr_rules.h); no context and no device
+extern "C" int hfmi_qr_rules_predict(int policy, int has_B, int trust_first, int pass, int first_clean, int failed, int shifted, double gram_dev,
+                                     int k, int qr_wide_min, int* words) {
+  if (!words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (policy < QR_CHECKED || policy > QR_TRUSTED || pass < 0 || k < 1) HFMI_FAIL(HFMI_ERR_INVALID, "qr_rules_predict: bad argument");
+  const qr_issue how = qr_issue_of((qr_policy)policy, has_B != 0, trust_first != 0, pass, first_clean != 0);
+  words[0] = how;
+  words[1] = qr_verdict(how, pass, qr_status{failed, shifted, gram_dev}, chol_qr_rules(1, k).max_passes);
+  words[2] = qr_route_wide(k, qr_wide_min, (qr_policy)policy);
+  return HFMI_OK;
+}
+extern "C" int hfmi_qr_late_verdict_predict(int k, int failed2, int shifted2, double gram_dev2, int first_trusted, int failed1, int shifted1,
+                                            const double* norm, const double* rdiag, int* stands) {
+  if (!norm || !rdiag || !stands) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (k < 1 || k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "qr_late_verdict_predict: k=%d out of range [1,%d]", k, SM_MAXK);
+  const qr_status st1 = {failed1, shifted1, 0.0};
+  *stands = qr_late_verdict(qr_status{failed2, shifted2, gram_dev2}, first_trusted ? &st1 : nullptr, norm, rdiag, k);
+  return HFMI_OK;
 }

@@ -6,12 +6,6 @@
 
 #include "hfmi_internal.h"
 
-static int ctx_late_pinned(hfmi_ctx* ctx, void** out) {
-  if (!ctx->late_pinned) HIP_TRY(hipHostMalloc(&ctx->late_pinned, 256 + (SM_LD + SM_MAXK) * sizeof(double), hipHostMallocDefault));
-  *out = ctx->late_pinned;
-  return HFMI_OK;
-}
-
 // ------------------------------------------------------------------ Rayleigh-Ritz
 extern "C" int hfmi_sym_eig_small(hfmi_ctx* ctx, const double* host_T, int k, int sort_by_abs, double* host_d, double* host_V) {
   if (!ctx || !host_T || !host_d) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
@@ -146,61 +140,129 @@ static int op_rayleigh_quotient_gram(hfmi_op* A, const hfmi_block* Q, int slot_T
   return HFMI_OK;
 }
 
-// The double pass for 256 < k <= HFMI_WIDE_MAXK probe vectors.  The same algorithm with the small matrices in the wide arena:
-//   * A and B^-1 are applied in column panels of at most 256 vectors (op_apply_panels);
-//   * the orthogonalisation is qr_chol_wide (always checked), Gram-Schmidt with flag 2 or after HFMI_ERR_NUMERIC;
-//   * the Rayleigh quotient is ALWAYS the literal T = (A Q)^T Q -- the Gram-form shortcut and the trusted / deferred
-//     orthogonalisation passes of double_pass_impl stay narrow-only;
-//   * T goes to the whole-GPU eigensolver (sym_eig_large, device input), whose k x r eigenvectors come back through the host
-//     and are uploaded for U = Q V.
-static int double_pass_wide(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags, double* host_d,
-                            hfmi_block* U) {
-  hfmi_ctx* ctx = Omega->ctx;
-  const int64_t N = Omega->N;
-  const int k = Omega->nvec;
-  HFMI_TRY(ctx_wide(ctx, k));
-  hfmi_block Q, Y;
-  HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Q, N, k, &Q));
-  HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Y, N, k, &Y));
-  const hfmi_block* cur = Omega;
-  auto power_iterations = [&]() -> int {
-    cur = Omega;
-    for (int it = 0; it < s; ++it) {
-      if (Binv) {
-        int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-        HFMI_TRY(op_apply_panels(A, cur, &Y));
-        phase_end(ctx, ph);
-        ph = phase_begin(ctx, HFMI_PHASE_BINV);
-        HFMI_TRY(op_apply_panels(Binv, &Y, &Q));
-        phase_end(ctx, ph);
-        cur = &Q;
-      } else {
-        hfmi_block* dst = (cur == &Q) ? &Y : &Q;
-        const int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-        HFMI_TRY(op_apply_panels(A, cur, dst));
-        phase_end(ctx, ph);
-        cur = dst;
-      }
+// Power iterations without orthogonalisation, X_0 = Omega (never modified), X_i = (B^-1) A X_{i-1}, for the double and the single
+// pass at any width (panels of 256 beyond that).  The iterates alternate between X0 and X1; with B^-1 the product A X_{i-1} lands
+// in Ybar, or, when the caller keeps none, in X1 -- every iterate is then X0.  prev / cur: X_{s-1} and X_s.
+struct power_iter {
+  hfmi_op *A, *Binv;
+  const hfmi_block* Omega;
+  int s;
+  hfmi_block *X0, *X1, *Ybar;
+  const hfmi_block *prev, *cur;
+};
+static int solve_power_iterations(power_iter& it) {
+  hfmi_ctx* ctx = it.Omega->ctx;
+  hfmi_block* const ax = it.Binv ? (it.Ybar ? it.Ybar : it.X1) : nullptr;
+  it.prev = it.cur = it.Omega;
+  for (int i = 0; i < it.s; ++i) {
+    hfmi_block* dst = (it.cur == it.X0 && ax != it.X1) ? it.X1 : it.X0;
+    int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
+    HFMI_TRY(op_apply_panels(it.A, it.cur, it.Binv ? ax : dst));
+    phase_end(ctx, ph);
+    if (it.Binv) {
+      ph = phase_begin(ctx, HFMI_PHASE_BINV);
+      HFMI_TRY(op_apply_panels(it.Binv, ax, dst));
+      phase_end(ctx, ph);
     }
+    it.prev = it.cur;
+    it.cur = dst;
+  }
+  return HFMI_OK;
+}
+
+// Q = orth(X_s) in place: Gram-Schmidt with flag 2, else Cholesky-QR WITHOUT the safety copy hfmi_borth_qr(AUTO) keeps (a pass over
+// N x k): if a column turns out to be numerically dependent, the block is recomputed from Omega (deterministic, every rank takes the
+// same branch) and handed to the reference's Gram-Schmidt rule
+static int solve_orthonormalise(power_iter& it, hfmi_op* B, int flags, qr_policy policy, qr_result* qr) {
+  hfmi_block* Qp = const_cast<hfmi_block*>(it.cur);
+  *qr = qr_result();
+  if (flags & 2) return hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr);
+  const int qs = qr_chol(Qp, B, nullptr, false, policy, qr);
+  if (qs != HFMI_ERR_NUMERIC) return qs;
+  *qr = qr_result();
+  HFMI_TRY(solve_power_iterations(it));
+  return hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr);
+}
+
+static int check_lu_words(const hfmi_status_words* lu_st, const char* who, bool has_B) {
+  if (lu_st->failed == 1) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the sketch products W = P^T Q / Z = Y^T Q have non-finite entries", who);
+  if (lu_st->failed == 3) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the solve W^-1 Z overflowed (non-finite pivot or solution)", who);
+  if (lu_st->failed)
+    HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: rank-deficient sketch: W = P^T %sQ is singular (min |pivot| %.2e, max |pivot| %.2e); "
+              "the probe block has dependent columns or the operator's range is smaller than the sketch", who, has_B ? "B " : "",
+              lu_st->min_pivot_ratio, lu_st->gram_dev);
+  return HFMI_OK;
+}
+
+// The tail of every fused solve of at most 256 vectors, T in SM_T: eigensolve; status words and eigenvalues to pinned memory on the
+// auxiliary stream beside the back-transformation U = Q (S V[:, :r]) instead of behind it; both streams synchronised; then the
+// checks in the order communicator, the caller's LU status words (lu_st, single pass), the orthogonalisation passes taken on trust
+// (qr->late: *repeat_checked = true and HFMI_OK when they did not hold -- the caller repeats the solve on the checked path, which
+// decides between the Gram-Schmidt fall-back and an error), the eigensolver.
+// back: the small product S V that goes in front of U = Q ...; the two products also zero pad V[:, :r] to the 16 columns tsgemm_nn
+// expects (the eigensolver leaves SM_V's pad columns as they were)
+enum tail_back { BACK_V, BACK_RINV_V /* Q stands for Q R^-1, R^-1 in SM_RINV */, BACK_IDENTITY_V };
+static int solve_tail(const hfmi_block* Q, int r, int flags, tail_back back, const qr_result* qr, const hfmi_status_words* lu_st, bool has_B,
+                      const char* who, double* host_d, hfmi_block* U, bool* repeat_checked) {
+  hfmi_ctx* ctx = Q->ctx;
+  const int k = Q->nvec;
+  const bool late = qr && qr->late;
+  void* dv = nullptr;
+  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)SM_MAXK * sizeof(double), &dv));
+  int ph = phase_begin(ctx, HFMI_PHASE_EIG);
+  if (late) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));   // the late-check copies read the status words (done ms ago)
+  HFMI_TRY(launch_sym_eig(ctx, k, SM_T, SM_V, (double*)dv, flags & 1, (flags >> 3) & 1));
+  phase_end(ctx, ph);
+  void* dpin = nullptr;
+  HFMI_TRY(ctx_pinned(ctx, (size_t)r * sizeof(double), &dpin));
+  HFMI_TRY(side_copies_begin(ctx));        // no side_copies_end: nothing overwrites the sources before the synchronisation below
+  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HIP_TRY(hipMemcpyAsync(dpin, dv, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
+  ph = phase_begin(ctx, HFMI_PHASE_BACK);
+  if (back == BACK_IDENTITY_V) HFMI_TRY(launch_small_set_identity(ctx, k, SM_GRAM));
+  if (back != BACK_V) HFMI_TRY(launch_small_matmul(ctx, k, r, back == BACK_RINV_V ? SM_RINV : SM_GRAM, SM_V, SM_TMP2));
+  HFMI_TRY(launch_tsgemm_nn(ctx, Q->p, Q->ld, k, sm_ptr(ctx, back == BACK_V ? SM_V : SM_TMP2), SM_LD, r, 1.0, 0.0, U->p, U->ld, Q->N));
+  phase_end(ctx, ph);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
+  HFMI_TRY(ctx_check_comm(ctx));
+  if (lu_st) HFMI_TRY(check_lu_words(lu_st, who, has_B));
+  memcpy(host_d, dpin, (size_t)r * sizeof(double));
+  const hfmi_status_words st = *ctx->status_host;
+  print_status_dbg(&st);
+  if (late && !qr_late_stands((const qr_late_buffer*)ctx->late_pinned, k, qr->first_trusted)) {
+    *repeat_checked = true;
     return HFMI_OK;
-  };
-  HFMI_TRY(power_iterations());
-  hfmi_block* Qp = const_cast<hfmi_block*>(cur);
-  hfmi_block* AQ = (Qp == &Q) ? &Y : &Q;
-  int ph = phase_begin(ctx, HFMI_PHASE_QR);
-  if (flags & 2) {
-    HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
+  }
+  if (st.failed) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "%s: small eigensolve did not converge (off-diagonal %.2e)", who, st.offdiag);
+  return HFMI_OK;
+}
+
+// Rayleigh-Ritz of the double pass in the fixed arena (k <= 256): T in Gram form (see above; qr.deferred folds R^-1 in) or literally
+// (A Q)^T Q as the reference forms it, the one-CU eigensolver, U = Q V or Q (R^-1 V)
+static int rayleigh_ritz_narrow(hfmi_op* A, const hfmi_block* Qp, hfmi_block* AQ, bool gram_path, const qr_result& qr, int r, int flags,
+                                double* host_d, hfmi_block* U, bool* repeat_checked) {
+  hfmi_ctx* ctx = Qp->ctx;
+  const int k = Qp->nvec;
+  const int ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
+  if (gram_path) {
+    HFMI_TRY(op_rayleigh_quotient_gram(A, Qp, SM_T, qr.deferred));
   } else {
-    const int qs = qr_chol_wide(Qp, B, nullptr, nullptr);
-    if (qs == HFMI_ERR_NUMERIC) {     // recomputed from Omega (deterministic) and handed to the reference's Gram-Schmidt rule
-      HFMI_TRY(power_iterations());
-      HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
-    } else if (qs != HFMI_OK) {
-      return qs;
-    }
+    HFMI_TRY(hfmi_op_apply(A, Qp, AQ, 0));
+    HFMI_TRY(launch_tsgemm_tn(ctx, AQ->p, AQ->ld, k, Qp->p, Qp->ld, k, Qp->N, 1.0, 0.0, sm_ptr(ctx, SM_T), SM_LD, 1, 0));
   }
   phase_end(ctx, ph);
-  ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
+  return solve_tail(Qp, r, flags, qr.deferred ? BACK_RINV_V : BACK_V, &qr, nullptr, false, "double_pass", host_d, U, repeat_checked);
+}
+
+// ... and in the wide arena (256 < k <= HFMI_WIDE_MAXK): ALWAYS the literal T = (A Q)^T Q, A applied in column panels of 256 -- the
+// Gram-form shortcut and the trusted / deferred orthogonalisation passes stay narrow-only; T goes to the whole-GPU eigensolver
+// (sym_eig_large, device input), whose k x r eigenvectors come back through the host and are uploaded for U = Q V
+static int rayleigh_ritz_wide(hfmi_op* A, const hfmi_block* Qp, hfmi_block* AQ, int r, int flags, double* host_d, hfmi_block* U) {
+  hfmi_ctx* ctx = Qp->ctx;
+  const int64_t N = Qp->N;
+  const int k = Qp->nvec;
+  int ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
   double* T = wa_ptr(ctx, WA_T);                       // k x k, contiguous (ld = k): what sym_eig_large reads
   HFMI_TRY(op_apply_panels(A, Qp, AQ));
   HFMI_TRY(launch_tsgemm_tn(ctx, AQ->p, AQ->ld, k, Qp->p, Qp->ld, k, N, 1.0, 0.0, T, k, 1, 0));
@@ -221,6 +283,9 @@ static int double_pass_wide(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_bl
   return HFMI_OK;
 }
 
+// hippylib's doublePass / doublePassG: power iterations, orthonormalisation, Rayleigh-Ritz in the arena the width calls for.
+// late_checks: the first two Cholesky-QR passes of a Gram-form solve without B may be taken on trust (QR_TRUSTED); when they did not
+// hold, the solve is repeated from Omega with every pass checked.
 static int double_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_block* Omega, int r, int s, int flags,
                             double* host_d, hfmi_block* U, bool late_checks = true) {
   if (!A || !Omega || !host_d || !U) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
@@ -233,108 +298,25 @@ static int double_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_bl
   if (U->N != N || U->nvec != r) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: U must be %lld x %d", (long long)N, r);
   if (k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: at most %d probe vectors (got %d)", HFMI_WIDE_MAXK, k);
   if (s < 1) HFMI_FAIL(HFMI_ERR_INVALID, "double_pass: s must be >= 1");
-  if (k > SM_MAXK) return double_pass_wide(A, B, Binv, Omega, r, s, flags, host_d, U);
+  const bool wide = k > SM_MAXK;
+  if (wide) HFMI_TRY(ctx_wide(ctx, k));
   hfmi_block Q, Y;
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Q, N, k, &Q));
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Y, N, k, &Y));
-  // power iterations: Q <- (B^-1) A Q, starting from Omega (never modified)
-  const hfmi_block* cur = Omega;
-  auto power_iterations = [&]() -> int {
-    cur = Omega;
-    for (int it = 0; it < s; ++it) {
-      if (Binv) {
-        int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-        HFMI_TRY(hfmi_op_apply(A, cur, &Y, 0));
-        phase_end(ctx, ph);
-        ph = phase_begin(ctx, HFMI_PHASE_BINV);
-        HFMI_TRY(hfmi_op_apply(Binv, &Y, &Q, 0));
-        phase_end(ctx, ph);
-        cur = &Q;
-      } else {
-        hfmi_block* dst = (cur == &Q) ? &Y : &Q;
-        const int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-        HFMI_TRY(hfmi_op_apply(A, cur, dst, 0));
-        phase_end(ctx, ph);
-        cur = dst;
-      }
-    }
-    return HFMI_OK;
-  };
-  HFMI_TRY(power_iterations());
-  bool deferred = false;                                   // last Cholesky-QR pass left as R^-1 in SM_RINV
-  qr_late_checks late = {false, nullptr, nullptr, 0, nullptr, false};
-  hfmi_block* Qp = const_cast<hfmi_block*>(cur);           // holds the block to orthogonalise
+  power_iter it = {A, Binv, Omega, s, &Q, &Y, nullptr, Omega, Omega};
+  HFMI_TRY(solve_power_iterations(it));
+  hfmi_block* Qp = const_cast<hfmi_block*>(it.cur);        // holds the block to orthogonalise
   hfmi_block* AQ = (Qp == &Q) ? &Y : &Q;
-  int ph = phase_begin(ctx, HFMI_PHASE_QR);
-  if (flags & 2) {
-    HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
-  } else {
-    // Cholesky-QR in place WITHOUT the safety copy hfmi_borth_qr(AUTO) keeps (a pass over N x k): if a column turns
-    // out to be numerically dependent, the block is recomputed from Omega (deterministic, every rank takes the same
-    // branch) and handed to the reference's Gram-Schmidt rule
-    const bool gram_path = op_has_gram_form(A) && !(flags & 4);
-    if (gram_path && late_checks && !B) {
-      void* pin = nullptr;
-      HFMI_TRY(ctx_late_pinned(ctx, &pin));
-      late.st2 = (hfmi_status_words*)pin;
-      late.st1 = (hfmi_status_words*)((char*)pin + 128);
-      late.aux = (double*)((char*)pin + 256);
-    }
-    const int qs = qr_chol(Qp, B, nullptr, false, nullptr, gram_path ? &deferred : nullptr, late.st2 ? &late : nullptr);
-    if (qs == HFMI_ERR_NUMERIC) {
-      deferred = false;
-      HFMI_TRY(power_iterations());
-      HFMI_TRY(hfmi_borth_qr(Qp, B, nullptr, nullptr, HFMI_QR_MGS, nullptr));
-    } else if (qs != HFMI_OK) {
-      return qs;
-    }
-  }
+  const bool gram_path = !wide && op_has_gram_form(A) && !(flags & 4);
+  const qr_policy policy = !gram_path ? QR_CHECKED : (late_checks && !B) ? QR_TRUSTED : QR_DEFERRED;
+  qr_result qr;
+  const int ph = phase_begin(ctx, HFMI_PHASE_QR);
+  HFMI_TRY(solve_orthonormalise(it, B, flags, policy, &qr));
   phase_end(ctx, ph);
-  ph = phase_begin(ctx, HFMI_PHASE_RAYLEIGH);
-  if (op_has_gram_form(A) && !(flags & 4)) {
-    HFMI_TRY(op_rayleigh_quotient_gram(A, Qp, SM_T, deferred));
-  } else {
-    // T = (AQ)^T Q as the reference forms it
-    HFMI_TRY(hfmi_op_apply(A, Qp, AQ, 0));
-    HFMI_TRY(launch_tsgemm_tn(ctx, AQ->p, AQ->ld, k, Qp->p, Qp->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_T), SM_LD, 1, 0));
-  }
-  phase_end(ctx, ph);
-  // small eigensolve, U = Q V[:, :r]
-  void* dv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)SM_MAXK * sizeof(double), &dv));
-  ph = phase_begin(ctx, HFMI_PHASE_EIG);
-  if (late.used) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));   // the late-check copies read the status words (done ms ago)
-  HFMI_TRY(launch_sym_eig(ctx, k, SM_T, SM_V, (double*)dv, flags & 1, (flags >> 3) & 1));
-  phase_end(ctx, ph);
-  // eigenvalues and status words leave for the host now, beside the back-transformation, instead of behind it
-  void* dpin = nullptr;
-  HFMI_TRY(ctx_pinned(ctx, (size_t)r * sizeof(double), &dpin));
-  HFMI_TRY(side_copies_begin(ctx));
-  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
-  HIP_TRY(hipMemcpyAsync(dpin, dv, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
-  ph = phase_begin(ctx, HFMI_PHASE_BACK);
-  if (deferred) {   // U = (Q R^-1) V = Q (R^-1 V)
-    HFMI_TRY(launch_small_matmul(ctx, k, r, SM_RINV, SM_V, SM_TMP2));
-    HFMI_TRY(launch_tsgemm_nn(ctx, Qp->p, Qp->ld, k, sm_ptr(ctx, SM_TMP2), SM_LD, r, 1.0, 0.0, U->p, U->ld, N));
-  } else {
-    HFMI_TRY(launch_tsgemm_nn(ctx, Qp->p, Qp->ld, k, sm_ptr(ctx, SM_V), SM_LD, r, 1.0, 0.0, U->p, U->ld, N));
-  }
-  phase_end(ctx, ph);
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-  memcpy(host_d, dpin, (size_t)r * sizeof(double));
-  const hfmi_status_words st = *ctx->status_host;
-  print_status_dbg(&st);
-  if (late.used) {
-    // the second orthogonalisation pass was taken on trust: look at what it reported, now that the stream has drained
-    bool ok = !late.st2->failed && !late.st2->shifted && late.st2->gram_dev < 1e-2;
-    if (late.first_trusted && (late.st1->failed || late.st1->shifted)) ok = false;
-    for (int j = 0; j < late.k && ok; ++j)
-      if (!(late.aux[SM_LD + j] > 100.0 * 2.220446049250313e-16 * late.aux[j])) ok = false;
-    if (!ok) return double_pass_impl(A, B, Binv, Omega, r, s, flags, host_d, U, false);   // the checked path decides (MGS fall-back, errors)
-  }
-  if (st.failed) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "double_pass: small eigensolve did not converge (off-diagonal %.2e)", st.offdiag);
-  return HFMI_OK;
+  bool repeat_checked = false;
+  if (wide) HFMI_TRY(rayleigh_ritz_wide(A, Qp, AQ, r, flags, host_d, U));
+  else HFMI_TRY(rayleigh_ritz_narrow(A, Qp, AQ, gram_path, qr, r, flags, host_d, U, &repeat_checked));
+  return repeat_checked ? double_pass_impl(A, B, Binv, Omega, r, s, flags, host_d, U, false) : HFMI_OK;
 }
 
 extern "C" int hfmi_double_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U) {
@@ -374,44 +356,14 @@ static int sketch_eig_core(const hfmi_block* P, const hfmi_block* Y, const hfmi_
   HFMI_TRY(launch_tsgemm_tn(ctx, left->p, left->ld, k, Q_work->p, Q_work->ld, k, N, 1.0, 0.0, sm_ptr(ctx, SM_R), SM_LD, 1, 0));
   HFMI_TRY(launch_lu_solve(ctx, k, SM_GRAM, SM_R, SM_TMP, SM_TMP2, SM_T));
   phase_end(ctx, ph);
-  // the solve's status words leave for pinned memory before the eigensolver reuses them
-  void* pin = nullptr;
+  // the solve's status words leave for pinned memory (the late-check buffer's first slot) before the eigensolver reuses them
+  qr_late_buffer* pin = nullptr;
   HFMI_TRY(ctx_late_pinned(ctx, &pin));
-  hfmi_status_words* lu_st = (hfmi_status_words*)pin;
   HFMI_TRY(side_copies_begin(ctx));
-  HIP_TRY(hipMemcpyAsync(lu_st, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
+  HIP_TRY(hipMemcpyAsync(&pin->st2, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
   HFMI_TRY(side_copies_end(ctx));
   HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-  void* dv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)SM_MAXK * sizeof(double), &dv));
-  ph = phase_begin(ctx, HFMI_PHASE_EIG);
-  HFMI_TRY(launch_sym_eig(ctx, k, SM_T, SM_V, (double*)dv, flags & 1, (flags >> 3) & 1));
-  phase_end(ctx, ph);
-  void* dpin = nullptr;
-  HFMI_TRY(ctx_pinned(ctx, (size_t)r * sizeof(double), &dpin));
-  HFMI_TRY(side_copies_begin(ctx));
-  HIP_TRY(hipMemcpyAsync(ctx->status_host, ctx->status_dev, sizeof(hfmi_status_words), hipMemcpyDeviceToHost, ctx->aux_stream));
-  HIP_TRY(hipMemcpyAsync(dpin, dv, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->aux_stream));
-  ph = phase_begin(ctx, HFMI_PHASE_BACK);
-  // V[:, :r] zero padded to 16 columns, as tsgemm_nn expects (the eigensolver leaves SM_V's pad columns as they were)
-  HFMI_TRY(launch_small_set_identity(ctx, k, SM_GRAM));
-  HFMI_TRY(launch_small_matmul(ctx, k, r, SM_GRAM, SM_V, SM_TMP2));
-  HFMI_TRY(launch_tsgemm_nn(ctx, Q_work->p, Q_work->ld, k, sm_ptr(ctx, SM_TMP2), SM_LD, r, 1.0, 0.0, U->p, U->ld, N));
-  phase_end(ctx, ph);
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-  HFMI_TRY(ctx_check_comm(ctx));
-  if (lu_st->failed == 1) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the sketch products W = P^T Q / Z = Y^T Q have non-finite entries", who);
-  if (lu_st->failed == 3) HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: the solve W^-1 Z overflowed (non-finite pivot or solution)", who);
-  if (lu_st->failed)
-    HFMI_FAIL(HFMI_ERR_NUMERIC, "%s: rank-deficient sketch: W = P^T %sQ is singular (min |pivot| %.2e, max |pivot| %.2e); "
-              "the probe block has dependent columns or the operator's range is smaller than the sketch", who, B ? "B " : "",
-              lu_st->min_pivot_ratio, lu_st->gram_dev);
-  memcpy(host_d, dpin, (size_t)r * sizeof(double));
-  const hfmi_status_words st = *ctx->status_host;
-  print_status_dbg(&st);
-  if (st.failed) HFMI_FAIL(HFMI_ERR_NOT_CONVERGED, "%s: small eigensolve did not converge (off-diagonal %.2e)", who, st.offdiag);
-  return HFMI_OK;
+  return solve_tail(Q_work, r, flags, BACK_IDENTITY_V, nullptr, &pin->st2, B != nullptr, who, host_d, U, nullptr);
 }
 
 static int check_sketch_args(const hfmi_block* Omega, int r, const hfmi_block* U, const char* who) {
@@ -439,29 +391,11 @@ static int single_pass_impl(hfmi_op* A, hfmi_op* B, hfmi_op* Binv, const hfmi_bl
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SOLVE_Y, N, k, &X1));
   HFMI_TRY(ctx_tmp_view(ctx, TMP_SKETCH_Q, N, k, &W2));
   if (B) HFMI_TRY(ctx_tmp_view(ctx, TMP_SKETCH_BQ, N, k, &W3));
-  // power iterations without orthogonalisation (the loop of double_pass_impl); the last two iterates are kept
-  const hfmi_block* prev = Omega;
-  const hfmi_block* cur = Omega;
-  for (int it = 0; it < s; ++it) {
-    hfmi_block* dst = (cur == &X0) ? &X1 : &X0;
-    if (Binv) {
-      int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-      HFMI_TRY(hfmi_op_apply(A, cur, &W2, 0));                 // Ybar
-      phase_end(ctx, ph);
-      ph = phase_begin(ctx, HFMI_PHASE_BINV);
-      HFMI_TRY(hfmi_op_apply(Binv, &W2, dst, 0));
-      phase_end(ctx, ph);
-    } else {
-      const int ph = phase_begin(ctx, HFMI_PHASE_APPLY);
-      HFMI_TRY(hfmi_op_apply(A, cur, dst, 0));
-      phase_end(ctx, ph);
-    }
-    prev = cur;
-    cur = dst;
-  }
-  hfmi_block* Yb = const_cast<hfmi_block*>(cur);
-  if (B) return sketch_eig_core(prev, Yb, &W2, B, Yb, &W3, r, flags, host_d, U, who);   // Q in place of Y, B Q in W3
-  return sketch_eig_core(prev, Yb, nullptr, nullptr, &W2, nullptr, r, flags, host_d, U, who);
+  power_iter it = {A, Binv, Omega, s, &X0, &X1, &W2, Omega, Omega};   // the last two iterates are kept, and Ybar = A X_{s-1} in W2
+  HFMI_TRY(solve_power_iterations(it));
+  hfmi_block* Yb = const_cast<hfmi_block*>(it.cur);
+  if (B) return sketch_eig_core(it.prev, Yb, &W2, B, Yb, &W3, r, flags, host_d, U, who);   // Q in place of Y, B Q in W3
+  return sketch_eig_core(it.prev, Yb, nullptr, nullptr, &W2, nullptr, r, flags, host_d, U, who);
 }
 
 extern "C" int hfmi_single_pass(hfmi_op* A, const hfmi_block* Omega, int r, int s, int flags, double* host_d, hfmi_block* U) {

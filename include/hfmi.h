@@ -489,6 +489,33 @@ HFMI_API int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale, 
 #define HFMI_EIG_PLAN_INSTANCES 13
 HFMI_API int hfmi_eig_plan_predict(int n, int nvec, int64_t lds_per_block, int64_t defl1_static_lds, int64_t* scalars, int64_t* regions,
                                    int64_t* levels, int64_t* walk);
+/* The rules of repeated Cholesky-QR (hfmi_borth_qr, the orthogonalisation inside the fused solves; csrc/hfmi_qr_rules.h) for given
+ * values, from the functions the loops themselves ask: no context and no device.  policy: what the caller lets the loop leave
+ * undone -- CHECKED: every pass's status words are read; DEFERRED: the last pass's R^-1 is left for the caller to fold in; TRUSTED:
+ * deferred, and the first two passes' words are judged by the caller after the solve.  has_B: a B inner product (every pass is then
+ * a checked one); trust_first: the tuning key "qr_trust_first"; pass: 0-based; first_clean: pass 0 was trusted or reported no shift;
+ * failed, shifted, gram_dev: the status words of this pass (not read by the two TRUST issues; a NaN defect is "not yet orthonormal").
+ * words[0] = how the pass is issued (HFMI_QR_ISSUE_*), words[1] = what follows from its status words (HFMI_QR_NEXT_*),
+ * words[2] = 1 when a call of k vectors under that policy takes the wide arena at tuning key "qr_wide_min" = qr_wide_min. */
+#define HFMI_QR_POLICY_CHECKED 0
+#define HFMI_QR_POLICY_DEFERRED 1
+#define HFMI_QR_POLICY_TRUSTED 2
+#define HFMI_QR_ISSUE_TRUST_FIRST 0      /* status words to their own slot, apply R^-1, no read */
+#define HFMI_QR_ISSUE_TRUST_SECOND 1     /* words and the R_jj / ||z_j|| table to pinned memory, stop with R^-1 deferred */
+#define HFMI_QR_ISSUE_READ_THEN_APPLY 2  /* read the words, apply R^-1 only if another pass follows */
+#define HFMI_QR_ISSUE_APPLY_THEN_READ 3  /* snapshot the words, apply R^-1, then read */
+#define HFMI_QR_NEXT_FAIL_NOT_PD 0       /* HFMI_ERR_NUMERIC: not positive definite even after shifting */
+#define HFMI_QR_NEXT_DONE 1
+#define HFMI_QR_NEXT_DONE_DEFERRED 2
+#define HFMI_QR_NEXT_AGAIN 3
+#define HFMI_QR_NEXT_FAIL_MAX_PASSES 4   /* HFMI_ERR_NUMERIC: no convergence in 6 passes */
+HFMI_API int hfmi_qr_rules_predict(int policy, int has_B, int trust_first, int pass, int first_clean, int failed, int shifted, double gram_dev,
+                                   int k, int qr_wide_min, int* words /* 3 */);
+/* The late verdict on a TRUSTED call of k <= 256 vectors: the second pass's words, the first pass's when first_trusted, and the table
+ * norm[j] = ||z_j|| of the input column, rdiag[j] = R_jj of the accumulated factor (a column counts as dependent unless
+ * R_jj > 100 eps ||z_j||).  *stands = 1: the result stands, 0: the solve is repeated on the checked path. */
+HFMI_API int hfmi_qr_late_verdict_predict(int k, int failed2, int shifted2, double gram_dev2, int first_trusted, int failed1, int shifted1,
+                                          const double* norm, const double* rdiag, int* stands);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */

@@ -116,6 +116,63 @@ def test_first_qr_pass_on_trust_equals_the_checked_path(ctx, rate, s):
     np.testing.assert_array_equal(res[0][1], res[1][1])
 
 
+def test_rank_deficient_gram_form_solve_is_the_same_with_and_without_trust(ctx):
+    """120 snapshots of latent rank 40 under 60 probe vectors: the block handed to the QR has 20 numerically dependent columns.
+    With the first pass on trust the late verdict sends the solve to the checked path, without it the checked passes find the
+    dependent column themselves; both end in the Gram-Schmidt fall-back and return the same bits.  The eigenvalues that are not
+    round-off agree with the oracle to the bars of test_fuzz_double_pass_against_the_oracle."""
+    from hippyflow_amd import _lib as L
+    rng = np.random.default_rng(4040)
+    N, n, latent, k, r, s = 4225, 120, 40, 60, 30, 1
+    U0 = np.linalg.qr(rng.standard_normal((N, latent)))[0]
+    X = (rng.standard_normal((n, latent)) * np.exp(-0.1 * np.arange(latent))) @ U0.T
+    op = hf.SnapshotGramOperator(X)
+    Om = rng.standard_normal((N, k))
+    res = {}
+    try:
+        for trust in (1, 0):
+            L.call("hfmi_tuning_set", b"qr_trust_first", trust)
+            d, U = hf.doublePass(op, hf.MultiVector.from_dense(Om), r, s=s)
+            res[trust] = (d, U.to_dense())
+    finally:
+        L.call("hfmi_tuning_set", b"qr_trust_first", 1)
+    np.testing.assert_array_equal(res[0][0], res[1][0])
+    np.testing.assert_array_equal(res[0][1], res[1][1])
+    d, Ud = res[1]
+    d_ref, _ = hp_o.double_pass_blas3(lambda W: np.asfortranarray(X.T @ (X @ W) / n), np.asfortranarray(Om), r, s=s)
+    big = d_ref > 1e-10 * d_ref[0]
+    assert big.sum() == r                                   # the 30 leading eigenvalues of a rank-40 operator
+    e = np.max(np.abs(d[big] - d_ref[big]) / np.maximum(d_ref[big], 1e-7 * d_ref[0]))
+    o = np.linalg.norm(Ud[:, big].T @ Ud[:, big] - np.eye(int(big.sum())))
+    print("rank-deficient Gram-form solve: eigenvalue error %.3e, orthonormality defect %.3e" % (e, o))
+    assert e < 1e-8 and o < 1e-9, (e, o)
+
+
+def test_wide_qr_knob_does_not_reach_the_fused_solve(ctx):
+    """The tuning key "qr_wide_min" moves hfmi_borth_qr (a checked call) to the wide arena from that width on; the Gram-form solve's
+    deferred / trusted orthogonalisation has no wide form, so its route must stay narrow: at k = 48 >= 17 the solve returns the same
+    bits with and without the knob."""
+    from hippyflow_amd import _lib as L
+    rng = np.random.default_rng(4848)
+    N, n, k, r = 4225, 100, 48, 20
+    U0 = np.linalg.qr(rng.standard_normal((N, n)))[0]
+    X = (rng.standard_normal((n, n)) * np.exp(-0.1 * np.arange(n))) @ U0.T
+    op = hf.SnapshotGramOperator(X)
+    Om = hf.MultiVector.from_dense(rng.standard_normal((N, k)))
+    res = {}
+    try:
+        for wide_min in (257, 17):
+            L.call("hfmi_tuning_set", b"qr_wide_min", wide_min)
+            d, U = hf.doublePass(op, Om, r, s=1)
+            res[wide_min] = (d, U.to_dense())
+    finally:
+        L.call("hfmi_tuning_set", b"qr_wide_min", 257)
+        L.call("hfmi_tuning_set", b"qr_trust_first", 1)
+    assert np.all(np.isfinite(res[257][0])) and res[257][0][0] > 0
+    np.testing.assert_array_equal(res[257][0], res[17][0])
+    np.testing.assert_array_equal(res[257][1], res[17][1])
+
+
 def test_fuzz_whole_gpu_eigensolver_sizes(ctx):
     """20 random sizes n in [257, 3000] of the whole-GPU eigensolver (hfmi_eig_blocked.hip: panels above 2048 rows, one launch per column
     below, divide and conquer, block reflectors), primes and n = 1 mod 64 included, three kinds of spectra, against numpy.linalg.eigh:

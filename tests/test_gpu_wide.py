@@ -1,4 +1,4 @@
-"""GPU suite: orthogonalisation and double pass beyond 256 vectors, up to 2048 (hfmi_chol_wide.hip, qr_chol_wide, double_pass_wide).
+"""GPU suite: orthogonalisation and double pass beyond 256 vectors, up to 2048 (hfmi_chol_wide.hip, qr_chol_wide, the wide back end of double_pass_impl).
 
   1. the wide Cholesky + inverse kernel family through hfmi_test_chol_wide: Higham's backward bound, the inverse, triangularity,
      bit-identical reruns, the shifted and the failing attempt against the numpy twin;
