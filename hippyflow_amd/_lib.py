@@ -134,6 +134,7 @@ SIGNATURES = {
                           C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)],
     "hfmi_eig_plan_predict": [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                               C.POINTER(C.c_int64)],
+    "hfmi_small_plan_predict": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
     "hfmi_qr_rules_predict": [C.c_int] * 7 + [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int)],
     "hfmi_qr_late_verdict_predict": [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _D, _D, C.POINTER(C.c_int)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],

@@ -1,6 +1,6 @@
 // Blocked Cholesky factorisation with the triangular inverse, k <= 256, on the fp64 MFMA of ONE compute unit (round 3).
 //
-// The column-at-a-time kernels of hfmi_small.hip (k_chol_tile) spend a barrier, an LDS hand-off and a reciprocal square
+// The column-at-a-time kernels of hfmi_chol_col.hip (k_chol_tile) spend a barrier, an LDS hand-off and a reciprocal square
 // root on each of the k columns of the factorisation and again on each of the k rows of the inverse: 1.6 k cycles per
 // column, 0.2 ms at k = 138 -- twice per solve.  Here the matrix is cut into 16 x 16 blocks that live in the MFMA's
 // accumulator layout in registers, and a step handles sixteen columns:
@@ -25,14 +25,13 @@
 // factors) are those of k_chol_tile.  Kernel time 80 -> 25 us at k = 74, 205 -> 55 us at k = 138, 730 -> 170 us at k = 256; per
 // block step about 4.8 k cycles for the diagonal block (scripts/chol_diag_probe.hip), 2.7 k for the block row, 2.3 k for the
 // trailing update at k = 138 (HFMI_DEBUG_TIMING=1 prints the three sums).
+// launch_chol_mfma launches what chol_mfma_plan (hfmi_small_plan.h) says.
 #include "hfmi_internal.h"
-
-#include <stdlib.h>
-#include <string.h>
+#include "hfmi_small_dev.h"
+#include "hfmi_small_plan.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 #define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#define EPS_D 2.220446049250313e-16
 
 namespace {
 
@@ -88,8 +87,6 @@ __device__ __forceinline__ int cm_opaque(int x) {
 // memory (s_waitcnt vmcnt(0)): with it every step would wait for the acknowledgement of the rows of R and R^-1 it has just
 // stored, which nobody reads before the kernel ends (or before the __syncthreads() in front of the running product).
 __device__ __forceinline__ void cm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int CM_SCR = 4 * 16 * 17;   // padded 16 x 16 blocks of scratch per wave: input / R_KK, Z_KK, two dump blocks
 
 // 64-bit DPP: lane l gets x of lane I of its own row of sixteen (row_newbcast, the one DPP mode the double-precision ALU has) --
 // as a plain copy and fused into the accumulate acc += bcast_I(src) * mul.  The compiler neither knows these instructions
@@ -529,27 +526,31 @@ __global__ __launch_bounds__(64 * NW) void k_chol_mfma(const double* __restrict_
 
 }  // namespace
 
+// the instance <NW, SLOTS> of a plan (HFMI_CHOL_MFMA_CASES, hfmi_small_plan.h); null: not compiled
+typedef decltype(&k_chol_mfma<8, 2>) chol_mfma_fn;
+static chol_mfma_fn chol_mfma_kernel(int nw, int slots) {
+  switch (100 * nw + slots) {
+#define X(NWV, SLV, NBMAX)   \
+  case 100 * (NWV) + (SLV): \
+    return k_chol_mfma<NWV, SLV>;
+    HFMI_CHOL_MFMA_CASES(X)
+#undef X
+  }
+  return nullptr;
+}
+
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol) {
   if (k < 1 || k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "chol_mfma: k=%d out of range", k);
   if (pivot_tol <= 0.0) pivot_tol = 64.0 * k * EPS_D;
-  const int nb = (k + 15) / 16;
-#define CHOL_MFMA(NWV, SLV)                                                                                                     \
-  do {                                                                                                                         \
-    auto kern = k_chol_mfma<NWV, SLV>;                                                                                         \
-    const size_t shm = (size_t)(32 + 5 * 256 + (NWV) * CM_SCR + 2 * nb * 256) * sizeof(double);                                \
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));                     \
-    hipLaunchKernelGGL(kern, dim3(1), dim3(64 * (NWV)), shm, ctx->stream, sm_ptr(ctx, slot_gram), SM_LD, k, sm_ptr(ctx, slot_r), \
-                       sm_ptr(ctx, slot_rinv), sm_ptr(ctx, slot_rtot), sm_ptr(ctx, SM_TMP2), SM_LD, rtot_mode, full_r,         \
-                       shift_rel, pivot_tol, sm_ptr(ctx, SM_AUX), sm_ptr(ctx, SM_AUX) + SM_LD, ctx->status_dev);               \
-  } while (0)
-  // slots = nb (nb + 1) / 2 over the waves
-  if (nb <= 5) CHOL_MFMA(8, 2);          // k <= 80: 15 slots
-  else if (nb <= 7) CHOL_MFMA(8, 4);     // k <= 112: 28
-  else if (nb <= 9) CHOL_MFMA(8, 6);     // k <= 144: 45
-  else if (nb <= 12) CHOL_MFMA(8, 10);   // k <= 192: 78
-  else CHOL_MFMA(8, 17);                 // k <= 256: 136 (sixteen waves would have 128 registers each: not enough)
-#undef CHOL_MFMA
+  const small_plan p = chol_mfma_plan(k);
+  const small_launch& L = p.launch[0];
+  const chol_mfma_fn kern = chol_mfma_kernel(L.t[0], L.t[1]);
+  if (!kern) HFMI_FAIL(HFMI_ERR_INVALID, "chol_mfma: no k_chol_mfma<%d, %d>", L.t[0], L.t[1]);
+  HFMI_TRY(small_raise_lds((const void*)kern, L));
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(L.threads), L.lds, ctx->stream, sm_ptr(ctx, slot_gram), SM_LD, k, sm_ptr(ctx, slot_r),
+                     sm_ptr(ctx, slot_rinv), sm_ptr(ctx, slot_rtot), sm_ptr(ctx, SM_TMP2), SM_LD, rtot_mode, full_r, shift_rel, pivot_tol,
+                     sm_ptr(ctx, SM_AUX), sm_ptr(ctx, SM_AUX) + SM_LD, ctx->status_dev);
   HIP_TRY(hipGetLastError());
   return HFMI_OK;
 }

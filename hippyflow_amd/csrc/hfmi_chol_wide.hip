@@ -1,5 +1,5 @@
 // Cholesky factorisation with inverse of a k x k Gram matrix for 256 < k <= HFMI_WIDE_MAXK (2048), spread over the GPU: the
-// contract of launch_chol_inv (hfmi_small.hip / hfmi_chol.hip) beyond what one compute unit holds.  Everything lives in the wide
+// contract of launch_chol_inv (hfmi_chol_col.hip / hfmi_chol.hip) beyond what one compute unit holds.  Everything lives in the wide
 // arena of the context (row-major, ld = round_up(k, 32)):
 //   G = R^T R,  R upper -> WA_R,  R^-1 upper -> WA_RINV (strict lower triangles written as zeros),
 //   Rtot <- R (first pass) or R Rtot -> WA_RTOT,  AUX: original column norms, then diag(Rtot),

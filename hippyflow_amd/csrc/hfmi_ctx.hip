@@ -343,6 +343,24 @@ extern "C" int hfmi_eig_plan_predict(int n, int nvec, int64_t lds_per_block, int
   return HFMI_OK;
 }
 
+// the launch plan of a call of the one-workgroup k x k stage, from the planner its launcher asks (hfmi_small_plan.h); no device involved
+static_assert(SMALL_KNOB_WORDS == HFMI_SMALL_KNOB_WORDS && SMALL_PLAN_WORDS == HFMI_SMALL_PLAN_WORDS,
+              "include/hfmi.h sizes the arrays of hfmi_small_plan_predict");
+extern "C" int hfmi_small_plan_predict(int kind, int k, int method, const int* knobs, int64_t* words) {
+  if (!words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  const small_knobs kn = knobs ? small_knobs_from_words(knobs) : small_knobs_ref();
+  small_plan p;
+  switch (kind) {
+    case SMALL_KIND_CHOL: p = chol_plan(k, kn); break;
+    case SMALL_KIND_EIGH: p = sym_eig_route(method, kn) ? jacobi_eig_plan(k, kn) : dc_eig_plan(k, kn); break;
+    case SMALL_KIND_SVD: p = jacobi_svd_plan(k, kn); break;
+    case SMALL_KIND_LU: p = lu_plan(k); break;
+    default: HFMI_FAIL(HFMI_ERR_INVALID, "small_plan_predict: unknown kind %d", kind);
+  }
+  small_plan_words(p, kn, words);
+  return HFMI_OK;
+}
+
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
   if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;
@@ -495,6 +513,16 @@ int api_tuning_set(const char* key, int value) {
     return 1;
   }
   return 0;
+}
+// Tuning knobs (A/B measurements): the contractions' live in tsgemm_knobs (hfmi_tsgemm_plan.h), the k x k stage's in small_knobs
+// (hfmi_small_plan.h), the other subsystems keep their own
+extern "C" int hfmi_tuning_set(const char* key, int value) {
+  if (key && tsgemm_knob_set(key, value)) {}
+  else if (key && small_knob_set(key, value)) {}
+  else if (key && api_tuning_set(key, value)) {}
+  else if (key && pchol_tuning_set(key, value)) {}
+  else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
+  return HFMI_OK;
 }
 
 // ------------------------------------------------------------------ instrumentation

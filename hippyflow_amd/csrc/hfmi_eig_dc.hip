@@ -29,10 +29,7 @@
 #include "hfmi_dc_common.h"
 
 namespace {
-constexpr int DC_THREADS = 1024;
-constexpr int DC_WAVES = 16;
-constexpr int DC_MAXN = 256;
-
+// DC_THREADS, DC_WAVES, DC_MAXN: hfmi_small_plan.h, with the plan of launch_dc_eig
 
 // ------------------------------------------------------------------------------------------------ tridiagonalisation
 // per-phase shader-clock counters of wave 0 (build with -DHFMI_DC_TICKS; every s_memtime read drains the LDS queue, so the
@@ -1059,75 +1056,88 @@ __global__ void k_leaf_gather(const leaf_desc* __restrict__ leaves, double* __re
 }
 }  // namespace
 
+// the instances of a plan (HFMI_TRI_*_CASES, HFMI_DC_CASES, HFMI_DC_BACK_CASES of hfmi_small_plan.h); null: not compiled
+typedef decltype(&k_tridiag<4, 1, 8>) tridiag_fn;
+static tridiag_fn tridiag_kernel(int ri, int cj, int nw, int lr) {
+  switch (((ri * 10 + cj) * 10 + nw) * 100 + lr) {
+#define TRI_KEY(RI, CJ, NW, LR) (((RI) * 10 + (CJ)) * 10 + (NW)) * 100 + (LR)
+#define X(KMAX, RI, CJ)      \
+  case TRI_KEY(RI, CJ, 4, 0): \
+    return k_tridiag<RI, CJ, 4>;
+    HFMI_TRI_W4_CASES(X)
+#undef X
+#define X(KMAX, RI, CJ)      \
+  case TRI_KEY(RI, CJ, 8, 0): \
+    return k_tridiag<RI, CJ, 8>;
+    HFMI_TRI_W8_CASES(X)
+#undef X
+#define X(KMAX, RI, CJ, LR)   \
+  case TRI_KEY(RI, CJ, 8, LR): \
+    return k_tridiag<RI, CJ, 8, LR>;
+    HFMI_TRI_LDS_CASES(X)
+#undef X
+#undef TRI_KEY
+  }
+  return nullptr;
+}
+typedef decltype(&k_dc<8>) dc_fn;
+typedef decltype(&k_dc_batch<8>) dc_batch_fn;
+typedef decltype(&k_dc_back<5>) dc_back_fn;
+static dc_fn dc_kernel(int g) {
+  switch (g) {
+#define X(KMAX, G) \
+  case G:          \
+    return k_dc<G>;
+    HFMI_DC_CASES(X)
+#undef X
+  }
+  return nullptr;
+}
+static dc_batch_fn dc_batch_kernel(int g) {
+  switch (g) {
+#define X(KMAX, G) \
+  case G:          \
+    return k_dc_batch<G>;
+    HFMI_DC_CASES(X)
+#undef X
+  }
+  return nullptr;
+}
+static dc_back_fn dc_back_kernel(int el) {
+  switch (el) {
+#define X(KMAX, EL) \
+  case EL:          \
+    return k_dc_back<EL>;
+    HFMI_DC_BACK_CASES(X)
+#undef X
+  }
+  return nullptr;
+}
+
 // T (k x k, SM slot, row-major) -> eigenvalues (descending, or by magnitude) into dvals (device, k), eigenvectors into the
-// columns of slot_v.  Same contract as launch_jacobi_eig.
+// columns of slot_v.  Same contract as launch_jacobi_eig.  Launches what dc_eig_plan says: k_tridiag, k_dc, k_dc_top, k_dc_back.
 int launch_dc_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, int sort_by_abs) {
   if (k < 1 || k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "dc_eig: k=%d out of range", k);
-  const int ldq = (int)round_up(k, 16);
-  const size_t mat = (size_t)ldq * ldq;
-  // scratch: d, e, tau (3 x 256), reflectors (256 x ldq), Q, Qt, S, perm + scale exponent
-  const size_t doubles = 3 * DC_MAXN + (size_t)DC_MAXN * ldq + 3 * mat;
+  const small_plan p = dc_eig_plan(k, small_knobs_ref());
   void* wv = nullptr;
-  HFMI_TRY(ctx_ws(ctx, WS_MISC, doubles * sizeof(double) + (DC_MAXN + 16) * sizeof(int) + 16 * sizeof(long long) + (3 * DC_MAXN + 16) * sizeof(int), &wv));
-  double* dvec = (double*)wv;
-  double* evec = dvec + DC_MAXN;
-  double* tauv = evec + DC_MAXN;
-  double* Vh = tauv + DC_MAXN;
-  double* Qm = Vh + (size_t)DC_MAXN * ldq;
-  double* Qt = Qm + mat;
-  double* Sm = Qt + mat;
-  int* perm = (int*)(Sm + mat);
-  int* sexp = perm + DC_MAXN;
-  long long* ticks = (long long*)(sexp + 16);
-  int* top_meta = (int*)(ticks + 16);
-  const double* T = sm_ptr(ctx, slot_t);
-  static int tri_waves = 0;     // HFMI_TRI_WAVES = 4 | 8: A/B of the workgroup shape
-  if (!tri_waves) {
-    const char* e = getenv("HFMI_TRI_WAVES");
-    tri_waves = (e && atoi(e) == 4) ? 4 : 8;
-  }
-#define TRI(RIV, CJV, NWV)                                                                                                        \
-  hipLaunchKernelGGL((k_tridiag<RIV, CJV, NWV>), dim3(1), dim3(64 * NWV), 0, ctx->stream, T, SM_LD, k, dvec, evec, Vh, ldq, tauv, \
-                     sexp, ticks)
-  if (tri_waves == 4) {
-    if (k <= 32) TRI(8, 1, 4);
-    else if (k <= 64) TRI(16, 1, 4);
-    else if (k <= 80) TRI(20, 2, 4);
-    else if (k <= 96) TRI(24, 2, 4);
-    else if (k <= 128) TRI(32, 2, 4);
-    else if (k <= 144) TRI(36, 3, 4);
-    else if (k <= 160) TRI(40, 3, 4);
-    else if (k <= 192) TRI(48, 3, 4);
-    else TRI(64, 4, 4);
-  } else {
-    if (k <= 32) TRI(4, 1, 8);
-    else if (k <= 64) TRI(8, 1, 8);
-    else if (k <= 96) TRI(12, 2, 8);
-    else if (k <= 128) TRI(16, 2, 8);
-    else if (k <= 160) TRI(20, 3, 8);
-    else {
-      // 160 < k <= 256: 64 k^2 doubles leave no registers for anything else (the compiler spills 84..99 values per thread
-      // and the reduction runs 3x slower), so the last LR rows live in LDS; the shapes below are the ones that do not spill
-      // (k <= 192) or spill 5 values (k <= 224); above that 64 rows are all the LDS holds beside the work arrays
-#define TRI_LDS(RIV, CJV, LRV)                                                                                                   \
-  do {                                                                                                                          \
-    auto kern = k_tridiag<RIV, CJV, 8, LRV>;                                                                                    \
-    const size_t shm = (size_t)(LRV) * 64 * (CJV) * sizeof(double);                                                             \
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));                      \
-    hipLaunchKernelGGL(kern, dim3(1), dim3(512), shm, ctx->stream, T, SM_LD, k, dvec, evec, Vh, ldq, tauv, sexp, ticks);        \
-  } while (0)
-      if (k <= 192) TRI_LDS(20, 3, 32);
-      else if (k <= 224) TRI_LDS(20, 4, 64);
-      else TRI_LDS(24, 4, 64);
-#undef TRI_LDS
-    }
-  }
-#undef TRI
+  HFMI_TRY(ctx_ws(ctx, WS_MISC, (size_t)p.ws_bytes, &wv));
+  const dc_ws w = dc_ws_carve(p, wv);
+  double *dvec = (double*)w.dvec, *evec = (double*)w.evec, *tauv = (double*)w.tauv, *Vh = (double*)w.Vh;
+  double *Qm = (double*)w.Qm, *Qt = (double*)w.Qt, *Sm = (double*)w.Sm;
+  int *perm = (int*)w.perm, *sexp = (int*)w.sexp, *top_meta = (int*)w.top_meta;
+  long long* ticks = (long long*)w.ticks;
+  const int ldq = p.ldq;
+  int li = 0;
+  const small_launch& tri = p.launch[li++];
+  const tridiag_fn ktri = tridiag_kernel(tri.t[0], tri.t[1], tri.t[2], tri.t[3]);
+  if (!ktri) HFMI_FAIL(HFMI_ERR_INVALID, "dc_eig: no k_tridiag<%d, %d, %d, %d>", tri.t[0], tri.t[1], tri.t[2], tri.t[3]);
+  HFMI_TRY(small_raise_lds((const void*)ktri, tri));
+  hipLaunchKernelGGL(ktri, dim3(tri.grid), dim3(tri.threads), tri.lds, ctx->stream, sm_ptr(ctx, slot_t), SM_LD, k, dvec, evec, Vh, ldq, tauv,
+                     sexp, ticks);
   HIP_TRY(hipGetLastError());
   dc_args a;
   a.n = k;
-  a.levels = 0;
-  while ((1 << a.levels) < k) ++a.levels;
+  a.levels = p.levels;
   a.sort_by_abs = sort_by_abs ? 1 : 0;
   a.dvec = dvec;
   a.evec = evec;
@@ -1140,42 +1150,26 @@ int launch_dc_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, i
   a.perm = perm;
   a.status = ctx->status_dev;
   a.ticks = ticks;
-  static int split_top = -1;    // HFMI_DC_SPLIT_TOP=0: the last merge's product inside k_dc (A/B)
-  if (split_top < 0) {
-    const char* e = getenv("HFMI_DC_SPLIT_TOP");
-    split_top = e ? atoi(e) : 1;
-  }
-  a.split_top = (split_top && k >= 32) ? 1 : 0;
+  a.split_top = p.split_top;
   a.top_meta = top_meta;
-  if (k <= 128) hipLaunchKernelGGL((k_dc<8>), dim3(1), dim3(DC_THREADS), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_dc<4>), dim3(1), dim3(DC_THREADS), 0, ctx->stream, a);
+  const small_launch& dc = p.launch[li++];
+  const dc_fn kdc = dc_kernel(dc.t[0]);
+  if (!kdc) HFMI_FAIL(HFMI_ERR_INVALID, "dc_eig: no k_dc<%d>", dc.t[0]);
+  hipLaunchKernelGGL(kdc, dim3(dc.grid), dim3(dc.threads), dc.lds, ctx->stream, a);
   HIP_TRY(hipGetLastError());
-  if (a.split_top) {
-    // level 0 is the last of the ping-pong merges (levels - 1 of them: the deepest level works in place): its input is the
-    // buffer after levels - 2 swaps
-    const int before = a.levels >= 2 ? a.levels - 2 : 0;
-    const double* Qin0 = (before & 1) ? Qt : Qm;
-    double* Qout0 = (before & 1) ? Qm : Qt;
-    const int T = (k + 15) / 16;
-    hipLaunchKernelGGL(k_dc_top, dim3(T * T + 16), dim3(64), 0, ctx->stream, Qin0, Qout0, Sm, ldq, k, top_meta);
+  if (p.split_top) {
+    const small_launch& top = p.launch[li++];
+    hipLaunchKernelGGL(k_dc_top, dim3(top.grid), dim3(top.threads), top.lds, ctx->stream, p.top_from_qt ? Qt : Qm, p.top_from_qt ? Qm : Qt, Sm,
+                       ldq, k, top_meta);
     HIP_TRY(hipGetLastError());
   }
-  double* Vout = sm_ptr(ctx, slot_v);
-  const int blocks = (k + 3) / 4;
-  const int swaps = a.levels >= 1 ? a.levels - 1 : 0;  // the deepest level is solved in place (2 x 2 blocks in closed form)
-  const double* Qfin = (swaps & 1) ? Qt : Qm;          // the other merges ping-pong between the two buffers
-#define BACK(ELV) \
-  hipLaunchKernelGGL((k_dc_back<ELV>), dim3(blocks), dim3(64), 0, ctx->stream, Qfin, ldq, k, Vh, ldq, tauv, perm, Vout, SM_LD)
-  if (k <= 80) BACK(5);
-  else if (k <= 96) BACK(6);
-  else if (k <= 128) BACK(8);
-  else if (k <= 144) BACK(9);
-  else if (k <= 192) BACK(12);
-  else BACK(16);
-#undef BACK
+  const small_launch& back = p.launch[li++];
+  const dc_back_fn kback = dc_back_kernel(back.t[0]);
+  if (!kback) HFMI_FAIL(HFMI_ERR_INVALID, "dc_eig: no k_dc_back<%d>", back.t[0]);
+  hipLaunchKernelGGL(kback, dim3(back.grid), dim3(back.threads), back.lds, ctx->stream, p.fin_in_qt ? Qt : Qm, ldq, k, Vh, ldq, tauv, perm,
+                     sm_ptr(ctx, slot_v), SM_LD);
   HIP_TRY(hipGetLastError());
-  static const bool timing = env_flag("HFMI_DC_TIMING");
-  if (timing) {
+  if (p.timing) {
     long long h[16];
     HIP_TRY(hipMemcpyAsync(h, ticks, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1256,8 +1250,7 @@ int launch_dc_leaves(hfmi_ctx* ctx, int n, int Lf, const double* dvec, const dou
   HIP_TRY(hipStreamSynchronize(ctx->stream));      // args / desc are pageable host memory
   const leaf_desc* ddesc = (const leaf_desc*)(base + off_desc);
   hipLaunchKernelGGL(k_leaf_prep, dim3(nleaf), dim3(256), 0, ctx->stream, ddesc, n, dvec, evec);
-  if (nlmax <= 128) hipLaunchKernelGGL((k_dc_batch<8>), dim3(nleaf), dim3(DC_THREADS), 0, ctx->stream, (const dc_args*)(base + off_args));
-  else hipLaunchKernelGGL((k_dc_batch<4>), dim3(nleaf), dim3(DC_THREADS), 0, ctx->stream, (const dc_args*)(base + off_args));
+  hipLaunchKernelGGL(dc_batch_kernel(dc_group(nlmax)), dim3(nleaf), dim3(DC_THREADS), 0, ctx->stream, (const dc_args*)(base + off_args));
   hipLaunchKernelGGL(k_leaf_gather, dim3(nlmax, nleaf), dim3(256), 0, ctx->stream, ddesc, Dout, Qbig, ldq, fail);
   HIP_TRY(hipGetLastError());
   return HFMI_OK;

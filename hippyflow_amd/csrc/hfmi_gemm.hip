@@ -404,17 +404,6 @@ int launch_reduce_partials(hfmi_ctx* ctx, const double* part, const reduce_call&
   return HFMI_OK;
 }
 
-// Tuning knobs (A/B measurements): the contractions' live in tsgemm_knobs (hfmi_tsgemm_plan.h), the other subsystems keep their own
-extern "C" int hfmi_tuning_set(const char* key, int value) {
-  if (key && tsgemm_knob_set(key, value)) {}
-  else if (key && eig_tuning_set(key, value)) {}
-  else if (key && chol_tuning_set(key, value)) {}
-  else if (key && api_tuning_set(key, value)) {}
-  else if (key && pchol_tuning_set(key, value)) {}
-  else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
-  return HFMI_OK;
-}
-
 // the instance <MT, NT, TR, WAVES, R4> of a plan; null: not compiled
 typedef void (*tn_kernel_t)(const double*, int64_t, int, const double*, int64_t, int, int64_t, int64_t, int, int, double*, int64_t, int64_t,
                             int64_t, int, int, TnTail);

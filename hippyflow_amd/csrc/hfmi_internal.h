@@ -10,6 +10,7 @@
 
 #include "hfmi.h"
 #include "hfmi_qr_rules.h"
+#include "hfmi_small_plan.h"
 #include "hfmi_tsgemm_plan.h"
 
 // ------------------------------------------------------------------ errors
@@ -56,6 +57,7 @@ struct hfmi_block {
 // Small dense matrices live in one fixed device arena (row-major, ld = SM_LD).
 #define SM_MAXK 256
 #define SM_LD 256
+static_assert(SMALL_MAXK == SM_MAXK, "hfmi_small_plan.h plans for matrices of the small arena");
 enum { SM_GRAM = 0, SM_R, SM_RINV, SM_RTOT, SM_T, SM_V, SM_TMP, SM_TMP2, SM_AUX, SM_NSLOTS };
 
 // Small dense matrices of 256 < k <= HFMI_WIDE_MAXK vectors (the wide Cholesky-QR and double pass) live in a second arena that a
@@ -373,20 +375,24 @@ int launch_gamma_apply(hfmi_ctx* ctx, double* G, int ldg, int ndata, int q, int 
 int launch_gamma_apply_cm(hfmi_ctx* ctx, const double* Gc, double* out, int64_t ld, int ndata, int q, int k, const double* gamma,
                           int ldgam);
 
-// ------------------------------------------------------------------ small dense kernels (hfmi_small.hip)
+// ------------------------------------------------------------------ the one-workgroup k x k stage (plans: hfmi_small_plan.h)
+// the dynamic-LDS attribute of a kernel, raised where its plan says so
+static inline int small_raise_lds(const void* kern, const small_launch& L) {
+  if (L.raise) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+  return HFMI_OK;
+}
+// hfmi_chol_col.hip (column-at-a-time kernels) and hfmi_chol.hip (blocked MFMA kernel, the default):
 // G (k x k, SM slot) = R^T R; writes R (upper), Rinv (upper); if rtot_accumulate, Rtot <- R * Rtot.
 // Status words (min pivot ratio, defect, shifted/failed) land in ctx->status_dev.
 int launch_chol_inv(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode,
                     int full_r, double shift_rel, double pivot_tol);
-// T (k x k) -> eigenvalues (sorted descending) into dvals (device, k), eigenvectors into slot_v (columns).
+// hfmi_jacobi.hip: T (k x k) -> eigenvalues (sorted descending) into dvals (device, k), eigenvectors into slot_v (columns).
 int launch_jacobi_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, int sort_by_abs);
 // the same contract by Householder tridiagonalisation + divide and conquer (hfmi_eig_dc.hip): LAPACK dsyevd's algorithm
 // family, i.e. what the reference's np.linalg.eigh runs; absolute accuracy eps ||T||
 int launch_dc_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, int sort_by_abs);
-// dispatcher: method 0 = default (divide and conquer unless tuning "eig" = 1), 1 = Jacobi (high relative accuracy)
+// dispatcher (sym_eig_route): method 0 = default (divide and conquer unless tuning "eig" = 1), 1 = Jacobi (high relative accuracy)
 int launch_sym_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, int sort_by_abs, int method);
-int eig_tuning_set(const char* key, int value);   // 1 = key handled
-int chol_tuning_set(const char* key, int value);  // "chol": 0 = blocked MFMA kernel (default), 1 = column-at-a-time kernels
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol);   // hfmi_chol.hip
 // ------------------------------------------------------------------ wide Cholesky + inverse (hfmi_chol_wide.hip)
@@ -398,18 +404,17 @@ int ctx_wide(hfmi_ctx* ctx, int k);      // make the arena hold k x k matrices (
 // words, which it also returns on the host (it synchronises the stream: the restart with the shifted diagonal is the host's decision)
 int launch_chol_wide(hfmi_ctx* ctx, int k, int rtot_mode, double shift_rel, double pivot_tol, hfmi_status_words* host_st);
 int pchol_tuning_set(const char* key, int value); // "pchol_grid": cap on the workgroups of the pivoted Cholesky launches (hfmi_pchol.hip)
-int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first", "qr_wide_min"; hfmi_ctx.hip)
+int api_tuning_set(const char* key, int value);   // 1 = key handled ("comm_panels", "prof_level", "qr_trust_first", "qr_wide_min"; hfmi_ctx.hip, as hfmi_tuning_set)
 extern int g_comm_panels;      // row panels of an overlapped rank reduction (hfmi_op.hip reads HFMI_COMM_PANELS when -1)
 extern int g_qr_trust_first;   // first Cholesky-QR pass taken on trust (hfmi_qr.hip reads HFMI_QR_TRUST_FIRST when -1)
-int launch_small_set_identity(hfmi_ctx* ctx, int k, int slot);
+int launch_small_set_identity(hfmi_ctx* ctx, int k, int slot);   // hfmi_small.hip, as the product below
 // slot_c (k x r, zero padded to 16 columns) = slot_a (k x k) * slot_b[:, :r]
 int launch_small_matmul(hfmi_ctx* ctx, int k, int r, int slot_a, int slot_b, int slot_c);
-// R (k x k, slot_r) = U diag(s) V^T: singular values descending in svals (device), U -> slot_u, V -> slot_v (columns)
+// hfmi_jacobi.hip: R (k x k, slot_r) = U diag(s) V^T: singular values descending in svals (device), U -> slot_u, V -> slot_v (columns)
 int launch_jacobi_svd(hfmi_ctx* ctx, int k, int slot_r, int slot_u, int slot_v, double* svals);
-// X (m x m, slot_x) = W^-1 Z by LU with partial pivoting (slot_a: working copy of W), and when slot_t >= 0 also
+// hfmi_lu.hip: X (m x m, slot_x) = W^-1 Z by LU with partial pivoting (slot_a: working copy of W), and when slot_t >= 0 also
 // T = (X + X^T) / 2 into slot_t.  Status words: min / max |pivot|, failed = 1 non-finite input, 2 singular W.
 int launch_lu_solve(hfmi_ctx* ctx, int m, int slot_w, int slot_z, int slot_a, int slot_x, int slot_t);
-int lu_panel_width(int m);   // panel width of launch_lu_solve's blocked form (m: one panel in LDS)
 
 constexpr int HFMI_EIG_MAXN = 16384;     // largest symmetric eigenproblem (hfmi_sym_eig_small / _leading, hfmi_block_gram_eig)
 // symmetric eigensolve for 256 < n <= HFMI_EIG_MAXN: host in, host out.  hfmi_eig_blocked.hip (panel tridiagonalisation on the MFMA, divide

@@ -1,6 +1,6 @@
 // B-orthogonal thin QR of libhfmi.so (include/hfmi.h): repeated (shifted) Cholesky-QR (up to 256 vectors in the fixed small-matrix
 // arena, up to 2048 in the wide one), the reference's Gram-Schmidt rule and the dispatcher between them.  Host side only; kernels
-// live in hfmi_gemm.hip / hfmi_gemm_nn.hip / hfmi_small.hip / hfmi_chol.hip / hfmi_chol_wide.hip.
+// live in hfmi_gemm.hip / hfmi_gemm_nn.hip / hfmi_chol_col.hip / hfmi_chol.hip / hfmi_chol_wide.hip.
 #include <math.h>
 #include <string.h>
 

@@ -489,6 +489,31 @@ HFMI_API int hfmi_plan_predict(int kind, int m, int k, int64_t N, double scale, 
 #define HFMI_EIG_PLAN_INSTANCES 13
 HFMI_API int hfmi_eig_plan_predict(int n, int nvec, int64_t lds_per_block, int64_t defl1_static_lds, int64_t* scalars, int64_t* regions,
                                    int64_t* levels, int64_t* walk);
+/* The launch plan of one call of the one-compute-unit k x k stage (k <= 256: the Cholesky of every Cholesky-QR pass, the Rayleigh-Ritz
+ * eigensolve, the SVD, the LU of the single pass), computed on the host by the planner the launcher itself asks
+ * (csrc/hfmi_small_plan.h): no context and no device.  kind: HFMI_SMALL_PLAN_*; method (EIGH only): 1 = the caller asks for Jacobi.
+ * knobs: HFMI_SMALL_KNOB_WORDS ints, or NULL for the process's own (environment read once, hfmi_tuning_set "chol" / "eig"):
+ *    0 small_threads   1 chol_env (HFMI_CHOL=tile)   2 chol_generic   3 chol_tile   4 jacobi_db   5 jacobi_replay_lds
+ *    6 eig_env (HFMI_EIG=jacobi)   7 tri_waves   8 dc_split_top   9 dc_timing   10 tuning key "chol" (-1: never set)   11 tuning key "eig"
+ * words[HFMI_SMALL_PLAN_WORDS], zero-filled first:
+ *    0 refusal (0: none; 1: k outside 1 .. 256; 2: Jacobi, no instance holds that many blocks per thread)    1 launches
+ *    2 bytes of the workspace    3 regions of the workspace
+ *    4 route (Cholesky: 1 = column-at-a-time kernels, 0 = blocked MFMA kernel; EIGH: 1 = Jacobi, 0 = divide and conquer)
+ *    5 the working matrix is in LDS (column Cholesky, Jacobi, SVD)    6 Jacobi, SVD: k rounded up to even
+ *    7 Jacobi: 2 x 2 blocks per thread; LU: panel width; blocked Cholesky: 16-row blocks
+ *    8, 9, 10 divide and conquer: leading dimension of its matrices, tree levels, 1 = the last merge's product is k_dc_top's
+ *   11 divide and conquer, bit 0: k_dc_top reads the second buffer, bit 1: the eigenvectors end in the second buffer, bit 2: timing
+ *   12 ... 4 launches x 9, in launch order: kernel family (enum small_family of the header), four template parameters, threads, grid,
+ *      dynamic LDS bytes, 1 = the dynamic-LDS attribute is raised to them
+ *   48 ... 12 regions x 2, in layout order (HFMI_DC_REGIONS / HFMI_JACOBI_REGIONS of the header): byte offset, bytes
+ *   72 ... the HFMI_SMALL_KNOB_WORDS knobs the plan was made with */
+#define HFMI_SMALL_PLAN_CHOL 0
+#define HFMI_SMALL_PLAN_EIGH 1
+#define HFMI_SMALL_PLAN_SVD 2
+#define HFMI_SMALL_PLAN_LU 3
+#define HFMI_SMALL_KNOB_WORDS 12
+#define HFMI_SMALL_PLAN_WORDS 84
+HFMI_API int hfmi_small_plan_predict(int kind, int k, int method, const int* knobs, int64_t* words);
 /* The rules of repeated Cholesky-QR (hfmi_borth_qr, the orthogonalisation inside the fused solves; csrc/hfmi_qr_rules.h) for given
  * values, from the functions the loops themselves ask: no context and no device.  policy: what the caller lets the loop leave
  * undone -- CHECKED: every pass's status words are read; DEFERRED: the last pass's R^-1 is left for the caller to fold in; TRUSTED:

@@ -1,4 +1,4 @@
-"""numpy twin of k_lu_solve (hippyflow_amd/csrc/hfmi_small.hip): X = W^-1 Z by right-looking blocked LU with partial
+"""numpy twin of k_lu_solve (hippyflow_amd/csrc/hfmi_lu.hip): X = W^-1 Z by right-looking blocked LU with partial
 pivoting, the right-hand sides carried as extra columns right of W, then back substitution.  Test infrastructure only
 (the CPU suite checks the recurrences here against LAPACK; the GPU suite checks the kernel)."""
 import numpy as np
