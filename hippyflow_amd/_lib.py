@@ -17,6 +17,8 @@ WIDE_MAX_VECTORS = 2048                                # orthogonalize / Borthog
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
 KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
 KERNEL_NO_DIAGONAL = -1                                # HFMI_KERNEL_NO_DIAGONAL: no target of a cross-covariance is a source
+GRID_COV_MAX_NODES = 2048                              # nodes per axis of hfmi_op_kernel_cov_grid (FFTCOV_MAXN of hfmi_fftcov_plan.h)
+FFTCOV_PLAN_WORDS = 96                                 # HFMI_FFTCOV_PLAN_WORDS of include/hfmi.h
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
 PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h
 
@@ -78,6 +80,8 @@ SIGNATURES = {
     "hfmi_op_kernel_cov": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
     "hfmi_op_kernel_cross_cov": [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _PP],
     "hfmi_op_kernel_cov_rows": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_grid": [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
+    "hfmi_fftcov_plan_predict": [C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

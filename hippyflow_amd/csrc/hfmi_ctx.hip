@@ -361,6 +361,20 @@ extern "C" int hfmi_small_plan_predict(int kind, int k, int method, const int* k
   return HFMI_OK;
 }
 
+// the launch plan of the FFT apply of a kernel covariance on a grid, from the planner fftcov_apply asks (hfmi_fftcov_plan.h)
+static_assert(FFTCOV_PLAN_WORDS == HFMI_FFTCOV_PLAN_WORDS, "include/hfmi.h sizes the array of hfmi_fftcov_plan_predict");
+extern "C" int hfmi_fftcov_plan_predict(int d, const int64_t* n, int nvec, int64_t budget_bytes, int64_t* words) {
+  if (!n || !words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_plan_predict: d = %d is not 1, 2 or 3", d);
+  for (int c = 0; c < d; ++c)
+    if (n[c] < 1 || n[c] > FFTCOV_MAXN) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_plan_predict: n[%d] = %lld is not in 1 .. %d", c, (long long)n[c], FFTCOV_MAXN);
+  if (nvec < 0) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_plan_predict: negative number of vectors");
+  fftcov_plan p = fftcov_plan_passes(d, n, false);
+  fftcov_plan_chunks(p, nvec, budget_bytes, fftcov_pairs_knob());
+  fftcov_plan_words(p, words);
+  return HFMI_OK;
+}
+
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
   if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;
@@ -521,6 +535,7 @@ extern "C" int hfmi_tuning_set(const char* key, int value) {
   else if (key && small_knob_set(key, value)) {}
   else if (key && api_tuning_set(key, value)) {}
   else if (key && pchol_tuning_set(key, value)) {}
+  else if (key && fftcov_knob_set(key, value)) {}
   else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
   return HFMI_OK;
 }

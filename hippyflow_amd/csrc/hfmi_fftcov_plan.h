@@ -1,0 +1,192 @@
+// Launch plan of the FFT apply of a kernel covariance on a regular grid (hfmi_op_kernel_cov_grid, hfmi_fftcov.hip).  Host only, plain
+// C++17, nothing from HIP: given the grid and the number of vectors the planner fills a plain struct with the embedding lengths, the
+// pass list (axis, direction, fused multiply, fused scatter / gather), and for every pass the lines a workgroup takes, its threads, its
+// LDS and its grid; and the pairs of columns per chunk of the work buffer from a byte budget.  The launcher plans, then launches what
+// the plan says; hfmi_fftcov_plan_predict (include/hfmi.h) writes the same struct out without a device and tests/test_fftcov_plan_cpu.py
+// holds it to a Python statement of the rules (tests/helpers/fftcov_plan_twin.py).
+//
+// The embedding: axis c of n[c] nodes is padded to P_c = the smallest power of two >= 2 n[c] - 1 (1 when n[c] = 1); the work buffer of
+// one pair of columns is a complex P_0 x P_1 x P_2 array, axis 0 fastest.  The transforms run in place and leave every axis in the
+// digit-reversed order of a decimation-in-frequency FFT; the spectrum is computed by the same passes and is stored in that order, and
+// the inverse passes (decimation in time) take that order and return the natural one: nothing is ever permuted.
+//
+// Passes of an apply in d dimensions (2 d - 1 of them):  forward along axis 0 with the scatter of W fused into its loads, forward
+// along 1 .. d - 2, then ONE pass along axis d - 1 that transforms forward, multiplies by Lambda / P and transforms back while the
+// line sits in LDS, inverse along d - 2 .. 1, and inverse along axis 0 with the gather into Y fused into its stores.  d = 1 is one
+// pass.  What a pass along axis a moves:  the axes below a are in the frequency domain and full (P_b); the axes above a hold data only
+// in their first n_b positions (zero padding before their forward pass, the part nobody reads after their inverse pass), so only
+// those lines exist for the pass.  Along a itself a pass that starts with the forward transform loads n_a entries and fills the
+// rest of the line with zeros in LDS; a pass that ends with the inverse transform stores n_a entries.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+constexpr int FFTCOV_MAXN = 2048;               // nodes per axis: P_c <= 4096, one line fits the LDS of a workgroup
+constexpr int FFTCOV_MAXP = 4096;
+constexpr int FFTCOV_LDS_BYTES = 163840;        // LDS of a workgroup on gfx950, static + dynamic
+constexpr int FFTCOV_MAX_LINES = 256;           // lines per workgroup: the two static tables of k_fftcov_pass (line base, node base)
+constexpr int FFTCOV_STATIC_LDS = 2 * 8 * FFTCOV_MAX_LINES;
+constexpr int FFTCOV_MAX_THREADS = 512;
+constexpr int FFTCOV_MAX_PASSES = 5;
+constexpr int FFTCOV_MAX_PAIRS = 4096;          // pairs per chunk: the y extent of a launch grid
+constexpr int64_t FFTCOV_DEFAULT_BUDGET = (int64_t)512 << 20;   // bytes of work buffer an apply may take unless told otherwise
+constexpr int FFTCOV_ELEMS = 2048;              // complex entries a workgroup aims to hold (short lines: 2048 / L lines)
+constexpr int FFTCOV_STRIDED_ELEMS = 8192;      // ... and may hold so that a strided pass takes 4 adjacent lines (64 contiguous bytes)
+
+enum { FFTCOV_FWD = 1, FFTCOV_MUL = 2, FFTCOV_INV = 4, FFTCOV_SCATTER = 8, FFTCOV_GATHER = 16 };
+
+struct fftcov_pass {
+  int axis, flags;
+  int L, logL;            // line length P_axis
+  int64_t stride;         // entries between consecutive positions of a line: the product of P_b over b < axis
+  int64_t nlines;         // lines of the pass (per pair)
+  int nload, nstore;      // positions of a line that are read (the rest is zero) and written
+  int lpw, loglpw;        // lines per workgroup: consecutive line numbers, i.e. adjacent in memory on a strided axis
+  int ls;                 // entries between lines in LDS (L + padding)
+  int threads;
+  int lds;                // dynamic LDS: lpw * ls entries of 16 bytes + the twiddles max(L / 4, 1)
+  int64_t grid_x;         // ceil(nlines / lpw); the launch is grid_x x pairs-of-the-chunk
+  // line number -> first entry:  inner = line & (stride - 1), o = line / stride, base = inner + (o % oe0) * os0 + (o / oe0) * os1
+  int64_t oe0, os0, os1;
+};
+struct fftcov_plan {
+  int d;
+  int64_t n[3];
+  int P[3];
+  int64_t Ptot;
+  int npasses;
+  fftcov_pass pass[FFTCOV_MAX_PASSES];
+  int twiddles;           // entries of the table: exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
+  int Pmax;
+  int64_t pair_bytes;     // work buffer of one pair: 16 Ptot
+  int pairs;              // ceil(nvec / 2)
+  int chunk_pairs;        // pairs per chunk
+  int nchunks;
+};
+
+// tuning key "fftcov_pairs": pairs per chunk, 0 = from the byte budget.  Results do not depend on it.
+inline int& fftcov_pairs_knob() {
+  static int v = 0;
+  return v;
+}
+inline bool fftcov_knob_set(const char* key, int v) {
+  if (strcmp(key, "fftcov_pairs") || v < 0 || v > FFTCOV_MAX_PAIRS) return false;
+  fftcov_pairs_knob() = v;
+  return true;
+}
+
+inline int fftcov_embed_len(int64_t n) {
+  int P = 1;
+  while (P < 2 * n - 1) P *= 2;
+  return P;
+}
+inline int fftcov_log2(int64_t v) {
+  int l = 0;
+  while (((int64_t)1 << l) < v) ++l;
+  return l;
+}
+
+// one pass along `axis`; ext[b]: positions of axis b > axis that hold data (n_b for an apply, P_b for the spectrum's own transform)
+inline fftcov_pass fftcov_make_pass(const fftcov_plan& p, int axis, int flags, const int64_t* ext, int nload, int nstore) {
+  fftcov_pass q;
+  memset(&q, 0, sizeof(q));
+  q.axis = axis;
+  q.flags = flags;
+  q.L = p.P[axis];
+  q.logL = fftcov_log2(q.L);
+  q.stride = 1;
+  for (int b = 0; b < axis; ++b) q.stride *= p.P[b];
+  const int64_t e1 = axis < 1 ? ext[1] : 1, e2 = axis < 2 ? ext[2] : 1;
+  q.nlines = q.stride * e1 * e2;
+  q.nload = nload;
+  q.nstore = nstore;
+  if (axis == 0) q.oe0 = ext[1], q.os0 = p.P[0], q.os1 = (int64_t)p.P[0] * p.P[1];
+  else if (axis == 1) q.oe0 = ext[2], q.os0 = (int64_t)p.P[0] * p.P[1], q.os1 = 0;
+  else q.oe0 = 1, q.os0 = 0, q.os1 = 0;
+  // lines per workgroup: a power of two, so that a strided group never straddles the inner index when stride >= lpw
+  int lpw = FFTCOV_ELEMS / q.L;
+  if (lpw < 1) lpw = 1;
+  if (q.stride > 1) {
+    int wide = FFTCOV_STRIDED_ELEMS / q.L;
+    if (wide > 4) wide = 4;
+    if (lpw < wide) lpw = wide;
+  }
+  if (lpw > FFTCOV_MAX_LINES) lpw = FFTCOV_MAX_LINES;
+  while (lpw > 1 && lpw / 2 >= q.nlines) lpw /= 2;
+  q.lpw = lpw;
+  q.loglpw = fftcov_log2(lpw);
+  // LDS padding between lines: the loads and stores of a strided pass put lpw adjacent lines side by side, and a power-of-two
+  // line stride would land them on the same banks; 16 / lpw entries of 16 bytes spread lpw lines x 16 / lpw positions over 256 bytes
+  const int pad = lpw == 1 ? 0 : (lpw >= 16 || q.L < 16) ? 1 : 16 / lpw;
+  q.ls = q.L + pad;
+  q.lds = 16 * (lpw * q.ls + (q.L / 4 > 1 ? q.L / 4 : 1));
+  const int64_t items = (int64_t)lpw * q.L / 4;          // radix-4 butterflies of a step
+  int threads = (int)((items + 63) / 64 * 64);
+  if (threads < 64) threads = 64;
+  if (threads > FFTCOV_MAX_THREADS) threads = FFTCOV_MAX_THREADS;
+  q.threads = threads;
+  q.grid_x = (q.nlines + lpw - 1) / lpw;
+  return q;
+}
+
+// the embedding and the passes; spectrum: the d forward passes over the whole padded array that turn the first column into Lambda
+inline fftcov_plan fftcov_plan_passes(int d, const int64_t* n, bool spectrum) {
+  fftcov_plan p;
+  memset(&p, 0, sizeof(p));
+  p.d = d;
+  p.Ptot = 1;
+  p.Pmax = 1;
+  for (int c = 0; c < 3; ++c) {
+    p.n[c] = c < d ? n[c] : 1;
+    p.P[c] = fftcov_embed_len(p.n[c]);
+    p.Ptot *= p.P[c];
+    if (p.P[c] > p.Pmax) p.Pmax = p.P[c];
+  }
+  p.twiddles = p.Pmax / 4 > 1 ? p.Pmax / 4 : 1;
+  p.pair_bytes = 16 * p.Ptot;
+  int64_t ext[3];
+  for (int c = 0; c < 3; ++c) ext[c] = spectrum ? p.P[c] : p.n[c];
+  int np = 0;
+  if (spectrum) {
+    for (int a = 0; a < d; ++a) p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_FWD, ext, p.P[a], p.P[a]);
+  } else {
+    for (int a = 0; a < d - 1; ++a)
+      p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_FWD | (a == 0 ? FFTCOV_SCATTER : 0), ext, (int)p.n[a], p.P[a]);
+    p.pass[np++] = fftcov_make_pass(p, d - 1, FFTCOV_FWD | FFTCOV_MUL | FFTCOV_INV | (d == 1 ? FFTCOV_SCATTER | FFTCOV_GATHER : 0), ext,
+                                    (int)p.n[d - 1], (int)p.n[d - 1]);
+    for (int a = d - 2; a >= 0; --a)
+      p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_INV | (a == 0 ? FFTCOV_GATHER : 0), ext, p.P[a], (int)p.n[a]);
+  }
+  p.npasses = np;
+  return p;
+}
+
+// pairs per chunk: what the budget holds, at least one, at most all and FFTCOV_MAX_PAIRS; forced > 0 (the tuning key) overrides the budget
+inline void fftcov_plan_chunks(fftcov_plan& p, int nvec, int64_t budget_bytes, int forced) {
+  p.pairs = (nvec + 1) / 2;
+  if (budget_bytes <= 0) budget_bytes = FFTCOV_DEFAULT_BUDGET;
+  int64_t c = forced > 0 ? forced : budget_bytes / p.pair_bytes;
+  if (c > FFTCOV_MAX_PAIRS) c = FFTCOV_MAX_PAIRS;
+  if (c > p.pairs) c = p.pairs;
+  if (c < 1) c = 1;
+  p.chunk_pairs = (int)c;
+  p.nchunks = p.pairs > 0 ? (p.pairs + p.chunk_pairs - 1) / p.chunk_pairs : 0;
+}
+
+// ------------------------------------------------------------------ hfmi_fftcov_plan_predict's record
+constexpr int FFTCOV_HEAD_WORDS = 16;
+constexpr int FFTCOV_PASS_WORDS = 16;
+constexpr int FFTCOV_PLAN_WORDS = FFTCOV_HEAD_WORDS + FFTCOV_MAX_PASSES * FFTCOV_PASS_WORDS;
+inline void fftcov_plan_words(const fftcov_plan& p, int64_t* w) {
+  memset(w, 0, sizeof(int64_t) * FFTCOV_PLAN_WORDS);
+  const int64_t head[FFTCOV_HEAD_WORDS] = {p.d, p.P[0], p.P[1], p.P[2], p.Ptot, p.pairs, p.chunk_pairs, p.nchunks,
+                                           p.npasses, p.pair_bytes, p.twiddles, p.Pmax, FFTCOV_STATIC_LDS, 0, 0, 0};
+  memcpy(w, head, sizeof(head));
+  for (int i = 0; i < p.npasses; ++i) {
+    const fftcov_pass& q = p.pass[i];
+    const int64_t v[FFTCOV_PASS_WORDS] = {q.axis, q.flags, q.L, q.stride, q.nlines, q.nload, q.nstore, q.lpw,
+                                          q.ls, q.threads, q.lds, q.lds + FFTCOV_STATIC_LDS, q.grid_x, q.oe0, q.os0, q.os1};
+    memcpy(w + FFTCOV_HEAD_WORDS + i * FFTCOV_PASS_WORDS, v, sizeof(v));
+  }
+}

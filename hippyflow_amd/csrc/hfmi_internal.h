@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hfmi.h"
+#include "hfmi_fftcov_plan.h"
 #include "hfmi_qr_rules.h"
 #include "hfmi_small_plan.h"
 #include "hfmi_tsgemm_plan.h"
@@ -214,7 +215,8 @@ struct hfmi_csr {
   int cheb_state;
 };
 
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS };
+struct fftcov_state;
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID };
 
 struct hfmi_op {
   hfmi_ctx* ctx;
@@ -242,6 +244,7 @@ struct hfmi_op {
   double* kc_t;
   int64_t kc_M, kc_diag;
   bool kc_slab;
+  fftcov_state* fc;      // OP_KERNEL_COV_GRID: the grid, the node map, Lambda, the twiddles and the work buffer (owned; hfmi_fftcov.hip)
   hfmi_host_apply_fn host_fn;
   void* host_user;
   int64_t host_N;
@@ -294,6 +297,14 @@ int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int fami
 int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
                             int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
                             int64_t ldy, int nvec, int accumulate);
+
+// Kernel covariance on a regular grid by FFT (hfmi_fftcov.hip; plans: hfmi_fftcov_plan.h).  create checks the arguments, uploads the
+// node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy frees what create made (the caller synchronised)
+int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
+                  double ell, double nugget, fftcov_state** out);
+int64_t fftcov_points(const fftcov_state* st);
+int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
+void fftcov_destroy(fftcov_state* st);
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

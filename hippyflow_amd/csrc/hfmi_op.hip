@@ -173,6 +173,20 @@ extern "C" int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points,
   *out = op;
   return HFMI_OK;
 }
+extern "C" int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                       int family, double sigma, double ell, double nugget, hfmi_op** out) {
+  if (!ctx || !n || !h || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget));
+  hfmi_op* op = op_new(ctx, OP_KERNEL_COV_GRID);
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  const int s = fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, &op->fc);
+  if (s != HFMI_OK) {
+    delete op;
+    return s;
+  }
+  *out = op;
+  return HFMI_OK;
+}
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
   if (!ctx || !M || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   hfmi_op* op = op_new(ctx, OP_CSR);
@@ -259,8 +273,9 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
   if (!op) return HFMI_OK;
-  if (op->gamma_inv || op->weights || op->kc_x || op->kc_t) {
+  if (op->gamma_inv || op->weights || op->kc_x || op->kc_t || op->fc) {
     (void)hipStreamSynchronize(op->ctx->stream);
+    if (op->fc) fftcov_destroy(op->fc);
     if (op->gamma_inv) (void)hipFree(op->gamma_inv);
     if (op->weights) (void)hipFree(op->weights);
     if (op->kc_x) (void)hipFree(op->kc_x);
@@ -466,6 +481,13 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       // Y (+)= C W: the kernel adds into Y itself
       return launch_kernel_cov(ctx, op->kc_x, op->kc_N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget, W->p, W->ld,
                                Y->p, Y->ld, k, beta != 0.0);
+    }
+    case OP_KERNEL_COV_GRID: {
+      const int64_t N = fftcov_points(op->fc);
+      if (N != W->N || N != Y->N)
+        HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)N, (long long)W->N, (long long)Y->N);
+      // Y (+)= C W: the gather of the last pass adds into Y itself
+      return fftcov_apply(ctx, op->fc, W->p, W->ld, Y->p, Y->ld, k, beta != 0.0);
     }
     case OP_KERNEL_CROSS: {
       const int64_t N = op->kc_N, M = op->kc_M;

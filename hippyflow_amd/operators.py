@@ -10,6 +10,7 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``MeanJJTfromDataOperator``                     JJT summed/averaged: modeling/jacobian.py:169-193, activeSubspaceProjector.py:640-645
 * ``npToDeviceOperator``                          npToDolfinOperator, modeling/operatorWrappers.py:19-52 (symmetric case)
 * ``KernelCovarianceOperator``                    the same role for a kernel covariance given by node coordinates, never assembled
+* ``GridKernelCovarianceOperator``                that covariance on the nodes of a regular grid, applied by FFT (hfmi_fftcov.hip)
 * ``KernelCrossCovarianceOperator``               K(T, S) between two point sets (Nystrom extension); ``KernelCovarianceOperator.rows`` /
                                                   ``.sharded``: a row slab of C per rank, completed by the collective's SUM
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
@@ -277,6 +278,82 @@ class KernelCovarianceOperator(DeviceOperator):
         if size > 1 and not _is_null_collective(collective):
             op._attach_sum(collective)
         return op
+
+
+def _check_grid(shape, spacing, nodes, origin, family, ell, nugget):
+    """The argument rules of hfmi_op_kernel_cov_grid that need no device; returns (shape, spacing, nodes or None, origin) as arrays."""
+    if family not in L.KERNEL_FAMILIES:
+        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+    n = np.atleast_1d(np.asarray(shape, dtype=np.int64))
+    if n.ndim != 1 or not 1 <= n.size <= 3:
+        raise ValueError("a grid has 1, 2 or 3 axes, got shape %r" % (shape,))
+    if n.min() < 1 or n.max() > L.GRID_COV_MAX_NODES:
+        raise ValueError("every axis of the grid has 1 .. %d nodes, got %r" % (L.GRID_COV_MAX_NODES, tuple(int(v) for v in n)))
+    h = np.asarray(spacing, dtype=np.float64)
+    h = np.full(n.size, float(h)) if h.ndim == 0 else h
+    if h.shape != n.shape or not np.all(np.isfinite(h)) or not np.all(h > 0.0):
+        raise ValueError("spacing: one positive finite number per axis, got %r" % (spacing,))
+    o = np.zeros(n.size) if origin is None else np.asarray(origin, dtype=np.float64)
+    if o.shape != n.shape or not np.all(np.isfinite(o)):
+        raise ValueError("origin: one finite number per axis, got %r" % (origin,))
+    total = int(np.prod(n))
+    if nodes is not None:
+        nodes = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64))
+        if nodes.ndim != 1 or nodes.size < 1:
+            raise ValueError("nodes: a non-empty 1-D array of grid node indices")
+        if nodes.min() < 0 or nodes.max() >= total:
+            raise ValueError("nodes must lie in 0 .. %d" % (total - 1))
+        if np.unique(nodes).size != nodes.size:
+            raise ValueError("nodes must be distinct")
+    if not float(ell) > 0.0:
+        raise ValueError("the correlation length must be positive")
+    if not float(nugget) >= 0.0:
+        raise ValueError("the nugget must not be negative")
+    return np.ascontiguousarray(n), np.ascontiguousarray(h), nodes, o
+
+
+def grid_node_points(shape, spacing, nodes=None, origin=None):
+    """(N, d) coordinates ``origin + index * spacing`` of grid nodes, axis 0 fastest: node g = i0 + n0 (i1 + n1 i2)."""
+    n = np.atleast_1d(np.asarray(shape, dtype=np.int64))
+    g = np.arange(int(np.prod(n)), dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64)
+    h = np.broadcast_to(np.asarray(spacing, dtype=np.float64), n.shape)
+    o = np.zeros(n.size) if origin is None else np.asarray(origin, dtype=np.float64)
+    pts = np.empty((g.size, n.size))
+    for c in range(n.size):
+        pts[:, c] = o[c] + (g % n[c]) * h[c]
+        g = g // n[c]
+    return pts
+
+
+class GridKernelCovarianceOperator(DeviceOperator):
+    """The kernel covariance of ``KernelCovarianceOperator`` over nodes of a REGULAR grid, applied by FFT (hfmi_fftcov.hip): the matrix is
+    block-Toeplitz with Toeplitz blocks, its circulant embedding is diagonalised by the FFT, and y = C x costs a few streaming passes
+    over the padded grid per pair of vectors instead of 2 N^2 flops per vector -- the same C x up to rounding, not an approximation.
+    ``shape``: nodes per axis (1, 2 or 3 axes of at most 2048 nodes, axis 0 fastest: node g = i0 + n0 (i1 + n1 i2), the numbering of
+    ``workloads.grid_points``); ``spacing``: a number or one per axis; ``nodes``: the grid node of every point (distinct, any order;
+    None = all nodes in order); ``origin``: coordinates of node 0 (only ``.points`` sees it).  ``.shape`` is the operator's (N, N) as
+    for every ``DeviceOperator``; the grid is ``.grid_shape``.  Two vectors ride one complex transform, so a column's result depends
+    on its partner in the last bits; two applies of the same block are bit-identical.  ``matrix_free()`` is the
+    ``KernelCovarianceOperator`` over the same points (what ``pivoted_cholesky`` takes)."""
+
+    def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None):
+        n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget)
+        N = int(np.prod(n)) if nodes is None else int(nodes.size)
+        super().__init__(ctx, N)
+        self.grid_shape = tuple(int(v) for v in n)
+        self.spacing, self.origin, self.nodes = h, o, nodes
+        self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
+        self.points = L.as_f64(grid_node_points(n, h, nodes, o))
+        L.call("hfmi_op_kernel_cov_grid", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes), N,
+               L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget, C.byref(self._op))
+
+    def to_dense(self, rows=None):
+        """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows)
+
+    def matrix_free(self):
+        """The ``KernelCovarianceOperator`` over the same points: 2 N^2 k flops per apply, no padded grid in memory."""
+        return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx)
 
 
 def _is_null_collective(collective):

@@ -30,8 +30,8 @@ from .collectives import CollectiveOperator, MatrixMultCollectiveOperator, NullC
 from . import hostvec as H
 from .multivector import ingest_stream, MatMvMult, MultiVector, mv_to_dense
 from .lowrank import pivoted_cholesky
-from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, KernelCovarianceOperator,
-                        KernelCrossCovarianceOperator, nystrom_extend,
+from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, GridKernelCovarianceOperator,
+                        KernelCovarianceOperator, KernelCrossCovarianceOperator, nystrom_extend,
                         MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
                         SnapshotGramOperator, Solver2Operator, as_device_operator)
@@ -718,10 +718,11 @@ class KLEProjector:
 
     def extend(self, points):
         """The decoder's columns at other ``points`` (an (M, d) array): the Nystrom extension K(points, X) . encoder . diag(1 / d_KLE)
-        of the KLE computed by ``construct_input_subspace('mass' | 'identity')`` from a ``KernelCovarianceOperator`` prior.C.  A
+        of the KLE computed by ``construct_input_subspace('mass' | 'identity')`` from a ``KernelCovarianceOperator`` prior.C (or a
+        ``GridKernelCovarianceOperator``: the cross-covariance is built from its ``.points`` and kernel).  A
         ``MultiVector`` of M rows; at the projector's own nodes (and without a nugget) it reproduces the decoder to the accuracy of the
         eigensolve.  ValueError for 'prior' orthogonality, a covariance that is not a kernel, or before the subspace exists."""
-        if not isinstance(self.C, KernelCovarianceOperator):
+        if not isinstance(self.C, (KernelCovarianceOperator, GridKernelCovarianceOperator)):
             raise ValueError("extend: prior.C must be a KernelCovarianceOperator (got %s)" % type(self.C).__name__)
         if self.R_orthogonal:
             raise ValueError("extend: the Nystrom extension is for 'mass' and 'identity' orthogonality, not 'prior'")
@@ -753,12 +754,14 @@ class KLEProjector:
             raise ValueError("kernel_factor_rank: the factor route gives 'mass' and 'identity' orthogonality, not 'prior'")
         if orthogonality not in ('mass', 'identity'):
             raise ValueError(orthogonality)
-        if not isinstance(self.C, KernelCovarianceOperator):
+        if not isinstance(self.C, (KernelCovarianceOperator, GridKernelCovarianceOperator)):
             raise ValueError("kernel_factor_rank: prior.C must be a KernelCovarianceOperator (got %s)" % type(self.C).__name__)
         if not isinstance(self.M, CsrOperator):
             raise ValueError("kernel_factor_rank: prior.M must be an assembled matrix (it is only a host operator here)")
         M = self.M if orthogonality == 'mass' else None
-        self.kle_factor = pivoted_cholesky(self.C, int(self.kernel_factor_rank))
+        # the factorisation reads entries of C: of a grid operator, through its matrix-free form
+        C_entries = self.C.matrix_free() if isinstance(self.C, GridKernelCovarianceOperator) else self.C
+        self.kle_factor = pivoted_cholesky(C_entries, int(self.kernel_factor_rank))
         self.d_KLE, self.V_KLE, MV = self.kle_factor.eig(self.parameters['rank'], M)
         self.kle_eigenvalue_error_bound = self.kle_factor.eigenvalue_error_bound(M)
         self.M_orthogonal = M is not None

@@ -194,6 +194,35 @@ HFMI_API int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_targets,
  *     of 0 .. N, summed in any order, reproduce the square apply bit for bit. */
 HFMI_API int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, int64_t row0, int64_t nrows, hfmi_op** out);
+/*     the same covariance over nodes of a REGULAR GRID, applied by FFT in O(P log P) per pair of vectors instead of 2 N^2 flops per
+ *     vector (hfmi_fftcov.hip).  The grid has n[0] x ... x n[d-1] nodes, d = 1, 2 or 3, spacing h[c] > 0 along axis c, axis 0 fastest:
+ *     node g = i0 + n[0] (i1 + n[1] i2) (the numbering of hfmi_block_fill_matern32).  Point i of the operator is grid node host_nodes[i]
+ *     (N distinct indices in [0, prod n), any order; copied to the device); NULL = all nodes in order, N = prod n.  The matrix is the
+ *     one hfmi_op_kernel_cov has over those points.  For a stationary kernel it is block-Toeplitz with Toeplitz blocks; embedded in a
+ *     circulant of P_c = the smallest power of two >= 2 n[c] - 1 (1 when n[c] = 1) entries along axis c, with first column
+ *     c[j] = sigma^2 phi(|offset(j)| / ell), offset_c = min(j_c, P_c - j_c) h[c], c[0] += nugget, it is diagonalised by the FFT and the
+ *     product is EXACT up to rounding: scatter W into the zero-padded grid, transform, multiply by Lambda = FFT(c) (real, computed once
+ *     at creation on the device by the same kernels), transform back, gather the nodes into Y.  Two real columns ride one complex
+ *     transform, z = w_j + i w_{j+1}, paired from the first column of the block handed to the apply (a last odd column pairs with
+ *     zeros): a column's result depends on its partner in the last bits.  No atomics: two applies of the same block are bit-identical,
+ *     whatever the tuning key "fftcov_pairs" says.  Block storage contract as every operator.  The operator owns Lambda, the twiddle
+ *     table (built on the host in long double, rounded once) and a work buffer of 16 prod P_c bytes per pair of a chunk.
+ *     HFMI_ERR_INVALID: d outside 1..3, n[c] < 1 or > 2048, h[c] <= 0 or not finite, N < 1, a node out of range or repeated, NULL nodes
+ *     with N != prod n, unknown family, ell <= 0, nugget < 0; at apply, blocks of another length.  HFMI_ERR_HIP with the sizes in the
+ *     message when the work buffer of one pair cannot be allocated.  hfmi_pchol_create refuses this operator. */
+HFMI_API int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
+                                     const int64_t* host_nodes_or_null, int64_t N, int family, double sigma, double ell,
+                                     double nugget, hfmi_op** out);
+/*     its launch plan, from the planner the launcher asks (csrc/hfmi_fftcov_plan.h); no context and no device.  nvec vectors, a work
+ *     buffer budget in bytes (<= 0: the default, 512 MiB); the tuning key "fftcov_pairs" counts as in an apply.
+ *     words[HFMI_FFTCOV_PLAN_WORDS]:  0 d  1-3 P_c  4 prod P_c  5 pairs = ceil(nvec / 2)  6 pairs per chunk  7 chunks  8 passes
+ *     9 bytes of work buffer per pair  10 twiddle entries  11 max P_c  12 static LDS of the pass kernel; then 16 words per pass from
+ *     word 16:  axis, flags (1 forward, 2 multiply, 4 inverse, 8 scatter fused, 16 gather fused), line length, line stride, lines,
+ *     positions loaded, positions stored, lines per workgroup, LDS line stride, threads, dynamic LDS, static + dynamic LDS, grid x
+ *     (grid y = the pairs of the chunk), and the line map oe0, os0, os1:  line l starts at entry
+ *     (l mod stride) + ((l div stride) mod oe0) os0 + ((l div stride) div oe0) os1. */
+#define HFMI_FFTCOV_PLAN_WORDS 96
+HFMI_API int hfmi_fftcov_plan_predict(int d, const int64_t* n, int nvec, int64_t budget_bytes, int64_t* words);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
@@ -618,7 +647,9 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * ("qr_wide_min", 17..257) width from which hfmi_borth_qr takes the wide Cholesky-QR (default 257; lower values let tests compare
  * the two routes at widths both serve);
  * ("pchol_grid", 0..65535) most workgroups per launch of hfmi_pchol_create (0 = what the device holds, default): a small value makes every
- * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits. */
+ * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits;
+ * ("fftcov_pairs", 0..4096) pairs of columns per chunk of the work buffer of hfmi_op_kernel_cov_grid (0 = from the byte budget,
+ * default): results do not depend on it, bit for bit. */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
 /* phases of hfmi_double_pass[_g], accumulated between hfmi_profile_begin and hfmi_profile_end (milliseconds, summed
  * over the solves in the region; device phases by HIP events on the context's stream, the HOST_* legs by the host's
