@@ -140,6 +140,8 @@ SIGNATURES = {
                               C.POINTER(C.c_int64)],
     "hfmi_small_plan_predict": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
     "hfmi_qr_rules_predict": [C.c_int] * 7 + [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int)],
+    "hfmi_cheb_rules_predict": [C.c_double] * 3 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    "hfmi_lanczos_bracket_predict": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_qr_late_verdict_predict": [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _D, _D, C.POINTER(C.c_int)],
     "hfmi_bench_peaks": [_P, _D, _D, _D],
     "hfmi_bench_loaded_peak": [_P, _D, _D],

@@ -7,16 +7,17 @@
 // the right-hand side in and one of the solution out.  Almost all the work is sparse products -- the smoother steps, the
 // residual, restriction R = P^T, prolongation P, A p -- and with lanes across the k columns of one row the gathers of the
 // neighbour rows are contiguous runs (hfmi_cheb.hip's header: 1.5 TB/s for the column-major one-thread-per-row SpMM of the
-// block CG against the row-major step's rate).  A column-major CG (csr_pcg_solve, hfmi_cheb.hip) would transpose to row-major and
+// block CG against the row-major step's rate).  A column-major CG (csr_pcg_solve, hfmi_sparse.hip) would transpose to row-major and
 // back around every V-cycle: four extra passes per iteration on the fine level.  The per-column inner products of CG are
 // the price: they reduce over the row groups of a workgroup in LDS, then over workgroups in a fixed order (deterministic).
 //
 // V-cycle on level l (A_l, P_l: level l+1 -> l, R_l = P_l^T, explicit, so no transposed product is needed):
 //   x = cheb(0, b); r = b - A x; b_{l+1} = R r; x_{l+1} = V_{l+1}(b_{l+1}); x += P x_{l+1}; x = cheb(x, b)
 // cheb(x0, b) is the Chebyshev iteration of hfmi_cheb.hip (launch_cheb_first / launch_cheb_step, one fused kernel per step:
-// D^-1 (b - A x) and the three-term update) of degree `degree` on [lmin, lmax] of D^-1 A_l; the same polynomial before and
-// after, so the V-cycle is symmetric.  Coarsest level: x = A_L^-1 b with the explicit dense inverse (<= 500 rows, one small
-// product).  tests/helpers/amg_vcycle_twin.py is the same sequence in numpy.
+// D^-1 (b - A x) and the three-term update, coefficients from cheb_recurrence of hfmi_spsolve_rules.h) of degree `degree` on
+// [lmin, lmax] of D^-1 A_l; the same polynomial before and after, so the V-cycle is symmetric.  Coarsest level: x = A_L^-1 b
+// with the explicit dense inverse (<= 500 rows, one small product).  tests/helpers/amg_vcycle_twin.py is the same sequence in
+// numpy.
 //
 // Block PCG: independent recurrences per column (alpha_j, beta_j on the device), the V-cycle as preconditioner; a column is
 // done when its recursive residual ||r_j|| <= rel_tol ||b_j||, and the solve when every column is -- then the TRUE residual
@@ -25,12 +26,12 @@
 // block is zero-filled: never NaN, never a silently wrong answer.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "hfmi_internal.h"
+#include "hfmi_rm_dev.h"
 
 struct amg_level {
-  hfmi_csr* A;            // this level's matrix (not owned); its inv_diag is filled at hfmi_amg_create / add_level
+  const hfmi_csr* A;      // this level's matrix (not owned); its Jacobi preconditioner is prepared at hfmi_amg_create / add_level
   const hfmi_csr* P;      // prolongation from level l+1 (n_l x n_{l+1}); null on the coarsest level
   const hfmi_csr* R;      // restriction P^T (n_{l+1} x n_l)
   double lmin, lmax;      // Chebyshev interval of D^-1 A (smoothed levels only)
@@ -45,37 +46,11 @@ struct hfmi_amg {
   double* coarse_inv;     // dense n_L x n_L row-major, device
   int kcap;
   double* pcg[6];         // row-major N x kcap: b, x, r, z, p, Ap
-  double* part;           // per-(column, workgroup) partial sums
+  double* part;           // per-(column, workgroup) partial sums of the reductions (kcap x RM_CHUNKS)
   double* sc;             // device scalars, 8 x kcap
 };
 
 namespace {
-constexpr int AMG_CHUNKS = 1024;   // workgroups of the reduction kernels (fixed: the summation order does not vary)
-
-// thread t of a 256-thread workgroup: row t / k of the workgroup's current group of rows, column t % k (k <= 256); k > 256:
-// one row at a time, the threads stride over its columns (the map of hfmi_cheb.hip)
-struct rm_map {
-  int rows_per_pass, rl, j0, jstep;
-  bool live;
-};
-__device__ __forceinline__ rm_map rm_thread(int k) {
-  rm_map m;
-  if (k <= 256) {
-    m.rows_per_pass = 256 / k;
-    m.rl = threadIdx.x / k;
-    m.j0 = threadIdx.x - m.rl * k;
-    m.jstep = k;
-    m.live = m.rl < m.rows_per_pass;
-  } else {
-    m.rows_per_pass = 1;
-    m.rl = 0;
-    m.j0 = threadIdx.x;
-    m.jstep = 256;
-    m.live = true;
-  }
-  return m;
-}
-
 // Y (nrows x k) = M X (+ Y when ACC): restriction (R_l, ~30 entries a row) and prolongation with correction (P_l)
 template <bool ACC>
 __global__ __launch_bounds__(256) void k_amg_spmm_rm(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
@@ -113,55 +88,6 @@ __global__ __launch_bounds__(256) void k_amg_coarse_rm(const double* __restrict_
   }
 }
 
-// Per-column reductions over a row-major (nrows x k) array pair, one partial per (column, workgroup), in LDS across the
-// row groups of the workgroup in a fixed order.
-//   UPDATE = false:  part = <A_j, B_j>
-//   UPDATE = true:   alpha_j = rz_j / pap_j (0 when pap_j is not > 0 or alpha is not finite: that column is reported by the
-//                    host, and no inf / NaN enters x); X += alpha P, R -= alpha AP; part = <R_j, R_j> (new R)
-template <bool UPDATE>
-__global__ __launch_bounds__(256) void k_amg_colred(int64_t nrows, int k, const double* __restrict__ A, const double* __restrict__ B,
-                                                   double* __restrict__ X, double* __restrict__ R, const double* __restrict__ P,
-                                                   const double* __restrict__ AP, const double* __restrict__ rz,
-                                                   const double* __restrict__ pap, double* __restrict__ part) {
-  __shared__ double sh[256];
-  const rm_map m = rm_thread(k);
-  for (int jb = 0; jb < k; jb += 256) {                // k <= 256: one trip
-    double acc = 0.0;
-    const int j = (k <= 256) ? m.j0 : jb + (int)threadIdx.x;
-    if (m.live && j < k) {
-      double alpha = 0.0;
-      if (UPDATE) {
-        const double pp = pap[j];
-        alpha = pp > 0.0 ? rz[j] / pp : 0.0;
-        if (!std::isfinite(alpha)) alpha = 0.0;
-      }
-      for (int64_t row = (int64_t)blockIdx.x * m.rows_per_pass + m.rl; row < nrows; row += (int64_t)gridDim.x * m.rows_per_pass) {
-        const int64_t e = row * k + j;
-        if (UPDATE) {
-          X[e] += alpha * P[e];
-          const double r = R[e] - alpha * AP[e];
-          R[e] = r;
-          acc += r * r;
-        } else {
-          acc += A[e] * B[e];
-        }
-      }
-    }
-    sh[threadIdx.x] = (m.live && j < k) ? acc : 0.0;
-    __syncthreads();
-    if (k <= 256) {
-      if ((int)threadIdx.x < k) {
-        double s = 0.0;
-        for (int g = 0; g < m.rows_per_pass; ++g) s += sh[g * k + threadIdx.x];
-        part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-      }
-    } else if (j < k) {
-      part[(int64_t)j * gridDim.x + blockIdx.x] = sh[threadIdx.x];
-    }
-    __syncthreads();
-  }
-}
-
 // P = Z + beta_j P, beta_j = rz_new_j / rz_j (0 when rz_j is not > 0: a converged or broken-down column restarts from Z)
 __global__ __launch_bounds__(256) void k_amg_pcg_dir(int64_t nrows, int k, double* __restrict__ P, const double* __restrict__ Z,
                                                     const double* __restrict__ rz_new, const double* __restrict__ rz) {
@@ -176,27 +102,18 @@ __global__ __launch_bounds__(256) void k_amg_pcg_dir(int64_t nrows, int k, doubl
 }
 }  // namespace
 
-static unsigned rm_grid(hfmi_ctx* ctx, int64_t nrows, int k) {
-  const int rows_per_pass = k <= 256 ? 256 / k : 1;
-  int64_t g = (nrows + rows_per_pass - 1) / rows_per_pass;
-  const int64_t cap = (int64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 16;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
+constexpr int AMG_WG_PER_CU = 16;   // cap of rm_grid for the V-cycle's products
 static int launch_amg_spmm(hfmi_ctx* ctx, const hfmi_csr* M, const double* X, double* Y, int k, bool acc) {
   if (acc)
-    hipLaunchKernelGGL((k_amg_spmm_rm<true>), dim3(rm_grid(ctx, M->nrows, k)), dim3(256), 0, ctx->stream, M->indptr, M->indices, M->data, M->nrows, k, X, Y);
+    hipLaunchKernelGGL((k_amg_spmm_rm<true>), dim3(rm_grid(ctx, M->nrows, k, AMG_WG_PER_CU)), dim3(256), 0, ctx->stream, M->indptr, M->indices, M->data, M->nrows, k, X, Y);
   else
-    hipLaunchKernelGGL((k_amg_spmm_rm<false>), dim3(rm_grid(ctx, M->nrows, k)), dim3(256), 0, ctx->stream, M->indptr, M->indices, M->data, M->nrows, k, X, Y);
+    hipLaunchKernelGGL((k_amg_spmm_rm<false>), dim3(rm_grid(ctx, M->nrows, k, AMG_WG_PER_CU)), dim3(256), 0, ctx->stream, M->indptr, M->indices, M->data, M->nrows, k, X, Y);
   HIP_TRY(hipGetLastError());
   return HFMI_OK;
 }
 // out[j] = <A_j, B_j> over row-major (nrows x k) arrays
 static int amg_dots(hfmi_amg* g, const double* A, const double* B, int64_t nrows, int k, double* out) {
-  hipLaunchKernelGGL((k_amg_colred<false>), dim3(AMG_CHUNKS), dim3(256), 0, g->ctx->stream, nrows, k, A, B, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, g->part);
-  HIP_TRY(hipGetLastError());
-  return launch_dots_final(g->ctx, g->part, AMG_CHUNKS, k, out);
+  return launch_rm_coldots(g->ctx, A, B, nrows, k, g->part, out);
 }
 
 static void amg_free_work(hfmi_amg* g) {
@@ -236,7 +153,7 @@ static int amg_reserve(hfmi_amg* g, int k) {
     }
   }
   for (double*& p : g->pcg) HFMI_TRY(amg_alloc(ctx, &p, (size_t)g->lv[0].n * kk));
-  HFMI_TRY(amg_alloc(ctx, &g->part, kk * AMG_CHUNKS));
+  HFMI_TRY(amg_alloc(ctx, &g->part, kk * RM_CHUNKS));
   HFMI_TRY(amg_alloc(ctx, &g->sc, 8 * kk));
   g->kcap = k;
   return HFMI_OK;
@@ -246,24 +163,23 @@ static int amg_reserve(hfmi_amg* g, int k) {
 // finite spare array on return (the pointers may be swapped)
 static int amg_smooth(hfmi_amg* g, amg_level& L, const double* b, double** x, double** t, int k, bool from_zero) {
   hfmi_ctx* ctx = g->ctx;
-  const double theta = 0.5 * (L.lmax + L.lmin), delta = 0.5 * (L.lmax - L.lmin);
-  double rho = delta / theta;
+  cheb_recurrence rec(L.lmin, L.lmax);
   double *cur, *prev;
   if (from_zero) {
     // x_1 = D^-1 b / theta into one array, x_0 = 0 into the other
     cur = *t;
     prev = *x;
-    HFMI_TRY(launch_cheb_first(ctx, b, cur, prev, L.A->inv_diag, L.n, k, 1.0 / theta));
+    HFMI_TRY(launch_cheb_first(ctx, b, cur, prev, L.A->solve.inv_diag, L.n, k, rec.inv_theta()));
   } else {
     // x_1 = x_0 + D^-1 (b - A x_0) / theta (the spare array's old contents are multiplied by c1 = 0)
-    HFMI_TRY(launch_cheb_step(ctx, L.A, b, *x, *t, k, 0.0, 1.0 / theta, false));
+    HFMI_TRY(launch_cheb_step(ctx, L.A, b, *x, *t, k, 0.0, rec.inv_theta(), false));
     cur = *t;
     prev = *x;
   }
   for (int s = 1; s < g->degree; ++s) {
-    const double rho_new = 1.0 / (2.0 * theta / delta - rho);
-    HFMI_TRY(launch_cheb_step(ctx, L.A, b, cur, prev, k, rho_new * rho, 2.0 * rho_new / delta, false));
-    rho = rho_new;
+    double c1, c2;
+    rec.next(&c1, &c2);
+    HFMI_TRY(launch_cheb_step(ctx, L.A, b, cur, prev, k, c1, c2, false));
     std::swap(cur, prev);
   }
   *x = cur;
@@ -277,7 +193,7 @@ static int amg_vcycle_rm(hfmi_amg* g, int l, const double* b, double* xout, int 
   hfmi_ctx* ctx = g->ctx;
   amg_level& L = g->lv[l];
   if (l == (int)g->lv.size() - 1) {
-    hipLaunchKernelGGL(k_amg_coarse_rm, dim3(rm_grid(ctx, L.n, k)), dim3(256), 0, ctx->stream, g->coarse_inv, (int)L.n, k, b, xout);
+    hipLaunchKernelGGL(k_amg_coarse_rm, dim3(rm_grid(ctx, L.n, k, AMG_WG_PER_CU)), dim3(256), 0, ctx->stream, g->coarse_inv, (int)L.n, k, b, xout);
     HIP_TRY(hipGetLastError());
     return HFMI_OK;
   }
@@ -301,13 +217,6 @@ static int amg_check_ready(const hfmi_amg* g) {
 }
 
 // ------------------------------------------------------------------ C ABI
-static int prep_inv_diag(hfmi_ctx* ctx, hfmi_csr* M) {
-  if (!M->inv_diag) {
-    HIP_TRY(hipMalloc((void**)&M->inv_diag, (size_t)M->nrows * sizeof(double)));
-    HFMI_TRY(launch_csr_diag_inv(ctx, M));
-  }
-  return HFMI_OK;
-}
 static bool bracket_ok(double lmin, double lmax) { return std::isfinite(lmin) && std::isfinite(lmax) && lmin > 0.0 && lmax > lmin; }
 
 extern "C" int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, double lmax, int degree, hfmi_amg** out) {
@@ -315,8 +224,7 @@ extern "C" int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, do
   if (A->nrows != A->ncols) HFMI_FAIL(HFMI_ERR_INVALID, "amg_create: matrix must be square");
   if (degree < 1 || degree > 16) HFMI_FAIL(HFMI_ERR_INVALID, "amg_create: Chebyshev degree %d outside 1..16", degree);
   HIP_TRY(hipSetDevice(ctx->device));
-  hfmi_csr* Am = const_cast<hfmi_csr*>(A);
-  HFMI_TRY(prep_inv_diag(ctx, Am));
+  HFMI_TRY(csr_prepare_jacobi(ctx, A));
   hfmi_amg* g = new (std::nothrow) hfmi_amg();
   if (!g) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   g->ctx = ctx;
@@ -326,7 +234,7 @@ extern "C" int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, do
   for (double*& p : g->pcg) p = nullptr;
   g->part = g->sc = nullptr;
   amg_level L = {};
-  L.A = Am;
+  L.A = A;
   L.lmin = lmin;
   L.lmax = lmax;
   L.n = A->nrows;
@@ -344,14 +252,13 @@ extern "C" int hfmi_amg_add_level(hfmi_amg* g, const hfmi_csr* P, const hfmi_csr
               (long long)nf, (long long)P->nrows, (long long)P->ncols, (long long)R->nrows, (long long)R->ncols, (long long)nc,
               (long long)Ac->ncols);
   HIP_TRY(hipSetDevice(g->ctx->device));
-  hfmi_csr* Am = const_cast<hfmi_csr*>(Ac);
-  HFMI_TRY(prep_inv_diag(g->ctx, Am));
+  HFMI_TRY(csr_prepare_jacobi(g->ctx, Ac));
   HIP_TRY(hipStreamSynchronize(g->ctx->stream));
   amg_free_work(g);                               // the level list changes: work arrays are sized again at the next solve
   g->lv.back().P = P;
   g->lv.back().R = R;
   amg_level L = {};
-  L.A = Am;
+  L.A = Ac;
   L.lmin = lmin;
   L.lmax = lmax;
   L.n = nc;
@@ -424,21 +331,12 @@ extern "C" int hfmi_amg_vcycle(hfmi_amg* g, const hfmi_block* B, hfmi_block* X) 
   return HFMI_OK;
 }
 
-static int read_scalars(hfmi_ctx* ctx, const double* dev, size_t count, double* host) {
-  void* pin = nullptr;
-  HFMI_TRY(ctx_pinned(ctx, count * sizeof(double), &pin));
-  HIP_TRY(hipMemcpyAsync(pin, dev, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  memcpy(host, pin, count * sizeof(double));
-  return HFMI_OK;
-}
-
 static int amg_pcg_core(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
   hfmi_amg* g = op->amg;
   hfmi_ctx* ctx = g->ctx;
   const int k = W->nvec;
   const int64_t N = g->lv[0].n;
-  hfmi_csr* A = g->lv[0].A;
+  const hfmi_csr* A = g->lv[0].A;
   HFMI_TRY(amg_reserve(g, k));
   double *b = g->pcg[0], *x = g->pcg[1], *r = g->pcg[2], *z = g->pcg[3], *p = g->pcg[4], *ap = g->pcg[5];
   double* bb = g->sc;
@@ -455,7 +353,7 @@ static int amg_pcg_core(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
 
   HFMI_TRY(launch_block_to_dense(ctx, W->p, W->ld, b, N, k));
   HFMI_TRY(amg_dots(g, b, b, N, k, bb));
-  HFMI_TRY(read_scalars(ctx, bb, k, h_bb.data()));
+  HFMI_TRY(read_back(ctx, bb, k, h_bb.data()));
   for (int j = 0; j < k; ++j)
     if (!std::isfinite(h_bb[j])) HFMI_FAIL(HFMI_ERR_NUMERIC, "amg_pcg: non-finite right-hand side in vector %d", j);
   for (int j = 0; j < k; ++j) conv[j] = !(h_bb[j] > 0.0);                  // a zero right-hand side is solved by x = 0
@@ -476,10 +374,8 @@ static int amg_pcg_core(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
     ++it;
     HFMI_TRY(launch_amg_spmm(ctx, A, p, ap, k, false));                       // ap = A p
     HFMI_TRY(amg_dots(g, p, ap, N, k, pap));
-    hipLaunchKernelGGL((k_amg_colred<true>), dim3(AMG_CHUNKS), dim3(256), 0, ctx->stream, N, k, nullptr, nullptr, x, r, p, ap, rz, pap, g->part);
-    HIP_TRY(hipGetLastError());
-    HFMI_TRY(launch_dots_final(ctx, g->part, AMG_CHUNKS, k, rr));
-    HFMI_TRY(read_scalars(ctx, pr, 3 * (size_t)k, h_pr.data()));
+    HFMI_TRY(launch_rm_cg_update(ctx, N, k, x, r, p, ap, rz, pap, g->part, rr));
+    HFMI_TRY(read_back(ctx, pr, 3 * (size_t)k, h_pr.data()));
     bool done = true;
     for (int j = 0; j < k; ++j) {
       const double pp = h_pr[j], rj = h_pr[k + j], rzj = h_pr[2 * k + j];
@@ -500,7 +396,7 @@ static int amg_pcg_core(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
         // b - A x to rel_tol, and the recursive residual -- what PETSc's CG tests too -- decides.
         HFMI_TRY(launch_cheb_step(ctx, A, b, x, r, k, 0.0, 0.0, true));      // r = b - A x
         HFMI_TRY(amg_dots(g, r, r, N, k, rr));
-        HFMI_TRY(read_scalars(ctx, rr, k, h_pr.data() + k));
+        HFMI_TRY(read_back(ctx, rr, k, h_pr.data() + k));
         for (int j = 0; j < k; ++j) {
           conv[j] = h_pr[k + j] <= tol2 * h_bb[j];
           if (!conv[j]) ok = false;
@@ -518,7 +414,7 @@ static int amg_pcg_core(hfmi_op* op, const hfmi_block* W, hfmi_block* Y) {
     HFMI_TRY(amg_vcycle_rm(g, 0, r, z, k));                                   // z = V r
     HFMI_TRY(amg_dots(g, r, z, N, k, rz_new));
     HIP_TRY(hipMemcpyAsync(rzc, rz_new, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_amg_pcg_dir, dim3(rm_grid(ctx, N, k)), dim3(256), 0, ctx->stream, N, k, p, z, rz_new, rz);
+    hipLaunchKernelGGL(k_amg_pcg_dir, dim3(rm_grid(ctx, N, k, AMG_WG_PER_CU)), dim3(256), 0, ctx->stream, N, k, p, z, rz_new, rz);
     HIP_TRY(hipGetLastError());
     std::swap(rz, rz_new);
   }

@@ -1,8 +1,230 @@
-// Micro-benchmark entry points of libhfmi.so (include/hfmi.h) behind bench.py and the parity tests.  Host side only.
+// Micro-benchmarks of libhfmi.so (include/hfmi.h) behind bench.py and the parity tests: the peak kernels that measure the roofline
+// denominators in the same job, and the entry points that time or replay single contractions.
 #include <string.h>
 
 #include "hfmi_dgemm.h"
 #include "hfmi_internal.h"
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------ micro-benchmarks (roofline denominators)
+__global__ __launch_bounds__(256, 2) void k_bench_mfma(double* out, int iters) {
+  d4 acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = d4{0.0, 0.0, 0.0, 0.0};
+  double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+  if (s == 123.456) out[0] = s;
+}
+__global__ __launch_bounds__(256, 2) void k_bench_fma(double* out, int iters) {
+  double acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = threadIdx.x * 1e-9 + i;
+  const double a = 1.0000001, b = 1e-9;
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = fma(acc[i], a, b);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s += acc[i];
+  if (s == 123.456) out[0] = s;
+}
+__global__ void k_bench_copy(const d2* __restrict__ src, d2* __restrict__ dst, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
+}
+int launch_bench_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* fma_tflops, double* copy_gbs) {
+  void* buf = nullptr;
+  const size_t bytes = (size_t)2 << 30;  // 1 GiB read + 1 GiB write per copy
+  HFMI_TRY(ctx_ws(ctx, WS_STAGE, bytes, &buf));
+  double* out = (double*)buf;
+  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  float ms = 0.f;
+  // fp64 MFMA: 4 waves/CU (one per SIMD) x 8 independent accumulators
+  const int it1 = 2000, g1 = cus * 16;
+  hipLaunchKernelGGL(k_bench_mfma, dim3(g1), dim3(256), 0, ctx->stream, out, 100);
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  hipLaunchKernelGGL(k_bench_mfma, dim3(g1), dim3(256), 0, ctx->stream, out, it1);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *mfma_tflops = (double)g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
+  // fp64 vector FMA: 8 waves/CU x 16 independent chains
+  const int it2 = 2000, g2 = cus * 32;
+  hipLaunchKernelGGL(k_bench_fma, dim3(g2), dim3(256), 0, ctx->stream, out, 100);
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  hipLaunchKernelGGL(k_bench_fma, dim3(g2), dim3(256), 0, ctx->stream, out, it2);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *fma_tflops = (double)g2 * 256 * it2 * 16 * 2.0 / (ms * 1e-3) / 1e12;
+  // HBM copy
+  const int64_t n = (int64_t)(bytes / 2 / sizeof(d2));
+  d2* src = (d2*)buf;
+  d2* dst = src + n;
+  hipLaunchKernelGGL(k_bench_copy, dim3(cus * 8), dim3(256), 0, ctx->stream, src, dst, n);
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int rep = 0; rep < 5; ++rep) hipLaunchKernelGGL(k_bench_copy, dim3(cus * 8), dim3(256), 0, ctx->stream, src, dst, n);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *copy_gbs = 5.0 * (double)bytes / (ms * 1e-3) / 1e9;
+  return HFMI_OK;
+}
+
+// The same loop on FULL-MANTISSA operands: every lane holds eight Gaussian values per operand, and each MFMA of an iteration takes
+// another pair of them (the register pairs rotate through the eight accumulators), so operand and accumulator bits toggle like
+// those of the solve's contractions on Gaussian data.  The constant-operand loop above multiplies 1 +- tid 1e-9: almost no
+// toggling, a clock (2.35-2.40 GHz) that random data does not see under the power limit (MI355X_MICROARCH.md, "DVFS give-back").
+__global__ __launch_bounds__(256, 2) void k_bench_mfma_rand(const double* __restrict__ vals, double* out, int iters) {
+  d4 acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = d4{0.0, 0.0, 0.0, 0.0};
+  double a[8], b[8];
+  const double* src = vals + ((size_t)blockIdx.x % 64) * 4096 + threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    a[i] = src[256 * i];
+    b[i] = src[256 * (8 + i)];
+  }
+  for (int it = 0; it < iters; it += 8) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(i + r) & 7], b[(i + 3 * r) & 7], acc[i], 0, 0, 0);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+  if (s == 123.456) out[0] = s;
+}
+__global__ void k_bench_copy_loop(const d2* __restrict__ src, d2* __restrict__ dst, int64_t n, int reps) {
+  for (int rep = 0; rep < reps; ++rep)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+      __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
+}
+// The fp64 MFMA rate this box sustains WHILE HBM is being streamed: the constant-operand MFMA loop on the context's stream with
+// the copy kernel running beside it on the auxiliary stream (two workgroups per CU, ~3 TB/s).  The big contractions of the
+// solve run in exactly that regime (their clock is set by the power limit), so this, not the cold
+// micro-benchmark, is the in-job ceiling their fraction should be read against.
+int launch_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_tflops, double* copy_gbs) {
+  void* buf = nullptr;
+  const size_t bytes = (size_t)2 << 30;
+  HFMI_TRY(ctx_ws(ctx, WS_STAGE, bytes + 4096, &buf));
+  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  const int64_t n = (int64_t)(bytes / 2 / sizeof(d2));
+  d2* src = (d2*)buf;
+  d2* dst = src + n;
+  double* out = (double*)(dst + n);
+  hipEvent_t c0, c1;
+  HIP_TRY(hipEventCreate(&c0));
+  HIP_TRY(hipEventCreate(&c1));
+  const int it1 = 2000, g1 = cus * 16, copies = 24, reps = 3;
+  hipLaunchKernelGGL(k_bench_mfma, dim3(g1), dim3(256), 0, ctx->stream, out, 100);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipEventRecord(c0, ctx->aux_stream));
+  // ONE resident launch (its workgroups keep their slots beside the MFMA waves), four workgroups per CU
+  hipLaunchKernelGGL(k_bench_copy_loop, dim3(cus * 4), dim3(256), 0, ctx->aux_stream, src, dst, n, copies);
+  HIP_TRY(hipEventRecord(c1, ctx->aux_stream));
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int rep = 0; rep < reps; ++rep) hipLaunchKernelGGL(k_bench_mfma, dim3(g1), dim3(256), 0, ctx->stream, out, it1);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventSynchronize(c1));
+  float ms = 0.f, msc = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&msc, c0, c1));
+  (void)hipEventDestroy(c0);
+  (void)hipEventDestroy(c1);
+  *mfma_tflops = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
+  *copy_gbs = (double)copies * (double)bytes / (msc * 1e-3) / 1e9;   // over the whole copy window (part of it runs alone)
+  return HFMI_OK;
+}
+
+// read-only stream: what a contraction that only READS its big operand can get from HBM (the copy above also writes)
+__global__ __launch_bounds__(256) void k_bench_read(const d2* __restrict__ src, double* out, int64_t n) {
+  double s = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * 256 * 8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 * 8 + threadIdx.x; i + 7 * 256 < n; i += stride) {
+    d2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = src[i + 256 * u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u].x + v[u].y;
+  }
+  if (s == 123.456) out[0] = s;
+}
+int launch_bench_read(hfmi_ctx* ctx, double* read_gbs) {
+  void* buf = nullptr;
+  const size_t bytes = (size_t)2 << 30;
+  HFMI_TRY(ctx_ws(ctx, WS_STAGE, bytes + 4096, &buf));
+  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  const int64_t n = (int64_t)(bytes / sizeof(d2));
+  double* out = (double*)((char*)buf + bytes);
+  float ms = 0.f;
+  hipLaunchKernelGGL(k_bench_read, dim3(cus * 8), dim3(256), 0, ctx->stream, (const d2*)buf, out, n);
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int rep = 0; rep < 5; ++rep) hipLaunchKernelGGL(k_bench_read, dim3(cus * 8), dim3(256), 0, ctx->stream, (const d2*)buf, out, n);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *read_gbs = 5.0 * (double)bytes / (ms * 1e-3) / 1e9;
+  return HFMI_OK;
+}
+
+// fp64 MFMA rate on Gaussian operands: alone, and with the copy kernel streaming HBM beside it (the regime of the solve's big
+// contractions) -- the denominators bench.py reports as roofline.frac_of_in_job_random_operand_peak[_while_streaming]
+int launch_bench_random_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* mfma_tflops_streaming, double* copy_gbs) {
+  void* buf = nullptr;
+  const size_t bytes = (size_t)2 << 30;
+  const size_t nvals = (size_t)64 * 4096;
+  HFMI_TRY(ctx_ws(ctx, WS_STAGE, bytes + 4096 + nvals * sizeof(double), &buf));
+  const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  const int64_t n = (int64_t)(bytes / 2 / sizeof(d2));
+  d2* src = (d2*)buf;
+  d2* dst = src + n;
+  double* out = (double*)(dst + n);
+  double* vals = out + 512;
+  HFMI_TRY(launch_randn(ctx, vals, (int64_t)nvals, 1, (int64_t)nvals, 0x5eedULL, 7u, 1.0));
+  const int it1 = 2000, g1 = cus * 16, copies = 24, reps = 3;
+  float ms = 0.f, msc = 0.f;
+  hipLaunchKernelGGL(k_bench_mfma_rand, dim3(g1), dim3(256), 0, ctx->stream, vals, out, 104);
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int rep = 0; rep < reps; ++rep) hipLaunchKernelGGL(k_bench_mfma_rand, dim3(g1), dim3(256), 0, ctx->stream, vals, out, it1);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *mfma_tflops = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
+  hipEvent_t c0, c1;
+  HIP_TRY(hipEventCreate(&c0));
+  HIP_TRY(hipEventCreate(&c1));
+  HIP_TRY(hipEventRecord(c0, ctx->aux_stream));
+  hipLaunchKernelGGL(k_bench_copy_loop, dim3(cus * 4), dim3(256), 0, ctx->aux_stream, src, dst, n, copies);
+  HIP_TRY(hipEventRecord(c1, ctx->aux_stream));
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int rep = 0; rep < reps; ++rep) hipLaunchKernelGGL(k_bench_mfma_rand, dim3(g1), dim3(256), 0, ctx->stream, vals, out, it1);
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventSynchronize(c1));
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&msc, c0, c1));
+  (void)hipEventDestroy(c0);
+  (void)hipEventDestroy(c1);
+  *mfma_tflops_streaming = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
+  *copy_gbs = (double)copies * (double)bytes / (msc * 1e-3) / 1e9;
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ entry points
 
 extern "C" int hfmi_bench_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, int nsplit, int reps, double* host_C, double* avg_ms) {
   if (!A || !B) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");

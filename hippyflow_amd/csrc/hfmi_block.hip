@@ -299,12 +299,10 @@ extern "C" int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int6
   m->nrows = nrows;
   m->ncols = ncols;
   m->nnz = nnz;
-  m->inv_diag = nullptr;
   m->ell_w = 0;
   m->ell_idx = nullptr;
   m->ell_val = nullptr;
-  m->gersh_lmax = m->cheb_lmin = m->cheb_lmax = 0.0;
-  m->cheb_state = 0;
+  m->solve = {};            // nothing prepared, nothing estimated
   if (nrows == ncols) {
     // Gershgorin bound on the spectrum of D^-1 A: max_i sum_j |a_ij| / a_ii (used by the Chebyshev solve; 0 = no bound: a
     // row without a positive diagonal entry)
@@ -319,7 +317,7 @@ extern "C" int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int6
       if (!(dii > 0.0)) ok = false;
       else g = std::max(g, sum / dii);
     }
-    m->gersh_lmax = ok ? g : 0.0;
+    m->solve.gersh_lmax = ok ? g : 0.0;
   }
   {
     // ELL image when the longest row is short and the padding stays below 1.5x (FEM mass / stiffness matrices)
@@ -358,7 +356,7 @@ extern "C" int hfmi_csr_destroy(hfmi_csr* m) {
   (void)hipFree(m->indptr);
   (void)hipFree(m->indices);
   (void)hipFree(m->data);
-  if (m->inv_diag) (void)hipFree(m->inv_diag);
+  if (m->solve.inv_diag) (void)hipFree(m->solve.inv_diag);
   if (m->ell_idx) (void)hipFree(m->ell_idx);
   if (m->ell_val) (void)hipFree(m->ell_val);
   delete m;

@@ -361,6 +361,35 @@ extern "C" int hfmi_small_plan_predict(int kind, int k, int method, const int* k
   return HFMI_OK;
 }
 
+// the rules of the sparse SPD solves, from the functions cheb_solve, amg_smooth and launch_cheb_step ask (hfmi_spsolve_rules.h)
+static_assert(CHEB_RULES_WORDS == HFMI_CHEB_RULES_WORDS, "include/hfmi.h sizes the array of hfmi_cheb_rules_predict");
+extern "C" int hfmi_cheb_rules_predict(double lmin, double lmax, double rel_tol, int max_iter, int64_t nrows, int k, int resid, const int* knobs,
+                                       int nsteps, double* coef, int64_t* words) {
+  if (!words || (nsteps > 0 && !coef)) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (!(lmin > 0.0) || !(lmax >= lmin) || nrows < 1 || k < 1 || nsteps < 0) HFMI_FAIL(HFMI_ERR_INVALID, "cheb_rules_predict: bad argument");
+  const spsolve_knobs kn = knobs ? spsolve_knobs_make(knobs[0], knobs[1], knobs[2]) : spsolve_knobs_ref();
+  cheb_rules_words(cheb_solve_plan(lmin, lmax, rel_tol, max_iter), cheb_step_plan(nrows, k, resid != 0, kn), kn, words);
+  cheb_recurrence rec(lmin, lmax);
+  if (coef) {
+    coef[0] = rec.inv_theta();
+    coef[1] = rec.spread() ? 1.0 : 0.0;
+    for (int i = 0; i < nsteps && rec.spread(); ++i) rec.next(coef + 2 + 2 * i, coef + 3 + 2 * i);
+  }
+  return HFMI_OK;
+}
+extern "C" int hfmi_lanczos_bracket_predict(int m, const double* rz, const double* pap, double gersh_lmax, int* refusal, double* values) {
+  if (!refusal || !values || (m > 0 && (!rz || !pap)) || m < 0) HFMI_FAIL(HFMI_ERR_INVALID, "lanczos_bracket_predict: bad argument");
+  lanczos_run run;
+  bool spd = true;
+  for (int i = 0; i < m && spd; ++i) spd = run.push(rz[i], pap[i], rz[i + 1]);
+  cheb_bracket br = lanczos_bracket(run.alpha, run.beta, gersh_lmax);
+  if (!spd && br.refusal != LANCZOS_NO_GERSHGORIN) br = cheb_bracket{LANCZOS_NOT_SPD, 0.0, 0.0, 0.0, 0.0};   // cheb_estimate's order
+  *refusal = br.refusal;
+  const double v[4] = {br.tmin, br.tmax, br.lmin, br.lmax};
+  memcpy(values, v, sizeof(v));
+  return HFMI_OK;
+}
+
 // the launch plan of the FFT apply of a kernel covariance on a grid, from the planner fftcov_apply asks (hfmi_fftcov_plan.h)
 static_assert(FFTCOV_PLAN_WORDS == HFMI_FFTCOV_PLAN_WORDS, "include/hfmi.h sizes the array of hfmi_fftcov_plan_predict");
 extern "C" int hfmi_fftcov_plan_predict(int d, const int64_t* n, int nvec, int64_t budget_bytes, int64_t* words) {

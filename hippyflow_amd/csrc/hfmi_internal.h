@@ -12,6 +12,7 @@
 #include "hfmi_fftcov_plan.h"
 #include "hfmi_qr_rules.h"
 #include "hfmi_small_plan.h"
+#include "hfmi_spsolve_rules.h"
 #include "hfmi_tsgemm_plan.h"
 
 // ------------------------------------------------------------------ errors
@@ -175,7 +176,7 @@ enum hfmi_tmp_slot {
   TMP_QR_BZ = 4,          // qr_chol / qr_mgs: B Q when the caller wants no BQ
   TMP_QR_SAVE = 5,        // borth_qr(AUTO): the input, for the Gram-Schmidt fall-back
   TMP_QR_WIDE = 6,        // qr_chol_wide: the other half of the Q <- Q R^-1 ping-pong (out of place beyond 256 columns)
-  TMP_KRYLOV_0 = 8,       // csr_pcg_solve and its Chebyshev route (hfmi_cheb.hip): r / row-major b
+  TMP_KRYLOV_0 = 8,       // csr_pcg_solve (hfmi_sparse.hip) and its Chebyshev route (hfmi_cheb.hip): r / row-major b
   TMP_KRYLOV_1 = 9,       //   z / x_0
   TMP_KRYLOV_2 = 10,      //   p / x_1
   TMP_KRYLOV_3 = 11,      //   A p
@@ -201,18 +202,21 @@ struct hfmi_csr {
   int64_t* indptr;
   int32_t* indices;
   double* data;
-  double* inv_diag;  // Jacobi preconditioner (lazy)
   // ELLPACK image (slot-major: entry s of row i at [s * nrows + i]) built at creation when the rows are short and
   // even (FEM matrices): consecutive lanes then read consecutive (index, value) pairs.  ell_w == 0: CSR kernel only.
   int ell_w;
   int32_t* ell_idx;
   double* ell_val;
-  // spectrum of the Jacobi-scaled matrix D^-1 A for the Chebyshev solve (hfmi_cheb.hip): an upper bound from Gershgorin's
-  // circles (computed from the host arrays at creation), a lower bound from the Lanczos matrix of one scalar CG run on the
-  // device (lazily, first solve); cheb_state: 0 = not estimated yet, 1 = usable, -1 = do not use (estimate failed / a solve
-  // did not reach its tolerance)
-  double gersh_lmax, cheb_lmin, cheb_lmax;
-  int cheb_state;
+  // What the solvers learn about the matrix, lazily: the matrix itself is const to them.  inv_diag: the Jacobi preconditioner
+  // (csr_prepare_jacobi).  Spectrum of the Jacobi-scaled matrix D^-1 A for the Chebyshev solve (hfmi_cheb.hip): an upper bound from
+  // Gershgorin's circles (computed from the host arrays at creation), a bracket from the Lanczos matrix of one scalar CG run on
+  // the device (first solve); cheb_state: 0 = not estimated yet, 1 = usable, -1 = do not use (estimate failed / a solve did not
+  // reach its tolerance)
+  mutable struct solve_state {
+    double* inv_diag;
+    double gersh_lmax, cheb_lmin, cheb_lmax;
+    int cheb_state;
+  } solve;
 };
 
 struct fftcov_state;
@@ -255,8 +259,11 @@ struct hfmi_op {
   int comm_op;
   bool reduced_by_panels; // the last apply already reduced its result over the ranks, panel by panel (hfmi_op.hip)
 };
-// Y = M^-1 W for an SPD CSR matrix by Chebyshev iteration, or Jacobi-preconditioned block CG (hfmi_cheb.hip)
+// Y = M^-1 W for an SPD CSR matrix by Chebyshev iteration, or Jacobi-preconditioned block CG (hfmi_sparse.hip)
 int csr_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
+int csr_prepare_jacobi(hfmi_ctx* ctx, const hfmi_csr* M);   // M->solve.inv_diag, made the first time it is asked for
+// the Chebyshev route of csr_pcg_solve (hfmi_cheb.hip); *handled = false: nothing written to Y, the caller runs the block CG
+int cheb_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, bool* handled);
 // Y = A^-1 W by AMG-preconditioned block CG (hfmi_amg.hip); Y zero-filled on error
 int amg_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
 // in-place all-reduce of `count` doubles of device memory on the communicator's context stream (hfmi_comm.hip)
@@ -336,6 +343,14 @@ bool qr_late_stands(const qr_late_buffer* late, int k, bool first_trusted);   //
 int borth_qr(hfmi_block* Q, hfmi_op* B, hfmi_block* BQ, double* host_R, bool want_r, int method, int* passes);
 
 // ------------------------------------------------------------------ kernel launchers (hfmi_misc.hip)
+// 2-D elementwise launch geometry: x over row pairs (16 B per lane), y over vectors (grid-stride)
+static inline dim3 ew_grid(int64_t N, int nvec) {
+  const int64_t pairs = (N + 1) / 2;
+  int64_t gx = (pairs + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  int gy = nvec < 1024 ? nvec : 1024;
+  return dim3((unsigned)gx, (unsigned)gy);
+}
 int launch_fill(hfmi_ctx* ctx, double* p, int64_t N, int nvec, int64_t ld, double value, bool include_pad);
 int launch_zero_pad(hfmi_ctx* ctx, double* p, int64_t N, int nvec, int64_t ld);
 int launch_row_scale(hfmi_ctx* ctx, double* G, int ld, int m, int k, const double* w);
@@ -349,14 +364,31 @@ int launch_philox_raw(hfmi_ctx* ctx, uint32_t* out, int64_t N, int nvec, uint64_
 int launch_dense_to_block(hfmi_ctx* ctx, const double* dense, double* p, int64_t ld, int64_t N, int nvec);
 int launch_block_to_dense(hfmi_ctx* ctx, const double* p, int64_t ld, double* dense, int64_t N, int nvec);
 int launch_block_to_dense_ld(hfmi_ctx* ctx, const double* p, int64_t ld, double* dense, int64_t ldd, int64_t N, int nvec);
-int launch_csr_spmm(hfmi_ctx* ctx, const hfmi_csr* M, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec,
-                    bool accumulate);
-int launch_csr_diag_inv(hfmi_ctx* ctx, hfmi_csr* M);
-// Chebyshev iteration on row-major (nrows x k) work arrays (hfmi_cheb.hip)
+// out[j] = the sum of the nchunks partials of column j, fixed order (device out)
+int launch_dots_final(hfmi_ctx* ctx, const double* part, int nchunks, int nvec, double* out);
+// out[j] = <A_j, B_j> for j < nvec (device out)
+int launch_col_dots(hfmi_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t N, int nvec,
+                    double* out);
+// small q x q (row-major) applied to each sample's q x k slab of G in place: G_i <- Gamma G_i
+int launch_gamma_apply(hfmi_ctx* ctx, double* G, int ldg, int ndata, int q, int k, const double* gamma, int ldgam);
+int launch_gamma_apply_cm(hfmi_ctx* ctx, const double* Gc, double* out, int64_t ld, int ndata, int q, int k, const double* gamma,
+                          int ldgam);
+
+// ------------------------------------------------------------------ Chebyshev iteration and reductions on row-major (nrows x k) arrays (hfmi_cheb.hip)
+unsigned rm_grid(hfmi_ctx* ctx, int64_t nrows, int k, int per_cu);   // a workgroup per group of rows (hfmi_rm_dev.h), at most per_cu a CU
 int launch_cheb_first(hfmi_ctx* ctx, const double* B, double* X1, double* X0, const double* inv_diag, int64_t nrows, int k, double inv_theta);
 int launch_cheb_step(hfmi_ctx* ctx, const hfmi_csr* M, const double* B, const double* Xc, double* Xp, int k, double c1, double c2, bool resid);
-int launch_rm_colsq(hfmi_ctx* ctx, const double* A, int64_t nrows, int k, double* out);
-int launch_dots_final(hfmi_ctx* ctx, const double* part, int nchunks, int nvec, double* out);
+// per-column reductions, fixed summation order; part: k * RM_CHUNKS doubles of the caller's, or null for the context's workspace
+constexpr int RM_CHUNKS = 1024;
+int launch_rm_colsq(hfmi_ctx* ctx, const double* A, int64_t nrows, int k, double* part, double* out);                      // <A_j, A_j>
+int launch_rm_coldots(hfmi_ctx* ctx, const double* A, const double* B, int64_t nrows, int k, double* part, double* out);   // <A_j, B_j>
+// alpha_j = rz_j / pap_j (0 unless pap_j > 0 and alpha_j finite): X += alpha P, R -= alpha AP, rr_j = <R_j, R_j>
+int launch_rm_cg_update(hfmi_ctx* ctx, int64_t nrows, int k, double* X, double* R, const double* P, const double* AP, const double* rz,
+                        const double* pap, double* part, double* rr);
+
+// ------------------------------------------------------------------ sparse products and the kernels of the block CG (hfmi_sparse.hip)
+int launch_csr_spmm(hfmi_ctx* ctx, const hfmi_csr* M, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec,
+                    bool accumulate);
 // Y = M X fused with the per-column dots dots[j] = <X_j, Y_j> (PCG: p . A p); needs the ELL image
 int launch_ell_spmm_dot(hfmi_ctx* ctx, const hfmi_csr* M, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec,
                         double* dots);
@@ -368,9 +400,6 @@ int launch_pcg_update(hfmi_ctx* ctx, double* y, int64_t ldy, double* r, int64_t 
 // p_j = D^-1 r_j + (rz_new_j / rz_j) p_j
 int launch_pcg_direction(hfmi_ctx* ctx, double* p, int64_t ldp, const double* r, int64_t ldr, const double* inv_diag,
                          int64_t N, int nvec, const double* rz_new, const double* rz);
-// out[j] = <A_j, B_j> for j < nvec (device out)
-int launch_col_dots(hfmi_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t N, int nvec,
-                    double* out);
 // per-column updates used by PCG / MGS (coefficients on device)
 // y_j += sign * (num_j / den_j) * x_j   (den may be null -> coefficient num_j)
 int launch_col_axpy_dev(hfmi_ctx* ctx, double* y, int64_t ldy, const double* x, int64_t ldx, int64_t N, int nvec,
@@ -381,10 +410,6 @@ int launch_col_xpby_dev(hfmi_ctx* ctx, double* p, int64_t ldp, const double* z, 
 // z_j = inv_diag .* r_j
 int launch_diag_scale(hfmi_ctx* ctx, double* z, int64_t ldz, const double* r, int64_t ldr, const double* inv_diag,
                       int64_t N, int nvec);
-// small q x q (row-major) applied to each sample's q x k slab of G in place: G_i <- Gamma G_i
-int launch_gamma_apply(hfmi_ctx* ctx, double* G, int ldg, int ndata, int q, int k, const double* gamma, int ldgam);
-int launch_gamma_apply_cm(hfmi_ctx* ctx, const double* Gc, double* out, int64_t ld, int ndata, int q, int k, const double* gamma,
-                          int ldgam);
 
 // ------------------------------------------------------------------ the one-workgroup k x k stage (plans: hfmi_small_plan.h)
 // the dynamic-LDS attribute of a kernel, raised where its plan says so
@@ -437,8 +462,3 @@ int sym_eig_large(hfmi_ctx* ctx, const double* host_T, int n, int sort_by_abs, d
 
 int eig_dgemm_bench(hfmi_ctx* ctx, int M, int N, int K, int ta, int tb, int reps, const double* host_A, const double* host_B,
                     double* host_C, double* avg_ms);
-// micro-benchmarks
-int launch_bench_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* fma_tflops, double* copy_gbs);
-int launch_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_tflops, double* copy_gbs);
-int launch_bench_read(hfmi_ctx* ctx, double* read_gbs);
-int launch_bench_random_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* mfma_tflops_streaming, double* copy_gbs);

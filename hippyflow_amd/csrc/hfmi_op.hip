@@ -227,8 +227,8 @@ extern "C" int hfmi_op_solver_info(const hfmi_op* op, int* iterations, int* meth
   if (!op || op->kind != OP_CSR_PCG) HFMI_FAIL(HFMI_ERR_INVALID, "op_solver_info: not a sparse solver operator");
   if (iterations) *iterations = op->last_iters;
   if (method) *method = op->last_method;
-  if (lmin) *lmin = op->csr->cheb_state == 1 ? op->csr->cheb_lmin : 0.0;
-  if (lmax) *lmax = op->csr->cheb_state == 1 ? op->csr->cheb_lmax : 0.0;
+  if (lmin) *lmin = op->csr->solve.cheb_state == 1 ? op->csr->solve.cheb_lmin : 0.0;
+  if (lmax) *lmax = op->csr->solve.cheb_state == 1 ? op->csr->solve.cheb_lmax : 0.0;
   return HFMI_OK;
 }
 extern "C" int hfmi_op_compose3(hfmi_ctx* ctx, hfmi_op* a, hfmi_op* b, hfmi_op* c, hfmi_op** out) {

@@ -570,6 +570,26 @@ HFMI_API int hfmi_qr_rules_predict(int policy, int has_B, int trust_first, int p
  * R_jj > 100 eps ||z_j||).  *stands = 1: the result stands, 0: the solve is repeated on the checked path. */
 HFMI_API int hfmi_qr_late_verdict_predict(int k, int failed2, int shifted2, double gram_dev2, int first_trusted, int failed1, int shifted1,
                                           const double* norm, const double* rdiag, int* stands);
+/* The rules of the sparse SPD solves (hfmi_op_csr_pcg, the smoother of hfmi_amg_*; csrc/hfmi_spsolve_rules.h) for given values, from the
+ * functions the drivers themselves ask: no context and no device.  [lmin, lmax]: the bracket of the spectrum of D^-1 A; rel_tol,
+ * max_iter: the operator's; a Chebyshev step on nrows x k arrays, resid != 0: the residual launch.  knobs: 3 ints (HFMI_PCG,
+ * HFMI_CHEB_THREADMAP as 0 / 1, HFMI_CHEB_UNR as the integer it was set to), or NULL for the process's own (environment read once).
+ * coef (may be NULL when nsteps = 0): 2 + 2 nsteps doubles -- 1 / theta of the first step, 1.0 when the interval has a width
+ * (lmax - lmin > 1e-12 (lmax + lmin)) else 0.0 (then no (c1, c2) is written), then (c1, c2) of steps 2, 3, ... of the three-term iteration.
+ * words[HFMI_CHEB_RULES_WORDS]:
+ *    0 planned steps   1 route: 0 = Chebyshev, 1 = this matrix is left to the block CG (planned > max_iter or > 200)
+ *    2 rounds (each ends with a look at the true residual)   3 .. 6 steps of round 0 .. 3 (0: not run)
+ *    7 step kernel: 1 = k_cheb_step_wave (one wave per row), 0 = k_cheb_step (one thread per entry)   8 rows per wave   9 workgroups
+ *   10, 11, 12 the knobs the plan was made with (HFMI_CHEB_UNR: anything but 2 and 4 is 1) */
+#define HFMI_CHEB_RULES_WORDS 13
+HFMI_API int hfmi_cheb_rules_predict(double lmin, double lmax, double rel_tol, int max_iter, int64_t nrows, int k, int resid, const int* knobs,
+                                     int nsteps, double* coef, int64_t* words);
+/* The bracket the Chebyshev solve makes of one scalar Jacobi-CG run of m iterations: rz[i] = r.z before iteration i (m + 1 values, the
+ * last one after the last iteration), pap[i] = p.Ap of iteration i; gersh_lmax: Gershgorin's bound on D^-1 A (0: none).
+ * *refusal: 0 = none, 1 = no Gershgorin bound, 2 = p.Ap <= 0 or a non-finite r.z (not SPD), 3 = fewer than 3 iterations,
+ * 4 = smallest Ritz value <= 0, 5 = largest below smallest.  values[4] (refusal 0, 4, 5): the Ritz values tmin, tmax of the Lanczos
+ * matrix by Sturm bisection, and (refusal 0) the bracket lmin = 0.9 tmin, lmax = min(gersh_lmax, 1.05 tmax), never below tmax. */
+HFMI_API int hfmi_lanczos_bracket_predict(int m, const double* rz, const double* pap, double gersh_lmax, int* refusal, double* values);
 /* C (M x N) = op(A) op(B), column-major host operands with their natural leading dimensions (A: ta ? K x M : M x K; B: tb ? N x K : K x N),
  * on the general fp64 MFMA product of the eigensolver: the N x N x N congruence products of the deterministic POD's N-dimensional route
  * (la.eigh of PODProjector.py:812-833 reformulated in the state dimension when the snapshots outnumber it: hippyflow_amd/projectors.py) */

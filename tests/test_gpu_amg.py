@@ -68,6 +68,33 @@ def test_device_vcycle_equals_cpu_twin(ctx, k):
         assert rel(X.to_dense()[:, j], ref[:, j]) <= 1e-12
 
 
+_LU64 = {}
+
+
+@pytest.mark.parametrize("k", [128, 129, 255, 256, 257])
+def test_vcycle_and_solve_at_the_thread_map_boundaries(ctx, k):
+    """The widths at which the smoother's step changes kernel (128 / 129) and the row-major thread map changes shape (256 / 257): the
+    tolerances of test_device_vcycle_equals_cpu_twin and test_amg_solver_accuracy_and_iterations at nx = 64, and the same bytes
+    from a second solve of the same block (the reductions of the block CG sum in a fixed order)."""
+    A, S = solver_for(64)
+    if not _LU64:
+        _LU64["lu"] = spla.splu(A.tocsc())
+    B = np.random.default_rng(k).standard_normal((A.shape[0], k))
+    Bmv, X = hf.MultiVector.from_dense(B), hf.MultiVector(A.shape[0], k)
+    S.vcycle(Bmv, X)
+    ref = twin.vcycle(S.hierarchy(), B)
+    assert rel(X.to_dense(), ref) <= 1e-12
+    for j in range(0, k, max(1, k // 5)):
+        assert rel(X.to_dense()[:, j], ref[:, j]) <= 1e-12
+    Xs = solve(S, B)
+    info = S.info()
+    assert info["method"] == "amg-cg" and 0 < info["iterations"] <= 25, info
+    res = np.linalg.norm(B - A @ Xs, axis=0) / np.linalg.norm(B, axis=0)
+    assert res.max() <= 1e-12, res.max()
+    assert rel(Xs, _LU64["lu"].solve(B)) <= 1e-9
+    assert solve(S, B).tobytes() == Xs.tobytes()
+
+
 # ------------------------------------------------------------------ 5. CsrAMGSolver on A = M + 0.1 K up to N = 2e5
 @pytest.mark.parametrize("nx", [64, 256, 447])
 def test_amg_solver_accuracy_and_iterations(ctx, nx):

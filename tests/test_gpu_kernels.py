@@ -272,6 +272,38 @@ def test_sparse_solver_chebyshev_and_cg_routes(ctx, k):
     assert np.all(np.linalg.norm(res, axis=0) <= 1e-10 * np.linalg.norm(X, axis=0) + 1e-300)
 
 
+_MASS_1500 = {}
+
+
+@pytest.mark.parametrize("k", [128, 129, 255, 256, 257])
+def test_sparse_solver_at_the_thread_map_boundaries(ctx, k):
+    """The widths at which the Chebyshev step changes kernel (wave per row up to 128 even columns) and the row-major thread map
+    changes shape (one row group of <= 256 columns, then strides of 256): the tolerances of
+    test_sparse_solver_chebyshev_and_cg_routes at N = 1500, and the same bytes from a second solve of the same block (the
+    reductions sum in a fixed order)."""
+    import scipy.sparse.linalg as spla
+    N = 1500
+    if not _MASS_1500:
+        _MASS_1500["M"] = _fem(N)[0]
+        _MASS_1500["lu"] = spla.splu(_MASS_1500["M"].tocsc())
+        _MASS_1500["solver"] = hf.CsrPCGSolver(_MASS_1500["M"], rel_tol=1e-13)
+    M, lu, solver = _MASS_1500["M"], _MASS_1500["lu"], _MASS_1500["solver"]
+    rng = np.random.default_rng(k)
+    X = rng.standard_normal((N, k)) * np.exp(rng.standard_normal(k))[None, :]
+    X[:, k // 2] = 0.0
+    Xmv, Z, Z2 = hf.MultiVector.from_dense(X), hf.MultiVector(N, k), hf.MultiVector(N, k)
+    solver.matMvMult(Xmv, Z)
+    info = solver.info()
+    assert info["method"] == "chebyshev" and 20 <= info["iterations"] <= 40
+    Zd = Z.to_dense()
+    res = M @ Zd - X
+    assert np.all(np.linalg.norm(res, axis=0) <= 2e-13 * np.linalg.norm(X, axis=0) + 1e-300)
+    assert not Zd[:, k // 2].any()
+    assert rel(Zd, lu.solve(X)) < 1e-11
+    solver.matMvMult(Xmv, Z2)
+    assert Z2.to_dense().tobytes() == Zd.tobytes()
+
+
 @pytest.mark.parametrize("k", [1, 13, 84])
 def test_csr_irregular_rows_use_the_csr_kernel(ctx, k):
     """A matrix with one dense row and empty rows has no ELL image (padding > 1.5x): SpMM and PCG must take the
