@@ -565,8 +565,17 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_jacobi_svd(const double* __re
   const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
   const int grp = tid >> 4, gl = tid & 15, ngrp = nthr >> 4;
   const int n = (k + 1) & ~1, np = n / 2;
+  // power-of-two scaling to max |entry| in [1, 2), undone on sigma at the end (exact both ways, so U, V and the bits of sigma do
+  // not depend on it): the pair test below multiplies two squared column norms, the FOURTH power of the data, which unscaled
+  // leaves the exponent range for entries beyond 1e+-77 -- every pair then looked orthogonal and R came back unrotated
+  double amax = 0.0;
   for (int i = wave; i < k; i += nw)
-    for (int j = lane; j < k; j += 64) W[j * ldw + i] = R[i * ldr + j];
+    for (int j = lane; j < k; j += 64) amax = fmax(amax, fabs(R[i * ldr + j]));
+  amax = -block_min(-amax, red);
+  int sexp = 0;
+  if (amax > 0.0 && isfinite(amax)) sexp = ilogb(amax);
+  for (int i = wave; i < k; i += nw)
+    for (int j = lane; j < k; j += 64) W[j * ldw + i] = ldexp(R[i * ldr + j], -sexp);
   for (int j = tid; j < n; j += nthr) who[j] = (short)j;
   __syncthreads();
   int sweeps = 0, cur = 0;
@@ -640,7 +649,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_jacobi_svd(const double* __re
     for (int j = 0; j < k; ++j)
       if (sig[j] > ki || (sig[j] == ki && j < i)) ++rank;
     perm[rank] = i;
-    svals[rank] = ki;
+    svals[rank] = ldexp(ki, sexp);
   }
   __syncthreads();
   // left singular vectors U[:, c] = w_perm[c] / sigma  (row-major k x k output)

@@ -71,6 +71,8 @@ extern "C" int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double
   if (!ctx || !host_R || !host_sigma) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   if (k < 1 || k > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "svd_small: k=%d out of range [1,%d]", k, SM_MAXK);
   HIP_TRY(hipSetDevice(ctx->device));
+  for (size_t i = 0; i < (size_t)k * k; ++i)
+    if (!std::isfinite(host_R[i])) HFMI_FAIL(HFMI_ERR_NUMERIC, "svd_small (k=%d): the matrix has non-finite entries", k);
   HFMI_TRY(upload_small(ctx, host_R, k, k, sm_ptr(ctx, SM_T), SM_LD));
   void* dv = nullptr;
   HFMI_TRY(ctx_ws(ctx, WS_G, (size_t)SM_MAXK * sizeof(double), &dv));
@@ -424,22 +426,54 @@ extern "C" int hfmi_sketch_eig(const hfmi_block* P, const hfmi_block* Y, const h
   return sketch_eig_core(P, Y, Ybar, B, &Qw, B ? &BQw : nullptr, r, flags, host_d, U, "sketch_eig");
 }
 
-// np.linalg.solve(W, Z) of the single-pass methods on the device, host in and host out (kernel tests)
-extern "C" int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X) {
-  if (!ctx || !host_W || !host_Z || !host_X) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  if (m < 1 || m > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "small_solve: m=%d out of range [1,%d]", m, SM_MAXK);
+// np.linalg.solve(W, Z) of the single-pass methods on the device, host in and host out (kernel tests): the one body of
+// hfmi_small_solve and hfmi_test_lu_solve.  Upload, k_lu_solve launched as the single pass launches it (same slots; T into the
+// eigensolver's slot when want_T), status words, then whatever the caller asks for -- host_X, host_LU (the factored working copy),
+// host_T (the mp x mp region of the T slot, NaN filled before the launch).  The status is handed back, not judged.
+static int small_copy_out(hfmi_ctx* ctx, int slot, int n, double* host) {
+  std::vector<double> tmp((size_t)n * SM_LD);
+  HFMI_TRY(read_back(ctx, sm_ptr(ctx, slot), tmp.size(), tmp.data()));
+  for (int i = 0; i < n; ++i) memcpy(host + (size_t)i * n, tmp.data() + (size_t)i * SM_LD, (size_t)n * sizeof(double));
+  return HFMI_OK;
+}
+static int lu_solve_host(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, bool want_T, hfmi_status_words* st,
+                         double* host_X, double* host_LU, double* host_T) {
   HIP_TRY(hipSetDevice(ctx->device));
   HFMI_TRY(upload_small(ctx, host_W, m, m, sm_ptr(ctx, SM_GRAM), SM_LD));
   HFMI_TRY(upload_small(ctx, host_Z, m, m, sm_ptr(ctx, SM_R), SM_LD));
-  HFMI_TRY(launch_lu_solve(ctx, m, SM_GRAM, SM_R, SM_TMP, SM_TMP2, -1));
+  const int mp = (int)round_up(m, 16) < SM_LD ? (int)round_up(m, 16) : SM_LD;
+  if (want_T) {
+    const std::vector<double> nan_fill((size_t)mp * SM_LD, std::nan("7"));
+    HFMI_TRY(upload_small(ctx, nan_fill.data(), mp, SM_LD, sm_ptr(ctx, SM_T), SM_LD));
+  }
+  HFMI_TRY(launch_lu_solve(ctx, m, SM_GRAM, SM_R, SM_TMP, SM_TMP2, want_T ? SM_T : -1));
+  HFMI_TRY(read_status(ctx, st));
+  if (host_X) HFMI_TRY(small_copy_out(ctx, SM_TMP2, m, host_X));
+  if (host_LU) HFMI_TRY(small_copy_out(ctx, SM_TMP, m, host_LU));
+  if (want_T && host_T) HFMI_TRY(small_copy_out(ctx, SM_T, mp, host_T));
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_small_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, double* host_X) {
+  if (!ctx || !host_W || !host_Z || !host_X) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (m < 1 || m > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "small_solve: m=%d out of range [1,%d]", m, SM_MAXK);
   hfmi_status_words st;
-  HFMI_TRY(read_status(ctx, &st));
+  HFMI_TRY(lu_solve_host(ctx, host_W, host_Z, m, false, &st, nullptr, nullptr, nullptr));
   if (st.failed == 1) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): non-finite input", m);
   if (st.failed == 3) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): the elimination overflowed (non-finite pivot or solution)", m);
   if (st.failed) HFMI_FAIL(HFMI_ERR_NUMERIC, "small_solve (m=%d): the matrix is singular (min |pivot| %.2e, max |pivot| %.2e)", m,
                            st.min_pivot_ratio, st.gram_dev);
-  std::vector<double> tmp((size_t)m * SM_LD);
-  HFMI_TRY(read_back(ctx, sm_ptr(ctx, SM_TMP2), (size_t)m * SM_LD, tmp.data()));
-  for (int i = 0; i < m; ++i) memcpy(host_X + (size_t)i * m, tmp.data() + (size_t)i * SM_LD, (size_t)m * sizeof(double));
+  return small_copy_out(ctx, SM_TMP2, m, host_X);
+}
+
+extern "C" int hfmi_test_lu_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, int want_T, double* host_X,
+                                  double* host_LU, double* host_status, double* host_T) {
+  if (!ctx || !host_W || !host_Z || !host_X || !host_LU || !host_status || (want_T && !host_T)) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (m < 1 || m > SM_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "test_lu_solve: m=%d out of range [1,%d]", m, SM_MAXK);
+  hfmi_status_words st;
+  HFMI_TRY(lu_solve_host(ctx, host_W, host_Z, m, want_T != 0, &st, host_X, host_LU, host_T));
+  host_status[0] = st.min_pivot_ratio;
+  host_status[1] = st.gram_dev;
+  host_status[2] = st.failed;
   return HFMI_OK;
 }

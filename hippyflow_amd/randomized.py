@@ -275,7 +275,12 @@ def doublePassG(A, B, Binv, Omega, k, s=1, check=False, sort_by_abs=False, use_m
 
 
 def svd_small(R, ctx=None):
-    """np.linalg.svd(R) of a small square matrix on the device (one-sided Jacobi): R = U diag(s) V^T."""
+    """np.linalg.svd(R) of a small square matrix (k <= 256) on the device (one-sided Jacobi): R = U diag(s) V^T, s
+    descending.  V is orthogonal always.  A column of U that belongs to an exactly zero singular value is zero (there is
+    nothing to normalise, as ``orthogonalize`` leaves a zero column of Q); the other columns are orthonormal and
+    (U * s) @ V.T reproduces R.  Singular values are relatively accurate where the data determine them (R = B D with a
+    well-conditioned B).  The result does not depend on the scale of R: 2^e R gives the same U and V and 2^e s, bit for
+    bit.  A non-finite entry raises HfmiError."""
     R = L.as_f64(R)
     k = R.shape[0]
     sv, U, V = np.empty(k), np.empty((k, k)), np.empty((k, k))

@@ -388,7 +388,9 @@ HFMI_API int hfmi_block_gram_eig(const hfmi_block* A, const hfmi_block* B, int s
 
 /* np.linalg.svd(R) of the small factor inside hp.accuracyEnhancedSVD (activeSubspaceProjector.py:813-834,1026):
  * R (host, k x k row-major) = U diag(sigma) V^T, sigma descending; U, V row-major k x k (columns = vectors).
- * One-workgroup one-sided Jacobi in LDS (full relative accuracy of small singular values). */
+ * One-workgroup one-sided Jacobi in LDS (full relative accuracy of small singular values), scaled by a power of two on
+ * entry: 2^e R returns the same U, V and 2^e sigma.  V is orthogonal always; the column of U of an exactly zero
+ * singular value is zero.  HFMI_ERR_NUMERIC for non-finite input. */
 HFMI_API int hfmi_svd_small(hfmi_ctx* ctx, const double* host_R, int k, double* host_sigma, double* host_U, double* host_V);
 
 /* ---------------------------------------------------------------- full solves (a5, a6)
@@ -446,6 +448,14 @@ HFMI_API int hfmi_bench_tsgemm_nn(const hfmi_block* A, const double* host_S, hfm
  * min pivot ratio, || D^-1/2 G D^-1/2 - I ||_F, shifted, failed (R and R^-1 are zero filled when failed). */
 HFMI_API int hfmi_test_chol_wide(hfmi_ctx* ctx, int k, const double* host_G, double shift_rel, double pivot_tol, double* host_R,
                                  double* host_Rinv, double* host_status);
+/* The LU solve kernel behind hfmi_small_solve and the single pass with everything it leaves behind (tests): host_W, host_Z, host_X,
+ * host_LU m x m row-major, m <= 256; host_LU is the factored working copy (L below the diagonal, U on and above it, rows in pivoted
+ * order); host_status[3] = min |pivot|, max |pivot|, failed (0, or 1 / 2 / 3 as hfmi_small_solve reports them).  The status is
+ * returned, never turned into an error.  want_T != 0: the kernel also writes T = (X + X^T) / 2 into the eigensolver's slot as the
+ * single pass has it do, and host_T receives the whole mp x mp (mp = min(round_up(m, 16), 256), row-major) region of that slot,
+ * which is filled with NaNs before the launch -- whatever the kernel does not write shows.  host_T may be NULL when want_T == 0. */
+HFMI_API int hfmi_test_lu_solve(hfmi_ctx* ctx, const double* host_W, const double* host_Z, int m, int want_T, double* host_X,
+                                double* host_LU, double* host_status, double* host_T);
 HFMI_API int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, double scale, double beta, int colmajor, int ldc,
                                  int nsplit, double* host_C);
 /* Plan record: every launch of a contraction kernel (k_tsgemm_tn, k_tsgemm_nn[_res], k_tsgemm_ss[b]) and of a partial-sum

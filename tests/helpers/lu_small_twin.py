@@ -17,13 +17,17 @@ def lu_panel_width(m):
     return ((avail // m) - 1) & ~15
 
 
-def lu_solve_blocked(W, Z, nb=None):
-    """returns (X, min |pivot|, max |pivot|, failed) with the kernel's status rule"""
+def lu_solve_blocked(W, Z, nb=None, full=False):
+    """returns (X, min |pivot|, max |pivot|, failed) with the kernel's status rule; full=True appends (LU, piv): the
+    factored working copy as the kernel leaves it (L below the diagonal, U on and above; a panel's row swaps reach the
+    columns to its RIGHT only, so the L columns of earlier panels keep the rows they had -- lu_factors() sorts that
+    out) and piv[j] = the row swapped with row j at step j.  Non-finite input (failed == 1) has neither: zeros."""
     W = np.asarray(W, dtype=np.float64)
     m = W.shape[0]
     nb = lu_panel_width(m) if nb is None else nb
+    ipiv = np.arange(m)
     if not (np.isfinite(W).all() and np.isfinite(Z).all()):
-        return np.zeros((m, m)), 0.0, 0.0, 1
+        return (np.zeros((m, m)), 0.0, 0.0, 1) + ((np.zeros((m, m)), ipiv) if full else ())
     A = np.hstack([W.copy(), np.asarray(Z, dtype=np.float64).copy()])   # [W | Z]: columns >= m are the right-hand sides
     invd = np.zeros(m)
     pmin, pmax = np.inf, 0.0
@@ -44,6 +48,7 @@ def lu_solve_blocked(W, Z, nb=None):
             pn[jj + 1:, jj + 1:] -= np.outer(l, pn[jj, jj + 1:])
             pn[jj + 1:, jj] = l
         A[j0:, j0:j0 + nbc] = pn                                         # 2. back, swaps on the columns to the right
+        ipiv[j0:j0 + nbc] = j0 + piv
         right = slice(j0 + nbc, 2 * m)
         for jj in range(nbc):
             p = j0 + piv[jj]
@@ -54,10 +59,29 @@ def lu_solve_blocked(W, Z, nb=None):
         if m - j0 > nbc:                                                 # 4. A22 -= L21 U12
             A[j0 + nbc:, right] -= pn[nbc:, :nbc] @ A[j0:j0 + nbc, right]
     X = A[:, m:]
+    extra = (A[:, :m].copy(), ipiv) if full else ()
     for t in range(m - 1, 0, -1):                                        # back substitution, rows scaled at the end
         X[:t] -= np.outer(A[:t, t], X[t] * invd[t])
     X *= invd[:, None]
     if not (np.isfinite(X).all() and np.isfinite(pmin) and np.isfinite(pmax)):
-        return np.zeros((m, m)), pmin, pmax, 3                           # overflow during the elimination
+        return (np.zeros((m, m)), pmin, pmax, 3) + extra                 # overflow during the elimination
     failed = 0 if pmin > m * EPS * pmax else 2
-    return X.copy(), pmin, pmax, failed
+    return (X.copy(), pmin, pmax, failed) + extra
+
+
+def lu_factors(LU, piv, nb=None):
+    """(L, U, perm) with W[perm] = L U from the working copy and the swaps of lu_solve_blocked(full=True) or of the
+    kernel: the swaps of the panels after a column's own are applied to that column of L, which the elimination
+    leaves undone because nobody reads it again."""
+    LU = np.asarray(LU)
+    m = LU.shape[0]
+    nb = lu_panel_width(m) if nb is None else nb
+    L = np.tril(LU, -1)
+    perm = np.arange(m)
+    for j in range(m):
+        p = int(piv[j])
+        if p != j:
+            perm[[j, p]] = perm[[p, j]]
+            done = (j // nb) * nb                                         # columns of the panels before step j's
+            L[[j, p], :done] = L[[p, j], :done]
+    return L + np.eye(m, dtype=LU.dtype), np.triu(LU), perm
