@@ -133,6 +133,8 @@ SIGNATURES = {
     "hfmi_test_tsgemm_tn": [_P, _P, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P],
     "hfmi_test_chol_wide": [_P, C.c_int, _P, C.c_double, C.c_double, _P, _P, _P],
     "hfmi_test_lu_solve": [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P],
+    "hfmi_test_own_fail": [C.c_int, C.c_int],
+    "hfmi_test_own_counts": [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "hfmi_plan_clear": [_P],
     "hfmi_plan_read": [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hfmi_plan_predict": [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,

@@ -36,18 +36,22 @@ struct amg_level {
   const hfmi_csr* R;      // restriction P^T (n_{l+1} x n_l)
   double lmin, lmax;      // Chebyshev interval of D^-1 A (smoothed levels only)
   int64_t n;
-  double *b, *x, *t, *res;  // row-major n x kcap work arrays (level 0: t and res only; coarsest: b and x only)
+  dev_buf<double> b, x, t, res;  // row-major n x kcap work arrays (level 0: t and res only; coarsest: b and x only)
 };
 
 struct hfmi_amg {
-  hfmi_ctx* ctx;
+  ~hfmi_amg() {           // a V-cycle may still be queued
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  hfmi_ctx* ctx = nullptr;
   std::vector<amg_level> lv;
-  int degree;
-  double* coarse_inv;     // dense n_L x n_L row-major, device
-  int kcap;
-  double* pcg[6];         // row-major N x kcap: b, x, r, z, p, Ap
-  double* part;           // per-(column, workgroup) partial sums of the reductions (kcap x RM_CHUNKS)
-  double* sc;             // device scalars, 8 x kcap
+  int degree = 0;
+  dev_buf<double> coarse_inv;   // dense n_L x n_L row-major
+  int kcap = 0;
+  dev_buf<double> pcg[6];       // row-major N x kcap: b, x, r, z, p, Ap
+  dev_buf<double> part;         // per-(column, workgroup) partial sums of the reductions (kcap x RM_CHUNKS)
+  dev_buf<double> sc;           // device scalars, 8 x kcap
 };
 
 namespace {
@@ -117,18 +121,15 @@ static int amg_dots(hfmi_amg* g, const double* A, const double* B, int64_t nrows
 }
 
 static void amg_free_work(hfmi_amg* g) {
-  for (auto& L : g->lv) {
-    for (double** p : {&L.b, &L.x, &L.t, &L.res})
-      if (*p) (void)hipFree(*p), *p = nullptr;
-  }
-  for (double*& p : g->pcg)
-    if (p) (void)hipFree(p), p = nullptr;
-  if (g->part) (void)hipFree(g->part), g->part = nullptr;
-  if (g->sc) (void)hipFree(g->sc), g->sc = nullptr;
+  for (auto& L : g->lv)
+    for (dev_buf<double>* p : {&L.b, &L.x, &L.t, &L.res}) p->reset();
+  for (dev_buf<double>& p : g->pcg) p.reset();
+  g->part.reset();
+  g->sc.reset();
   g->kcap = 0;
 }
-static int amg_alloc(hfmi_ctx* ctx, double** p, size_t count) {
-  HIP_TRY(hipMalloc((void**)p, count * sizeof(double)));
+static int amg_alloc(hfmi_ctx* ctx, dev_buf<double>* p, size_t count) {
+  OWN_TRY(p->alloc(count));
   HIP_TRY(hipMemsetAsync(*p, 0, count * sizeof(double), ctx->stream));   // the smoother's spare array must hold finite values
   return HFMI_OK;
 }
@@ -152,7 +153,7 @@ static int amg_reserve(hfmi_amg* g, int k) {
       HFMI_TRY(amg_alloc(ctx, &L.res, cnt));
     }
   }
-  for (double*& p : g->pcg) HFMI_TRY(amg_alloc(ctx, &p, (size_t)g->lv[0].n * kk));
+  for (dev_buf<double>& p : g->pcg) HFMI_TRY(amg_alloc(ctx, &p, (size_t)g->lv[0].n * kk));
   HFMI_TRY(amg_alloc(ctx, &g->part, kk * RM_CHUNKS));
   HFMI_TRY(amg_alloc(ctx, &g->sc, 8 * kk));
   g->kcap = k;
@@ -229,16 +230,12 @@ extern "C" int hfmi_amg_create(hfmi_ctx* ctx, const hfmi_csr* A, double lmin, do
   if (!g) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   g->ctx = ctx;
   g->degree = degree;
-  g->coarse_inv = nullptr;
-  g->kcap = 0;
-  for (double*& p : g->pcg) p = nullptr;
-  g->part = g->sc = nullptr;
   amg_level L = {};
   L.A = A;
   L.lmin = lmin;
   L.lmax = lmax;
   L.n = A->nrows;
-  g->lv.push_back(L);
+  g->lv.push_back(std::move(L));
   *out = g;
   return HFMI_OK;
 }
@@ -262,7 +259,7 @@ extern "C" int hfmi_amg_add_level(hfmi_amg* g, const hfmi_csr* P, const hfmi_csr
   L.lmin = lmin;
   L.lmax = lmax;
   L.n = nc;
-  g->lv.push_back(L);
+  g->lv.push_back(std::move(L));
   return HFMI_OK;
 }
 
@@ -277,11 +274,10 @@ extern "C" int hfmi_amg_set_coarse(hfmi_amg* g, int n, const double* host_inv) {
   for (int64_t i = 0; i < (int64_t)n * n; ++i)
     if (!std::isfinite(host_inv[i])) HFMI_FAIL(HFMI_ERR_NUMERIC, "amg_set_coarse: non-finite entry in the coarse inverse");
   HIP_TRY(hipSetDevice(g->ctx->device));
-  double* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, (size_t)n * n * sizeof(double)));
+  dev_buf<double> d;
+  OWN_TRY(d.alloc((size_t)n * n));
   HIP_TRY(hipMemcpy(d, host_inv, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
-  if (g->coarse_inv) (void)hipFree(g->coarse_inv);
-  g->coarse_inv = d;
+  g->coarse_inv = std::move(d);
   return HFMI_OK;
 }
 
@@ -294,11 +290,6 @@ extern "C" int hfmi_amg_info(const hfmi_amg* g, int* levels, int64_t* rows, int 
 }
 
 extern "C" int hfmi_amg_destroy(hfmi_amg* g) {
-  if (!g) return HFMI_OK;
-  (void)hipSetDevice(g->ctx->device);
-  (void)hipStreamSynchronize(g->ctx->stream);
-  amg_free_work(g);
-  if (g->coarse_inv) (void)hipFree(g->coarse_inv);
   delete g;
   return HFMI_OK;
 }

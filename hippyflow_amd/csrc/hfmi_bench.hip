@@ -123,9 +123,9 @@ int launch_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_tflops, double* copy_gb
   d2* src = (d2*)buf;
   d2* dst = src + n;
   double* out = (double*)(dst + n);
-  hipEvent_t c0, c1;
-  HIP_TRY(hipEventCreate(&c0));
-  HIP_TRY(hipEventCreate(&c1));
+  hip_event c0, c1;
+  OWN_TRY(c0.create());
+  OWN_TRY(c1.create());
   const int it1 = 2000, g1 = cus * 16, copies = 24, reps = 3;
   hipLaunchKernelGGL(k_bench_mfma, dim3(g1), dim3(256), 0, ctx->stream, out, 100);
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -142,8 +142,6 @@ int launch_bench_loaded_peak(hfmi_ctx* ctx, double* mfma_tflops, double* copy_gb
   float ms = 0.f, msc = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   HIP_TRY(hipEventElapsedTime(&msc, c0, c1));
-  (void)hipEventDestroy(c0);
-  (void)hipEventDestroy(c1);
   *mfma_tflops = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
   *copy_gbs = (double)copies * (double)bytes / (msc * 1e-3) / 1e9;   // over the whole copy window (part of it runs alone)
   return HFMI_OK;
@@ -203,9 +201,9 @@ int launch_bench_random_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* mfma_t
   HIP_TRY(hipEventSynchronize(ctx->ev1));
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   *mfma_tflops = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
-  hipEvent_t c0, c1;
-  HIP_TRY(hipEventCreate(&c0));
-  HIP_TRY(hipEventCreate(&c1));
+  hip_event c0, c1;
+  OWN_TRY(c0.create());
+  OWN_TRY(c1.create());
   HIP_TRY(hipEventRecord(c0, ctx->aux_stream));
   hipLaunchKernelGGL(k_bench_copy_loop, dim3(cus * 4), dim3(256), 0, ctx->aux_stream, src, dst, n, copies);
   HIP_TRY(hipEventRecord(c1, ctx->aux_stream));
@@ -217,8 +215,6 @@ int launch_bench_random_peaks(hfmi_ctx* ctx, double* mfma_tflops, double* mfma_t
   HIP_TRY(hipEventSynchronize(c1));
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   HIP_TRY(hipEventElapsedTime(&msc, c0, c1));
-  (void)hipEventDestroy(c0);
-  (void)hipEventDestroy(c1);
   *mfma_tflops_streaming = (double)reps * g1 * 4 * it1 * 8 * (2.0 * 16 * 16 * 4) / (ms * 1e-3) / 1e12;
   *copy_gbs = (double)copies * (double)bytes / (msc * 1e-3) / 1e9;
   return HFMI_OK;

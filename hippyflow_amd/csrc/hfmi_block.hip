@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 
 #include "hfmi_internal.h"
@@ -17,8 +18,7 @@ extern "C" int hfmi_block_create(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block*
   HFMI_TRY(block_alloc(ctx, N, nvec, &b));
   hipError_t e = hipMemsetAsync(b->p, 0, (size_t)b->ld * nvec * sizeof(double), ctx->stream);
   if (e != hipSuccess) {
-    (void)hipFree(b->p);
-    delete b;
+    (void)hfmi_block_destroy(b);
     HFMI_FAIL(HFMI_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
   }
   *out = b;
@@ -116,20 +116,22 @@ extern "C" int hfmi_block_upload(hfmi_block* b, const double* host, int layout) 
 // not blocked) for everything uploaded so far.
 extern "C" int hfmi_host_alloc_pinned(size_t bytes, void** out) {
   if (!out || bytes == 0) HFMI_FAIL(HFMI_ERR_INVALID, "host_alloc_pinned: bad argument");
-  HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  void* p = nullptr;
+  OWN_TRY(own_acquire(OWN_PINNED, bytes, &p));
+  *out = p;      // the caller's from here: counted, but no owner object
   return HFMI_OK;
 }
 extern "C" int hfmi_host_free_pinned(void* p) {
-  if (p) HIP_TRY(hipHostFree(p));
+  own_release(OWN_PINNED, p);
   return HFMI_OK;
 }
 extern "C" int hfmi_block_upload_async(hfmi_block* b, const double* host_pinned, int layout, int64_t* ticket) {
   if (!b || !host_pinned) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   hfmi_ctx* ctx = b->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->ingest_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->ingest_stream, hipStreamNonBlocking));
-    for (int i = 0; i < HFMI_INGEST_RING; ++i) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_ingest[i], hipEventDisableTiming));
+  if (!ctx->ingest_stream) {      // the ring first: the stream is what says that both exist
+    for (hip_event& e : ctx->ev_ingest) OWN_TRY(e.create(hipEventDisableTiming));
+    OWN_TRY(ctx->ingest_stream.create(hipStreamNonBlocking));
   }
   // the block may still be read by work queued on the compute stream (a view that is being refilled): order behind it
   HIP_TRY(hipEventRecord(ctx->ev_status, ctx->stream));
@@ -146,10 +148,10 @@ extern "C" int hfmi_block_upload_async(hfmi_block* b, const double* host_pinned,
     HFMI_TRY(ctx_ws(ctx, WS_INGEST, (size_t)b->N * b->nvec * sizeof(double), &stage));
     HIP_TRY(hipMemcpyAsync(stage, host_pinned, (size_t)b->N * b->nvec * sizeof(double), hipMemcpyHostToDevice, ctx->ingest_stream));
     HIP_TRY(hipEventRecord(ctx->ev_ingest[slot], ctx->ingest_stream));     // the pinned buffer is free from here
-    hipStream_t saved = ctx->stream;                                        // the launchers enqueue on ctx->stream
-    ctx->stream = ctx->ingest_stream;
+    auto saved = std::move(ctx->stream);                                    // the launchers enqueue on ctx->stream
+    ctx->stream.borrow(ctx->ingest_stream);
     const int s = launch_dense_to_block(ctx, (const double*)stage, b->p, b->ld, b->N, b->nvec);
-    ctx->stream = saved;
+    ctx->stream = std::move(saved);
     if (s != HFMI_OK) return s;
   } else {
     HFMI_FAIL(HFMI_ERR_INVALID, "block_upload_async: unknown layout %d", layout);
@@ -293,16 +295,12 @@ extern "C" int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int6
   for (int64_t z = 0; z < nnz; ++z)
     if (indices[z] < 0 || indices[z] >= ncols) HFMI_FAIL(HFMI_ERR_INVALID, "csr_create: column index out of range");
   HIP_TRY(hipSetDevice(ctx->device));
-  hfmi_csr* m = new (std::nothrow) hfmi_csr();
+  std::unique_ptr<hfmi_csr> m(new (std::nothrow) hfmi_csr());      // nothing prepared, nothing estimated
   if (!m) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   m->ctx = ctx;
   m->nrows = nrows;
   m->ncols = ncols;
   m->nnz = nnz;
-  m->ell_w = 0;
-  m->ell_idx = nullptr;
-  m->ell_val = nullptr;
-  m->solve = {};            // nothing prepared, nothing estimated
   if (nrows == ncols) {
     // Gershgorin bound on the spectrum of D^-1 A: max_i sum_j |a_ij| / a_ii (used by the Chebyshev solve; 0 = no bound: a
     // row without a positive diagonal entry)
@@ -334,31 +332,24 @@ extern "C" int hfmi_csr_create(hfmi_ctx* ctx, int64_t nrows, int64_t ncols, int6
           ev[(size_t)s * nrows + i] = in ? data[b + s] : 0.0;
         }
       }
-      HIP_TRY(hipMalloc((void**)&m->ell_idx, ei.size() * sizeof(int32_t)));
-      HIP_TRY(hipMalloc((void**)&m->ell_val, ev.size() * sizeof(double)));
+      OWN_TRY(m->ell_idx.alloc(ei.size()));
+      OWN_TRY(m->ell_val.alloc(ev.size()));
       HIP_TRY(hipMemcpy(m->ell_idx, ei.data(), ei.size() * sizeof(int32_t), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(m->ell_val, ev.data(), ev.size() * sizeof(double), hipMemcpyHostToDevice));
       m->ell_w = (int)wmax;
     }
   }
-  HIP_TRY(hipMalloc((void**)&m->indptr, (size_t)(nrows + 1) * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&m->indices, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&m->data, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
+  OWN_TRY(m->indptr.alloc((size_t)(nrows + 1)));
+  OWN_TRY(m->indices.alloc((size_t)std::max<int64_t>(nnz, 1)));
+  OWN_TRY(m->data.alloc((size_t)std::max<int64_t>(nnz, 1)));
   HIP_TRY(hipMemcpy(m->indptr, indptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(m->indices, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(m->data, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-  *out = m;
+  *out = m.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_csr_destroy(hfmi_csr* m) {
-  if (!m) return HFMI_OK;
-  (void)hipStreamSynchronize(m->ctx->stream);
-  (void)hipFree(m->indptr);
-  (void)hipFree(m->indices);
-  (void)hipFree(m->data);
-  if (m->solve.inv_diag) (void)hipFree(m->solve.inv_diag);
-  if (m->ell_idx) (void)hipFree(m->ell_idx);
-  if (m->ell_val) (void)hipFree(m->ell_val);
+  if (m) (void)hipStreamSynchronize(m->ctx->stream);     // before the arrays go: a kernel may still read them
   delete m;
   return HFMI_OK;
 }

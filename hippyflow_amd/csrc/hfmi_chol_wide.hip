@@ -233,15 +233,9 @@ int cw_gemm(hfmi_ctx* ctx, int M, int N, int K, double alpha, const double* A, c
 int ctx_wide(hfmi_ctx* ctx, int k) {
   if (k < 1 || k > HFMI_WIDE_MAXK) HFMI_FAIL(HFMI_ERR_INVALID, "wide arena: k=%d out of range [1,%d]", k, HFMI_WIDE_MAXK);
   const int ld = (int)round_up(k, 32);
-  if (ctx->wide && ctx->wide_cap >= ld) return HFMI_OK;
-  if (ctx->wide) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->wide);
-    ctx->wide = nullptr;
-    ctx->wide_cap = 0;
-  }
-  const size_t doubles = (size_t)WA_NSLOTS * ld * ld + wa_tail_doubles(ld);
-  HIP_TRY(hipMalloc((void**)&ctx->wide, doubles * sizeof(double)));
+  const size_t doubles = (size_t)WA_NSLOTS * ld * ld + wa_tail_doubles(ld);      // grows with ld: large enough means laid out for >= ld
+  if (ctx->wide.count() >= doubles) return HFMI_OK;
+  OWN_TRY(grow(ctx->wide, doubles, [&] { return (int)hipStreamSynchronize(ctx->stream); }));
   ctx->wide_cap = ld;
   HIP_TRY(hipMemsetAsync(ctx->wide, 0, doubles * sizeof(double), ctx->stream));
   return HFMI_OK;

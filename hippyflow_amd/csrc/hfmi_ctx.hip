@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <memory>
 #include <new>
 
 #include "hfmi_eig_plan.h"
@@ -37,21 +38,17 @@ extern "C" int hfmi_device_count(int* count) {
 }
 
 // ------------------------------------------------------------------ device memory: pool of released block storage
+// block storage back to the device, once nothing queued on the stream can still use it
+static void storage_free(hfmi_ctx* ctx, void* p) {
+  (void)hipStreamSynchronize(ctx->stream);
+  own_release(OWN_DEVICE, p);
+}
 static void pool_flush(hfmi_ctx* ctx) {
   if (ctx->pool.empty()) return;
   (void)hipStreamSynchronize(ctx->stream);
-  for (auto& e : ctx->pool) (void)hipFree(e.p);
+  for (auto& e : ctx->pool) own_release(OWN_DEVICE, e.p);
   ctx->pool.clear();
   ctx->pool_bytes = 0;
-}
-static hipError_t ctx_malloc(hfmi_ctx* ctx, void** p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess && !ctx->pool.empty()) {      // give the pooled storage back and try once more
-    (void)hipGetLastError();
-    pool_flush(ctx);
-    e = hipMalloc(p, bytes);
-  }
-  return e;
 }
 // storage of a destroyed block: kept for reuse (same stream order as every other use of it) or freed
 void pool_release(hfmi_ctx* ctx, void* p, size_t bytes) {
@@ -61,8 +58,7 @@ void pool_release(hfmi_ctx* ctx, void* p, size_t bytes) {
     ctx->pool_bytes += bytes;
     return;
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(p);
+  storage_free(ctx, p);
 }
 static void* pool_take(hfmi_ctx* ctx, size_t bytes) {
   for (size_t i = ctx->pool.size(); i-- > 0;)
@@ -84,8 +80,13 @@ int block_alloc(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out) {
   b->nvec = nvec;
   b->ld = round_up(N, 32);
   b->owner = true;
-  b->p = (double*)pool_take(ctx, (size_t)b->ld * nvec * sizeof(double));
-  hipError_t e = b->p ? hipSuccess : ctx_malloc(ctx, (void**)&b->p, (size_t)b->ld * nvec * sizeof(double));
+  const size_t bytes = (size_t)b->ld * nvec * sizeof(double);
+  b->p = (double*)pool_take(ctx, bytes);
+  hipError_t e = b->p ? hipSuccess : (hipError_t)own_acquire(OWN_DEVICE, bytes, (void**)&b->p);
+  if (e != hipSuccess && !ctx->pool.empty()) {      // give the pooled storage back and try once more
+    pool_flush(ctx);
+    e = (hipError_t)own_acquire(OWN_DEVICE, bytes, (void**)&b->p);
+  }
   if (e != hipSuccess) {
     const double gb = (double)b->ld * nvec * 8 / 1e9;
     delete b;
@@ -114,31 +115,27 @@ int ctx_check_comm(hfmi_ctx* ctx) {
 }
 
 int ctx_ws(hfmi_ctx* ctx, int slot, size_t bytes, void** out) {
-  if (bytes > ctx->ws_bytes[slot]) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  auto& buf = ctx->ws[slot];
+  const auto drain = [&]() -> int {
+    hipError_t e = hipStreamSynchronize(ctx->stream);
     // buffers other streams work in: the panel reductions' staging area (auxiliary stream), the ingest buffer
-    if (slot == WS_COMM) HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-    if (slot == WS_INGEST) HIP_TRY(hipStreamSynchronize(ctx->ingest_stream));
-    if (ctx->ws[slot]) HIP_TRY(hipFree(ctx->ws[slot]));
-    ctx->ws[slot] = nullptr;
-    ctx->ws_bytes[slot] = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    HIP_TRY(ctx_malloc(ctx, &ctx->ws[slot], want));
-    ctx->ws_bytes[slot] = want;
+    if (e == hipSuccess && slot == WS_COMM) e = hipStreamSynchronize(ctx->aux_stream);
+    if (e == hipSuccess && slot == WS_INGEST) e = hipStreamSynchronize(ctx->ingest_stream);
+    return (int)e;
+  };
+  const size_t slack = bytes / 4 + 4096;
+  int e = grow(buf, bytes, drain, slack);
+  if (e != 0 && !ctx->pool.empty()) {      // give the pooled storage back and try once more
+    pool_flush(ctx);
+    e = grow(buf, bytes, drain, slack);
   }
-  *out = ctx->ws[slot];
+  OWN_TRY(e);
+  *out = buf.get();
   return HFMI_OK;
 }
 int ctx_pinned(hfmi_ctx* ctx, size_t bytes, void** out) {
-  if (bytes > ctx->pinned_bytes) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->pinned) HIP_TRY(hipHostFree(ctx->pinned));
-    ctx->pinned = nullptr;
-    ctx->pinned_bytes = 0;
-    HIP_TRY(hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault));
-    ctx->pinned_bytes = bytes;
-  }
-  *out = ctx->pinned;
+  OWN_TRY(grow(ctx->pinned, bytes, [&] { return (int)hipStreamSynchronize(ctx->stream); }));
+  *out = ctx->pinned.get();
   return HFMI_OK;
 }
 
@@ -154,93 +151,48 @@ extern "C" int hfmi_ctx_create(int device, hfmi_ctx** out) {
   HIP_TRY(hipSetDevice(device));
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
-  hfmi_ctx* c = new (std::nothrow) hfmi_ctx();
+  std::unique_ptr<hfmi_ctx> c(new (std::nothrow) hfmi_ctx());
   if (!c) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   c->device = device;
   c->num_cus = prop.multiProcessorCount;
   c->lds_per_block = prop.sharedMemPerBlock;
-  c->defl1_static_lds = 0;
-  c->defl1_static_known = false;
-  c->own_stream = true;
-  c->compose_depth = 0;
-  for (int i = 0; i < WS_NSLOTS; ++i) {
-    c->ws[i] = nullptr;
-    c->ws_bytes[i] = 0;
-  }
-  c->pinned = nullptr;
-  c->pinned_bytes = 0;
-  c->pinned_cb = nullptr;
-  c->pinned_cb_bytes = 0;
-  c->xfer = nullptr;
-  c->pool_bytes = 0;
-  for (int i = 0; i < HFMI_PHASE_COUNT; ++i) c->phase_ms[i] = 0.0;
-  c->profiling = false;
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&c->ev0));
-  HIP_TRY(hipEventCreate(&c->ev1));
-  HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming));
-  for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&c->ev_cb[i], hipEventDisableTiming));
-  for (int i = 0; i < 8; ++i) HIP_TRY(hipEventCreateWithFlags(&c->ev_panel[i], hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  c->ingest_stream = nullptr;
-  c->ingest_seq = 0;
-  c->late_pinned = nullptr;
-  c->wide = nullptr;
-  c->wide_cap = 0;
-  c->nn_hook = nullptr;
-  c->nn_hook_user = nullptr;
-  c->nn_hook_panels = 0;
-  c->nn_hook_called = false;
-  c->nn_upper_hint = false;
-  c->plan_count = 0;
-  HIP_TRY(hipMalloc((void**)&c->small, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double)));
-  HIP_TRY(hipMemsetAsync(c->small, 0, (size_t)SM_NSLOTS * SM_MAXK * SM_LD * sizeof(double), c->stream));
-  HIP_TRY(hipMalloc((void**)&c->status_dev, 2 * sizeof(hfmi_status_words)));      // [1]: a factorisation taken on trust (qr_chol)
-  HIP_TRY(hipMemsetAsync(c->status_dev, 0, 2 * sizeof(hfmi_status_words), c->stream));
-  HIP_TRY(hipHostMalloc((void**)&c->status_host, sizeof(hfmi_status_words), hipHostMallocDefault));
+  OWN_TRY(c->stream.create(hipStreamNonBlocking));
+  OWN_TRY(c->ev0.create());
+  OWN_TRY(c->ev1.create());
+  OWN_TRY(c->aux_stream.create(hipStreamNonBlocking));
+  OWN_TRY(c->ev_status.create(hipEventDisableTiming));
+  OWN_TRY(c->ev_side.create(hipEventDisableTiming));
+  for (hip_event& e : c->ev_cb) OWN_TRY(e.create(hipEventDisableTiming));
+  for (hip_event& e : c->ev_panel) OWN_TRY(e.create(hipEventDisableTiming));
+  OWN_TRY(c->ev_join.create(hipEventDisableTiming));
+  OWN_TRY(c->small.alloc((size_t)SM_NSLOTS * SM_MAXK * SM_LD));
+  HIP_TRY(hipMemsetAsync(c->small, 0, c->small.bytes(), c->stream));
+  OWN_TRY(c->status_words.alloc(2));
+  c->status_dev = c->status_words;
+  HIP_TRY(hipMemsetAsync(c->status_dev, 0, c->status_words.bytes(), c->stream));
+  OWN_TRY(c->status_host.alloc(1));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  *out = c;
+  *out = c.release();
   return HFMI_OK;
 }
 
-extern "C" int hfmi_ctx_destroy(hfmi_ctx* ctx) {
-  if (!ctx) return HFMI_OK;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (hfmi_comm* c : ctx->watched_comms) comm_forget_ctx(c);    // a communicator destroyed after its context must not look for it
-  ctx->watched_comms.clear();
-  for (hfmi_block* b : ctx->tmp_blocks)
+// What a kernel may still use is released only after the streams have drained; the members then go in reverse order of their
+// declaration, the streams last.
+hfmi_ctx::~hfmi_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (aux_stream) (void)hipStreamSynchronize(aux_stream);
+  if (ingest_stream) (void)hipStreamSynchronize(ingest_stream);
+  for (hfmi_comm* c : watched_comms) comm_forget_ctx(c);    // a communicator destroyed after its context must not look for it
+  for (hfmi_block* b : tmp_blocks)
     if (b) {
-      if (b->owner && b->p) (void)hipFree(b->p);
+      if (b->owner && b->p) own_release(OWN_DEVICE, b->p);
       delete b;
     }
-  pool_flush(ctx);
-  for (int i = 0; i < WS_NSLOTS; ++i)
-    if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
-  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-  if (ctx->pinned_cb) (void)hipHostFree(ctx->pinned_cb);
-  if (ctx->late_pinned) (void)hipHostFree(ctx->late_pinned);
-  xfer_destroy(ctx);
-  for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ctx->ev_cb[i]);
-  for (int i = 0; i < 8; ++i) (void)hipEventDestroy(ctx->ev_panel[i]);
-  (void)hipEventDestroy(ctx->ev_join);
-  if (ctx->ingest_stream) {
-    (void)hipStreamSynchronize(ctx->ingest_stream);
-    for (int i = 0; i < HFMI_INGEST_RING; ++i) (void)hipEventDestroy(ctx->ev_ingest[i]);
-    (void)hipStreamDestroy(ctx->ingest_stream);
-  }
-  (void)hipFree(ctx->small);
-  if (ctx->wide) (void)hipFree(ctx->wide);
-  (void)hipFree(ctx->status_dev);
-  (void)hipHostFree(ctx->status_host);
-  (void)hipEventDestroy(ctx->ev0);
-  (void)hipEventDestroy(ctx->ev1);
-  (void)hipEventDestroy(ctx->ev_status);
-  (void)hipEventDestroy(ctx->ev_side);
-  (void)hipStreamDestroy(ctx->aux_stream);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+  for (auto& e : pool) own_release(OWN_DEVICE, e.p);
+  xfer_destroy(this);
+}
+extern "C" int hfmi_ctx_destroy(hfmi_ctx* ctx) {
   delete ctx;
   return HFMI_OK;
 }
@@ -409,14 +361,13 @@ extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (hip_stream == nullptr) {
-    if (!ctx->own_stream) {
-      HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-      ctx->own_stream = true;
+    if (!ctx->stream.owned()) {
+      decltype(ctx->stream) own;      // the caller's stream stays in place when this fails
+      OWN_TRY(own.create(hipStreamNonBlocking));
+      ctx->stream = std::move(own);
     }
   } else {
-    if (ctx->own_stream) HIP_TRY(hipStreamDestroy(ctx->stream));
-    ctx->stream = (hipStream_t)hip_stream;
-    ctx->own_stream = false;
+    ctx->stream.borrow((hipStream_t)hip_stream);
   }
   return HFMI_OK;
 }
@@ -467,8 +418,7 @@ int ctx_tmp_view(hfmi_ctx* ctx, int idx, int64_t N, int nvec, hfmi_block* out) {
   if ((int)ctx->tmp_blocks.size() <= idx) ctx->tmp_blocks.resize(idx + 1, nullptr);
   hfmi_block* b = ctx->tmp_blocks[idx];
   if (b && (b->N != N || b->nvec < nvec)) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(b->p);
+    storage_free(ctx, b->p);
     delete b;
     b = nullptr;
     ctx->tmp_blocks[idx] = nullptr;
@@ -581,9 +531,9 @@ int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N) {
   // algorithmic work (each operand touched once): flops 2 N m k, bytes 8 (N m + N k + m k)
   r.flops = 2.0 * (double)N * (double)m * (double)k;
   r.bytes = 8.0 * ((double)N * m + (double)N * k + (double)m * k);
-  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return -1;
+  if (r.e0.create() != 0 || r.e1.create() != 0) return -1;
   (void)hipEventRecord(r.e0, ctx->stream);
-  ctx->prof.push_back(r);
+  ctx->prof.push_back(std::move(r));
   return (int)ctx->prof.size() - 1;
 }
 int prof_stop(hfmi_ctx* ctx, int idx) {
@@ -594,9 +544,9 @@ int phase_begin_on(hfmi_ctx* ctx, int phase, hipStream_t st) {
   if (!ctx->profiling || g_prof_level < 2) return -1;
   hfmi_ctx::phase_rec r;
   r.phase = phase;
-  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return -1;
+  if (r.e0.create() != 0 || r.e1.create() != 0) return -1;
   (void)hipEventRecord(r.e0, st);
-  ctx->phase_events.push_back(r);
+  ctx->phase_events.push_back(std::move(r));
   return (int)ctx->phase_events.size() - 1;
 }
 void phase_end_on(hfmi_ctx* ctx, int idx, hipStream_t st) {
@@ -611,15 +561,7 @@ extern "C" int hfmi_profile_phases(hfmi_ctx* ctx, double* ms_out) {
 }
 extern "C" int hfmi_profile_begin(hfmi_ctx* ctx) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
-  for (auto& r : ctx->prof) {
-    (void)hipEventDestroy(r.e0);
-    (void)hipEventDestroy(r.e1);
-  }
   ctx->prof.clear();
-  for (auto& r : ctx->phase_events) {
-    (void)hipEventDestroy(r.e0);
-    (void)hipEventDestroy(r.e1);
-  }
   ctx->phase_events.clear();
   for (int i = 0; i < HFMI_PHASE_COUNT; ++i) ctx->phase_ms[i] = 0.0;
   ctx->profiling = true;
@@ -634,10 +576,7 @@ extern "C" int hfmi_profile_end(hfmi_ctx* ctx, int max_groups, int* ngroups, int
   int ng = 0;
   for (auto& r : ctx->prof) {
     float t = 0.f;
-    const bool ok = hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess;
-    (void)hipEventDestroy(r.e0);
-    (void)hipEventDestroy(r.e1);
-    if (!ok) continue;
+    if (hipEventElapsedTime(&t, r.e0, r.e1) != hipSuccess) continue;
     int g = 0;
     for (; g < ng; ++g)
       if (kind[g] == r.kind && shape[3 * g] == r.m && shape[3 * g + 1] == r.k && shape[3 * g + 2] == r.N) break;
@@ -660,8 +599,6 @@ extern "C" int hfmi_profile_end(hfmi_ctx* ctx, int max_groups, int* ngroups, int
   for (auto& r : ctx->phase_events) {
     float t = 0.f;
     if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) ctx->phase_ms[r.phase] += t;
-    (void)hipEventDestroy(r.e0);
-    (void)hipEventDestroy(r.e1);
   }
   ctx->phase_events.clear();
   *ngroups = ng;

@@ -22,25 +22,26 @@
 #include <math.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "hfmi_kcov_eval.h"
 
 struct fftcov_state {
-  int d;
-  int64_t n[3];
-  double h[3];
-  int64_t N;               // points of the operator
-  int64_t nnodes;          // prod n
-  int family;
-  double sigma, ell, nugget;
-  int64_t* inv;            // device, nnodes entries: the point that is grid node g, or -1; null: point g is node g
-  double2* tw;             // device: exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
-  double* lambda;          // device, prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
-  double2* work;           // device: work_pairs arrays of prod P_c entries
-  int work_pairs;
+  int d = 0;
+  int64_t n[3] = {1, 1, 1};
+  double h[3] = {1.0, 1.0, 1.0};
+  int64_t N = 0;           // points of the operator
+  int64_t nnodes = 0;      // prod n
+  int family = 0;
+  double sigma = 0.0, ell = 0.0, nugget = 0.0;
+  dev_buf<int64_t> inv;    // nnodes entries: the point that is grid node g, or -1; empty: point g is node g
+  dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
+  dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
+  dev_buf<double2> work;   // work_pairs() arrays of prod P_c entries
   fftcov_plan plan;        // the passes of an apply
+  int work_pairs() const { return (int)(work.bytes() / (size_t)plan.pair_bytes); }
 };
 
 struct fftcov_pass_args {
@@ -284,30 +285,21 @@ static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftco
 
 int64_t fftcov_points(const fftcov_state* st) { return st->N; }
 
-void fftcov_destroy(fftcov_state* st) {
-  if (!st) return;
-  if (st->inv) (void)hipFree(st->inv);
-  if (st->tw) (void)hipFree(st->tw);
-  if (st->lambda) (void)hipFree(st->lambda);
-  if (st->work) (void)hipFree(st->work);
-  delete st;
-}
+void fftcov_destroy(fftcov_state* st) { delete st; }
 
 static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* host_inv) {
   const fftcov_plan& p = st->plan;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_pass, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   // the work buffer of one pair and Lambda: what decides whether the padded grid fits at all
-  hipError_t e = hipMalloc((void**)&st->work, (size_t)p.pair_bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&st->lambda, (size_t)p.Ptot * sizeof(double));
+  hipError_t e = (hipError_t)st->work.alloc((size_t)p.pair_bytes / sizeof(double2));
+  if (e == hipSuccess) e = (hipError_t)st->lambda.alloc((size_t)p.Ptot);
   if (e != hipSuccess) {
-    (void)hipGetLastError();
     HFMI_FAIL(HFMI_ERR_HIP, "kernel_cov_grid: the padded grid %d x %d x %d needs %lld bytes of work buffer per pair of vectors and %lld bytes of spectrum: %s",
               p.P[0], p.P[1], p.P[2], (long long)p.pair_bytes, (long long)(p.Ptot * 8), hipGetErrorString(e));
   }
-  st->work_pairs = 1;
   if (host_inv) {
-    HIP_TRY(hipMalloc((void**)&st->inv, (size_t)st->nnodes * sizeof(int64_t)));
+    OWN_TRY(st->inv.alloc((size_t)st->nnodes));
     HIP_TRY(hipMemcpy(st->inv, host_inv, (size_t)st->nnodes * sizeof(int64_t), hipMemcpyHostToDevice));
   }
   // twiddles: long double on the host, rounded once
@@ -317,7 +309,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
     const long double a = -two_pi * (long double)k / (long double)p.Pmax;
     tw[k] = double2{(double)cosl(a), (double)sinl(a)};
   }
-  HIP_TRY(hipMalloc((void**)&st->tw, tw.size() * sizeof(double2)));
+  OWN_TRY(st->tw.alloc(tw.size()));
   HIP_TRY(hipMemcpy(st->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
   // Lambda = FFT(first column) / P by the forward passes over the whole padded array
   kcov_params K;
@@ -356,22 +348,20 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
       inv[g] = i;
     }
   }
-  fftcov_state* st = new (std::nothrow) fftcov_state();
+  std::unique_ptr<fftcov_state, void (*)(fftcov_state*)> st(new (std::nothrow) fftcov_state(), fftcov_destroy);
   if (!st) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   st->d = d;
   for (int c = 0; c < 3; ++c) st->n[c] = c < d ? n[c] : 1, st->h[c] = c < d ? h[c] : 1.0;
   st->N = N;
   st->nnodes = nnodes;
   st->family = family, st->sigma = sigma, st->ell = ell, st->nugget = nugget;
-  st->inv = nullptr, st->tw = nullptr, st->lambda = nullptr, st->work = nullptr, st->work_pairs = 0;
   st->plan = fftcov_plan_passes(d, st->n, false);
-  const int s = fftcov_create_device(ctx, st, host_nodes ? inv.data() : nullptr);
+  const int s = fftcov_create_device(ctx, st.get(), host_nodes ? inv.data() : nullptr);
   if (s != HFMI_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    fftcov_destroy(st);
+    (void)hipStreamSynchronize(ctx->stream);      // before the buffers go: the kernels queued so far use them
     return s;
   }
-  *out = st;
+  *out = st.release();
   return HFMI_OK;
 }
 
@@ -379,17 +369,15 @@ int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, 
   if (nvec < 1) return HFMI_OK;
   fftcov_plan p = st->plan;
   fftcov_plan_chunks(p, nvec, 0, fftcov_pairs_knob());
-  if (p.chunk_pairs > st->work_pairs) {
-    // grow the work buffer to the chunk; when the device has no room for it the apply runs in the chunks the buffer holds (same results)
-    double2* bigger = nullptr;
-    if (hipMalloc((void**)&bigger, (size_t)p.chunk_pairs * (size_t)p.pair_bytes) == hipSuccess) {
+  if (p.chunk_pairs > st->work_pairs()) {
+    // grow the work buffer to the chunk: the larger one first, so that when the device has no room for it the apply runs in the
+    // chunks the buffer at hand holds (same results)
+    dev_buf<double2> bigger;
+    if (bigger.alloc((size_t)p.chunk_pairs * ((size_t)p.pair_bytes / sizeof(double2))) == 0) {
       HIP_TRY(hipStreamSynchronize(ctx->stream));
-      (void)hipFree(st->work);
-      st->work = bigger;
-      st->work_pairs = p.chunk_pairs;
+      st->work = std::move(bigger);
     } else {
-      (void)hipGetLastError();
-      fftcov_plan_chunks(p, nvec, 0, st->work_pairs);
+      fftcov_plan_chunks(p, nvec, 0, st->work_pairs());
     }
   }
   for (int c = 0; c < p.nchunks; ++c) {

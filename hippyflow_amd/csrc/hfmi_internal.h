@@ -10,6 +10,7 @@
 
 #include "hfmi.h"
 #include "hfmi_fftcov_plan.h"
+#include "hfmi_own.h"
 #include "hfmi_qr_rules.h"
 #include "hfmi_small_plan.h"
 #include "hfmi_spsolve_rules.h"
@@ -30,6 +31,7 @@ void hfmi_set_error(const char* fmt, ...);
       return HFMI_ERR_HIP;                                                                     \
     }                                                                                          \
   } while (0)
+#define OWN_TRY(expr) HIP_TRY((hipError_t)(expr))   // own_acquire, the owners' alloc / create and grow (hfmi_own.h)
 #define HFMI_TRY(expr)        \
   do {                        \
     int _s = (expr);          \
@@ -81,69 +83,67 @@ struct hfmi_status_words {  // device-resident, read back by the host after smal
 
 struct hfmi_comm;
 struct xfer_state;
+// Owns everything below it.  Members are destroyed in reverse order of declaration, after the destructor's body (hfmi_ctx.hip) has
+// waited for the streams: the streams are declared first so that they outlive the events and buffers used on them.
 struct hfmi_ctx {
-  int device;
-  hipStream_t stream;
-  bool own_stream;
-  hipEvent_t ev0, ev1;
-  hipStream_t aux_stream;         // status read-backs that overlap work queued on `stream`
-  hipEvent_t ev_status;
-  hipEvent_t ev_side;             // small device -> host copies taken off the main stream (late QR checks, eigenvalues)
-  int num_cus;
-  size_t lds_per_block;          // LDS a workgroup may have on this device (static + dynamic; hipDeviceProp_t::sharedMemPerBlock)
-  size_t defl1_static_lds;        // static LDS of k_dcl_deflate<1>, read once per context (hfmi_eig_blocked.hip)
-  bool defl1_static_known;
-  void* ws[WS_NSLOTS];
-  size_t ws_bytes[WS_NSLOTS];
-  double* small;                  // SM_NSLOTS * SM_MAXK * SM_LD doubles
-  double* wide;                   // wide arena: WA_NSLOTS matrices of wide_cap x wide_cap doubles + wa_tail_doubles(); null until needed
-  int wide_cap;                   // leading dimension the arena was sized for (a multiple of 32)
-  hfmi_status_words* status_dev;  // device
-  hfmi_status_words* status_host; // pinned
-  void* pinned;                   // pinned host staging
-  size_t pinned_bytes;
+  ~hfmi_ctx();
+  int device = 0;
+  hip_stream stream;              // the library's own, or the caller's (hfmi_ctx_set_stream: referred to, never released)
+  hip_stream aux_stream;          // status read-backs that overlap work queued on `stream`
+  hip_stream ingest_stream;       // streaming ingest: uploads from pinned host memory on their own stream; made by the first upload
+  hip_event ev0, ev1;
+  hip_event ev_status;
+  hip_event ev_side;              // small device -> host copies taken off the main stream (late QR checks, eigenvalues)
+  int num_cus = 0;
+  size_t lds_per_block = 0;       // LDS a workgroup may have on this device (static + dynamic; hipDeviceProp_t::sharedMemPerBlock)
+  size_t defl1_static_lds = 0;    // static LDS of k_dcl_deflate<1>, read once per context (hfmi_eig_blocked.hip)
+  bool defl1_static_known = false;
+  dev_buf<unsigned char> ws[WS_NSLOTS];   // workspaces (ctx_ws); count = bytes
+  dev_buf<double> small;          // SM_NSLOTS * SM_MAXK * SM_LD doubles
+  dev_buf<double> wide;           // wide arena: WA_NSLOTS matrices of wide_cap x wide_cap doubles + wa_tail_doubles(); empty until needed
+  int wide_cap = 0;               // leading dimension the arena is laid out for (a multiple of 32; ctx_wide)
+  dev_buf<hfmi_status_words> status_words;   // [1]: a factorisation taken on trust (qr_chol)
+  hfmi_status_words* status_dev = nullptr;   // the slot of status_words the next small kernel reports into (qr_chol redirects it around one launch)
+  pinned_buf<hfmi_status_words> status_host;
+  pinned_buf<unsigned char> pinned;       // pinned host staging (ctx_pinned); count = bytes
   std::vector<hfmi_block*> tmp_blocks;  // cached temporaries for the fused solves
   // storage of destroyed blocks kept for the next hfmi_block_create of the same size (a solve per step returns a fresh
   // U and the caller drops the previous one: without the pool every step pays a hipFree -- a device synchronisation --
   // and a hipMalloc); entries <= 2 GB, at most 16 entries / 8 GB, flushed when an allocation fails
   struct pool_entry { void* p; size_t bytes; };
   std::vector<pool_entry> pool;
-  size_t pool_bytes;
+  size_t pool_bytes = 0;
   // optional per-launch event timing of the two MFMA kernel classes
-  bool profiling;
-  struct prof_rec { int kind; int64_t m, k, N; hipEvent_t e0, e1; double flops, bytes; };
+  bool profiling = false;
+  struct prof_rec { int kind; int64_t m, k, N; hip_event e0, e1; double flops, bytes; };
   std::vector<prof_rec> prof;
   // phases of the fused solves (HFMI_PHASE_*, include/hfmi.h): event pairs on the stream while profiling, plus the
   // host-side wall clock of the host-callback legs
-  struct phase_rec { int phase; hipEvent_t e0, e1; };
+  struct phase_rec { int phase; hip_event e0, e1; };
   std::vector<phase_rec> phase_events;
-  double phase_ms[HFMI_PHASE_COUNT];
-  // second pinned staging area (host-callback operators: double-buffered W and Y slabs)
+  double phase_ms[HFMI_PHASE_COUNT] = {};
   // row-panel hook of tsgemm_nn (hfmi_gemm_nn.hip): when set, a large product is issued as a few launches over consecutive
   // row ranges and the hook is called after each with the rows that are final -- hfmi_op_apply reduces those rows over the
   // ranks on the auxiliary stream while the next panel is computed
-  int (*nn_hook)(void* user, double* Y, int64_t ldy, int r, int64_t row0, int64_t rows);
-  void* nn_hook_user;
-  int nn_hook_panels;
-  bool nn_hook_called;
+  int (*nn_hook)(void* user, double* Y, int64_t ldy, int r, int64_t row0, int64_t rows) = nullptr;
+  void* nn_hook_user = nullptr;
+  int nn_hook_panels = 0;
+  bool nn_hook_called = false;
   // set around ONE launch_tsgemm_nn call by a caller that knows its small matrix is upper triangular (Q <- Q R^-1 of the QR):
   // the resident-S kernel then skips the column tiles that are structurally zero at each reduction step (bit-identical results)
-  bool nn_upper_hint;
-  hipEvent_t ev_panel[8], ev_join;
-  // streaming ingest: uploads from pinned host memory on their own stream, a ring of completion events = tickets
-  hipStream_t ingest_stream;
-  hipEvent_t ev_ingest[HFMI_INGEST_RING];
-  int64_t ingest_seq;
-  void* late_pinned;              // status words / R_jj table of an orthogonalisation pass taken on trust (hfmi_qr.hip)
+  bool nn_upper_hint = false;
+  hip_event ev_panel[8], ev_join;
+  hip_event ev_ingest[HFMI_INGEST_RING];   // ring of completion events of the ingest stream = tickets
+  int64_t ingest_seq = 0;
+  pinned_buf<unsigned char> late_pinned;   // status words / R_jj table of an orthogonalisation pass taken on trust (qr_late_buffer, hfmi_qr.hip)
   std::vector<hfmi_comm*> watched_comms;   // communicators whose device-side error word the host synchronisation points check
-  void* pinned_cb;
-  size_t pinned_cb_bytes;
-  hipEvent_t ev_cb[4];            // D2H done x2, H2D done x2
-  xfer_state* xfer;               // pinned ring + host threads of the large host <-> device transfers (hfmi_xfer.hip), lazily created
-  int compose_depth;              // OP_COMPOSE3 applications in progress (nested compositions use separate temporaries)
+  pinned_buf<double> pinned_cb;   // second pinned staging area (host-callback operators: double-buffered W and Y slabs)
+  hip_event ev_cb[4];             // D2H done x2, H2D done x2
+  xfer_state* xfer = nullptr;     // pinned ring + host threads of the large host <-> device transfers (hfmi_xfer.hip), lazily created
+  int compose_depth = 0;          // OP_COMPOSE3 applications in progress (nested compositions use separate temporaries)
   // plan record (hfmi_plan_clear / hfmi_plan_read, include/hfmi.h): which contraction / reduction instance every launch was
   int plan_ring[HFMI_PLAN_RING][HFMI_PLAN_WORDS];
-  int64_t plan_count;             // launches since the last clear
+  int64_t plan_count = 0;         // launches since the last clear
 };
 // the slot of the next record, to be filled by one of the *_plan_words helpers (hfmi_tsgemm_plan.h)
 static inline int* plan_slot(hfmi_ctx* ctx) { return ctx->plan_ring[ctx->plan_count++ % HFMI_PLAN_RING]; }
@@ -158,10 +158,11 @@ void phase_end_on(hfmi_ctx* ctx, int idx, hipStream_t st);
 int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N);  // returns record index or -1
 int prof_stop(hfmi_ctx* ctx, int idx);
 
-static inline double* sm_ptr(hfmi_ctx* c, int slot) { return c->small + (size_t)slot * SM_MAXK * SM_LD; }
+static inline double* sm_ptr(hfmi_ctx* c, int slot) { return c->small.get() + (size_t)slot * SM_MAXK * SM_LD; }
 int ctx_ws(hfmi_ctx* ctx, int slot, size_t bytes, void** out);
 int ctx_pinned(hfmi_ctx* ctx, size_t bytes, void** out);
-// uninitialised storage for an N x nvec block, from the pool of released blocks or hipMalloc; pool_release gives it back
+// uninitialised storage for an N x nvec block, from the pool of released blocks or the device; pool_release gives it back (to the pool,
+// or when that is full to the device after waiting for the stream).  hfmi_block stays a plain struct that views copy by value.
 int block_alloc(hfmi_ctx* ctx, int64_t N, int nvec, hfmi_block** out);
 void pool_release(hfmi_ctx* ctx, void* p, size_t bytes);
 // Cached temporaries of the context, one block per slot.  Slots of different owners may all be live at once, because the owners
@@ -197,25 +198,25 @@ int upload_small(hfmi_ctx* ctx, const double* host, int rows, int cols, double* 
 int check_same_shape(const hfmi_block* a, const hfmi_block* b, const char* what);
 
 struct hfmi_csr {
-  hfmi_ctx* ctx;
-  int64_t nrows, ncols, nnz;
-  int64_t* indptr;
-  int32_t* indices;
-  double* data;
+  hfmi_ctx* ctx = nullptr;
+  int64_t nrows = 0, ncols = 0, nnz = 0;
+  dev_buf<int64_t> indptr;
+  dev_buf<int32_t> indices;
+  dev_buf<double> data;
   // ELLPACK image (slot-major: entry s of row i at [s * nrows + i]) built at creation when the rows are short and
   // even (FEM matrices): consecutive lanes then read consecutive (index, value) pairs.  ell_w == 0: CSR kernel only.
-  int ell_w;
-  int32_t* ell_idx;
-  double* ell_val;
+  int ell_w = 0;
+  dev_buf<int32_t> ell_idx;
+  dev_buf<double> ell_val;
   // What the solvers learn about the matrix, lazily: the matrix itself is const to them.  inv_diag: the Jacobi preconditioner
   // (csr_prepare_jacobi).  Spectrum of the Jacobi-scaled matrix D^-1 A for the Chebyshev solve (hfmi_cheb.hip): an upper bound from
   // Gershgorin's circles (computed from the host arrays at creation), a bracket from the Lanczos matrix of one scalar CG run on
   // the device (first solve); cheb_state: 0 = not estimated yet, 1 = usable, -1 = do not use (estimate failed / a solve did not
   // reach its tolerance)
   mutable struct solve_state {
-    double* inv_diag;
-    double gersh_lmax, cheb_lmin, cheb_lmax;
-    int cheb_state;
+    dev_buf<double> inv_diag;
+    double gersh_lmax = 0.0, cheb_lmin = 0.0, cheb_lmax = 0.0;
+    int cheb_state = 0;
   } solve;
 };
 
@@ -223,41 +224,42 @@ struct fftcov_state;
 enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID };
 
 struct hfmi_op {
-  hfmi_ctx* ctx;
-  hfmi_op_kind kind;
-  hfmi_block X;          // snapshot / Jacobian / dense block (by value: a view, not owned)
-  int ndata, q;
-  double* gamma_inv;     // device q x q row-major (ld = round_up(q,16)) or null
-  double* weights;       // device, one per vector of X (general diagonal of a low-rank operator) or null
-  double scale;
-  const hfmi_csr* csr;
-  double rel_tol;
-  int max_iter;
-  int last_iters;
-  int last_method;        // sparse solver: 0 = block CG, 1 = Chebyshev, 2 = AMG-preconditioned CG (hfmi_op_solver_info)
-  hfmi_amg* amg;          // OP_AMG_PCG: the multigrid hierarchy (not owned)
-  hfmi_op *a, *b, *c;
-  // OP_KERNEL_COV: the point coordinates on the device, one array of kc_N doubles per dimension (owned), and the kernel
-  double* kc_x;
-  int64_t kc_N;
-  int kc_d, kc_family;
-  double kc_sigma, kc_ell, kc_nugget;
+  ~hfmi_op();              // waits for the stream when the operator owns device memory (hfmi_op.hip)
+  hfmi_ctx* ctx = nullptr;
+  hfmi_op_kind kind = OP_SNAPSHOT_GRAM;
+  hfmi_block X = {};     // snapshot / Jacobian / dense block (by value: a view, not owned)
+  int ndata = 0, q = 0;
+  dev_buf<double> gamma_inv;   // q x q row-major (ld = round_up(q,16)) or empty
+  dev_buf<double> weights;     // one per vector of X (general diagonal of a low-rank operator) or empty
+  double scale = 1.0;
+  const hfmi_csr* csr = nullptr;
+  double rel_tol = 0.0;
+  int max_iter = 0;
+  int last_iters = 0;
+  int last_method = 0;    // sparse solver: 0 = block CG, 1 = Chebyshev, 2 = AMG-preconditioned CG (hfmi_op_solver_info)
+  hfmi_amg* amg = nullptr;   // OP_AMG_PCG: the multigrid hierarchy (not owned)
+  hfmi_op *a = nullptr, *b = nullptr, *c = nullptr;
+  // OP_KERNEL_COV: the point coordinates on the device, one array of kc_N doubles per dimension, and the kernel
+  dev_buf<double> kc_x;
+  int64_t kc_N = 0;
+  int kc_d = 0, kc_family = 0;
+  double kc_sigma = 0.0, kc_ell = 0.0, kc_nugget = 0.0;
   // OP_KERNEL_CROSS: K(T, S) with S in kc_x (kc_N points).  kc_slab: T = S[kc_diag : kc_diag + kc_M], Y is addressed at row kc_diag and
-  // an overwriting apply zeroes its other rows (hfmi_op_kernel_cov_rows).  Otherwise T is kc_t (owned, one array of kc_M doubles per
+  // an overwriting apply zeroes its other rows (hfmi_op_kernel_cov_rows).  Otherwise T is kc_t (one array of kc_M doubles per
   // dimension) and Y has kc_M rows; kc_diag: target i is source i + kc_diag, HFMI_KERNEL_NO_DIAGONAL for none (hfmi_op_kernel_cross_cov).
-  double* kc_t;
-  int64_t kc_M, kc_diag;
-  bool kc_slab;
-  fftcov_state* fc;      // OP_KERNEL_COV_GRID: the grid, the node map, Lambda, the twiddles and the work buffer (owned; hfmi_fftcov.hip)
-  hfmi_host_apply_fn host_fn;
-  void* host_user;
-  int64_t host_N;
-  int host_chunk;        // > 0: the callback is invoked on slabs of this many vectors (pipelined with the copies)
-  hfmi_post_apply_fn post_fn;
-  void* post_user;
-  hfmi_comm* comm;       // rank average / sum of the result block (hfmi_op_set_collective), null = none
-  int comm_op;
-  bool reduced_by_panels; // the last apply already reduced its result over the ranks, panel by panel (hfmi_op.hip)
+  dev_buf<double> kc_t;
+  int64_t kc_M = 0, kc_diag = 0;
+  bool kc_slab = false;
+  fftcov_state* fc = nullptr;   // OP_KERNEL_COV_GRID: the grid, the node map, Lambda, the twiddles and the work buffer (owned; hfmi_fftcov.hip)
+  hfmi_host_apply_fn host_fn = nullptr;
+  void* host_user = nullptr;
+  int64_t host_N = 0;
+  int host_chunk = 0;    // > 0: the callback is invoked on slabs of this many vectors (pipelined with the copies)
+  hfmi_post_apply_fn post_fn = nullptr;
+  void* post_user = nullptr;
+  hfmi_comm* comm = nullptr;   // rank average / sum of the result block (hfmi_op_set_collective), null = none
+  int comm_op = 0;
+  bool reduced_by_panels = false; // the last apply already reduced its result over the ranks, panel by panel (hfmi_op.hip)
 };
 // Y = M^-1 W for an SPD CSR matrix by Chebyshev iteration, or Jacobi-preconditioned block CG (hfmi_sparse.hip)
 int csr_pcg_solve(hfmi_op* op, const hfmi_block* W, hfmi_block* Y);
@@ -306,7 +308,7 @@ int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const dou
                             int64_t ldy, int nvec, int accumulate);
 
 // Kernel covariance on a regular grid by FFT (hfmi_fftcov.hip; plans: hfmi_fftcov_plan.h).  create checks the arguments, uploads the
-// node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy frees what create made (the caller synchronised)
+// node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy deletes the state (the caller synchronised)
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
                   double ell, double nugget, fftcov_state** out);
 int64_t fftcov_points(const fftcov_state* st);
@@ -432,7 +434,7 @@ int launch_sym_eig(hfmi_ctx* ctx, int k, int slot_t, int slot_v, double* dvals, 
 int launch_chol_mfma(hfmi_ctx* ctx, int k, int slot_gram, int slot_r, int slot_rinv, int slot_rtot, int rtot_mode, int full_r,
                      double shift_rel, double pivot_tol);   // hfmi_chol.hip
 // ------------------------------------------------------------------ wide Cholesky + inverse (hfmi_chol_wide.hip)
-static inline double* wa_ptr(hfmi_ctx* c, int slot) { return c->wide + (size_t)slot * c->wide_cap * c->wide_cap; }
+static inline double* wa_ptr(hfmi_ctx* c, int slot) { return c->wide.get() + (size_t)slot * c->wide_cap * c->wide_cap; }
 static inline double* wa_aux(hfmi_ctx* c) { return wa_ptr(c, WA_NSLOTS); }   // [0, k): original column norms; [ld, ld + k): diag(Rtot)
 int ctx_wide(hfmi_ctx* ctx, int k);      // make the arena hold k x k matrices (allocates / regrows; zero filled)
 // The contract of launch_chol_inv on the wide arena with ld = round_up(k, 32): G = WA_GRAM -> R (WA_R), R^-1 (WA_RINV), both upper

@@ -4,6 +4,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 
 #include "hfmi_internal.h"
@@ -12,10 +13,8 @@
 static hfmi_op* op_new(hfmi_ctx* ctx, hfmi_op_kind kind) {
   hfmi_op* op = new (std::nothrow) hfmi_op();
   if (!op) return nullptr;
-  memset((void*)op, 0, sizeof(*op));
   op->ctx = ctx;
   op->kind = kind;
-  op->scale = 1.0;
   return op;
 }
 extern "C" int hfmi_op_snapshot_gram(hfmi_ctx* ctx, const hfmi_block* X, double scale, hfmi_op** out) {
@@ -30,20 +29,16 @@ extern "C" int hfmi_op_snapshot_gram(hfmi_ctx* ctx, const hfmi_block* X, double 
 }
 extern "C" int hfmi_op_low_rank(hfmi_ctx* ctx, const hfmi_block* U, const double* host_d, hfmi_op** out) {
   if (!ctx || !U || !host_d || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  hfmi_op* op = op_new(ctx, OP_SNAPSHOT_GRAM);
+  std::unique_ptr<hfmi_op> op(op_new(ctx, OP_SNAPSHOT_GRAM));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   op->X = *U;
   op->X.owner = false;
   op->scale = 1.0;
   hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&op->weights, (size_t)U->nvec * sizeof(double));
+  if (e == hipSuccess) e = (hipError_t)op->weights.alloc((size_t)U->nvec);
   if (e == hipSuccess) e = hipMemcpy(op->weights, host_d, (size_t)U->nvec * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (op->weights) (void)hipFree(op->weights);
-    delete op;
-    HFMI_FAIL(HFMI_ERR_HIP, "op_low_rank: %s", hipGetErrorString(e));
-  }
-  *out = op;
+  if (e != hipSuccess) HFMI_FAIL(HFMI_ERR_HIP, "op_low_rank: %s", hipGetErrorString(e));
+  *out = op.release();
   return HFMI_OK;
 }
 static int op_jac(hfmi_ctx* ctx, hfmi_op_kind kind, const hfmi_block* J, int ndata, int q, const double* host_gamma_inv,
@@ -52,7 +47,7 @@ static int op_jac(hfmi_ctx* ctx, hfmi_op_kind kind, const hfmi_block* J, int nda
   if (ndata <= 0 || q <= 0 || (int64_t)ndata * q != J->nvec)
     HFMI_FAIL(HFMI_ERR_INVALID, "jacobian operator: ndata*q = %lld must equal the number of stored rows %d",
               (long long)ndata * q, J->nvec);
-  hfmi_op* op = op_new(ctx, kind);
+  std::unique_ptr<hfmi_op> op(op_new(ctx, kind));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   op->X = *J;
   op->X.owner = false;
@@ -61,11 +56,10 @@ static int op_jac(hfmi_ctx* ctx, hfmi_op_kind kind, const hfmi_block* J, int nda
   op->scale = scale;
   if (host_gamma_inv) {
     const int ld = (int)round_up(q, 16);
-    HIP_TRY(hipMalloc((void**)&op->gamma_inv, (size_t)q * ld * sizeof(double)));
-    int s = upload_small(ctx, host_gamma_inv, q, q, op->gamma_inv, ld);
-    if (s != HFMI_OK) return s;
+    OWN_TRY(op->gamma_inv.alloc((size_t)q * ld));
+    HFMI_TRY(upload_small(ctx, host_gamma_inv, q, q, op->gamma_inv, ld));
   }
-  *out = op;
+  *out = op.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_op_jtj(hfmi_ctx* ctx, const hfmi_block* J, int ndata, int q, const double* host_gamma_inv,
@@ -95,37 +89,30 @@ static int kcov_check(const char* who, int64_t N, int d, int family, double ell,
   return HFMI_OK;
 }
 // host points (n x d row-major) -> one array per coordinate on the device (the kernel reads x_c[j] for runs of consecutive j)
-static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t n, int d, double** out) {
+static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t n, int d, dev_buf<double>* out) {
   std::vector<double> soa((size_t)n * d);
   for (int64_t i = 0; i < n; ++i)
     for (int c = 0; c < d; ++c) soa[(size_t)c * n + i] = host_points[(size_t)i * d + c];
-  double* x = nullptr;
+  dev_buf<double> x;
   hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&x, soa.size() * sizeof(double));
+  if (e == hipSuccess) e = (hipError_t)x.alloc(soa.size());
   if (e == hipSuccess) e = hipMemcpy(x, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (x) (void)hipFree(x);
-    HFMI_FAIL(HFMI_ERR_HIP, "kernel covariance points: %s", hipGetErrorString(e));
-  }
-  *out = x;
+  if (e != hipSuccess) HFMI_FAIL(HFMI_ERR_HIP, "kernel covariance points: %s", hipGetErrorString(e));
+  *out = std::move(x);
   return HFMI_OK;
 }
 static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, hfmi_op** out) {
-  hfmi_op* op = op_new(ctx, kind);
+  std::unique_ptr<hfmi_op> op(op_new(ctx, kind));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  const int s = kcov_upload_points(ctx, host_points, N, d, &op->kc_x);
-  if (s != HFMI_OK) {
-    delete op;
-    return s;
-  }
+  HFMI_TRY(kcov_upload_points(ctx, host_points, N, d, &op->kc_x));
   op->kc_N = N;
   op->kc_d = d;
   op->kc_family = family;
   op->kc_sigma = sigma;
   op->kc_ell = ell;
   op->kc_nugget = nugget;
-  *out = op;
+  *out = op.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
@@ -145,17 +132,14 @@ extern "C" int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_target
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: diag_offset = %lld with M = %lld targets does not lie inside the N = %lld sources",
               (long long)diag_offset, (long long)M, (long long)N);
   }
-  hfmi_op* op = nullptr;
-  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &op));
-  const int s = kcov_upload_points(ctx, host_targets, M, d, &op->kc_t);
-  if (s != HFMI_OK) {
-    (void)hfmi_op_destroy(op);
-    return s;
-  }
+  hfmi_op* raw = nullptr;
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &raw));
+  std::unique_ptr<hfmi_op> op(raw);
+  HFMI_TRY(kcov_upload_points(ctx, host_targets, M, d, &op->kc_t));
   op->kc_M = M;
   op->kc_diag = diag_offset;
   op->kc_slab = false;
-  *out = op;
+  *out = op.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
@@ -177,14 +161,10 @@ extern "C" int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n, c
                                        int family, double sigma, double ell, double nugget, hfmi_op** out) {
   if (!ctx || !n || !h || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget));
-  hfmi_op* op = op_new(ctx, OP_KERNEL_COV_GRID);
+  std::unique_ptr<hfmi_op> op(op_new(ctx, OP_KERNEL_COV_GRID));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  const int s = fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, &op->fc);
-  if (s != HFMI_OK) {
-    delete op;
-    return s;
-  }
-  *out = op;
+  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, &op->fc));
+  *out = op.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
@@ -271,16 +251,11 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
   op->comm_op = reduce_op;
   return HFMI_OK;
 }
+hfmi_op::~hfmi_op() {
+  if (gamma_inv || weights || kc_x || kc_t || fc) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
+  fftcov_destroy(fc);
+}
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
-  if (!op) return HFMI_OK;
-  if (op->gamma_inv || op->weights || op->kc_x || op->kc_t || op->fc) {
-    (void)hipStreamSynchronize(op->ctx->stream);
-    if (op->fc) fftcov_destroy(op->fc);
-    if (op->gamma_inv) (void)hipFree(op->gamma_inv);
-    if (op->weights) (void)hipFree(op->weights);
-    if (op->kc_x) (void)hipFree(op->kc_x);
-    if (op->kc_t) (void)hipFree(op->kc_t);
-  }
   delete op;
   return HFMI_OK;
 }
@@ -302,17 +277,10 @@ static int host_apply_pipelined(hfmi_op* op, const hfmi_block* W, hfmi_block* Y)
   const int nchunks = (k + chunk - 1) / chunk;
   const size_t wslab = (size_t)chunk * N, yslab = (size_t)chunk * NY;
   const int nbuf = nchunks > 1 ? 2 : 1;
-  const size_t need = (size_t)nbuf * (wslab + yslab) * sizeof(double);
-  if (need > ctx->pinned_cb_bytes) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->pinned_cb) HIP_TRY(hipHostFree(ctx->pinned_cb));
-    ctx->pinned_cb = nullptr;
-    ctx->pinned_cb_bytes = 0;
-    HIP_TRY(hipHostMalloc(&ctx->pinned_cb, need, hipHostMallocDefault));
-    ctx->pinned_cb_bytes = need;
-  }
-  double* wbuf[2] = {(double*)ctx->pinned_cb, (double*)ctx->pinned_cb + (nbuf - 1) * wslab};
-  double* ybuf[2] = {(double*)ctx->pinned_cb + nbuf * wslab, (double*)ctx->pinned_cb + nbuf * wslab + (nbuf - 1) * yslab};
+  OWN_TRY(grow(ctx->pinned_cb, (size_t)nbuf * (wslab + yslab), [&] { return (int)hipStreamSynchronize(ctx->stream); }));
+  double* const cb = ctx->pinned_cb;
+  double* wbuf[2] = {cb, cb + (nbuf - 1) * wslab};
+  double* ybuf[2] = {cb + nbuf * wslab, cb + nbuf * wslab + (nbuf - 1) * yslab};
   auto fetch = [&](int c) -> int {      // slab c of W -> wbuf[c & 1] on the auxiliary stream
     const int c0 = c * chunk, nc = std::min(chunk, k - c0);
     HIP_TRY(hipMemcpy2DAsync(wbuf[c & 1], (size_t)N * sizeof(double), W->p + (int64_t)c0 * W->ld, (size_t)W->ld * sizeof(double),

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 
 #include "hfmi_kcov_eval.h"
@@ -171,11 +172,16 @@ int pchol_tuning_set(const char* key, int value) {
 }
 
 struct hfmi_pchol {
-  hfmi_ctx* ctx;
-  double* p;                // the factor's storage: max_rank columns from the block allocator, padding rows and unused columns +0.0
-  size_t bytes;
-  hfmi_block L;             // the first `rank` columns, by value (a view, not an owner)
-  int rank, stop_reason;
+  ~hfmi_pchol() {           // the storage goes back where it came from; the pool keeps it in stream order
+    if (!p) return;
+    (void)hipSetDevice(ctx->device);
+    pool_release(ctx, p, bytes);
+  }
+  hfmi_ctx* ctx = nullptr;
+  double* p = nullptr;      // the factor's storage: max_rank columns from the block allocator, padding rows and unused columns +0.0
+  size_t bytes = 0;
+  hfmi_block L = {};        // the first `rank` columns, by value (a view, not an owner)
+  int rank = 0, stop_reason = HFMI_PCHOL_MAX_RANK;
   std::vector<int64_t> pivots;
   std::vector<double> trace;
 };
@@ -256,41 +262,30 @@ extern "C" int hfmi_pchol_create(hfmi_op* op, int max_rank, double rel_tol, hfmi
   const int64_t ntiles = (N + PC_THREADS - 1) / PC_THREADS;
   int grid = (int)std::min<int64_t>(ntiles, (int64_t)per_cu * ctx->num_cus);
   if (g_pchol_grid > 0) grid = std::min(grid, g_pchol_grid);
-  hfmi_pchol* h = new (std::nothrow) hfmi_pchol();
+  std::unique_ptr<hfmi_pchol> h(new (std::nothrow) hfmi_pchol());
   if (!h) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   h->ctx = ctx;
-  h->p = nullptr;
-  h->rank = 0;
-  h->stop_reason = HFMI_PCHOL_MAX_RANK;
   hfmi_block* b = nullptr;
-  int s = block_alloc(ctx, N, kmax, &b);
-  if (s != HFMI_OK) {
-    delete h;
-    return s;
-  }
+  HFMI_TRY(block_alloc(ctx, N, kmax, &b));
   h->L = *b;
   h->L.owner = false;
   h->p = b->p;
   h->bytes = (size_t)b->ld * kmax * sizeof(double);
   delete b;
-  double* scratch = nullptr;
-  const size_t scratch_bytes = ((size_t)N + kmax + 3 * (size_t)grid) * sizeof(double) + sizeof(pc_pick);
+  dev_buf<double> scratch;
+  const size_t scratch_doubles = (size_t)N + kmax + 3 * (size_t)grid + sizeof(pc_pick) / sizeof(double);
+  int s = HFMI_OK;
   hipError_t e = hipMemsetAsync(h->p, 0, h->bytes, ctx->stream);
-  if (e == hipSuccess) e = hipMalloc((void**)&scratch, scratch_bytes);
+  if (e == hipSuccess) e = (hipError_t)scratch.alloc(scratch_doubles);
   if (e != hipSuccess) {
     hfmi_set_error("pchol: %s", hipGetErrorString(e));
     s = HFMI_ERR_HIP;
   } else {
-    s = pchol_run(h, op, kmax, rel_tol, scratch, grid);
+    s = pchol_run(h.get(), op, kmax, rel_tol, scratch, grid);
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  if (scratch) (void)hipFree(scratch);
-  if (s != HFMI_OK) {
-    pool_release(ctx, h->p, h->bytes);
-    delete h;
-    return s;
-  }
-  *out = h;
+  (void)hipStreamSynchronize(ctx->stream);      // before the scratch goes
+  if (s != HFMI_OK) return s;
+  *out = h.release();
   return HFMI_OK;
 }
 extern "C" int hfmi_pchol_info(const hfmi_pchol* h, int* rank, int* stop_reason, double* trace0) {
@@ -313,9 +308,6 @@ extern "C" int hfmi_pchol_factor(const hfmi_pchol* h, const hfmi_block** L) {
   return HFMI_OK;
 }
 extern "C" int hfmi_pchol_destroy(hfmi_pchol* h) {
-  if (!h) return HFMI_OK;
-  (void)hipSetDevice(h->ctx->device);
-  pool_release(h->ctx, h->p, h->bytes);
   delete h;
   return HFMI_OK;
 }

@@ -59,8 +59,8 @@ static int qr_fail(qr_next next, int pass, double gram_dev) {
 }
 
 int ctx_late_pinned(hfmi_ctx* ctx, qr_late_buffer** out) {
-  if (!ctx->late_pinned) HIP_TRY(hipHostMalloc(&ctx->late_pinned, sizeof(qr_late_buffer), hipHostMallocDefault));
-  *out = (qr_late_buffer*)ctx->late_pinned;
+  if (!ctx->late_pinned) OWN_TRY(ctx->late_pinned.alloc(sizeof(qr_late_buffer)));
+  *out = (qr_late_buffer*)ctx->late_pinned.get();
   return HFMI_OK;
 }
 // A second pass on trust: its status words (and those of a trusted first pass) and the R_jj / ||z_j|| table leave for pinned memory

@@ -232,7 +232,7 @@ static int solve_tail(const hfmi_block* Q, int r, int flags, tail_back back, con
   memcpy(host_d, dpin, (size_t)r * sizeof(double));
   const hfmi_status_words st = *ctx->status_host;
   print_status_dbg(&st);
-  if (late && !qr_late_stands((const qr_late_buffer*)ctx->late_pinned, k, qr->first_trusted)) {
+  if (late && !qr_late_stands((const qr_late_buffer*)ctx->late_pinned.get(), k, qr->first_trusted)) {
     *repeat_checked = true;
     return HFMI_OK;
   }

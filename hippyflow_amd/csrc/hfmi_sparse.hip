@@ -129,7 +129,7 @@ int launch_csr_diag_inv(hfmi_ctx* ctx, const hfmi_csr* M) {
 }
 int csr_prepare_jacobi(hfmi_ctx* ctx, const hfmi_csr* M) {
   if (M->solve.inv_diag) return HFMI_OK;
-  HIP_TRY(hipMalloc((void**)&M->solve.inv_diag, (size_t)M->nrows * sizeof(double)));
+  OWN_TRY(M->solve.inv_diag.alloc((size_t)M->nrows));
   return launch_csr_diag_inv(ctx, M);
 }
 

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -85,38 +86,31 @@ __global__ __launch_bounds__(256) void k_xfer_out(xd2* __restrict__ dst, const x
 
 struct xfer_state {
   char* pin_dev = nullptr;        // the ring as the device sees it
-  char* pin = nullptr;
-  hipEvent_t ev[XF_NBUF];
-  bool have_events = false;
+  pinned_buf<char> pin;
+  hip_event ev[XF_NBUF];
   pool workers;
   int nthreads = 0;
 };
 
 static int xfer_get(hfmi_ctx* ctx, xfer_state** out) {
   if (!ctx->xfer) {
-    xfer_state* s = new (std::nothrow) xfer_state();
+    std::unique_ptr<xfer_state> s(new (std::nothrow) xfer_state());
     if (!s) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-    ctx->xfer = s;
-    HIP_TRY(hipHostMalloc((void**)&s->pin, XF_NBUF * XF_CHUNK, hipHostMallocDefault));
+    OWN_TRY(s->pin.alloc(XF_NBUF * XF_CHUNK));
     HIP_TRY(hipHostGetDevicePointer((void**)&s->pin_dev, s->pin, 0));
-    for (int i = 0; i < XF_NBUF; ++i) HIP_TRY(hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming));
-    s->have_events = true;
+    for (hip_event& e : s->ev) OWN_TRY(e.create(hipEventDisableTiming));
     const char* e = getenv("HFMI_XFER_THREADS");
     int nt = e ? atoi(e) : 0;
     if (nt <= 0) nt = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency() / 4));
     s->nthreads = std::min(nt, 32);
     s->workers.start(s->nthreads);
+    ctx->xfer = s.release();      // complete: the transfers divide by nthreads and write to the ring
   }
   *out = ctx->xfer;
   return HFMI_OK;
 }
 void xfer_destroy(hfmi_ctx* ctx) {
-  xfer_state* s = ctx->xfer;
-  if (!s) return;
-  if (s->have_events)
-    for (int i = 0; i < XF_NBUF; ++i) (void)hipEventDestroy(s->ev[i]);
-  if (s->pin) (void)hipHostFree(s->pin);
-  delete s;
+  delete ctx->xfer;
   ctx->xfer = nullptr;
 }
 

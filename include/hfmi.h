@@ -458,6 +458,15 @@ HFMI_API int hfmi_test_lu_solve(hfmi_ctx* ctx, const double* host_W, const doubl
                                 double* host_LU, double* host_status, double* host_T);
 HFMI_API int hfmi_test_tsgemm_tn(const hfmi_block* A, const hfmi_block* B, double scale, double beta, int colmajor, int ldc,
                                  int nsplit, double* host_C);
+/* Ownership of device resources (tests).  Every device buffer, pinned buffer, event and stream of the library (the communicator's
+ * excepted) is acquired and released in one place, which counts them per kind in that order (4 kinds), process-wide.
+ * hfmi_test_own_fail: acquisitions first .. first + count - 1, counted from this call (the next one is number 1), return
+ * hipErrorOutOfMemory without calling HIP; first = 0 disarms.  Nothing is launched and nothing faults: the failure is simulated on the
+ * host.  hfmi_test_own_counts: live[4] = handles acquired and not yet released, acquired[4] = acquisitions that succeeded so far,
+ * *pooled = storage of destroyed blocks the context keeps for reuse (counted in live[0] as well; 0 for a NULL context).  Any output
+ * may be NULL. */
+HFMI_API int hfmi_test_own_fail(int first, int count);
+HFMI_API int hfmi_test_own_counts(hfmi_ctx* ctx_or_null, int64_t* live, int64_t* acquired, int64_t* pooled);
 /* Plan record: every launch of a contraction kernel (k_tsgemm_tn, k_tsgemm_nn[_res], k_tsgemm_ss[b]) and of a partial-sum
  * reduction behind one appends HFMI_PLAN_WORDS ints to a ring of HFMI_PLAN_RING records on the context (host side, a few stores
  * per launch).  Word 0 is the kind, the others by kind:
