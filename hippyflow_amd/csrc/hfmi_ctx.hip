@@ -356,6 +356,21 @@ extern "C" int hfmi_fftcov_plan_predict(int d, const int64_t* n, int nvec, int64
   return HFMI_OK;
 }
 
+// ... and of a draw of the grid sampler at growth `growth` (hfmi_grid_sampler_draw asks the same planner)
+extern "C" int hfmi_fftcov_sample_plan_predict(int d, const int64_t* n, int growth, int nsamples, int64_t budget_bytes, int64_t* words) {
+  if (!n || !words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_sample_plan_predict: d = %d is not 1, 2 or 3", d);
+  for (int c = 0; c < d; ++c)
+    if (n[c] < 1 || n[c] > FFTCOV_MAXN) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_sample_plan_predict: n[%d] = %lld is not in 1 .. %d", c, (long long)n[c], FFTCOV_MAXN);
+  if (nsamples < 0) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_sample_plan_predict: negative number of draws");
+  if (!fftcov_growth_feasible(d, n, growth))
+    HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_sample_plan_predict: growth %d is outside 0..%d or takes an axis past %d entries", growth, FFTCOV_MAX_GROWTH, FFTCOV_MAXP);
+  fftcov_plan p = fftcov_sample_plan_passes(d, n, growth, false);
+  fftcov_plan_chunks(p, nsamples, budget_bytes, fftcov_pairs_knob());
+  fftcov_sample_plan_words(p, growth, words);
+  return HFMI_OK;
+}
+
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
   if (hip_stream != nullptr && ctx->stream == (hipStream_t)hip_stream) return HFMI_OK;
@@ -515,6 +530,7 @@ extern "C" int hfmi_tuning_set(const char* key, int value) {
   else if (key && api_tuning_set(key, value)) {}
   else if (key && pchol_tuning_set(key, value)) {}
   else if (key && fftcov_knob_set(key, value)) {}
+  else if (key && fftcov_sample_knob_set(key, value)) {}
   else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
   return HFMI_OK;
 }

@@ -19,6 +19,11 @@
 //
 // LDS: lpw * (L + pad) entries of 16 bytes and the twiddles, dynamic; two tables of 256 line bases, static (4 KiB).  The plan keeps
 // static + dynamic below the 160 KiB of a workgroup.  The bank layout (hfmi_fftcov_plan.h: pad) has not been measured.
+//
+// The same passes draw m ~ N(0, C) (hfmi_grid_sampler_*, the second half of this unit): k_fftcov_draw is the pass whose load is
+// generated -- sqrt(max(Lambda / P, 0)) times complex Philox / Box-Muller noise, hfmi_randn_math.h -- followed by the inverse passes of an
+// apply, on an embedding of the sampler's own.  Both kernels are one body (fftcov_pass_body<GEN>); the apply's instance has the
+// registers (44 VGPRs) and the LDS it had before the draw existed, the draw's takes 49 VGPRs and no scratch.
 #include <math.h>
 
 #include <algorithm>
@@ -27,6 +32,7 @@
 #include <vector>
 
 #include "hfmi_kcov_eval.h"
+#include "hfmi_randn_math.h"
 
 struct fftcov_state {
   int d = 0;
@@ -40,7 +46,8 @@ struct fftcov_state {
   dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
   dev_buf<double2> work;   // work_pairs() arrays of prod P_c entries
-  fftcov_plan plan;        // the passes of an apply
+  int growth = 0;          // the embedding's: 0 for an operator, a sampler may double every P_c up to three times
+  fftcov_plan plan;        // the passes of an apply, or of a draw (a sampler's state)
   int work_pairs() const { return (int)(work.bytes() / (size_t)plan.pair_bytes); }
 };
 
@@ -74,7 +81,29 @@ __device__ __forceinline__ double2 fc_twiddle(const double2* ltw, int k, int qm)
   return k >= qm ? double2{t.y, -t.x} : t;
 }
 
-__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_args A) {
+// what the generated load of a draw's first pass adds (hfmi_fftcov_plan.h: the noise's element map).  A type of its own, so that the apply's
+// kernel takes the argument block it always took.
+struct fftcov_gen_args {
+  uint32_t k0, k1;         // the seed
+  int64_t pair0;           // pair index of blockIdx.y = 0 in the stream of draws
+};
+
+// storage entries e0 (even) and e0 + 1 of pair `gp`: sqrt(max(lambda, 0)) (z_a + i z_b), four normals of one Philox output
+__device__ __forceinline__ void fc_coloured_noise(const fftcov_gen_args& G, uint32_t gp, int64_t e0, const double* lambda,
+                                                  const hfmi_rng::normal_consts& kc, double2& v0, double2& v1) {
+  const int64_t q = e0 >> 1;
+  uint32_t r[4];
+  double z[4];
+  hfmi_rng::philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), gp, FFTCOV_GEN_STREAM, G.k0, G.k1, r);
+  hfmi_rng::box_muller4(r, kc, z);
+  const double s0 = sqrt(fmax(lambda[e0], 0.0)), s1 = sqrt(fmax(lambda[e0 + 1], 0.0));
+  v0 = double2{s0 * z[0], s0 * z[1]};
+  v1 = double2{s1 * z[2], s1 * z[3]};
+}
+
+// GEN: the load is generated (the first pass of a draw); otherwise the pass of an apply, compiled to the code it always was
+template <bool GEN>
+__device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, const fftcov_gen_args& G) {
   extern __shared__ double2 fc_lds[];
   __shared__ int64_t lbase[FFTCOV_MAX_LINES];    // first entry of the line in the pair's array, -1: no such line
   __shared__ int64_t gbase[FFTCOV_MAX_LINES];    // axis-0 lines: grid node of position 0
@@ -105,24 +134,51 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_
   const bool strided = A.stride > 1;
   const int c0 = A.col0 + 2 * pair;
   const bool has1 = c0 + 1 < A.ncols;
-  for (int e = tid; e < total; e += nt) {
-    const int j = strided ? (e & (lpw - 1)) : (e >> logL);
-    const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
-    double2 v = double2{0.0, 0.0};
-    const int64_t b = lbase[j];
-    if (b >= 0 && p < A.nload) {
-      if (A.flags & FFTCOV_SCATTER) {
-        const int64_t g = gbase[j] + p;
-        const int64_t pt = A.inv ? A.inv[g] : g;
-        if (pt >= 0) {
-          v.x = A.W[(int64_t)c0 * A.ldw + pt];
-          if (has1) v.y = A.W[(int64_t)(c0 + 1) * A.ldw + pt];
-        }
-      } else {
-        v = buf[b + (int64_t)p * A.stride];
+  if constexpr (GEN) {
+    // one thread per two adjacent storage entries: positions p, p + 1 of a line on the contiguous axis, lines j, j + 1 (j even, so the
+    // first entry is even: line0 and every stride above the axis are) at one position on a strided one.  No operand but Lambda is
+    // read; the VALU work of the normals is what this part costs.  The bank layout of these LDS stores has not been measured either.
+    const hfmi_rng::normal_consts kc = hfmi_rng::make_consts(1.0);
+    const uint32_t gp = (uint32_t)(G.pair0 + pair);
+    if (total == 1) {      // prod P_c = 1: the single entry 0
+      if (tid == 0) {
+        uint32_t r[4];
+        double z[4];
+        hfmi_rng::philox4x32_10(0u, 0u, gp, FFTCOV_GEN_STREAM, G.k0, G.k1, r);
+        hfmi_rng::box_muller4(r, kc, z);
+        const double s0 = sqrt(fmax(A.lambda[0], 0.0));
+        x[0] = double2{s0 * z[0], s0 * z[1]};
       }
     }
-    x[j * ls + p] = v;
+    for (int u = tid; u < (total >> 1); u += nt) {
+      const int j = strided ? 2 * (u & ((lpw >> 1) - 1)) : (u >> (logL - 1));
+      const int p = strided ? (u >> (A.loglpw - 1)) : 2 * (u & ((L >> 1) - 1));
+      double2 v0 = double2{0.0, 0.0}, v1 = v0;
+      const int64_t b = lbase[j];
+      if (b >= 0) fc_coloured_noise(G, gp, b + (int64_t)p * A.stride, A.lambda, kc, v0, v1);
+      x[j * ls + p] = v0;
+      x[strided ? (j + 1) * ls + p : j * ls + p + 1] = v1;
+    }
+  } else {
+    for (int e = tid; e < total; e += nt) {
+      const int j = strided ? (e & (lpw - 1)) : (e >> logL);
+      const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+      double2 v = double2{0.0, 0.0};
+      const int64_t b = lbase[j];
+      if (b >= 0 && p < A.nload) {
+        if (A.flags & FFTCOV_SCATTER) {
+          const int64_t g = gbase[j] + p;
+          const int64_t pt = A.inv ? A.inv[g] : g;
+          if (pt >= 0) {
+            v.x = A.W[(int64_t)c0 * A.ldw + pt];
+            if (has1) v.y = A.W[(int64_t)(c0 + 1) * A.ldw + pt];
+          }
+        } else {
+          v = buf[b + (int64_t)p * A.stride];
+        }
+      }
+      x[j * ls + p] = v;
+    }
   }
   __syncthreads();
 
@@ -236,6 +292,10 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_
   }
 }
 
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_args A) { fftcov_pass_body<false>(A, fftcov_gen_args{}); }
+// the first pass of a draw (hfmi_grid_sampler_draw): generated load, inverse stages, store or gather
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_draw(fftcov_pass_args A, fftcov_gen_args G) { fftcov_pass_body<true>(A, G); }
+
 // the circulant's first column: entry (j0, j1, j2) is the kernel at the offsets min(j_c, P_c - j_c) h_c, the nugget on entry 0
 __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* buf, int64_t total, int l0, int l1, int P0, int P1, int P2,
                                                        double h0, double h1, double h2) {
@@ -260,8 +320,10 @@ __global__ __launch_bounds__(256) void k_fftcov_spectrum(const double2* buf, dou
     lambda[e] = buf[e].x * scale;
 }
 
+// gen: the pass's load is generated (FFTCOV_GEN, the first pass of a draw); null for every pass that loads
 static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftcov_plan& p, const fftcov_pass& q, int pairs, int col0,
-                              const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate) {
+                              const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate,
+                              const fftcov_gen_args* gen = nullptr) {
   fftcov_pass_args A;
   A.buf = st->work;
   A.pair_stride = p.Ptot;
@@ -278,7 +340,15 @@ static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftco
   if (q.lds + FFTCOV_STATIC_LDS > FFTCOV_LDS_BYTES || q.lpw > FFTCOV_MAX_LINES || q.grid_x > 0x7fffffff || pairs > 65535)
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: a pass of %d lines x %d entries (%d bytes of LDS, grid %lld x %d) cannot be launched", q.lpw,
               q.L, q.lds, (long long)q.grid_x, pairs);
-  hipLaunchKernelGGL(k_fftcov_pass, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A);
+  if (((q.flags & FFTCOV_GEN) != 0) != (gen != nullptr)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: a generated load and its seed go together");
+  if (gen) {
+    // two adjacent storage entries per thread: a line of >= 2 positions, or >= 2 adjacent lines from an even line number
+    const bool paired = q.stride > 1 ? (q.lpw >= 2 && q.nlines % 2 == 0) : (q.L >= 2 || (int64_t)q.lpw * q.L == 1);
+    if (!paired) HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: the noise pass of %d lines x %d entries does not pair its entries", q.lpw, q.L);
+    hipLaunchKernelGGL(k_fftcov_draw, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A, *gen);
+  } else {
+    hipLaunchKernelGGL(k_fftcov_pass, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A);
+  }
   HIP_TRY(hipGetLastError());
   return HFMI_OK;
 }
@@ -287,10 +357,12 @@ int64_t fftcov_points(const fftcov_state* st) { return st->N; }
 
 void fftcov_destroy(fftcov_state* st) { delete st; }
 
-static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* host_inv) {
+// inv: the node map's inverse, on the host, or on the device (inv_on_device: a sampler copies its operator's)
+static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* inv, bool inv_on_device = false) {
   const fftcov_plan& p = st->plan;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_pass, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
+  HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_draw, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   // the work buffer of one pair and Lambda: what decides whether the padded grid fits at all
   hipError_t e = (hipError_t)st->work.alloc((size_t)p.pair_bytes / sizeof(double2));
   if (e == hipSuccess) e = (hipError_t)st->lambda.alloc((size_t)p.Ptot);
@@ -298,9 +370,9 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
     HFMI_FAIL(HFMI_ERR_HIP, "kernel_cov_grid: the padded grid %d x %d x %d needs %lld bytes of work buffer per pair of vectors and %lld bytes of spectrum: %s",
               p.P[0], p.P[1], p.P[2], (long long)p.pair_bytes, (long long)(p.Ptot * 8), hipGetErrorString(e));
   }
-  if (host_inv) {
+  if (inv) {
     OWN_TRY(st->inv.alloc((size_t)st->nnodes));
-    HIP_TRY(hipMemcpy(st->inv, host_inv, (size_t)st->nnodes * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st->inv, inv, (size_t)st->nnodes * sizeof(int64_t), inv_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   }
   // twiddles: long double on the host, rounded once
   std::vector<double2> tw((size_t)p.twiddles);
@@ -318,7 +390,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
   hipLaunchKernelGGL(k_fftcov_column, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, st->work, p.Ptot, fftcov_log2(p.P[0]),
                      fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
   HIP_TRY(hipGetLastError());
-  const fftcov_plan sp = fftcov_plan_passes(st->d, st->n, true);
+  const fftcov_plan sp = fftcov_sample_plan_passes(st->d, st->n, st->growth, true);   // growth 0: fftcov_plan_passes(d, n, true)
   for (int i = 0; i < sp.npasses; ++i) HFMI_TRY(fftcov_launch_pass(ctx, st, sp, sp.pass[i], 1, 0, nullptr, 0, nullptr, 0, 0, 0));
   hipLaunchKernelGGL(k_fftcov_spectrum, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, st->work, st->lambda, p.Ptot, 1.0 / (double)p.Ptot);
   HIP_TRY(hipGetLastError());
@@ -365,9 +437,8 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
   return HFMI_OK;
 }
 
-int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
-  if (nvec < 1) return HFMI_OK;
-  fftcov_plan p = st->plan;
+// chunks of `nvec` columns, and a work buffer that holds one
+static int fftcov_fit_work(hfmi_ctx* ctx, fftcov_state* st, fftcov_plan& p, int nvec) {
   fftcov_plan_chunks(p, nvec, 0, fftcov_pairs_knob());
   if (p.chunk_pairs > st->work_pairs()) {
     // grow the work buffer to the chunk: the larger one first, so that when the device has no room for it the apply runs in the
@@ -380,9 +451,177 @@ int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, 
       fftcov_plan_chunks(p, nvec, 0, st->work_pairs());
     }
   }
+  return HFMI_OK;
+}
+
+int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+  if (nvec < 1) return HFMI_OK;
+  fftcov_plan p = st->plan;
+  HFMI_TRY(fftcov_fit_work(ctx, st, p, nvec));
   for (int c = 0; c < p.nchunks; ++c) {
     const int pair0 = c * p.chunk_pairs, pairs = std::min(p.chunk_pairs, p.pairs - pair0);
     for (int i = 0; i < p.npasses; ++i) HFMI_TRY(fftcov_launch_pass(ctx, st, p, p.pass[i], pairs, 2 * pair0, W, ldw, Y, ldy, nvec, accumulate));
   }
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ exact draws m ~ N(0, C) by circulant embedding (hfmi_grid_sampler_*)
+// The rules -- the grown embedding, the passes of a draw, the noise's element map, the floor and the clip's bound -- are in
+// hfmi_fftcov_plan.h.  A sampler is a state of its own (grid, kernel, node map, twiddles, Lambda of ITS embedding, work buffer): it
+// does not refer to the operator it was made from.
+
+// extremes of the stored spectrum: a plain two-stage reduction, fixed grid, fixed order, vector stores and no atomics, so that two
+// creations agree bit for bit
+struct fftcov_extremes {
+  double lmin, lmax, negsum;
+  int64_t nneg;
+};
+constexpr int FFTCOV_EXT_THREADS = 256;
+constexpr int FFTCOV_EXT_BLOCKS = 256;   // most partial records: the second stage is one workgroup with one thread each
+__device__ __forceinline__ fftcov_extremes fc_ext_join(const fftcov_extremes& a, const fftcov_extremes& b) {
+  return fftcov_extremes{fmin(a.lmin, b.lmin), fmax(a.lmax, b.lmax), a.negsum + b.negsum, a.nneg + b.nneg};
+}
+// FINAL: thread t of the one workgroup takes partial record t; otherwise block b takes the entries b, b + blocks, ... of 256-entry tiles
+template <bool FINAL>
+__global__ __launch_bounds__(FFTCOV_EXT_THREADS) void k_fftcov_extremes(const double* lambda, int64_t total, const fftcov_extremes* part,
+                                                                        int nparts, fftcov_extremes* out) {
+  __shared__ fftcov_extremes red[FFTCOV_EXT_THREADS];
+  const int tid = threadIdx.x;
+  fftcov_extremes v{INFINITY, -INFINITY, 0.0, 0};
+  if (FINAL) {
+    if (tid < nparts) v = part[tid];
+  } else {
+    for (int64_t e = (int64_t)blockIdx.x * FFTCOV_EXT_THREADS + tid; e < total; e += (int64_t)gridDim.x * FFTCOV_EXT_THREADS) {
+      const double l = lambda[e];
+      v.lmin = fmin(v.lmin, l);
+      v.lmax = fmax(v.lmax, l);
+      if (l < 0.0) v.negsum += l, ++v.nneg;
+    }
+  }
+  red[tid] = v;
+  __syncthreads();
+  for (int s = FFTCOV_EXT_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] = fc_ext_join(red[tid], red[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) out[FINAL ? 0 : blockIdx.x] = red[0];
+}
+
+static int fftcov_spectrum_extremes(hfmi_ctx* ctx, const fftcov_state* st, fftcov_extremes* host) {
+  const int64_t total = st->plan.Ptot;
+  const int blocks = (int)std::min<int64_t>((total + FFTCOV_EXT_THREADS - 1) / FFTCOV_EXT_THREADS, FFTCOV_EXT_BLOCKS);
+  dev_buf<fftcov_extremes> part;
+  OWN_TRY(part.alloc((size_t)blocks + 1));
+  hipLaunchKernelGGL(k_fftcov_extremes<false>, dim3((unsigned)blocks), dim3(FFTCOV_EXT_THREADS), 0, ctx->stream, st->lambda.get(), total, nullptr, 0,
+                     part.get());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_fftcov_extremes<true>, dim3(1), dim3(FFTCOV_EXT_THREADS), 0, ctx->stream, nullptr, 0, part.get(), blocks, part.get() + blocks);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, part.get() + blocks, sizeof(*host), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return HFMI_OK;
+}
+
+struct hfmi_grid_sampler {
+  hfmi_ctx* ctx = nullptr;
+  std::unique_ptr<fftcov_state, void (*)(fftcov_state*)> st{nullptr, fftcov_destroy};
+  double lambda_min = 0.0, lambda_max = 0.0;   // eigenvalues of the embedding's circulant (the stored spectrum times prod P_c)
+  int64_t n_clipped = 0;
+  double cov_error_bound = 0.0;
+};
+
+// the state of the operator's grid at one growth, its spectrum and the extremes of that
+static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, std::unique_ptr<fftcov_state, void (*)(fftcov_state*)>& st,
+                            fftcov_extremes* ext) {
+  st.reset(new (std::nothrow) fftcov_state());
+  if (!st) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  st->d = src->d;
+  for (int c = 0; c < 3; ++c) st->n[c] = src->n[c], st->h[c] = src->h[c];
+  st->N = src->N, st->nnodes = src->nnodes;
+  st->family = src->family, st->sigma = src->sigma, st->ell = src->ell, st->nugget = src->nugget;
+  st->growth = growth;
+  st->plan = fftcov_sample_plan_passes(st->d, st->n, growth, false);
+  HFMI_TRY(fftcov_create_device(ctx, st.get(), src->inv, true));
+  return fftcov_spectrum_extremes(ctx, st.get(), ext);
+}
+
+extern "C" int hfmi_grid_sampler_create(hfmi_op* op, int max_growth, int clip, hfmi_grid_sampler** out) {
+  if (!op || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (op->kind != OP_KERNEL_COV_GRID || !op->fc)
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: the operator is not a kernel covariance on a grid (hfmi_op_kernel_cov_grid)");
+  if (max_growth < 0 || max_growth > FFTCOV_MAX_GROWTH)
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: max_growth = %d outside 0..%d", max_growth, FFTCOV_MAX_GROWTH);
+  hfmi_ctx* ctx = op->ctx;
+  const fftcov_state* src = op->fc;
+  std::unique_ptr<hfmi_grid_sampler> s(new (std::nothrow) hfmi_grid_sampler());
+  if (!s) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  s->ctx = ctx;
+  fftcov_extremes ext{};
+  bool definite = false;
+  int g = std::min(fftcov_min_growth_knob(), max_growth);
+  while (g > 0 && !fftcov_growth_feasible(src->d, src->n, g)) --g;
+  for (;; ++g) {
+    const int status = grid_sampler_try(ctx, src, g, s->st, &ext);
+    if (status != HFMI_OK) {
+      (void)hipStreamSynchronize(ctx->stream);    // before the buffers go: the kernels queued so far use them
+      return status;
+    }
+    definite = ext.lmin >= -fftcov_floor(s->st->plan.Ptot, ext.lmax);
+    if (definite || g == max_growth || !fftcov_growth_feasible(src->d, src->n, g + 1)) break;
+  }
+  if (!definite && !clip)
+    HFMI_FAIL(HFMI_ERR_INVALID,
+              "grid_sampler: the embedding %d x %d x %d (growth %d, the last one tried) is indefinite: lambda_min / lambda_max = %.3e; allow a "
+              "larger growth or ask for clipping",
+              s->st->plan.P[0], s->st->plan.P[1], s->st->plan.P[2], g, ext.lmin / ext.lmax);
+  const double P = (double)s->st->plan.Ptot;
+  s->lambda_min = ext.lmin * P, s->lambda_max = ext.lmax * P;
+  s->n_clipped = definite ? 0 : ext.nneg;
+  s->cov_error_bound = definite ? 0.0 : -ext.negsum;
+  *out = s.release();
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_grid_sampler_info(const hfmi_grid_sampler* s, int* growth, int64_t* P, double* lambda_min, double* lambda_max,
+                                      int64_t* n_clipped, double* cov_error_bound) {
+  if (!s) HFMI_FAIL(HFMI_ERR_INVALID, "null sampler");
+  if (growth) *growth = s->st->growth;
+  if (P)
+    for (int c = 0; c < 3; ++c) P[c] = s->st->plan.P[c];
+  if (lambda_min) *lambda_min = s->lambda_min;
+  if (lambda_max) *lambda_max = s->lambda_max;
+  if (n_clipped) *n_clipped = s->n_clipped;
+  if (cov_error_bound) *cov_error_bound = s->cov_error_bound;
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_grid_sampler_draw(hfmi_grid_sampler* s, const hfmi_block* Y, uint64_t seed, int64_t first_sample, int accumulate) {
+  if (!s || !Y) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  fftcov_state* st = s->st.get();
+  if (Y->N != st->N) HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: draws have length %lld, the block's vectors %lld", (long long)st->N, (long long)Y->N);
+  if (first_sample < 0 || (first_sample & 1))
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: first_sample = %lld must be even and not negative (draws 2 p and 2 p + 1 are one transform)",
+              (long long)first_sample);
+  const int ncols = Y->nvec;
+  if (first_sample / 2 + (ncols + 1) / 2 > ((int64_t)1 << 32))
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: a seed has 2^33 draws, first_sample = %lld with %d columns goes past them", (long long)first_sample, ncols);
+  if (ncols < 1) return HFMI_OK;
+  hfmi_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  fftcov_plan p = st->plan;
+  HFMI_TRY(fftcov_fit_work(ctx, st, p, ncols));
+  for (int c = 0; c < p.nchunks; ++c) {
+    const int pair0 = c * p.chunk_pairs, pairs = std::min(p.chunk_pairs, p.pairs - pair0);
+    const fftcov_gen_args gen{(uint32_t)seed, (uint32_t)(seed >> 32), first_sample / 2 + pair0};
+    for (int i = 0; i < p.npasses; ++i)
+      HFMI_TRY(fftcov_launch_pass(ctx, st, p, p.pass[i], pairs, 2 * pair0, nullptr, 0, Y->p, Y->ld, ncols, accumulate != 0, i == 0 ? &gen : nullptr));
+  }
+  return HFMI_OK;
+}
+
+extern "C" int hfmi_grid_sampler_destroy(hfmi_grid_sampler* s) {
+  if (!s) return HFMI_OK;
+  (void)hipStreamSynchronize(s->ctx->stream);     // draws queued so far use the buffers
+  delete s;
   return HFMI_OK;
 }

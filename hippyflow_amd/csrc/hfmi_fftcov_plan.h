@@ -190,3 +190,96 @@ inline void fftcov_plan_words(const fftcov_plan& p, int64_t* w) {
     memcpy(w + FFTCOV_HEAD_WORDS + i * FFTCOV_PASS_WORDS, v, sizeof(v));
   }
 }
+
+// ------------------------------------------------------------------ the draw m ~ N(0, C) by circulant embedding (hfmi_grid_sampler_*)
+// A draw is the inverse half of an apply fed with coloured noise:  z = IFFT_unnormalised( sqrt(max(Lambda / P, 0)) (xi_1 + i xi_2) ) with
+// xi i.i.d. N(0, 1) on the padded grid; Re z and Im z on the nodes are two independent draws (Dietrich-Newsam, Wood-Chan).  Lambda's
+// storage order is arbitrary to i.i.d. noise, so nothing is permuted here either.  The square root needs a non-negative spectrum, which the
+// minimal embedding often lacks, so the sampler has an embedding of its own:  growth g doubles every P_c with n_c > 1 g times,
+// P_c = fftcov_embed_len(n_c) << g, feasible while every P_c <= FFTCOV_MAXP.
+//
+// Passes of a draw in d dimensions (d of them):  ONE pass along axis d - 1 whose load is GENERATED (FFTCOV_GEN: no operand is read but
+// Lambda), runs the inverse stages and stores n_{d-1} positions -- its lines are those of the apply's middle pass, every position of
+// the axes below -- then the apply's inverse passes along d - 2 .. 0, the last with the gather fused.  d = 1: generate, inverse, gather.
+// Pairs per chunk as fftcov_plan_chunks.
+//
+// The noise's element map (hfmi_randn_math.h has the probe draw's; oracle/philox.py is the checker of the integer stream): storage
+// entries 2 q and 2 q + 1 of pair p's padded array (entry e = s_0 + P_0 (s_1 + P_1 s_2), s_c the storage position along axis c) take one
+// Philox output,  x = philox4x32_10(ctr = (q lo, q hi, p, FFTCOV_GEN_STREAM), key = (seed lo, seed hi)),  (z_0 .. z_3) = box_muller4(x):
+// entry 2 q is sqrt(max(lambda[2 q], 0)) (z_0 + i z_1), entry 2 q + 1 is sqrt(max(lambda[2 q + 1], 0)) (z_2 + i z_3); prod P_c = 1 has the
+// single entry 0.  It depends on (seed, pair, storage position) only: lines per workgroup, chunks and "fftcov_pairs" change no bit.  Adjacent
+// storage entries are adjacent positions of a line on the contiguous axis and adjacent lines of a workgroup on a strided one (a strided
+// pass takes >= 2 lines, line numbers from an even one), so one thread always holds both and all four normals are used.
+//
+// Eigenvalues that are negative only by rounding:  floor = FFTCOV_FLOOR_C eps log2(prod P_c) lambda_max; entries in [-floor, 0) become 0
+// silently, an embedding whose lambda_min < -floor is indefinite.  FFTCOV_FLOOR_C = 16: in fp64 the squared exponential's spectra that
+// are zero to working precision come out (numpy's FFT) at -1.7e-16 (8 x 8, spacing 1/8, ell 0.4, g = 2, 3) and at -5.4e-16 / -0.9e-16
+// (33 nodes, spacing 1/32, ell 1, g = 2 / 3) of lambda_max, i.e. 0.04 to 0.27 of eps log2(prod P_c), while the smallest genuine negative
+// of the same grids (8 x 8, g = 1: -3.7e-7) is 1.7e8 of them: 16 leaves a factor 60 over the rounding seen, for the device's own
+// transform of the column, and 1e7 under anything real (tests/test_grid_sampler_twin_cpu.py asserts a factor 16 and 1e6).
+//
+// Clipping (the caller asked for it and no growth was definite): all negative entries are set to 0.  The covariance of the draw is then
+// C + E, E the restriction of the circulant with the spectrum -min(Lambda, 0): a positive semidefinite circulant, whose entries are
+// bounded in magnitude by its constant diagonal  sum |lambda^-| / prod P_c  = minus the sum of the stored negative Lambda / P.  That sum
+// is cov_error_bound: |Cov(draw) - C|_ij <= cov_error_bound for every i, j.
+enum { FFTCOV_GEN = 32 };
+constexpr uint32_t FFTCOV_GEN_STREAM = 0x67726964u;   // "grid": counter word 3 of the noise
+constexpr int FFTCOV_MAX_GROWTH = 3;
+constexpr double FFTCOV_FLOOR_C = 16.0;
+
+// tuning key "fftcov_min_growth": the growth a sampler's creation tries first (tests and measurements: a larger embedding than the rule takes)
+inline int& fftcov_min_growth_knob() {
+  static int v = 0;
+  return v;
+}
+inline bool fftcov_sample_knob_set(const char* key, int v) {
+  if (strcmp(key, "fftcov_min_growth") || v < 0 || v > FFTCOV_MAX_GROWTH) return false;
+  fftcov_min_growth_knob() = v;
+  return true;
+}
+
+inline bool fftcov_growth_feasible(int d, const int64_t* n, int growth) {
+  if (growth < 0 || growth > FFTCOV_MAX_GROWTH) return false;
+  for (int c = 0; c < d; ++c)
+    if (n[c] > 1 && ((int64_t)fftcov_embed_len(n[c]) << growth) > FFTCOV_MAXP) return false;
+  return true;
+}
+inline double fftcov_floor(int64_t Ptot, double lambda_max) {
+  const int l = fftcov_log2(Ptot);
+  return FFTCOV_FLOOR_C * 2.220446049250313e-16 * (double)(l > 1 ? l : 1) * lambda_max;
+}
+
+// the grown embedding and the passes of a draw; spectrum: the d forward passes over the whole padded array, as fftcov_plan_passes
+inline fftcov_plan fftcov_sample_plan_passes(int d, const int64_t* n, int growth, bool spectrum) {
+  fftcov_plan p;
+  memset(&p, 0, sizeof(p));
+  p.d = d;
+  p.Ptot = 1;
+  p.Pmax = 1;
+  for (int c = 0; c < 3; ++c) {
+    p.n[c] = c < d ? n[c] : 1;
+    p.P[c] = p.n[c] > 1 ? fftcov_embed_len(p.n[c]) << growth : 1;
+    p.Ptot *= p.P[c];
+    if (p.P[c] > p.Pmax) p.Pmax = p.P[c];
+  }
+  p.twiddles = p.Pmax / 4 > 1 ? p.Pmax / 4 : 1;
+  p.pair_bytes = 16 * p.Ptot;
+  int64_t ext[3];
+  for (int c = 0; c < 3; ++c) ext[c] = spectrum ? p.P[c] : p.n[c];
+  int np = 0;
+  if (spectrum) {
+    for (int a = 0; a < d; ++a) p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_FWD, ext, p.P[a], p.P[a]);
+  } else {
+    p.pass[np++] = fftcov_make_pass(p, d - 1, FFTCOV_GEN | FFTCOV_INV | (d == 1 ? FFTCOV_GATHER : 0), ext, p.P[d - 1], (int)p.n[d - 1]);
+    for (int a = d - 2; a >= 0; --a)
+      p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_INV | (a == 0 ? FFTCOV_GATHER : 0), ext, p.P[a], (int)p.n[a]);
+  }
+  p.npasses = np;
+  return p;
+}
+
+// hfmi_fftcov_sample_plan_predict's record: the words of fftcov_plan_words, word 13 = the growth
+inline void fftcov_sample_plan_words(const fftcov_plan& p, int growth, int64_t* w) {
+  fftcov_plan_words(p, w);
+  w[13] = growth;
+}

@@ -334,7 +334,13 @@ class GridKernelCovarianceOperator(DeviceOperator):
     None = all nodes in order); ``origin``: coordinates of node 0 (only ``.points`` sees it).  ``.shape`` is the operator's (N, N) as
     for every ``DeviceOperator``; the grid is ``.grid_shape``.  Two vectors ride one complex transform, so a column's result depends
     on its partner in the last bits; two applies of the same block are bit-identical.  ``matrix_free()`` is the
-    ``KernelCovarianceOperator`` over the same points (what ``pivoted_cholesky`` takes)."""
+    ``KernelCovarianceOperator`` over the same points (what ``pivoted_cholesky`` takes).
+
+    ``sampler(max_growth=3, on_indefinite="raise" | "clip", seed=0)`` returns a ``GridFieldSampler``: exact draws m ~ N(0, C) by
+    circulant embedding, d passes per pair of draws with the noise generated on the device, on an embedding grown until its spectrum
+    is non-negative (or clipped, with a reported bound on the covariance error).  It is the draw to use on a grid, above all for rough
+    kernels, short correlation lengths and large grids; ``PivotedCholesky.sample`` (of ``matrix_free()``) draws from L L^T instead and is
+    the one to prefer for draws at scattered points, or when a factor of small rank is at hand anyway."""
 
     def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None):
         n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget)
@@ -354,6 +360,69 @@ class GridKernelCovarianceOperator(DeviceOperator):
     def matrix_free(self):
         """The ``KernelCovarianceOperator`` over the same points: 2 N^2 k flops per apply, no padded grid in memory."""
         return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx)
+
+    def sampler(self, max_growth=3, on_indefinite="raise", seed=0):
+        """A ``GridFieldSampler``: exact draws m ~ N(0, C) at the cost of an apply (see the class)."""
+        return GridFieldSampler(self, max_growth=max_growth, on_indefinite=on_indefinite, seed=seed)
+
+
+class GridFieldSampler:
+    """Exact draws ``m ~ N(0, C)`` of a ``GridKernelCovarianceOperator`` by circulant embedding (hfmi_grid_sampler_*, hfmi_fftcov.hip):
+    coloured noise ``sqrt(Lambda / P) (xi_1 + i xi_2)`` generated on the device, transformed back by the operator's inverse passes; the real
+    and the imaginary part on the nodes are two independent draws, d passes per pair against the 2 d - 1 of an apply.  The sampler has
+    an embedding of its own: the minimal one is often indefinite, so every padded axis is doubled ``growth`` <= ``max_growth`` (0..3)
+    times until no eigenvalue is below minus a rounding floor.  If none is definite, ``on_indefinite="raise"`` raises ``HfmiError`` with
+    ``lambda_min / lambda_max`` of the last growth; ``"clip"`` zeroes the negative eigenvalues and reports ``n_clipped`` and
+    ``cov_error_bound``: every entry of ``Cov(draw) - C`` is at most that in magnitude.  ``growth``, ``embedding`` (P_c per grid axis),
+    ``lambda_min``, ``lambda_max``, ``n_clipped``, ``cov_error_bound`` are attributes.  The sampler keeps copies of what it needs: it does not
+    keep the operator alive.  Prefer ``PivotedCholesky.sample`` when the draws are wanted at scattered points (``sample_at``), when the
+    factor is needed anyway and its rank is small (smooth kernels, long correlation lengths), or when even three doublings leave a
+    clip whose bound is too large; prefer this one for rough kernels, short correlation lengths and large grids, where it is exact
+    and costs O(P log P) per pair."""
+
+    def __init__(self, op, max_growth=3, on_indefinite="raise", seed=0):
+        if not isinstance(op, GridKernelCovarianceOperator):
+            raise ValueError("GridFieldSampler: a GridKernelCovarianceOperator is required (got %s)" % type(op).__name__)
+        if on_indefinite not in ("raise", "clip"):
+            raise ValueError("on_indefinite is 'raise' or 'clip', got %r" % (on_indefinite,))
+        self.ctx = op.ctx
+        self.N = op.shape[0]
+        self.seed = int(seed)
+        self._next = 0                   # sample_block's counter: the next draw of the stream `seed`, kept even
+        self.handle = C.c_void_p()
+        L.call("hfmi_grid_sampler_create", op._op, int(max_growth), 1 if on_indefinite == "clip" else 0, C.byref(self.handle))
+        g, P, lo, hi, nc, bound = C.c_int(), (C.c_int64 * 3)(), C.c_double(), C.c_double(), C.c_int64(), C.c_double()
+        L.call("hfmi_grid_sampler_info", self.handle, C.byref(g), P, C.byref(lo), C.byref(hi), C.byref(nc), C.byref(bound))
+        self.growth = g.value
+        self.embedding = tuple(int(v) for v in P[:len(op.grid_shape)])
+        self.lambda_min, self.lambda_max = lo.value, hi.value
+        self.n_clipped, self.cov_error_bound = int(nc.value), bound.value
+
+    def sample(self, n, seed, first=0, out=None, accumulate=False):
+        """Draws ``first .. first + n - 1`` of the stream ``seed`` as a ``MultiVector`` of ``n`` vectors of length N (``out``, or a new
+        one; ``accumulate`` adds to ``out``).  Draws 2 p and 2 p + 1 are one transform: ``first`` must be even, and consecutive calls with
+        ``first = 0, n, 2 n, ...`` (n even) give the bits of one large call."""
+        if out is None:
+            out = MultiVector(self.N, int(n), ctx=self.ctx)
+        elif out.nvec() != int(n):
+            raise ValueError("sample: out has %d vectors, n = %d" % (out.nvec(), int(n)))
+        L.call("hfmi_grid_sampler_draw", self.handle, out.handle, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(first), 1 if accumulate else 0)
+        return out
+
+    def sample_block(self, n):
+        """(n, N) array of the next ``n`` draws of the stream of the seed given at construction: what ``_prior_sample_block`` asks of a
+        prior.  The counter advances by ``n`` rounded up to even (a dropped imaginary part is not handed out later)."""
+        X = self.sample(n, self.seed, first=self._next)
+        self._next += int(n) + (int(n) & 1)
+        return np.ascontiguousarray(X.to_dense().T)
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                L.load().hfmi_grid_sampler_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
 
 
 def _is_null_collective(collective):

@@ -66,6 +66,7 @@ typedef struct hfmi_op hfmi_op;
 typedef struct hfmi_comm hfmi_comm;
 typedef struct hfmi_amg hfmi_amg;
 typedef struct hfmi_pchol hfmi_pchol;
+typedef struct hfmi_grid_sampler hfmi_grid_sampler;
 
 /* ---------------------------------------------------------------- context */
 HFMI_API const char* hfmi_last_error(void);
@@ -223,6 +224,35 @@ HFMI_API int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n /* d
  *     (l mod stride) + ((l div stride) mod oe0) os0 + ((l div stride) div oe0) os1. */
 #define HFMI_FFTCOV_PLAN_WORDS 96
 HFMI_API int hfmi_fftcov_plan_predict(int d, const int64_t* n, int nvec, int64_t budget_bytes, int64_t* words);
+/*     EXACT draws m ~ N(0, C) of that covariance at the cost of an apply, by circulant embedding (Dietrich-Newsam, Wood-Chan):
+ *       z = IFFT_unnormalised( sqrt(max(Lambda / P, 0)) (xi_1 + i xi_2) ),  xi i.i.d. N(0, 1) on the padded grid;
+ *     Re z and Im z on the nodes are two independent draws.  d passes per pair of draws (an apply has 2 d - 1), no operand read but
+ *     Lambda: the first pass generates its load from Philox4x32-10 and the probe draw's Box-Muller (the element map, which depends
+ *     on (seed, pair, storage position) only, is stated in csrc/hfmi_fftcov_plan.h).  The square root needs Lambda >= 0, which the
+ *     operator's minimal embedding often lacks, so the sampler has an embedding of its own: growth g doubles every P_c with n[c] > 1
+ *     g times (while every P_c <= 4096).  hfmi_grid_sampler_create copies grid, kernel and node map from the operator (the sampler
+ *     does not depend on the operator's lifetime), then tries g = 0 .. max_growth and takes the first whose
+ *     lambda_min >= -floor, floor = 16 eps log2(prod P_c) lambda_max: eigenvalues in [-floor, 0) are rounding and become 0 silently.
+ *     If none qualifies: clip = 0 is HFMI_ERR_INVALID with lambda_min / lambda_max at the last growth tried in the message; clip = 1
+ *     takes that growth, sets every negative eigenvalue to 0 and reports their number and cov_error_bound = sum |lambda^-| / prod P_c:
+ *     the clipped part is a positive semidefinite circulant with that constant diagonal, so |Cov(draw) - C|_ij <= cov_error_bound for
+ *     all i, j.  hfmi_grid_sampler_info: the growth taken, P_c, the extreme eigenvalues of the embedding, n_clipped and the bound (0, 0
+ *     unless clipped); any pointer may be NULL.
+ *     hfmi_grid_sampler_draw: column j of Y (+)= draw first_sample + j of the stream `seed`; draws 2 p and 2 p + 1 are Re and Im of pair
+ *     p, so first_sample must be even, an odd number of columns drops the last Im, and chunks of a stream (first_sample = 0, 64, ...)
+ *     reproduce one large call bit for bit, whatever "fftcov_pairs" says.  Block storage contract as every operator: padding rows
+ *     untouched, accumulate != 0 adds.  No atomics.  Y is const as a HANDLE (its pointer, length and leading dimension are read, never
+ *     changed); the draw stores into the block's memory, rows below N of its columns.  The contract cases of this writer are in
+ *     tests/test_gpu_grid_sampler.py.
+ *     HFMI_ERR_INVALID: not a grid covariance operator, max_growth outside 0..3, Y of another length, first_sample odd or negative
+ *     or past the 2^33 draws of a seed.  hfmi_fftcov_sample_plan_predict: the draw's launch plan without a device, the words of
+ *     hfmi_fftcov_plan_predict (pass flag 32: generated load) with word 13 = growth; HFMI_ERR_INVALID for an infeasible growth. */
+HFMI_API int hfmi_grid_sampler_create(hfmi_op* grid_cov_op, int max_growth /* 0..3 */, int clip /* 0 | 1 */, hfmi_grid_sampler** out);
+HFMI_API int hfmi_grid_sampler_info(const hfmi_grid_sampler* s, int* growth, int64_t* P /* 3 */, double* lambda_min, double* lambda_max,
+                                    int64_t* n_clipped, double* cov_error_bound);
+HFMI_API int hfmi_grid_sampler_draw(hfmi_grid_sampler* s, const hfmi_block* Y, uint64_t seed, int64_t first_sample /* even */, int accumulate);
+HFMI_API int hfmi_grid_sampler_destroy(hfmi_grid_sampler* s);
+HFMI_API int hfmi_fftcov_sample_plan_predict(int d, const int64_t* n, int growth, int nsamples, int64_t budget_bytes, int64_t* words);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
@@ -688,7 +718,9 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * ("pchol_grid", 0..65535) most workgroups per launch of hfmi_pchol_create (0 = what the device holds, default): a small value makes every
  * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits;
  * ("fftcov_pairs", 0..4096) pairs of columns per chunk of the work buffer of hfmi_op_kernel_cov_grid (0 = from the byte budget,
- * default): results do not depend on it, bit for bit. */
+ * default): results do not depend on it, bit for bit; the draws of hfmi_grid_sampler_draw are chunked by it in the same way;
+ * ("fftcov_min_growth", 0..3) the growth hfmi_grid_sampler_create tries first (default 0; capped by its max_growth): a sampler on a larger
+ * embedding than the rule would take (tests, measurements). */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
 /* phases of hfmi_double_pass[_g], accumulated between hfmi_profile_begin and hfmi_profile_end (milliseconds, summed
  * over the solves in the region; device phases by HIP events on the context's stream, the HOST_* legs by the host's

@@ -1,0 +1,202 @@
+"""A numpy statement of the grid sampler (hfmi_grid_sampler_*, hfmi_fftcov.hip): exact draws m ~ N(0, C) of a kernel covariance on a
+regular grid by circulant embedding.  It restates the rules of hippyflow_amd/csrc/hfmi_fftcov_plan.h -- the grown embedding, the
+storage order of the spectrum, the noise's element map (through oracle/philox.py), the floor, the clip and its bound -- with
+``numpy.fft`` for the transforms, and it returns what the device cannot: the dense covariance of the draws.
+
+Storage order.  tests/helpers/fftcov_twin.py models the padded array as shape (P_{d-1}, ..., P_0), axis 0 of the grid fastest, i.e.
+entry e = s_0 + P_0 (s_1 + P_1 s_2).  The device's forward passes are in-place decimation-in-frequency radix-2 stages (a radix-4 step
+is two of them), so they leave every axis BIT-REVERSED: storage position s_c along axis c holds frequency rev(s_c), and Lambda lives
+in that order.  The inverse passes take it and return the natural order.  Noise entry e therefore colours frequency
+(rev(s_0), rev(s_1), rev(s_2)); i.i.d. noise does not care, but a twin that reproduces the device's draws must say it."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from oracle import philox                         # noqa: E402
+
+import fftcov_twin as ft                          # noqa: E402
+
+EPS = np.finfo(np.float64).eps
+STREAM = 0x67726964              # FFTCOV_GEN_STREAM: counter word 3 of the noise
+FLOOR_C = 16.0                   # FFTCOV_FLOOR_C
+MAXP = 4096
+MAX_GROWTH = 3
+
+# the issue's table: (shape, spacing, family, ell, growth the sampler must take at max_growth = 3)
+TABLE = [((13, 5), (0.1, 0.25), "matern12", 0.4, 0),
+         ((13, 5), (0.1, 0.25), "matern32", 0.4, 1),
+         ((13, 5), (0.1, 0.25), "matern32", 1.0, 2),
+         ((8, 8), (0.125, 0.125), "matern52", 1.0, 3),
+         ((8, 8), (0.125, 0.125), "sqexp", 0.4, 2),
+         ((7, 6, 5), (0.2, 0.2, 0.2), "matern12", 0.4, 1),
+         ((33,), (1.0 / 32,), "sqexp", 1.0, 2)]
+
+
+# the parity cases of the GPU suite (tests/test_gpu_grid_sampler.py), shared with the CPU check of their conditioning
+PARITY_SHAPES = [((33,), (1.0 / 32,), False), ((13, 5), (0.1, 0.25), False), ((19, 5), (0.1, 0.25), True), ((7, 6, 5), (0.2, 0.2, 0.2), False),
+                 ((1, 9), (0.1, 0.25), False)]           # (shape, spacing, a shuffled 3/4 subset of the nodes)
+PARITY_KERNELS = {"matern12": (0.4, 0.0), "matern32": (0.4, 0.0), "matern52": (0.4, 1e-3), "sqexp": (0.4, 1e-2)}   # family: (ell, nugget)
+PARITY_SIGMA = 1.3
+PARITY_COLUMNS = (1, 2, 7)
+PARITY_GROWTHS = (0, 2)
+# the statistics case: TABLE[0] (definite at growth 0); the twin passes it at this seed on the CPU (tests/test_grid_sampler_twin_cpu.py)
+STAT_SEED, STAT_DRAWS = 20261020, 8192
+# the consumer case: a KLE basis of TABLE[0]'s covariance, 256 draws, the projection error at rank 20
+KLE_SEED, KLE_DRAWS, KLE_RANKS = 31, 256, (5, 10, 15, 20)
+
+
+def parity_bound(P, sigma, nugget):
+    """|device - twin| <= 64 eps log2(prod P_c) sqrt(sigma^2 + nugget) 8: the noise is bit-defined, the transforms differ by rounding, 8 bounds |z|"""
+    return 64.0 * EPS * np.log2(P) * np.sqrt(sigma ** 2 + nugget) * 8.0
+
+
+def embedding(shape, growth):
+    """P_c per grid axis: embed_len(n_c) << growth for n_c > 1, 1 otherwise"""
+    return [ft.embed_len(int(n)) << growth if n > 1 else 1 for n in shape]
+
+
+def feasible(shape, growth):
+    return 0 <= growth <= MAX_GROWTH and max(embedding(shape, growth)) <= MAXP
+
+
+def first_column(shape, spacing, family, sigma, ell, nugget, growth):
+    """the grown circulant's first column, shape (P_{d-1}, ..., P_0)"""
+    P = embedding(shape, growth)
+    r2 = np.zeros(P[::-1])
+    for c, (Pc, h) in enumerate(zip(P, spacing)):
+        j = np.arange(Pc)
+        off = np.minimum(j, Pc - j) * h
+        r2 = r2 + (off ** 2).reshape([-1 if a == c else 1 for a in range(len(P))][::-1])
+    col = sigma ** 2 * ft.phi(family, np.sqrt(r2) / ell)
+    col[(0,) * len(P)] += nugget
+    return col
+
+
+def spectrum(shape, spacing, family, sigma, ell, nugget, growth):
+    """the eigenvalues of the embedding's circulant in natural frequency order, shape (P_{d-1}, ..., P_0)"""
+    return np.fft.fftn(first_column(shape, spacing, family, sigma, ell, nugget, growth)).real
+
+
+def spectrum_extended(shape, spacing, family, sigma, ell, nugget, growth):
+    """the same eigenvalues by a dense DFT in extended precision, rounded to fp64 once: what ``spectrum`` is within rounding of"""
+    out = first_column(shape, spacing, family, sigma, ell, nugget, growth).astype(np.clongdouble)
+    for ax, P in enumerate(out.shape):
+        k = np.arange(P)
+        ang = (np.outer(k, k) % P).astype(np.longdouble) * (2 * np.arccos(np.longdouble(-1)) / P)
+        out = np.moveaxis(np.tensordot(np.cos(ang) - 1j * np.sin(ang), out, axes=([1], [ax])), 0, ax)
+    return out.real.astype(np.float64)
+
+
+def bitrev(P):
+    """rev(s) for s < P, P a power of two"""
+    bits = int(P).bit_length() - 1
+    s = np.arange(P)
+    r = np.zeros(P, dtype=np.int64)
+    for b in range(bits):
+        r |= ((s >> b) & 1) << (bits - 1 - b)
+    return r
+
+
+def to_storage(a):
+    """natural order <-> storage order of an array of shape (P_{d-1}, ..., P_0): every axis bit-reversed (an involution)"""
+    return a[np.ix_(*[bitrev(P) for P in a.shape])]
+
+
+def floor(Ptot, lambda_max):
+    return FLOOR_C * EPS * max(1, int(Ptot).bit_length() - 1) * lambda_max
+
+
+def info(shape, spacing, family, sigma, ell, nugget, max_growth=3, clip=False):
+    """the record of hfmi_grid_sampler_info, by the creation rule: the first growth whose lambda_min >= -floor; else the last one
+    tried, clipped (or ValueError).  ``ratios``: lambda_min / lambda_max of every growth tried."""
+    ratios = []
+    g = 0
+    while True:
+        lam = spectrum(shape, spacing, family, sigma, ell, nugget, g)
+        lo, hi = lam.min(), lam.max()
+        ratios.append(lo / hi)
+        definite = lo >= -floor(lam.size, hi)
+        if definite or g == max_growth or not feasible(shape, g + 1):
+            break
+        g += 1
+    if not definite and not clip:
+        raise ValueError("indefinite: lambda_min / lambda_max = %.3e at growth %d" % (lo / hi, g))
+    neg = lam[lam < 0.0]
+    return dict(growth=g, embedding=embedding(shape, g), lambda_min=lo, lambda_max=hi, ratios=ratios,
+                n_clipped=0 if definite else int(neg.size), cov_error_bound=0.0 if definite else float(-neg.sum() / lam.size))
+
+
+def noise(Ptot, pair, seed):
+    """the complex noise of pair ``pair``, one entry per STORAGE position e < Ptot: entries 2 q, 2 q + 1 take the Philox output of
+    counter (q lo, q hi, pair, STREAM) under the key ``seed``: z_0 + i z_1 and z_2 + i z_3 of its four Box-Muller normals"""
+    q = np.arange((Ptot + 1) // 2, dtype=np.uint64)
+    seed = int(seed)
+    x = philox.philox4x32_10(q & np.uint64(0xFFFFFFFF), q >> np.uint64(32), np.uint64(pair), np.uint64(STREAM),
+                             np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF))
+    u = [(v.astype(np.float64) + 0.5) * 2.0 ** -32 for v in x]
+    out = np.empty(2 * q.size, dtype=np.complex128)
+    for half in (0, 1):
+        r = np.sqrt(-2.0 * np.log(u[2 * half]))
+        ang = 2.0 * np.pi * u[2 * half + 1]
+        out[half::2] = r * np.cos(ang) + 1j * (r * np.sin(ang))
+    return out[:Ptot]
+
+
+def node_index(shape, nodes=None):
+    g = np.arange(int(np.prod(shape))) if nodes is None else np.asarray(nodes, dtype=np.int64)
+    idx = []
+    for n in shape:
+        idx.append(g % n)
+        g = g // n
+    return tuple(idx[::-1])
+
+
+def draws(shape, spacing, family, sigma, ell, nugget, growth, n, seed, first=0, nodes=None, dtype=np.complex128, lam=None):
+    """(N, n) draws first .. first + n - 1 of the stream ``seed`` at growth ``growth``: pair p = draws 2 p, 2 p + 1 = Re, Im of
+    IFFT_unnormalised(sqrt(max(Lambda / P, 0)) noise), negative eigenvalues clipped whatever their size.  ``dtype``: the transform's
+    (numpy.clongdouble restates it in extended precision, with the same fp64 noise and spectrum); ``lam``: another spectrum than numpy's."""
+    assert first % 2 == 0
+    if lam is None:
+        lam = spectrum(shape, spacing, family, sigma, ell, nugget, growth)
+    amp_st = np.sqrt(np.maximum(to_storage(lam) / lam.size, 0.0))
+    idx = node_index(shape, nodes)
+    Y = np.empty((idx[0].size, n))
+    for j in range(0, n, 2):
+        coef_st = (amp_st.astype(np.float64) * noise(lam.size, (first + j) // 2, seed).reshape(lam.shape))
+        coef = to_storage(coef_st).astype(dtype)          # natural frequency order
+        z = _ifftn_unnormalised(coef)[idx]
+        Y[:, j] = z.real
+        if j + 1 < n:
+            Y[:, j + 1] = z.imag
+    return Y
+
+
+def _ifftn_unnormalised(a):
+    if a.dtype == np.complex128:
+        return np.fft.ifftn(a) * a.size
+    out = a                                              # extended precision: dense DFT matrices, axis by axis (small grids only)
+    for ax, P in enumerate(a.shape):
+        k = np.arange(P)
+        ang = (np.outer(k, k) % P).astype(np.longdouble) * (2 * np.arccos(np.longdouble(-1)) / P)
+        F = np.cos(ang) + 1j * np.sin(ang)
+        out = np.moveaxis(np.tensordot(F, out, axes=([1], [ax])), 0, ax)
+    return out
+
+
+def dense_cov(shape, spacing, family, sigma, ell, nugget, growth, nodes=None):
+    """Cov(draw): the restriction to the nodes of the circulant with the clipped spectrum max(Lambda, 0)"""
+    lam = spectrum(shape, spacing, family, sigma, ell, nugget, growth)
+    col = np.fft.ifftn(np.maximum(lam, 0.0)).real
+    idx = node_index(shape, nodes)
+    diff = tuple((i[:, None] - i[None, :]) % P for i, P in zip(idx, lam.shape))
+    return col[diff]
+
+
+def cov_tolerance(C, S, k=6.0):
+    """entrywise k-sigma band of an empirical covariance of S draws around C: Var(x_i x_j) = C_ii C_jj + C_ij^2"""
+    dg = np.diag(C)
+    return k * np.sqrt((np.outer(dg, dg) + C ** 2) / S)
