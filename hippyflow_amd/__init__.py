@@ -13,7 +13,7 @@ from .hostvec import ADJOINT, CONTROL, PARAMETER, STATE, HostMultiVector, HostVe
 from .multivector import (MatMvMult, MatMvTranspmult, MultiVector, MvDSmatMult, Vector, dense_to_mv_local, ingest_stream, mv_to_dense,
                           mv_to_dense_local)
 from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
-                        GridFieldSampler, GridKernelCovarianceOperator, grid_node_points, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
+                        GridCovarianceFactor, GridFieldSampler, GridKernelCovarianceOperator, GridKernelPrior, grid_node_points, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
                         kernel_cross_cov_host, nystrom_extend, shard_rows,
                         LowRankOperator, LowRankRectangularOperator, MassPreconditionedCovarianceOperator,
                         JJT, JTJ, Jacobian, MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableControlJacobian,
@@ -25,7 +25,7 @@ from .projectors import (ActiveSubspaceParameterList, ActiveSubspaceProjector, B
                          KLEParameterList, KLEProjector,
                          ParameterList, PODParameterList, PODProjector, PODProjectorFromData, weighted_l2_norm_vector)
 from .lowrank import PivotedCholesky, pivoted_cholesky
-from .randomized import (StreamedSketch, accuracyEnhancedSVD, doublePass, doublePassG, parRandom, singlePass, singlePassG,
+from .randomized import (StreamedSketch, accuracyEnhancedSVD, doublePass, doublePassC, doublePassG, parRandom, singlePass, singlePassG,
                          small_solve, svd_small, sym_eig_small)
 from .errors import input_output_error_test, projection_error_test
 from .io_utils import get_projectors, modify_projectors, spectrum_plot

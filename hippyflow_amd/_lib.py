@@ -88,6 +88,8 @@ SIGNATURES = {
     "hfmi_grid_sampler_draw": [_P, _P, C.c_uint64, C.c_int64, C.c_int],
     "hfmi_grid_sampler_destroy": [_P],
     "hfmi_fftcov_sample_plan_predict": [C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
+    "hfmi_op_grid_factor": [_P, C.c_int, _PP],
+    "hfmi_fftcov_factor_plan_predict": [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

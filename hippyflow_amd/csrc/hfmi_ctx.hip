@@ -370,6 +370,21 @@ extern "C" int hfmi_fftcov_sample_plan_predict(int d, const int64_t* n, int grow
   fftcov_sample_plan_words(p, growth, words);
   return HFMI_OK;
 }
+// ... and of an apply of the factor S (transpose 0) or S^T (1) of that embedding (hfmi_op_grid_factor asks the same planner)
+extern "C" int hfmi_fftcov_factor_plan_predict(int d, const int64_t* n, int growth, int transpose, int nvec, int64_t budget_bytes, int64_t* words) {
+  if (!n || !words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_factor_plan_predict: d = %d is not 1, 2 or 3", d);
+  for (int c = 0; c < d; ++c)
+    if (n[c] < 1 || n[c] > FFTCOV_MAXN) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_factor_plan_predict: n[%d] = %lld is not in 1 .. %d", c, (long long)n[c], FFTCOV_MAXN);
+  if (nvec < 0) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_factor_plan_predict: negative number of vectors");
+  if (transpose != 0 && transpose != 1) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_factor_plan_predict: transpose = %d is not 0 or 1", transpose);
+  if (!fftcov_growth_feasible(d, n, growth))
+    HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_factor_plan_predict: growth %d is outside 0..%d or takes an axis past %d entries", growth, FFTCOV_MAX_GROWTH, FFTCOV_MAXP);
+  fftcov_plan p = fftcov_factor_plan_passes(d, n, growth, transpose);
+  fftcov_plan_chunks(p, nvec, budget_bytes, fftcov_pairs_knob());
+  fftcov_factor_plan_words(p, growth, transpose, words);
+  return HFMI_OK;
+}
 
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");

@@ -24,6 +24,13 @@
 // generated -- sqrt(max(Lambda / P, 0)) times complex Philox / Box-Muller noise, hfmi_randn_math.h -- followed by the inverse passes of an
 // apply, on an embedding of the sampler's own.  Both kernels are one body (fftcov_pass_body<GEN>); the apply's instance has the
 // registers (44 VGPRs) and the LDS it had before the draw existed, the draw's takes 49 VGPRs and no scratch.
+//
+// And they apply the factor C = S S^T of a sampler's embedding (hfmi_op_grid_factor, the last part of this unit; the rules are in
+// hfmi_fftcov_plan.h): S = Rn Chat^(1/2) and S^T are the passes of an apply with the root table sqrt(max(Lambda / P, 0) / P) in place
+// of Lambda / P and the block of padded vectors on one side.  fftcov_pass_body serves that as it stands: its scatter and gather with no
+// node map, n0 = P_0 and all P_0 positions loaded / stored ARE the direct load and store of a block of length prod P_c, so every pass
+// of a factor in 2 or 3 dimensions is a launch of k_fftcov_pass.  Only the single fused pass of d = 1 needs the node map on one side
+// and none on the other; k_fftcov_factor (FAC) is the body with that choice read from the pass flags.  k_fftcov_root makes the table.
 #include <math.h>
 
 #include <algorithm>
@@ -45,6 +52,7 @@ struct fftcov_state {
   dev_buf<int64_t> inv;    // nnodes entries: the point that is grid node g, or -1; empty: point g is node g
   dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
+  dev_buf<double> root;    // a sampler's, made at its first factor: sqrt(max(lambda, 0) / prod P_c), the order of lambda
   dev_buf<double2> work;   // work_pairs() arrays of prod P_c entries
   int growth = 0;          // the embedding's: 0 for an operator, a sampler may double every P_c up to three times
   fftcov_plan plan;        // the passes of an apply, or of a draw (a sampler's state)
@@ -101,8 +109,9 @@ __device__ __forceinline__ void fc_coloured_noise(const fftcov_gen_args& G, uint
   v1 = double2{s1 * z[2], s1 * z[3]};
 }
 
-// GEN: the load is generated (the first pass of a draw); otherwise the pass of an apply, compiled to the code it always was
-template <bool GEN>
+// GEN: the load is generated (the first pass of a draw); otherwise the pass of an apply, compiled to the code it always was.
+// FAC: the fused pass of a factor in one dimension: FFTCOV_LOAD_FULL / FFTCOV_STORE_FULL drop the node map on that side
+template <bool GEN, bool FAC = false>
 __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, const fftcov_gen_args& G) {
   extern __shared__ double2 fc_lds[];
   __shared__ int64_t lbase[FFTCOV_MAX_LINES];    // first entry of the line in the pair's array, -1: no such line
@@ -168,7 +177,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
       if (b >= 0 && p < A.nload) {
         if (A.flags & FFTCOV_SCATTER) {
           const int64_t g = gbase[j] + p;
-          const int64_t pt = A.inv ? A.inv[g] : g;
+          const int64_t pt = (A.inv && !(FAC && (A.flags & FFTCOV_LOAD_FULL))) ? A.inv[g] : g;
           if (pt >= 0) {
             v.x = A.W[(int64_t)c0 * A.ldw + pt];
             if (has1) v.y = A.W[(int64_t)(c0 + 1) * A.ldw + pt];
@@ -276,7 +285,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
       const double2 v = x[j * ls + p];
       if (A.flags & FFTCOV_GATHER) {
         const int64_t g = gbase[j] + p;
-        const int64_t pt = A.inv ? A.inv[g] : g;
+        const int64_t pt = (A.inv && !(FAC && (A.flags & FFTCOV_STORE_FULL))) ? A.inv[g] : g;
         if (pt >= 0) {
           double* y0 = A.Y + (int64_t)c0 * A.ldy + pt;
           *y0 = A.accumulate ? *y0 + v.x : v.x;
@@ -295,6 +304,8 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_args A) { fftcov_pass_body<false>(A, fftcov_gen_args{}); }
 // the first pass of a draw (hfmi_grid_sampler_draw): generated load, inverse stages, store or gather
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_draw(fftcov_pass_args A, fftcov_gen_args G) { fftcov_pass_body<true>(A, G); }
+// the one pass of a factor in one dimension (hfmi_op_grid_factor): node map on one side, the block of padded vectors on the other
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_factor(fftcov_pass_args A) { fftcov_pass_body<false, true>(A, fftcov_gen_args{}); }
 
 // the circulant's first column: entry (j0, j1, j2) is the kernel at the offsets min(j_c, P_c - j_c) h_c, the nugget on entry 0
 __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* buf, int64_t total, int l0, int l1, int P0, int P1, int P2,
@@ -320,16 +331,23 @@ __global__ __launch_bounds__(256) void k_fftcov_spectrum(const double2* buf, dou
     lambda[e] = buf[e].x * scale;
 }
 
-// gen: the pass's load is generated (FFTCOV_GEN, the first pass of a draw); null for every pass that loads
+// the root table of a factor from the stored spectrum: negative entries (rounding, or the clipped ones) count as 0
+__global__ __launch_bounds__(256) void k_fftcov_root(const double* lambda, double* root, int64_t total, double P) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+    root[e] = sqrt(fmax(lambda[e], 0.0) / P);
+}
+
+// gen: the pass's load is generated (FFTCOV_GEN, the first pass of a draw); null for every pass that loads.  table: what the fused
+// multiply reads, null = Lambda / P (a factor's passes hand over the root table)
 static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftcov_plan& p, const fftcov_pass& q, int pairs, int col0,
                               const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate,
-                              const fftcov_gen_args* gen = nullptr) {
+                              const fftcov_gen_args* gen = nullptr, const double* table = nullptr) {
   fftcov_pass_args A;
   A.buf = st->work;
   A.pair_stride = p.Ptot;
   A.tw = st->tw;
   A.tw_step = p.Pmax / q.L;
-  A.lambda = st->lambda;
+  A.lambda = table ? table : st->lambda.get();
   A.flags = q.flags, A.L = q.L, A.logL = q.logL, A.lpw = q.lpw, A.loglpw = q.loglpw, A.ls = q.ls, A.nload = q.nload, A.nstore = q.nstore;
   A.stride = q.stride;
   A.logstride = fftcov_log2(q.stride);
@@ -341,7 +359,15 @@ static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftco
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: a pass of %d lines x %d entries (%d bytes of LDS, grid %lld x %d) cannot be launched", q.lpw,
               q.L, q.lds, (long long)q.grid_x, pairs);
   if (((q.flags & FFTCOV_GEN) != 0) != (gen != nullptr)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: a generated load and its seed go together");
-  if (gen) {
+  // a factor's pass that touches the block of padded vectors on one side only: that side's scatter / gather without a node map and
+  // with n0 = P_0 is the direct load / store; touching it on one side and the nodes on the other (d = 1) is k_fftcov_factor's
+  const int full = q.flags & (FFTCOV_LOAD_FULL | FFTCOV_STORE_FULL);
+  const bool both = (q.flags & FFTCOV_SCATTER) && (q.flags & FFTCOV_GATHER);
+  if (full && !both) A.inv = nullptr, A.n0 = p.P[0];
+  if (full && both) {
+    if (gen || q.nlines != 1) HFMI_FAIL(HFMI_ERR_INVALID, "grid_factor: a pass that loads and stores vectors is the single line of d = 1");
+    hipLaunchKernelGGL(k_fftcov_factor, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A);
+  } else if (gen) {
     // two adjacent storage entries per thread: a line of >= 2 positions, or >= 2 adjacent lines from an even line number
     const bool paired = q.stride > 1 ? (q.lpw >= 2 && q.nlines % 2 == 0) : (q.L >= 2 || (int64_t)q.lpw * q.L == 1);
     if (!paired) HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: the noise pass of %d lines x %d entries does not pair its entries", q.lpw, q.L);
@@ -363,6 +389,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_pass, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_draw, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
+  HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_factor, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   // the work buffer of one pair and Lambda: what decides whether the padded grid fits at all
   hipError_t e = (hipError_t)st->work.alloc((size_t)p.pair_bytes / sizeof(double2));
   if (e == hipSuccess) e = (hipError_t)st->lambda.alloc((size_t)p.Ptot);
@@ -524,16 +551,15 @@ static int fftcov_spectrum_extremes(hfmi_ctx* ctx, const fftcov_state* st, fftco
 
 struct hfmi_grid_sampler {
   hfmi_ctx* ctx = nullptr;
-  std::unique_ptr<fftcov_state, void (*)(fftcov_state*)> st{nullptr, fftcov_destroy};
+  std::shared_ptr<fftcov_state> st;            // shared with the factor operators made from this sampler (hfmi_op_grid_factor)
   double lambda_min = 0.0, lambda_max = 0.0;   // eigenvalues of the embedding's circulant (the stored spectrum times prod P_c)
   int64_t n_clipped = 0;
   double cov_error_bound = 0.0;
 };
 
 // the state of the operator's grid at one growth, its spectrum and the extremes of that
-static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, std::unique_ptr<fftcov_state, void (*)(fftcov_state*)>& st,
-                            fftcov_extremes* ext) {
-  st.reset(new (std::nothrow) fftcov_state());
+static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, std::shared_ptr<fftcov_state>& st, fftcov_extremes* ext) {
+  st.reset(new (std::nothrow) fftcov_state(), fftcov_destroy);
   if (!st) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   st->d = src->d;
   for (int c = 0; c < 3; ++c) st->n[c] = src->n[c], st->h[c] = src->h[c];
@@ -623,5 +649,57 @@ extern "C" int hfmi_grid_sampler_destroy(hfmi_grid_sampler* s) {
   if (!s) return HFMI_OK;
   (void)hipStreamSynchronize(s->ctx->stream);     // draws queued so far use the buffers
   delete s;
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ the factor C = S S^T of a sampler's embedding (hfmi_op_grid_factor)
+// The rules and the pass lists are in hfmi_fftcov_plan.h.  A factor operator shares the sampler's state (grid, node map, twiddles,
+// Lambda, work buffer) and adds the root table to it, once, at the first factor of a sampler: Lambda itself is never written, so the
+// sampler's draws are what they were.  Whoever goes last, sampler or operator, deletes the state.
+extern "C" int hfmi_op_grid_factor(hfmi_grid_sampler* s, int transpose, hfmi_op** out) {
+  if (!s || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (transpose != 0 && transpose != 1) HFMI_FAIL(HFMI_ERR_INVALID, "grid_factor: transpose = %d is not 0 (S) or 1 (S^T)", transpose);
+  hfmi_ctx* ctx = s->ctx;
+  fftcov_state* st = s->st.get();
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!st->root) {
+    const int64_t total = st->plan.Ptot;
+    dev_buf<double> root;
+    const hipError_t e = (hipError_t)root.alloc((size_t)total);
+    if (e != hipSuccess)
+      HFMI_FAIL(HFMI_ERR_HIP, "grid_factor: the root table of the embedding %d x %d x %d needs %lld bytes: %s", st->plan.P[0], st->plan.P[1],
+                st->plan.P[2], (long long)(total * 8), hipGetErrorString(e));
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cus * 8);
+    hipLaunchKernelGGL(k_fftcov_root, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, st->lambda.get(), root.get(), total, (double)total);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t done = hipStreamSynchronize(ctx->stream);   // whatever happened: `root` must not go while a kernel may write it
+    HIP_TRY(launched);
+    HIP_TRY(done);
+    st->root = std::move(root);
+  }
+  std::unique_ptr<hfmi_op> op(new (std::nothrow) hfmi_op());
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  op->ctx = ctx;
+  op->kind = OP_GRID_FACTOR;
+  op->fac = s->st;
+  op->fac_transpose = transpose;
+  *out = op.release();
+  return HFMI_OK;
+}
+
+int fftcov_factor_apply(hfmi_ctx* ctx, fftcov_state* st, int transpose, const hfmi_block* W, hfmi_block* Y, int accumulate) {
+  const int64_t Ptot = st->plan.Ptot, nin = transpose ? st->N : Ptot, nout = transpose ? Ptot : st->N;
+  if (W->N != nin || Y->N != nout)
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_factor: %s maps vectors of length %lld to length %lld, got %lld -> %lld", transpose ? "S^T" : "S",
+              (long long)nin, (long long)nout, (long long)W->N, (long long)Y->N);
+  const int nvec = W->nvec;
+  if (nvec < 1) return HFMI_OK;
+  fftcov_plan p = fftcov_factor_plan_passes(st->d, st->n, st->growth, transpose);
+  HFMI_TRY(fftcov_fit_work(ctx, st, p, nvec));
+  for (int c = 0; c < p.nchunks; ++c) {
+    const int pair0 = c * p.chunk_pairs, pairs = std::min(p.chunk_pairs, p.pairs - pair0);
+    for (int i = 0; i < p.npasses; ++i)
+      HFMI_TRY(fftcov_launch_pass(ctx, st, p, p.pass[i], pairs, 2 * pair0, W->p, W->ld, Y->p, Y->ld, nvec, accumulate, nullptr, st->root));
+  }
   return HFMI_OK;
 }

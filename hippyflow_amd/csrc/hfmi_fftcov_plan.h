@@ -249,8 +249,8 @@ inline double fftcov_floor(int64_t Ptot, double lambda_max) {
   return FFTCOV_FLOOR_C * 2.220446049250313e-16 * (double)(l > 1 ? l : 1) * lambda_max;
 }
 
-// the grown embedding and the passes of a draw; spectrum: the d forward passes over the whole padded array, as fftcov_plan_passes
-inline fftcov_plan fftcov_sample_plan_passes(int d, const int64_t* n, int growth, bool spectrum) {
+// the grown embedding of a sampler: P_c, their product, the twiddle table and the work buffer of one pair; no passes yet
+inline fftcov_plan fftcov_grown_embedding(int d, const int64_t* n, int growth) {
   fftcov_plan p;
   memset(&p, 0, sizeof(p));
   p.d = d;
@@ -264,6 +264,12 @@ inline fftcov_plan fftcov_sample_plan_passes(int d, const int64_t* n, int growth
   }
   p.twiddles = p.Pmax / 4 > 1 ? p.Pmax / 4 : 1;
   p.pair_bytes = 16 * p.Ptot;
+  return p;
+}
+
+// the grown embedding and the passes of a draw; spectrum: the d forward passes over the whole padded array, as fftcov_plan_passes
+inline fftcov_plan fftcov_sample_plan_passes(int d, const int64_t* n, int growth, bool spectrum) {
+  fftcov_plan p = fftcov_grown_embedding(d, n, growth);
   int64_t ext[3];
   for (int c = 0; c < 3; ++c) ext[c] = spectrum ? p.P[c] : p.n[c];
   int np = 0;
@@ -282,4 +288,50 @@ inline fftcov_plan fftcov_sample_plan_passes(int d, const int64_t* n, int growth
 inline void fftcov_sample_plan_words(const fftcov_plan& p, int growth, int64_t* w) {
   fftcov_plan_words(p, w);
   w[13] = growth;
+}
+
+// ------------------------------------------------------------------ the factor C = S S^T of a sampler's embedding (hfmi_op_grid_factor)
+// The embedding circulant Chat of a sampler has a non-negative (or clipped) spectrum, so its symmetric square root is a circulant too,
+// applied by the passes of an apply with a ROOT TABLE sqrt(max(lambda, 0) / prod P_c) in place of lambda (lambda: the stored
+// Lambda / prod P_c, same order, nothing permuted):  Chat^(1/2) xi = IFFT_unnormalised( root . FFT(xi) ).  With Rn the restriction to
+// the nodes,  S = Rn Chat^(1/2)  is N x prod P_c and S S^T = Rn Chat Rn^T = C exactly (C + E with |E_ij| <= cov_error_bound when clipped),
+// and  S^T = Chat^(1/2) Rn^T.  A padded vector is an ordinary block of length prod P_c in natural order, entry
+// e = s_0 + P_0 (s_1 + P_1 s_2): the scatter / gather path of a pass with NO node map and n0 = P_0 is exactly the direct load / store
+// of such a block (FFTCOV_LOAD_FULL / FFTCOV_STORE_FULL say on which side of the pass the block of padded vectors is).
+//
+// Passes (2 d - 1 per pair of columns, pairs per chunk as fftcov_plan_chunks):
+//   S    forward along 0 .. d - 2 over ALL lines (every axis above holds data in its P_b positions), the first loading P_0 positions
+//        straight from the input block; the fused pass along d - 1 loads P_{d-1}, multiplies by the root table and stores n_{d-1};
+//        then the apply's own inverse passes (lines of the first n_b positions only), the last gathering through the node map.
+//   S^T  the apply's own forward passes (scatter through the node map, zero fill); the fused pass along d - 1 loads n_{d-1} and stores
+//        P_{d-1}; then inverse along d - 2 .. 0 over ALL lines, the last storing P_0 positions straight into the output block.
+// d = 1 is the one fused pass, whose load and store sit on different sides: the only pass that k_fftcov_pass cannot run as it stands
+// (one node map serves its load and its store); k_fftcov_factor is the same body with the map dropped on the full side.
+enum { FFTCOV_LOAD_FULL = 64, FFTCOV_STORE_FULL = 128 };
+
+inline fftcov_plan fftcov_factor_plan_passes(int d, const int64_t* n, int growth, int transpose) {
+  fftcov_plan p = fftcov_grown_embedding(d, n, growth);
+  int64_t full[3], data[3];
+  for (int c = 0; c < 3; ++c) full[c] = p.P[c], data[c] = p.n[c];
+  const int64_t* fwd_ext = transpose ? data : full;   // lines of the forward half / of the inverse half
+  const int64_t* inv_ext = transpose ? full : data;
+  const int load_side = transpose ? 0 : FFTCOV_LOAD_FULL, store_side = transpose ? FFTCOV_STORE_FULL : 0;
+  auto in_len = [&](int a) { return transpose ? (int)p.n[a] : p.P[a]; };     // positions of a line on the input's side of the multiply
+  auto out_len = [&](int a) { return transpose ? p.P[a] : (int)p.n[a]; };    // ... and on the output's
+  int np = 0;
+  for (int a = 0; a < d - 1; ++a)
+    p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_FWD | (a == 0 ? FFTCOV_SCATTER | load_side : 0), fwd_ext, in_len(a), p.P[a]);
+  p.pass[np++] = fftcov_make_pass(p, d - 1, FFTCOV_FWD | FFTCOV_MUL | FFTCOV_INV | (d == 1 ? FFTCOV_SCATTER | FFTCOV_GATHER | load_side | store_side : 0),
+                                  data, in_len(d - 1), out_len(d - 1));
+  for (int a = d - 2; a >= 0; --a)
+    p.pass[np++] = fftcov_make_pass(p, a, FFTCOV_INV | (a == 0 ? FFTCOV_GATHER | store_side : 0), inv_ext, p.P[a], out_len(a));
+  p.npasses = np;
+  return p;
+}
+
+// hfmi_fftcov_factor_plan_predict's record: the words of fftcov_plan_words, word 13 = the growth, word 14 = transpose
+inline void fftcov_factor_plan_words(const fftcov_plan& p, int growth, int transpose, int64_t* w) {
+  fftcov_plan_words(p, w);
+  w[13] = growth;
+  w[14] = transpose;
 }

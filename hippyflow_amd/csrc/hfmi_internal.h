@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -221,7 +222,7 @@ struct hfmi_csr {
 };
 
 struct fftcov_state;
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID };
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR };
 
 struct hfmi_op {
   ~hfmi_op();              // waits for the stream when the operator owns device memory (hfmi_op.hip)
@@ -251,6 +252,9 @@ struct hfmi_op {
   int64_t kc_M = 0, kc_diag = 0;
   bool kc_slab = false;
   fftcov_state* fc = nullptr;   // OP_KERNEL_COV_GRID: the grid, the node map, Lambda, the twiddles and the work buffer (owned; hfmi_fftcov.hip)
+  // OP_GRID_FACTOR: the state of the sampler the factor was made from, shared with it (hfmi_op_grid_factor); 0: S, 1: S^T
+  std::shared_ptr<fftcov_state> fac;
+  int fac_transpose = 0;
   hfmi_host_apply_fn host_fn = nullptr;
   void* host_user = nullptr;
   int64_t host_N = 0;
@@ -314,6 +318,8 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
 int64_t fftcov_points(const fftcov_state* st);
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
 void fftcov_destroy(fftcov_state* st);
+// Y (+)= S W (transpose 0: length prod P_c -> N) or S^T W (1: N -> prod P_c), the factor of a sampler's embedding; checks the lengths
+int fftcov_factor_apply(hfmi_ctx* ctx, fftcov_state* st, int transpose, const hfmi_block* W, hfmi_block* Y, int accumulate);
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

@@ -252,7 +252,7 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
   return HFMI_OK;
 }
 hfmi_op::~hfmi_op() {
-  if (gamma_inv || weights || kc_x || kc_t || fc) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
+  if (gamma_inv || weights || kc_x || kc_t || fc || fac) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
   fftcov_destroy(fc);
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
@@ -457,6 +457,9 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       // Y (+)= C W: the gather of the last pass adds into Y itself
       return fftcov_apply(ctx, op->fc, W->p, W->ld, Y->p, Y->ld, k, beta != 0.0);
     }
+    case OP_GRID_FACTOR:
+      // Y (+)= S W or S^T W: the last pass adds into Y itself
+      return fftcov_factor_apply(ctx, op->fac.get(), op->fac_transpose, W, Y, beta != 0.0);
     case OP_KERNEL_CROSS: {
       const int64_t N = op->kc_N, M = op->kc_M;
       const int acc = beta != 0.0;

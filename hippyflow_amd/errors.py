@@ -4,7 +4,7 @@ Reference: KLEProjector.test_errors (modeling/KLEProjector.py:202-282), the inpu
 ActiveSubspaceProjector.test_errors (modeling/activeSubspaceProjector.py:1093-1124) and
 PODProjector.test_output_errors (modeling/PODProjector.py:439-476): for each requested rank r, project every
 test sample x onto span(U_r) -- x_r = U_r U_r^T B x (B = M or prior precision for B-orthonormal bases, B = I
-otherwise) -- and report mean and standard deviation of ||x - x_r||_2 / ||x||_2, averaged over ranks of the
+otherwise; a prior with a covariance and no precision hands over the ENCODER E = B U instead, x_r = U_r E_r^T x) -- and report mean and standard deviation of ||x - x_r||_2 / ||x||_2, averaged over ranks of the
 collective.  On the device all samples are handled as one block: C = U^T (B X) is one reduction GEMM, each rank's
 projection one expansion GEMM on the leading r vectors.
 """
@@ -15,9 +15,12 @@ from .multivector import MatMvMult, MultiVector, MvDSmatMult
 from .operators import as_device_operator
 
 
-def projection_error_test(U, samples, ranks=(None,), B=None, d=None, cut_off=1e-12, collective=None):
+def projection_error_test(U, samples, ranks=(None,), B=None, d=None, cut_off=1e-12, collective=None, encoder=None):
     """U: MultiVector of basis vectors (ordered by decreasing eigenvalue); samples: MultiVector (or (n, N) array)
-    of test vectors.  Returns (ranks_used, global_avg_rel_errors, global_std_rel_errors)."""
+    of test vectors.  ``encoder``: the block E = B U when B itself is not at hand (``doublePassC``); the coefficients are then
+    E^T x, and ``B`` must be None.  Returns (ranks_used, global_avg_rel_errors, global_std_rel_errors)."""
+    if encoder is not None and B is not None:
+        raise ValueError("projection_error_test: give B or the encoder B U, not both")
     collective = collective if collective is not None else NullCollective()
     if not isinstance(samples, MultiVector):
         samples = MultiVector.from_vectors(np.asarray(samples, dtype=np.float64), ctx=U.ctx)
@@ -32,7 +35,7 @@ def projection_error_test(U, samples, ranks=(None,), B=None, d=None, cut_off=1e-
         MatMvMult(as_device_operator(B, N, U.ctx), samples, BX)
     else:
         BX = samples
-    C = U.dot_mv(BX)                      # (k, ns): coefficients of every sample on every basis vector
+    C = (U if encoder is None else encoder).dot_mv(BX)     # (k, ns): coefficients of every sample on every basis vector
     denom = samples.norm()
     avg, std = np.ones(len(ranks)), np.zeros(len(ranks))
     E = MultiVector(N, ns, ctx=U.ctx)
@@ -47,13 +50,16 @@ def projection_error_test(U, samples, ranks=(None,), B=None, d=None, cut_off=1e-
 
 
 def input_output_error_test(observable, prior, U_out, V_in, rank_pairs, n_samples, Cinv=None, noise=None, collective=None,
-                            control_distribution=None):
+                            control_distribution=None, encoder=None):
     """PODProjector.input_output_error_test (modeling/PODProjector.py:541-655): how well the reduced map
     m -> U_r U_r^T q(V_s V_s^T [C^-1] m) reproduces q(m), for pairs (s, r) of input / output ranks, over ``n_samples`` prior
     draws.  The PDE solves stay the host's (``observable.solveFwd`` / ``evalu``, one per sample and one more per sample and
     rank pair, exactly the reference's count); everything between them is done on the whole batch on the device: the
     coefficients V^T (C^-1 M) of every sample on every input vector once, each pair's projected parameters as one expansion,
-    each pair's output projection and error norms as two more.  Returns (global_avg_rel_errors, global_std_rel_errors)."""
+    each pair's output projection and error norms as two more.  ``encoder``: the block C^-1 V_in in place of ``Cinv`` (a prior with a
+    covariance and no precision: the encoder ``doublePassC`` returns).  Returns (global_avg_rel_errors, global_std_rel_errors)."""
+    if encoder is not None and Cinv is not None:
+        raise ValueError("input_output_error_test: give Cinv or the encoder Cinv V_in, not both")
     from . import hostvec as H
     from .multivector import ingest_stream
     from .randomized import parRandom
@@ -84,7 +90,7 @@ def input_output_error_test(observable, prior, U_out, V_in, rank_pairs, n_sample
         MatMvMult(as_device_operator(Cinv, n_in, ctx), params, CP)
     else:
         CP = params
-    coeff = V_in.dot_mv(CP)                                 # (k_in, n_samples)
+    coeff = (V_in if encoder is None else encoder).dot_mv(CP)     # (k_in, n_samples)
     denom = observables.norm()
     projected = MultiVector(n_in, n_samples, ctx=ctx)
     avg, std = [], []

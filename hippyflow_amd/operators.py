@@ -11,6 +11,8 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``npToDeviceOperator``                          npToDolfinOperator, modeling/operatorWrappers.py:19-52 (symmetric case)
 * ``KernelCovarianceOperator``                    the same role for a kernel covariance given by node coordinates, never assembled
 * ``GridKernelCovarianceOperator``                that covariance on the nodes of a regular grid, applied by FFT (hfmi_fftcov.hip)
+* ``GridCovarianceFactor`` / ``GridKernelPrior``  its factor C = S S^T (hfmi_op_grid_factor) and the prior protocol over it: ``sample(noise, m)``
+                                                  with the caller's noise, ``Rsolver``, no ``R`` (``randomized.doublePassC`` needs none)
 * ``KernelCrossCovarianceOperator``               K(T, S) between two point sets (Nystrom extension); ``KernelCovarianceOperator.rows`` /
                                                   ``.sharded``: a row slab of C per rank, completed by the collective's SUM
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
@@ -416,6 +418,10 @@ class GridFieldSampler:
         self._next += int(n) + (int(n) & 1)
         return np.ascontiguousarray(X.to_dense().T)
 
+    def factor(self):
+        """The factor ``S`` of this sampler's embedding, C = S S^T (``GridCovarianceFactor``)."""
+        return GridCovarianceFactor(self)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -423,6 +429,133 @@ class GridFieldSampler:
                 self.handle = None
         except Exception:
             pass
+
+
+class GridCovarianceFactor(DeviceOperator):
+    """The factor ``S = Rn Chat^(1/2)`` of a ``GridFieldSampler``'s embedding (hfmi_op_grid_factor): ``S S^T = C`` up to rounding, ``C + E``
+    with ``|E_ij| <= cov_error_bound`` for a clipped sampler.  ``shape == (N, Ptot)``, ``Ptot = prod(sampler.embedding)``: ``mult`` /
+    ``matMvMult`` take padded vectors (natural order, entry e = s0 + P0 (s1 + P1 s2)) to the nodes, ``transpmult`` the other way;
+    ``transpose()`` is ``S^T`` as an operator of its own (what a whitened Hessian S^T H S composes).  ``init_vector(x, dim)``: 0 gives N
+    entries, 1 gives Ptot.  Ptot is 4 to 64 times N depending on the number of axes and the growth: that is the price of handing the
+    noise over instead of letting ``GridFieldSampler.sample`` generate it.  The operator keeps the sampler alive."""
+
+    def __init__(self, sampler, _transpose=False, _other=None):
+        if not isinstance(sampler, GridFieldSampler):
+            raise ValueError("GridCovarianceFactor: a GridFieldSampler is required (got %s)" % type(sampler).__name__)
+        Ptot = int(np.prod(sampler.embedding))
+        super().__init__(sampler.ctx, *((Ptot, sampler.N) if _transpose else (sampler.N, Ptot)))
+        self.sampler = sampler
+        self.is_transpose = bool(_transpose)
+        self._other = _other
+        L.call("hfmi_op_grid_factor", sampler.handle, 1 if _transpose else 0, C.byref(self._op))
+
+    def transpose(self):
+        """``S^T`` of ``S`` and back: an operator of shape ``shape[::-1]`` over the same sampler (made once)."""
+        if self._other is None:
+            self._other = GridCovarianceFactor(self.sampler, _transpose=not self.is_transpose, _other=self)
+        return self._other
+
+    def transpmult(self, x, y):
+        self.transpose().mult(x, y)
+
+    def matMvTranspmult(self, X, Y, accumulate=False):
+        self.transpose().matMvMult(X, Y, accumulate=accumulate)
+
+
+class _GridCovarianceSolver:
+    """``prior.Rsolver`` of a ``GridKernelPrior``: ``solve(y, x)`` is y = R^-1 x = C x, an apply and no solve."""
+
+    def __init__(self, op):
+        self.op = op
+
+    def init_vector(self, x, dim=0):
+        self.op.init_vector(x, dim)
+
+    def solve(self, y, x):
+        if H.is_host_vector(x):
+            X = MultiVector.from_vectors(np.asarray(x.get_local(), dtype=np.float64)[None, :], ctx=self.op.ctx)
+            Y = MultiVector(self.op.shape[0], 1, ctx=self.op.ctx)
+            self.op.matMvMult(X, Y)
+            y.set_local(Y.to_vectors()[0])
+            y.apply("")
+        else:
+            self.op.mult(x, y)
+
+    def _device_operator(self):
+        return self.op
+
+
+class GridKernelPrior:
+    """A ``GridKernelCovarianceOperator`` behind the PRIOR protocol of the drivers (projectors.py, datagen.py, datasets.py, errors.py):
+    ``init_vector(x, "noise")``, ``sample(noise, m)``, ``mean``, ``Rsolver``, ``M`` / ``Msolver`` -- with NO precision ``R``: a kernel
+    covariance has no sparse inverse, and a Krylov solve with C needs hundreds of applies where it converges at all.  Nothing here
+    solves with C.  ``sample`` is m = mean + S noise with the factor C = S S^T of a sampler's embedding (``GridCovarianceFactor``); the
+    prior-preconditioned active subspace takes ``randomized.doublePassC``, which works in encoder coordinates and needs C alone.
+
+    ``init_vector(x, dim)``: ``"noise"`` gives ``Ptot = prod(embedding)`` entries (4 to 64 times N, depending on the number of axes and
+    the growth), 0 / 1 give N.  ``sample(noise, m, add_mean=True)`` works on dolfin-like host vectors (or device ``Vector``s);
+    ``sample_block(n)`` hands out draws with noise generated on the device and stays the cheap route for many draws.  ``C`` is the
+    operator, ``Rsolver.solve(y, x)`` is y = C x; ``mean`` defaults to zero; ``M`` / ``Msolver`` are whatever the caller has (KLE with
+    ``orthogonality='mass'`` needs them).  ``growth``, ``embedding``, ``n_clipped`` and ``cov_error_bound`` are the sampler's.  ``R`` is
+    deliberately absent: reading it raises ``AttributeError`` pointing at ``doublePassC``."""
+
+    def __init__(self, op, mean=None, M=None, Msolver=None, max_growth=3, on_indefinite="raise", seed=0):
+        if not isinstance(op, GridKernelCovarianceOperator):
+            raise ValueError("GridKernelPrior: a GridKernelCovarianceOperator is required (got %s)" % type(op).__name__)
+        self.C = op
+        self.ctx = op.ctx
+        self.N = op.shape[0]
+        self.sampler = op.sampler(max_growth=max_growth, on_indefinite=on_indefinite, seed=seed)
+        self.S = self.sampler.factor()
+        self.Rsolver = _GridCovarianceSolver(op)
+        if M is not None:
+            self.M = M
+        if Msolver is not None:
+            self.Msolver = Msolver
+        mean = np.zeros(self.N) if mean is None else np.asarray(mean.get_local() if hasattr(mean, "get_local") else mean, dtype=np.float64)
+        if mean.shape != (self.N,):
+            raise ValueError("GridKernelPrior: the mean has %s entries, the operator %d points" % (mean.shape, self.N))
+        self._mean = mean.copy()
+        self.mean = H.new_host_vector()
+        self.mean.init(self.N)
+        self.mean.set_local(self._mean)
+        self.mean.apply("")
+
+    growth = property(lambda self: self.sampler.growth)
+    embedding = property(lambda self: self.sampler.embedding)
+    n_clipped = property(lambda self: self.sampler.n_clipped)
+    cov_error_bound = property(lambda self: self.sampler.cov_error_bound)
+
+    def __getattr__(self, name):          # only reached for attributes that are not there
+        if name == "R":
+            raise AttributeError("GridKernelPrior has no precision R = C^-1 and never solves with C: the prior-preconditioned double pass "
+                                 "is randomized.doublePassC(A, prior.C, Omega, k), encoders come out of it, draws are prior.sample")
+        raise AttributeError("%s object has no attribute %r" % (type(self).__name__, name))
+
+    def init_vector(self, x, dim):
+        x.init(self.S.shape[1] if dim == "noise" else self.N)
+
+    def sample(self, noise, m, add_mean=True):
+        """m = mean + S noise (``add_mean=False``: S noise); ``noise`` has ``Ptot`` entries, m has N."""
+        host = H.is_host_vector(noise)
+        xi = np.asarray(noise.get_local() if host else noise._mv.to_vectors()[0], dtype=np.float64)
+        if xi.shape != (self.S.shape[1],):
+            raise ValueError("GridKernelPrior.sample: the noise has %s entries, the embedding %d (init_vector(x, 'noise'))" % (xi.shape, self.S.shape[1]))
+        Xi = MultiVector.from_vectors(xi[None, :], ctx=self.ctx)
+        Y = MultiVector(self.N, 1, ctx=self.ctx)
+        self.S.matMvMult(Xi, Y)
+        y = Y.to_vectors()[0]
+        if add_mean:
+            y = y + self._mean
+        if H.is_host_vector(m):
+            m.set_local(y)
+            m.apply("")
+        else:
+            L.call("hfmi_block_upload", m._mv.handle, L.ptr(L.as_f64(y[None, :])), L.LAYOUT_VECTORS)
+
+    def sample_block(self, n):
+        """(n, N) array of the next n draws mean + N(0, C) with noise generated on the device (``GridFieldSampler.sample_block``)."""
+        return self.sampler.sample_block(n) + self._mean[None, :]
 
 
 def _is_null_collective(collective):

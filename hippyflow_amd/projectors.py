@@ -10,7 +10,8 @@ names, return tuples, stored attributes and saved-file names as the reference:
 FEniCS/hIPPYlib PDE work stays a host black box, reached through the REFERENCE'S OWN protocols: an ``observable``
 with ``generate_vector / init_vector / solveFwd / evalu / setLinearizationPoint / applyC / solveFwdIncremental / applyB`` and
 their adjoint counterparts (modeling/observable.py:66-323), a ``prior`` with ``init_vector(x, "noise")``,
-``sample(noise, m)``, ``mean``, ``R`` / ``Rsolver`` (or ``Hlr``), ``M`` / ``Msolver`` -- all on dolfin-like host vectors
+``sample(noise, m)``, ``mean``, ``R`` / ``Rsolver`` (or ``Hlr``; or a covariance ``C`` and no ``R``: ``operators.GridKernelPrior``),
+``M`` / ``Msolver`` -- all on dolfin-like host vectors
 (``hostvec.new_host_vector``).  The sampling loops of the reference run as they are written there
 (PODProjector.py:343-357, activeSubspaceProjector.py:163-248,347-397); what they produce is streamed into HBM through
 pinned buffers (``ingest_stream`` / ``upload_async``) and contracted on the device.
@@ -35,7 +36,7 @@ from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackO
                         MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
                         SnapshotGramOperator, Solver2Operator, as_device_operator)
-from .randomized import doublePass, doublePassG, parRandom, singlePass, singlePassG, sym_eig_small
+from .randomized import doublePass, doublePassC, doublePassG, parRandom, singlePass, singlePassG, sym_eig_small
 
 
 def _randomized(projector, generalized):
@@ -294,6 +295,7 @@ class ActiveSubspaceProjector:
         self.d_GN_noprior = None
         self.V_GN_noprior = None
         self.prior_preconditioned = None
+        self.E_GN = None          # the encoder R V_GN of a prior that has a covariance C and no R (doublePassC)
         self.d_NG = None
         self.U_NG = None
         self.Omega_GN = None
@@ -442,16 +444,25 @@ class ActiveSubspaceProjector:
 
         if operation == 'JTJ':
             if prior_preconditioned:
-                if hasattr(self.prior, "R"):
-                    B, Binv = self.prior.R, self.prior.Rsolver
+                self.E_GN = None
+                if not hasattr(self.prior, "R") and not hasattr(self.prior, "Hlr") and hasattr(self.prior, "C"):
+                    # a covariance and no precision (GridKernelPrior): the double pass in encoder coordinates, no solve with C
+                    if getattr(self, 'randomized_eigensolver', 'double_pass') != 'double_pass':
+                        raise NotImplementedError("a prior without R takes the double pass (doublePassC); there is no single-pass form of it")
+                    self.d_GN, self.V_GN, self.E_GN = doublePassC(average_op, self.prior.C, Omega, self.parameters['rank'], s=1)
+                    as_decoder, as_encoder = self.V_GN, self.E_GN
                 else:
-                    B, Binv = self.prior.Hlr, self.prior.Hlr
-                self.d_GN, self.V_GN = _randomized(self, True)(average_op, B, Binv, Omega, self.parameters['rank'], s=1)
-                as_decoder = self.V_GN
-                as_encoder = MultiVector(as_decoder)
-                MatMvMult(as_device_operator(B, N, self.ctx), as_decoder, as_encoder)
+                    if hasattr(self.prior, "R"):
+                        B, Binv = self.prior.R, self.prior.Rsolver
+                    else:
+                        B, Binv = self.prior.Hlr, self.prior.Hlr
+                    self.d_GN, self.V_GN = _randomized(self, True)(average_op, B, Binv, Omega, self.parameters['rank'], s=1)
+                    as_decoder = self.V_GN
+                    as_encoder = MultiVector(as_decoder)
+                    MatMvMult(as_device_operator(B, N, self.ctx), as_decoder, as_encoder)
             else:
                 self.d_GN, self.V_GN = _randomized(self, False)(average_op, Omega, self.parameters['rank'], s=1)
+                self.E_GN = None
                 as_decoder = self.V_GN
                 as_encoder = MultiVector(as_decoder)
             self.prior_preconditioned = prior_preconditioned
@@ -647,9 +658,13 @@ class ActiveSubspaceProjector:
                 self.construct_input_subspace()
             if samples is None:
                 samples = _prior_sample_block(self.prior, self.parameters['error_test_samples'], self.noise, self.observable)
-            B = self.prior.R if self.prior_preconditioned else None
+            encoder = self.E_GN if self.prior_preconditioned else None       # a prior without R: the stored encoder is R V_GN
+            if self.prior_preconditioned and encoder is None and not hasattr(self.prior, "R"):
+                raise RuntimeError("test_errors: the prior has no R and this projector holds no encoder (E_GN): the input basis was not "
+                                   "built by construct_input_subspace here; set E_GN to the saved encoder R V_GN, or construct again")
+            B = self.prior.R if self.prior_preconditioned and encoder is None else None
             _, avg, std = projection_error_test(self.V_GN, samples, ranks, B=B, d=self.d_GN, cut_off=cut_off,
-                                                collective=self.collective)
+                                                collective=self.collective, encoder=encoder)
             results += [avg, std]
         if test_output:
             if self.d_NG is None or len(self.d_NG) < want:

@@ -5,6 +5,7 @@ modeling/activeSubspaceProjector.py:449-463,556-577,654).
 
 ``doublePass(A, Omega, k, s=1)``             -> (d, U),   U^T U = I
 ``doublePassG(A, B, Binv, Omega, k, s=1)``   -> (d, U),   U^T B U = I,  A U ~ B U diag(d)
+``doublePassC(A, C, Omega, k, s=1)``         -> (d, U, E): doublePassG(A, C^-1, C) without C^-1; E = C^-1 U, E^T U = I
 ``singlePass(A, Omega, k, s=1)`` / ``singlePassG(A, B, Binv, Omega, k, s=1)``: the same results from s applications of
 A instead of s + 1 (hippylib's randomizedEigensolver.singlePass[G]); ``StreamedSketch`` builds their sketch A Omega while
 the samples are produced, without storing them
@@ -272,6 +273,49 @@ def doublePassG(A, B, Binv, Omega, k, s=1, check=False, sort_by_abs=False, use_m
     U = MultiVector(N, k, ctx=Omega.ctx)
     MvDSmatMult(Q, np.ascontiguousarray(V[:, :k]), U)
     return d, U
+
+
+def doublePassC(A, C, Omega, k, s=1, sort_by_abs=False, use_mgs=False):
+    """``doublePassG(A, R, Rsolver, Omega, k, s)`` for a prior given by its COVARIANCE C = R^-1 alone: the same (d, U) and the encoder
+    E = R U on top, with no R and no solve.  doublePassG builds Ybar = C A Omega, R-orthonormalises it to Q and forms T = Q^T A Q.
+    Write Q = C Qv: Qv is the C-orthonormalisation of Yv = A Omega (Qv^T C Qv = I) and Q = C Qv is the ``BQ`` block that the
+    B-orthogonalisation with B = C returns anyway.  So
+        Yv = (A C)^(s-1) A Omega,  (Qv, BQ) = C-orth(Yv),  T = BQ^T A BQ,  eigh(T) descending, W = its k leading vectors,
+        U = BQ W (decoder, U^T R U = I),  E = Qv W (encoder R U, E^T U = I).
+    In exact arithmetic this is doublePassG's (d, U) for the same Omega.  A may be wrapped in a ``CollectiveOperator`` /
+    ``MatrixMultCollectiveOperator`` as for doublePassG (the local device operator is applied, the block is all-reduced); C is an
+    operator on every rank (``GridKernelCovarianceOperator``, or anything ``as_device_operator`` takes).  Returns (d, U, E)."""
+    nvec = Omega.nvec()
+    assert nvec >= k
+    N = Omega.size()
+    A_dev, coll, mpi_op = _unwrap_collective(A)
+
+    def apply_A(X, Y):
+        if A_dev is not None and coll is not None:
+            A_dev.matMvMult(X, Y)
+            coll.allReduce(Y, mpi_op)
+        else:
+            MatMvMult(A_dev if A_dev is not None else A, X, Y)
+
+    C_dev = as_device_operator(C, N, Omega.ctx)
+    Yv = MultiVector(N, nvec, ctx=Omega.ctx)
+    apply_A(Omega, Yv)
+    if s > 1:
+        CY = MultiVector(N, nvec, ctx=Omega.ctx)
+        for _ in range(s - 1):
+            MatMvMult(C_dev, Yv, CY)
+            apply_A(CY, Yv)
+    BQ, _ = Yv.Borthogonalize(C_dev, L.QR_MGS if use_mgs else L.QR_AUTO)     # Yv becomes Qv
+    ABQ = MultiVector(N, nvec, ctx=Omega.ctx)
+    apply_A(BQ, ABQ)
+    T = ABQ.dot_mv(BQ)
+    d, V = sym_eig_small(T, sort_by_abs, Omega.ctx)
+    W = np.ascontiguousarray(V[:, :k])
+    U = MultiVector(N, k, ctx=Omega.ctx)
+    E = MultiVector(N, k, ctx=Omega.ctx)
+    MvDSmatMult(BQ, W, U)
+    MvDSmatMult(Yv, W, E)
+    return d[:k].copy(), U, E
 
 
 def svd_small(R, ctx=None):

@@ -253,6 +253,25 @@ HFMI_API int hfmi_grid_sampler_info(const hfmi_grid_sampler* s, int* growth, int
 HFMI_API int hfmi_grid_sampler_draw(hfmi_grid_sampler* s, const hfmi_block* Y, uint64_t seed, int64_t first_sample /* even */, int accumulate);
 HFMI_API int hfmi_grid_sampler_destroy(hfmi_grid_sampler* s);
 HFMI_API int hfmi_fftcov_sample_plan_predict(int d, const int64_t* n, int growth, int nsamples, int64_t budget_bytes, int64_t* words);
+/*     the FACTOR C = S S^T of a sampler's embedding as two operators, so that a grid covariance can take the caller's noise
+ *     (prior.sample(noise, m): m = mean + S noise) and whiten a Hessian (S^T H S) without any solve.  The embedding circulant Chat has
+ *     a non-negative (or clipped) spectrum; its symmetric square root is again a circulant, applied by the passes of an apply with
+ *     sqrt(max(Lambda / P, 0) / P) in place of Lambda / P, P = prod P_c:  Chat^(1/2) xi = IFFT_unnormalised( root . FFT(xi) ).  With Rn the
+ *     restriction to the operator's points,  S = Rn Chat^(1/2)  (transpose = 0) maps blocks of length P to blocks of length N and
+ *     S^T = Chat^(1/2) Rn^T  (transpose = 1) maps length N to length P;  S S^T = C up to rounding, C + E with |E_ij| <= cov_error_bound
+ *     for a clipped sampler.  A padded vector is an ordinary block in natural order, entry e = s0 + P0 (s1 + P1 s2): P is 4 to 64 times
+ *     N depending on d and the growth, which is what the caller's noise costs against hfmi_grid_sampler_draw's generated one.
+ *     Applied through hfmi_op_apply: 2 d - 1 passes per pair of columns, two real columns per complex transform (a last odd column
+ *     pairs with zeros), chunked by "fftcov_pairs" with identical bits; no atomics, two applies are bit-identical; block storage
+ *     contract as every operator (padding rows untouched, accumulate adds).  The root table is a second table made once per
+ *     sampler at its first factor: Lambda and the draws are untouched.  The operator shares the sampler's state: either may be
+ *     destroyed first.  HFMI_ERR_INVALID: NULL sampler, transpose outside 0 / 1; at apply, blocks of another length.
+ *     hfmi_fftcov_factor_plan_predict: the apply's launch plan without a device, the words of hfmi_fftcov_plan_predict (pass flags
+ *     64 / 128: the load / the store addresses the block of padded vectors) with word 13 = growth and word 14 = transpose;
+ *     HFMI_ERR_INVALID where hfmi_fftcov_sample_plan_predict says so, and for a transpose outside 0 / 1. */
+HFMI_API int hfmi_op_grid_factor(hfmi_grid_sampler* s, int transpose /* 0: S | 1: S^T */, hfmi_op** out);
+HFMI_API int hfmi_fftcov_factor_plan_predict(int d, const int64_t* n, int growth, int transpose, int nvec, int64_t budget_bytes,
+                                             int64_t* words);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
@@ -718,7 +737,8 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * ("pchol_grid", 0..65535) most workgroups per launch of hfmi_pchol_create (0 = what the device holds, default): a small value makes every
  * workgroup walk several row tiles at small N (tests); L and the pivots do not depend on it, the traces only in their last bits;
  * ("fftcov_pairs", 0..4096) pairs of columns per chunk of the work buffer of hfmi_op_kernel_cov_grid (0 = from the byte budget,
- * default): results do not depend on it, bit for bit; the draws of hfmi_grid_sampler_draw are chunked by it in the same way;
+ * default): results do not depend on it, bit for bit; the draws of hfmi_grid_sampler_draw and the applies of hfmi_op_grid_factor are
+ * chunked by it in the same way;
  * ("fftcov_min_growth", 0..3) the growth hfmi_grid_sampler_create tries first (default 0; capped by its max_growth): a sampler on a larger
  * embedding than the rule would take (tests, measurements). */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
