@@ -15,7 +15,7 @@ QR_CHOL, QR_MGS, QR_AUTO = 0, 1, 2
 UNIQUE_ID_BYTES = 256
 WIDE_MAX_VECTORS = 2048                                # orthogonalize / Borthogonalize / doublePass[G]: HFMI_WIDE_MAXK of the library
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
-KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3}     # HFMI_KERNEL_* of include/hfmi.h
+KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3, "matern1": 4}     # HFMI_KERNEL_* of include/hfmi.h
 KERNEL_NO_DIAGONAL = -1                                # HFMI_KERNEL_NO_DIAGONAL: no target of a cross-covariance is a source
 GRID_COV_MAX_NODES = 2048                              # nodes per axis of hfmi_op_kernel_cov_grid (FFTCOV_MAXN of hfmi_fftcov_plan.h)
 FFTCOV_PLAN_WORDS = 96                                 # HFMI_FFTCOV_PLAN_WORDS of include/hfmi.h
@@ -35,6 +35,15 @@ class HfmiError(RuntimeError):
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
 _D = C.POINTER(C.c_double)
+
+
+class KernelSpec(C.Structure):
+    """hfmi_kernel_spec of include/hfmi.h: what the hfmi_op_kernel_*_spec creators take in place of (family, sigma, ell, nugget)"""
+    _fields_ = [("family", C.c_int), ("d", C.c_int), ("sigma", C.c_double), ("ell", C.c_double), ("nugget", C.c_double),
+                ("metric", C.c_double * 9)]
+
+
+_SPEC = C.POINTER(KernelSpec)
 
 # name -> argtypes; every function returns int status except the two noted below
 SIGNATURES = {
@@ -81,6 +90,11 @@ SIGNATURES = {
     "hfmi_op_kernel_cross_cov": [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _PP],
     "hfmi_op_kernel_cov_rows": [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64, _PP],
     "hfmi_op_kernel_cov_grid": [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, _PP],
+    "hfmi_op_kernel_cov_spec": [_P, _P, C.c_int64, C.c_int, _SPEC, _PP],
+    "hfmi_op_kernel_cross_cov_spec": [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, _SPEC, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_rows_spec": [_P, _P, C.c_int64, C.c_int, _SPEC, C.c_int64, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_grid_spec": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC, _PP],
+    "hfmi_kernel_metric_factor": [_P, C.c_int, _P],
     "hfmi_fftcov_plan_predict": [C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_grid_sampler_create": [_P, C.c_int, C.c_int, _PP],
     "hfmi_grid_sampler_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -49,6 +49,8 @@ struct fftcov_state {
   int64_t nnodes = 0;      // prod n
   int family = 0;
   double sigma = 0.0, ell = 0.0, nugget = 0.0;
+  bool has_metric = false; // r^2 = |L^T diag(h) o|^2 / ell^2 with the factor below (k_fftcov_column_signed); false: the even column
+  double mL[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};   // lower Cholesky factor of the metric, row-major 3 x 3
   dev_buf<int64_t> inv;    // nnodes entries: the point that is grid node g, or -1; empty: point g is node g
   dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
@@ -307,7 +309,8 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_draw(fftcov_pass_
 // the one pass of a factor in one dimension (hfmi_op_grid_factor): node map on one side, the block of padded vectors on the other
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_factor(fftcov_pass_args A) { fftcov_pass_body<false, true>(A, fftcov_gen_args{}); }
 
-// the circulant's first column: entry (j0, j1, j2) is the kernel at the offsets min(j_c, P_c - j_c) h_c, the nugget on entry 0
+// the circulant's first column of an isotropic kernel of the four first families: entry (j0, j1, j2) is the kernel at the offsets
+// min(j_c, P_c - j_c) h_c, the nugget on entry 0
 __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* buf, int64_t total, int l0, int l1, int P0, int P1, int P2,
                                                        double h0, double h1, double h2) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -323,6 +326,52 @@ __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* b
       r2 = fma(dz, dz, r2);
     }
     buf[e] = double2{kcov_entry(K, r2, e == 0), 0.0};
+  }
+}
+// The column of a kernel with a metric, r^2 = o^T diag(h) G diag(h) o / ell^2, and of Matern-1 (PT = kcov_k1_params): such a kernel is
+// even in the offset vector only, not in each axis, so the column takes SIGNED offsets.  Storage position s_c stands for o_c = s_c below
+// P_c / 2 and s_c - P_c above it; at s_c = P_c / 2 (P_c >= 2) the entry is the mean over both signs of that offset, taken over every
+// axis at its half in the fixed order b = 0 .. 7 (bit c of b: the + sign on axis c).  An apply never reads a half position (P_c >= 2 n_c
+// wherever n_c > 1); the mean keeps the column jointly even, so its transform is real and k_fftcov_spectrum and every pass after it are
+// what they were.  With G = L L^T:  u = diag(h) o,  w = L^T u (w_c = sum_{e >= c} L_ec u_e, e ascending),  r^2 = w_0^2 + w_1^2 + w_2^2 in
+// that order -- the arithmetic the scattered operator does on its uploaded x' = L^T x.  tests/helpers/grid_metric_twin.py states the same.
+struct fftcov_metric_args {
+  double l00, l10, l11, l20, l21, l22;   // the lower factor, identity when there is no metric
+};
+template <class PT>
+__global__ __launch_bounds__(256) void k_fftcov_column_signed(PT K, fftcov_metric_args G, double2* buf, int64_t total, int l0, int l1, int P0,
+                                                              int P1, int P2, double h0, double h1, double h2) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int s0 = (int)(e & (P0 - 1)), s1 = (int)((e >> l0) & (P1 - 1)), s2 = (int)(e >> (l0 + l1));
+    const bool m0 = P0 > 1 && 2 * s0 == P0, m1 = K.d > 1 && P1 > 1 && 2 * s1 == P1, m2 = K.d > 2 && P2 > 1 && 2 * s2 == P2;
+    const double o0 = (double)(2 * s0 < P0 ? s0 : s0 - P0) * h0;     // at the half: -P_c / 2, the + sign comes from b
+    const double o1 = (double)(2 * s1 < P1 ? s1 : s1 - P1) * h1;
+    const double o2 = (double)(2 * s2 < P2 ? s2 : s2 - P2) * h2;
+    double sum = 0.0;
+    int cnt = 0;
+#pragma unroll 1
+    for (int b = 0; b < 8; ++b) {
+      if (((b & 1) && !m0) || ((b & 2) && !m1) || ((b & 4) && !m2)) continue;
+      const double u0 = (b & 1) ? -o0 : o0, u1 = (b & 2) ? -o1 : o1, u2 = (b & 4) ? -o2 : o2;
+      double w0 = G.l00 * u0, w1 = 0.0, w2 = 0.0;
+      if (K.d > 1) {
+        w0 = fma(G.l10, u1, w0);
+        w1 = G.l11 * u1;
+      }
+      if (K.d > 2) {
+        w0 = fma(G.l20, u2, w0);
+        w1 = fma(G.l21, u2, w1);
+        w2 = G.l22 * u2;
+      }
+      double r2 = w0 * w0;
+      if (K.d > 1) r2 = fma(w1, w1, r2);
+      if (K.d > 2) r2 = fma(w2, w2, r2);
+      sum += kcov_entry(K, r2, false);
+      ++cnt;
+    }
+    double v = sum / (double)cnt;      // cnt is 1, 2, 4 or 8
+    if (e == 0) v += K.nugget;
+    buf[e] = double2{v, 0.0};
   }
 }
 // Lambda / P: the transform of a real symmetric column is real, what the imaginary parts hold is rounding
@@ -411,11 +460,23 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
   OWN_TRY(st->tw.alloc(tw.size()));
   HIP_TRY(hipMemcpy(st->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
   // Lambda = FFT(first column) / P by the forward passes over the whole padded array
-  kcov_params K;
-  HFMI_TRY(kcov_params_init(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, st->nugget));   // no coordinates are read
   const int64_t blocks = std::min<int64_t>((p.Ptot + 255) / 256, (int64_t)ctx->num_cus * 8);
-  hipLaunchKernelGGL(k_fftcov_column, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, st->work, p.Ptot, fftcov_log2(p.P[0]),
-                     fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
+  const fftcov_metric_args G{st->mL[0], st->mL[3], st->mL[4], st->mL[6], st->mL[7], st->mL[8]};
+  if (st->family == HFMI_KERNEL_MATERN1) {
+    kcov_k1_params K;
+    HFMI_TRY(kcov_params_init_as(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, st->nugget));   // no coordinates are read
+    hipLaunchKernelGGL(k_fftcov_column_signed<kcov_k1_params>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, G, st->work, p.Ptot,
+                       fftcov_log2(p.P[0]), fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
+  } else {
+    kcov_params K;
+    HFMI_TRY(kcov_params_init(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, st->nugget));
+    if (st->has_metric)
+      hipLaunchKernelGGL(k_fftcov_column_signed<kcov_params>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, G, st->work, p.Ptot,
+                         fftcov_log2(p.P[0]), fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
+    else      // one of the four first families without a metric: the even column, as ever
+      hipLaunchKernelGGL(k_fftcov_column, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, st->work, p.Ptot, fftcov_log2(p.P[0]),
+                         fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
+  }
   HIP_TRY(hipGetLastError());
   const fftcov_plan sp = fftcov_sample_plan_passes(st->d, st->n, st->growth, true);   // growth 0: fftcov_plan_passes(d, n, true)
   for (int i = 0; i < sp.npasses; ++i) HFMI_TRY(fftcov_launch_pass(ctx, st, sp, sp.pass[i], 1, 0, nullptr, 0, nullptr, 0, 0, 0));
@@ -426,7 +487,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
 }
 
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, fftcov_state** out) {
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out) {
   int64_t nnodes = 1;
   for (int c = 0; c < d; ++c) {
     if (n[c] < 1 || n[c] > FFTCOV_MAXN)
@@ -454,6 +515,11 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
   st->N = N;
   st->nnodes = nnodes;
   st->family = family, st->sigma = sigma, st->ell = ell, st->nugget = nugget;
+  if (metric_factor) {      // d x d row-major lower factor -> the 3 x 3 of the state
+    st->has_metric = true;
+    for (int r = 0; r < d; ++r)
+      for (int c = 0; c < d; ++c) st->mL[3 * r + c] = metric_factor[(size_t)r * d + c];
+  }
   st->plan = fftcov_plan_passes(d, st->n, false);
   const int s = fftcov_create_device(ctx, st.get(), host_nodes ? inv.data() : nullptr);
   if (s != HFMI_OK) {
@@ -565,6 +631,8 @@ static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, 
   for (int c = 0; c < 3; ++c) st->n[c] = src->n[c], st->h[c] = src->h[c];
   st->N = src->N, st->nnodes = src->nnodes;
   st->family = src->family, st->sigma = src->sigma, st->ell = src->ell, st->nugget = src->nugget;
+  st->has_metric = src->has_metric;
+  std::copy(src->mL, src->mL + 9, st->mL);
   st->growth = growth;
   st->plan = fftcov_sample_plan_passes(st->d, st->n, growth, false);
   HFMI_TRY(fftcov_create_device(ctx, st.get(), src->inv, true));

@@ -311,10 +311,17 @@ int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const dou
                             int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
                             int64_t ldy, int nvec, int accumulate);
 
+// The metric of a kernel covariance, r^2 = delta^T G delta / ell^2 with G symmetric positive definite, enters through its lower Cholesky
+// factor G = L L^T: |L^T delta|^2 is the same number and cannot round below zero.  Scattered points are uploaded as x' = L^T x, so the
+// kernels see an isotropic problem; the grid's column takes L itself (hfmi_fftcov.hip).  kcov_metric_factor (hfmi_op.hip) checks G
+// (finite, |G_ij - G_ji| <= 4 eps max |G|, every pivot positive) and writes L row-major d x d, zeros above the diagonal.
+int kcov_metric_factor(const double* G, int d, double* L);
+
 // Kernel covariance on a regular grid by FFT (hfmi_fftcov.hip; plans: hfmi_fftcov_plan.h).  create checks the arguments, uploads the
 // node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy deletes the state (the caller synchronised)
+// metric_factor: the lower Cholesky factor of the kernel's metric (d x d row-major, kcov_metric_factor), or null for none
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, fftcov_state** out);
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out);
 int64_t fftcov_points(const fftcov_state* st);
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
 void fftcov_destroy(fftcov_state* st);

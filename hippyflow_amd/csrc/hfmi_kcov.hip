@@ -22,6 +22,11 @@
 // on the tile, wave or lane row that holds it, so with t = s[row0 : row0 + M] and diag_offset = row0 the result is the same bits as rows
 // row0 .. row0 + M - 1 of the square apply: a row slab per rank, summed over the ranks, IS the square apply.  The square instances take
 // kcov_params as before: neither their arguments nor their registers know of the second set.
+//
+// Matern-1 (the kcov_k1_params / kcov_k1_cross_params instances): the same kernel with phi = a K_1(a) of hfmi_kcov_k1.h behind kcov_entry.
+// Its evaluation is about 100 fp64 VALU instructions with log, exp, sqrt and a division, so that apply is bound by the VALU, not by the
+// matrix pipe; eval(s + 1) is still issued before the MFMAs of slab s.  A metric (r^2 = delta^T G delta) never reaches this unit: the
+// operator uploads x' = L^T x, G = L L^T (hfmi_op.hip).
 #include <algorithm>
 
 #include "hfmi_gemm_common.h"
@@ -45,7 +50,14 @@ __device__ __forceinline__ const double* kcov_t2(const kcov_cross_params& P) { r
 __device__ __forceinline__ int64_t kcov_diag_source(const kcov_params&, int64_t gi) { return gi; }
 __device__ __forceinline__ int64_t kcov_diag_source(const kcov_cross_params& P, int64_t gi) { return P.diag_offset >= 0 ? gi + P.diag_offset : -1; }
 
-template <int NT, class PT>      // PT: kcov_params (square) or kcov_cross_params (rectangular)
+// The Matern-1 evaluation needs some 40 VGPRs more than the others.  In its instances the leading dimensions pass through an empty
+// statement where they are used, so that the 64-bit column offsets of the prefetch and of the final store are computed there and not
+// kept in registers across the slab loop: 9 column tiles then fit without a spill (246 VGPRs).  The other instances do not see this.
+template <class PT> constexpr bool kcov_tight_registers = false;
+template <> constexpr bool kcov_tight_registers<kcov_k1_params> = true;
+template <> constexpr bool kcov_tight_registers<kcov_k1_cross_params> = true;
+
+template <int NT, class PT>      // PT: kcov_params (square) or kcov_cross_params (rectangular); kcov_k1_params / kcov_k1_cross_params: Matern-1
 __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(PT P, const double* __restrict__ W, int64_t ldw, double* __restrict__ Y,
                                                         int64_t ldy, int ncols, int accumulate) {
   __shared__ double wl[16 * NT * KC_JCP];
@@ -73,6 +85,7 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(PT P, const double* __re
     double pf[2 * NT], xpf;
     auto fetch = [&](int64_t j0) {
       const int64_t j = j0 + lane;
+      if constexpr (kcov_tight_registers<PT>) asm volatile("" : "+s"(ldw));
 #pragma unroll
       for (int e = 0; e < 2 * NT; ++e) {
         const int col = wave + KC_WAVES * e;
@@ -119,6 +132,7 @@ __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(PT P, const double* __re
         }
       }
     }
+    if constexpr (kcov_tight_registers<PT>) asm volatile("" : "+s"(ldy));
     // C/D layout of the f64 instruction: column lane & 15, rows (lane >> 4) + 4 r: the four lk-lanes of a column write 32 contiguous bytes
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -163,6 +177,7 @@ int kcov_params_init(kcov_params* out, const double* x, int64_t N, int d, int fa
     case HFMI_KERNEL_MATERN32: P.ca = 1.7320508075688772, P.p1 = 1.0; break;        // (1 + a) exp(-a), a = sqrt(3) r
     case HFMI_KERNEL_MATERN52: P.ca = 2.23606797749979, P.p1 = 1.0, P.p2 = 1.0 / 3.0; break;   // (1 + a + a^2/3) exp(-a), a = sqrt(5) r
     case HFMI_KERNEL_SQEXP: P.g1 = 0.0, P.g2 = 0.5; break;                           // exp(-r^2 / 2)
+    case HFMI_KERNEL_MATERN1: P.ca = 1.4142135623730951; break;                      // a K_1(a), a = sqrt(2) r: the kcov_k1_* instances
     default: HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: unknown kernel family %d", family);
   }
   *out = P;
@@ -193,9 +208,26 @@ static int kcov_panels(hfmi_ctx* ctx, const PT& P, int64_t M, const double* W, i
 
 int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
                       const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+  if (family == HFMI_KERNEL_MATERN1) {
+    kcov_k1_params P;
+    HFMI_TRY(kcov_params_init_as(&P, x, N, d, family, sigma, ell, nugget));
+    return kcov_panels(ctx, P, N, W, ldw, Y, ldy, nvec, accumulate);
+  }
   kcov_params P;
   HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
   return kcov_panels(ctx, P, N, W, ldw, Y, ldy, nvec, accumulate);
+}
+
+// the targets of the rectangular form, for either cross type
+template <class PT>
+static int kcov_cross_panels(hfmi_ctx* ctx, PT& P, const double* t, int64_t M, int64_t tstride, int64_t diag_offset, int d, const double* W,
+                             int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+  P.t0 = t;
+  P.t1 = d > 1 ? t + tstride : t;
+  P.t2 = d > 2 ? t + 2 * tstride : t;
+  P.M = M;
+  P.diag_offset = diag_offset >= 0 ? diag_offset : -1;
+  return kcov_panels(ctx, P, M, W, ldw, Y, ldy, nvec, accumulate);
 }
 
 int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
@@ -205,12 +237,12 @@ int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const dou
   if (diag_offset >= 0 && diag_offset + M > N)
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: targets %lld .. %lld are not sources (N = %lld)", (long long)diag_offset,
               (long long)(diag_offset + M - 1), (long long)N);
+  if (family == HFMI_KERNEL_MATERN1) {
+    kcov_k1_cross_params P;
+    HFMI_TRY(kcov_params_init_as(&P, x, N, d, family, sigma, ell, nugget));
+    return kcov_cross_panels(ctx, P, t, M, tstride, diag_offset, d, W, ldw, Y, ldy, nvec, accumulate);
+  }
   kcov_cross_params P;
   HFMI_TRY(kcov_params_init(&P, x, N, d, family, sigma, ell, nugget));
-  P.t0 = t;
-  P.t1 = d > 1 ? t + tstride : t;
-  P.t2 = d > 2 ? t + 2 * tstride : t;
-  P.M = M;
-  P.diag_offset = diag_offset >= 0 ? diag_offset : -1;
-  return kcov_panels(ctx, P, M, W, ldw, Y, ldy, nvec, accumulate);
+  return kcov_cross_panels(ctx, P, t, M, tstride, diag_offset, d, W, ldw, Y, ldy, nvec, accumulate);
 }

@@ -36,3 +36,28 @@ __device__ __forceinline__ double kcov_entry(const kcov_params& P, double r2, bo
   if (same_index) v += P.nugget;
   return v;
 }
+
+// HFMI_KERNEL_MATERN1, phi = a K_1(a) (hfmi_kcov_k1.h): the same blocks under types of their own, so that the evaluation is chosen by
+// overload and the instances of the four polynomial-times-exponential families are the code they were.  ca = sqrt(2); p1 .. g2 are unused.
+struct kcov_k1_params : kcov_params {};
+struct kcov_k1_cross_params : kcov_cross_params {};
+
+#include "hfmi_kcov_k1.h"
+
+__device__ __forceinline__ double kcov_k1_entry(const kcov_params& P, double r2, bool same_index) {
+  const double a = P.ca * sqrt(r2) * P.inv_ell;
+  double v = P.sigma2 * kcov_k1_phi(a);
+  if (same_index) v += P.nugget;
+  return v;
+}
+__device__ __forceinline__ double kcov_entry(const kcov_k1_params& P, double r2, bool same_index) { return kcov_k1_entry(P, r2, same_index); }
+__device__ __forceinline__ double kcov_entry(const kcov_k1_cross_params& P, double r2, bool same_index) { return kcov_k1_entry(P, r2, same_index); }
+
+// the parameter block of a family as the type its instances take: kcov_params_init, then the same bytes
+template <class PT>
+inline int kcov_params_init_as(PT* out, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget) {
+  kcov_params base;
+  HFMI_TRY(kcov_params_init(&base, x, N, d, family, sigma, ell, nugget));
+  static_cast<kcov_params&>(*out) = base;
+  return HFMI_OK;
+}

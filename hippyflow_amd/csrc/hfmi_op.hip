@@ -1,5 +1,7 @@
 // Operators of libhfmi.so (include/hfmi.h): constructors and setters of the tagged operator object, the pipelined host
 // callback, the panel-overlapped rank reduction and the application itself.  Host side only.
+#include <float.h>
+#include <math.h>
 #include <string.h>
 #include <time.h>
 
@@ -80,19 +82,30 @@ extern "C" int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** o
   return HFMI_OK;
 }
 // the checks every kernel covariance constructor shares
-static int kcov_check(const char* who, int64_t N, int d, int family, double ell, double nugget) {
+// last_family: HFMI_KERNEL_SQEXP for the creators that take a bare family, HFMI_KERNEL_MATERN1 for those that take a hfmi_kernel_spec
+static int kcov_check(const char* who, int64_t N, int d, int family, double ell, double nugget, int last_family = HFMI_KERNEL_SQEXP) {
   if (N < 1) HFMI_FAIL(HFMI_ERR_INVALID, "%s: needs at least one point (N = %lld)", who, (long long)N);
   if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "%s: points have 1, 2 or 3 coordinates, got d = %d", who, d);
-  if (family < HFMI_KERNEL_MATERN12 || family > HFMI_KERNEL_SQEXP) HFMI_FAIL(HFMI_ERR_INVALID, "%s: unknown kernel family %d", who, family);
+  if (family < HFMI_KERNEL_MATERN12 || family > last_family) HFMI_FAIL(HFMI_ERR_INVALID, "%s: unknown kernel family %d", who, family);
   if (!(ell > 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "%s: correlation length must be positive", who);
   if (!(nugget >= 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "%s: nugget must not be negative", who);
   return HFMI_OK;
 }
 // host points (n x d row-major) -> one array per coordinate on the device (the kernel reads x_c[j] for runs of consecutive j)
-static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t n, int d, dev_buf<double>* out) {
+// mL: the lower Cholesky factor of the kernel's metric (d x d row-major) or null; with it the device gets x' = L^T x,
+// x'_c = sum_{e >= c} L_ec x_e (e ascending), and |x'_i - x'_j|^2 = (x_i - x_j)^T G (x_i - x_j): the kernels see an isotropic problem
+static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t n, int d, dev_buf<double>* out, const double* mL = nullptr) {
   std::vector<double> soa((size_t)n * d);
   for (int64_t i = 0; i < n; ++i)
-    for (int c = 0; c < d; ++c) soa[(size_t)c * n + i] = host_points[(size_t)i * d + c];
+    for (int c = 0; c < d; ++c) {
+      const double* xi = host_points + (size_t)i * d;
+      double v = xi[c];
+      if (mL) {
+        v = mL[c * d + c] * xi[c];
+        for (int e = c + 1; e < d; ++e) v += mL[e * d + c] * xi[e];
+      }
+      soa[(size_t)c * n + i] = v;
+    }
   dev_buf<double> x;
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = (hipError_t)x.alloc(soa.size());
@@ -102,10 +115,10 @@ static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t 
   return HFMI_OK;
 }
 static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
-                       double nugget, hfmi_op** out) {
+                       double nugget, hfmi_op** out, const double* mL = nullptr) {
   std::unique_ptr<hfmi_op> op(op_new(ctx, kind));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  HFMI_TRY(kcov_upload_points(ctx, host_points, N, d, &op->kc_x));
+  HFMI_TRY(kcov_upload_points(ctx, host_points, N, d, &op->kc_x, mL));
   op->kc_N = N;
   op->kc_d = d;
   op->kc_family = family;
@@ -115,16 +128,18 @@ static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_poin
   *out = op.release();
   return HFMI_OK;
 }
-extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
-                                  double nugget, hfmi_op** out) {
+// The creators behind both entry-point sets: a bare family (last_family = HFMI_KERNEL_SQEXP, no metric) or a hfmi_kernel_spec
+// (last_family = HFMI_KERNEL_MATERN1; mL: the metric's lower factor or null)
+static int kcov_create(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                       int last_family, const double* mL, hfmi_op** out) {
   if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  HFMI_TRY(kcov_check("kernel_cov", N, d, family, ell, nugget));
-  return kcov_op_new(ctx, OP_KERNEL_COV, host_points, N, d, family, sigma, ell, nugget, out);
+  HFMI_TRY(kcov_check("kernel_cov", N, d, family, ell, nugget, last_family));
+  return kcov_op_new(ctx, OP_KERNEL_COV, host_points, N, d, family, sigma, ell, nugget, out, mL);
 }
-extern "C" int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
-                                        int family, double sigma, double ell, double nugget, int64_t diag_offset, hfmi_op** out) {
+static int kcov_cross_create(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d, int family,
+                             double sigma, double ell, double nugget, int64_t diag_offset, int last_family, const double* mL, hfmi_op** out) {
   if (!ctx || !host_targets || !host_sources || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  HFMI_TRY(kcov_check("kernel_cross_cov", N, d, family, ell, nugget));
+  HFMI_TRY(kcov_check("kernel_cross_cov", N, d, family, ell, nugget, last_family));
   if (M < 1) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: needs at least one target (M = %lld)", (long long)M);
   if (diag_offset == HFMI_KERNEL_NO_DIAGONAL) {
     if (nugget != 0.0) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: a nugget needs targets that are sources (diag_offset >= 0)");
@@ -133,39 +148,127 @@ extern "C" int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_target
               (long long)diag_offset, (long long)M, (long long)N);
   }
   hfmi_op* raw = nullptr;
-  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &raw));
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &raw, mL));
   std::unique_ptr<hfmi_op> op(raw);
-  HFMI_TRY(kcov_upload_points(ctx, host_targets, M, d, &op->kc_t));
+  HFMI_TRY(kcov_upload_points(ctx, host_targets, M, d, &op->kc_t, mL));
   op->kc_M = M;
   op->kc_diag = diag_offset;
   op->kc_slab = false;
   *out = op.release();
   return HFMI_OK;
 }
-extern "C" int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
-                                       double nugget, int64_t row0, int64_t nrows, hfmi_op** out) {
+static int kcov_rows_create(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                            int64_t row0, int64_t nrows, int last_family, const double* mL, hfmi_op** out) {
   if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  HFMI_TRY(kcov_check("kernel_cov_rows", N, d, family, ell, nugget));
+  HFMI_TRY(kcov_check("kernel_cov_rows", N, d, family, ell, nugget, last_family));
   if (row0 < 0 || nrows < 0 || row0 > N - nrows)
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_rows: rows %lld .. %lld + %lld do not lie inside 0 .. N = %lld", (long long)row0, (long long)row0,
               (long long)nrows, (long long)N);
   hfmi_op* op = nullptr;
-  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_points, N, d, family, sigma, ell, nugget, &op));
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_points, N, d, family, sigma, ell, nugget, &op, mL));
   op->kc_M = nrows;
   op->kc_diag = row0;
   op->kc_slab = true;
   *out = op;
   return HFMI_OK;
 }
-extern "C" int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
-                                       int family, double sigma, double ell, double nugget, hfmi_op** out) {
+static int kcov_grid_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family,
+                            double sigma, double ell, double nugget, int last_family, const double* mL, hfmi_op** out) {
   if (!ctx || !n || !h || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
-  HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget));
+  HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget, last_family));
   std::unique_ptr<hfmi_op> op(op_new(ctx, OP_KERNEL_COV_GRID));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, &op->fc));
+  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, mL, &op->fc));
   *out = op.release();
   return HFMI_OK;
+}
+extern "C" int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                                  double nugget, hfmi_op** out) {
+  return kcov_create(ctx, host_points, N, d, family, sigma, ell, nugget, HFMI_KERNEL_SQEXP, nullptr, out);
+}
+extern "C" int hfmi_op_kernel_cross_cov(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                        int family, double sigma, double ell, double nugget, int64_t diag_offset, hfmi_op** out) {
+  return kcov_cross_create(ctx, host_targets, M, host_sources, N, d, family, sigma, ell, nugget, diag_offset, HFMI_KERNEL_SQEXP, nullptr, out);
+}
+extern "C" int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
+                                       double nugget, int64_t row0, int64_t nrows, hfmi_op** out) {
+  return kcov_rows_create(ctx, host_points, N, d, family, sigma, ell, nugget, row0, nrows, HFMI_KERNEL_SQEXP, nullptr, out);
+}
+extern "C" int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                       int family, double sigma, double ell, double nugget, hfmi_op** out) {
+  return kcov_grid_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, HFMI_KERNEL_SQEXP, nullptr, out);
+}
+
+// G = L L^T, unblocked, column by column (the metric of a kernel covariance: hfmi_kcov_eval.h)
+int kcov_metric_factor(const double* G, int d, double* L) {
+  if (!G || !L) HFMI_FAIL(HFMI_ERR_INVALID, "kernel metric: null argument");
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "kernel metric: d = %d is not 1, 2 or 3", d);
+  double gmax = 0.0;
+  for (int i = 0; i < d * d; ++i) {
+    if (!isfinite(G[i])) HFMI_FAIL(HFMI_ERR_INVALID, "kernel metric: entry (%d, %d) is not finite", i / d, i % d);
+    gmax = std::max(gmax, fabs(G[i]));
+  }
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < i; ++j)
+      if (fabs(G[i * d + j] - G[j * d + i]) > 4.0 * DBL_EPSILON * gmax)
+        HFMI_FAIL(HFMI_ERR_INVALID, "kernel metric: not symmetric, G[%d][%d] = %.17g and G[%d][%d] = %.17g", i, j, G[i * d + j], j, i, G[j * d + i]);
+  for (int i = 0; i < d * d; ++i) L[i] = 0.0;
+  for (int j = 0; j < d; ++j) {
+    double piv = G[j * d + j];
+    for (int c = 0; c < j; ++c) piv -= L[j * d + c] * L[j * d + c];
+    if (!(piv > 0.0)) HFMI_FAIL(HFMI_ERR_INVALID, "kernel metric: not positive definite (pivot %d is %.3e)", j, piv);
+    const double root = sqrt(piv);
+    L[j * d + j] = root;
+    for (int i = j + 1; i < d; ++i) {
+      double v = G[i * d + j];      // the lower triangle is the one read
+      for (int c = 0; c < j; ++c) v -= L[i * d + c] * L[j * d + c];
+      L[i * d + j] = v / root;
+    }
+  }
+  return HFMI_OK;
+}
+extern "C" int hfmi_kernel_metric_factor(const double* G, int d, double* L) { return kcov_metric_factor(G, d, L); }
+
+// a descriptor's metric: null (all nine entries zero: the identity) or its factor in `store`
+static int kcov_spec_metric(const char* who, const hfmi_kernel_spec* spec, int d, double* store, const double** mL) {
+  if (!spec) HFMI_FAIL(HFMI_ERR_INVALID, "%s: null kernel descriptor", who);
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "%s: points have 1, 2 or 3 coordinates, got d = %d", who, d);
+  if (spec->d != d) HFMI_FAIL(HFMI_ERR_INVALID, "%s: the kernel descriptor is for d = %d, the points have d = %d", who, spec->d, d);
+  bool zero = true;
+  for (int i = 0; i < 9; ++i) zero = zero && spec->metric[i] == 0.0;
+  *mL = nullptr;
+  if (zero) return HFMI_OK;
+  HFMI_TRY(kcov_metric_factor(spec->metric, d, store));
+  *mL = store;
+  return HFMI_OK;
+}
+extern "C" int hfmi_op_kernel_cov_spec(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec* spec, hfmi_op** out) {
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec_metric("kernel_cov", spec, d, store, &mL));
+  return kcov_create(ctx, host_points, N, d, spec->family, spec->sigma, spec->ell, spec->nugget, HFMI_KERNEL_MATERN1, mL, out);
+}
+extern "C" int hfmi_op_kernel_cross_cov_spec(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                             const hfmi_kernel_spec* spec, int64_t diag_offset, hfmi_op** out) {
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec_metric("kernel_cross_cov", spec, d, store, &mL));
+  return kcov_cross_create(ctx, host_targets, M, host_sources, N, d, spec->family, spec->sigma, spec->ell, spec->nugget, diag_offset,
+                           HFMI_KERNEL_MATERN1, mL, out);
+}
+extern "C" int hfmi_op_kernel_cov_rows_spec(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec* spec,
+                                            int64_t row0, int64_t nrows, hfmi_op** out) {
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec_metric("kernel_cov_rows", spec, d, store, &mL));
+  return kcov_rows_create(ctx, host_points, N, d, spec->family, spec->sigma, spec->ell, spec->nugget, row0, nrows, HFMI_KERNEL_MATERN1, mL, out);
+}
+extern "C" int hfmi_op_kernel_cov_grid_spec(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                            const hfmi_kernel_spec* spec, hfmi_op** out) {
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec_metric("kernel_cov_grid", spec, d, store, &mL));
+  return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec->family, spec->sigma, spec->ell, spec->nugget, HFMI_KERNEL_MATERN1, mL, out);
 }
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
   if (!ctx || !M || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");

@@ -84,8 +84,10 @@ __global__ __launch_bounds__(PC_THREADS) void k_pchol_gather_row(const double* _
   if (c < j) prow[c] = L[(int64_t)c * ld + p];
 }
 
-// column j of L from the pivot (p, dp), the new diagonal and the workgroup's (max, lowest index, sum) of it
-__global__ __launch_bounds__(PC_THREADS) void k_pchol_column(kcov_params P, double* __restrict__ L, int64_t ld, int j, int64_t p, double dp,
+// column j of L from the pivot (p, dp), the new diagonal and the workgroup's (max, lowest index, sum) of it.  PT: kcov_params, or
+// kcov_k1_params for Matern-1 (the entry behind kcov_entry is what differs)
+template <class PT>
+__global__ __launch_bounds__(PC_THREADS) void k_pchol_column(PT P, double* __restrict__ L, int64_t ld, int j, int64_t p, double dp,
                                                              const double* __restrict__ prow, double* __restrict__ diag,
                                                              double* __restrict__ pmax, long long* __restrict__ pidx,
                                                              double* __restrict__ psum) {
@@ -194,11 +196,12 @@ static int pc_read_pick(hfmi_ctx* ctx, const pc_pick* dev, pc_pick* host) {
   return HFMI_OK;
 }
 
+template <class PT>
 static int pchol_run(hfmi_pchol* h, const hfmi_op* op, int kmax, double rel_tol, double* scratch, int grid) {
   hfmi_ctx* ctx = h->ctx;
   const int64_t N = op->kc_N, ld = h->L.ld;
-  kcov_params P;
-  HFMI_TRY(kcov_params_init(&P, op->kc_x, N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget));
+  PT P;
+  HFMI_TRY(kcov_params_init_as(&P, op->kc_x, N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget));
   // scratch: diag[N] | prow[kmax] | pmax[grid] | psum[grid] | pidx[grid] | pick
   double* diag = scratch;
   double* prow = diag + N;
@@ -232,7 +235,7 @@ static int pchol_run(hfmi_pchol* h, const hfmi_op* op, int kmax, double rel_tol,
                          (int64_t)pick.p, j, prow);
       HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_pchol_column, dim3(grid), dim3(PC_THREADS), 0, ctx->stream, P, h->p, ld, j, (int64_t)pick.p, pick.dp, prow, diag,
+    hipLaunchKernelGGL(k_pchol_column<PT>, dim3(grid), dim3(PC_THREADS), 0, ctx->stream, P, h->p, ld, j, (int64_t)pick.p, pick.dp, prow, diag,
                        pmax, pidx, psum);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_pchol_pick, dim3(1), dim3(PC_THREADS), 0, ctx->stream, grid, pmax, pidx, psum, pick_dev);
@@ -257,7 +260,9 @@ extern "C" int hfmi_pchol_create(hfmi_op* op, int max_rank, double rel_tol, hfmi
   const int64_t N = op->kc_N;
   const int kmax = (int)std::min<int64_t>(max_rank, N);
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column, PC_THREADS, 0));
+  const bool k1 = op->kc_family == HFMI_KERNEL_MATERN1;
+  if (k1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_k1_params>, PC_THREADS, 0));
+  else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_params>, PC_THREADS, 0));
   if (per_cu < 1) per_cu = 1;
   const int64_t ntiles = (N + PC_THREADS - 1) / PC_THREADS;
   int grid = (int)std::min<int64_t>(ntiles, (int64_t)per_cu * ctx->num_cus);
@@ -281,7 +286,7 @@ extern "C" int hfmi_pchol_create(hfmi_op* op, int max_rank, double rel_tol, hfmi
     hfmi_set_error("pchol: %s", hipGetErrorString(e));
     s = HFMI_ERR_HIP;
   } else {
-    s = pchol_run(h.get(), op, kmax, rel_tol, scratch, grid);
+    s = k1 ? pchol_run<kcov_k1_params>(h.get(), op, kmax, rel_tol, scratch, grid) : pchol_run<kcov_params>(h.get(), op, kmax, rel_tol, scratch, grid);
   }
   (void)hipStreamSynchronize(ctx->stream);      // before the scratch goes
   if (s != HFMI_OK) return s;

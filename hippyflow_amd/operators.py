@@ -214,30 +214,79 @@ def _points_array(points):
     return L.as_f64(pts)
 
 
-def kernel_cov_host(points, family, sigma, ell, nugget=0.0, rows=None):
+def _unknown_family(family):
+    return ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+
+
+def _check_metric(metric, d):
+    """None, or the metric as a (d, d) float64 array after the checks of hfmi_kernel_metric_factor: finite, symmetric to 4 eps max|G|,
+    positive definite.  A scalar is a 1 x 1 metric."""
+    if metric is None:
+        return None
+    G = np.array(metric, dtype=np.float64)
+    if G.ndim == 0:
+        G = G.reshape(1, 1)
+    if G.shape != (d, d):
+        raise ValueError("metric: a symmetric positive definite %d x %d matrix is required, got shape %r" % (d, d, G.shape))
+    if not np.all(np.isfinite(G)):
+        raise ValueError("metric: every entry must be finite")
+    if np.max(np.abs(G - G.T)) > 4.0 * np.finfo(np.float64).eps * np.max(np.abs(G)):
+        raise ValueError("metric: not symmetric")
+    try:
+        np.linalg.cholesky(G)
+    except np.linalg.LinAlgError:
+        raise ValueError("metric: not positive definite") from None
+    return np.ascontiguousarray(G)
+
+
+def _metric_points(pts, G):
+    """``pts @ L`` with G = L L^T: the coordinates in which the metric is the identity (``pts`` itself without a metric)"""
+    return pts if G is None else np.ascontiguousarray(pts @ np.linalg.cholesky(G))
+
+
+def _kernel_spec(family, d, sigma, ell, nugget, G):
+    """The hfmi_kernel_spec of a kernel: what Matern-1 and every kernel with a metric are created from."""
+    spec = L.KernelSpec(L.KERNEL_FAMILIES[family], int(d), float(sigma), float(ell), float(nugget))
+    if G is not None:
+        for i, v in enumerate(G.ravel()):
+            spec.metric[i] = v
+    return spec
+
+
+def _kernel_phi(family, dist, ell):
+    """phi(dist / ell) of ``kernel_cov_host`` for an array of distances"""
+    if family == "matern12":
+        return np.exp(-dist / ell)
+    if family == "matern32":
+        a = np.sqrt(3.0) * dist / ell
+        return (1.0 + a) * np.exp(-a)
+    if family == "matern52":
+        a = np.sqrt(5.0) * dist / ell
+        return (1.0 + a + a * a / 3.0) * np.exp(-a)
+    if family == "matern1":
+        from scipy.special import k1e
+        a = np.sqrt(2.0) * dist / ell
+        with np.errstate(invalid="ignore", under="ignore"):
+            return np.where(a > 0.0, a * k1e(a) * np.exp(-a), 1.0)
+    return np.exp(-0.5 * (dist / ell) ** 2)
+
+
+def kernel_cov_host(points, family, sigma, ell, nugget=0.0, rows=None, metric=None):
     """Dense host evaluation of the covariance ``KernelCovarianceOperator`` applies: C_ij = sigma^2 phi(|x_i - x_j| / ell)
     + nugget delta_ij (the delta is on the point INDEX), all rows or the rows ``rows``.  With r the scaled distance:
     'matern12' exp(-r); 'matern32' (1 + a) exp(-a), a = sqrt(3) r; 'matern52' (1 + a + a^2/3) exp(-a), a = sqrt(5) r;
-    'sqexp' exp(-r^2 / 2).  What tests and users compare the device operator against."""
+    'sqexp' exp(-r^2 / 2); 'matern1' a K_1(a), a = sqrt(2) r (1 at r = 0; ``scipy.special.k1e``).  ``metric``: a symmetric positive
+    definite d x d matrix G, r = sqrt(delta^T G delta) / ell, evaluated as the isotropic kernel on ``points @ L``, G = L L^T; None is
+    the identity.  What tests and users compare the device operator against."""
     if family not in L.KERNEL_FAMILIES:
-        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        raise _unknown_family(family)
     pts = _points_array(points)
+    pts = _metric_points(pts, _check_metric(metric, pts.shape[1]))
     r = np.arange(pts.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64)
     d2 = np.zeros((len(r), pts.shape[0]))
     for c in range(pts.shape[1]):
         d2 += (pts[r, c][:, None] - pts[None, :, c]) ** 2
-    dist = np.sqrt(d2)
-    if family == "matern12":
-        C = np.exp(-dist / ell)
-    elif family == "matern32":
-        a = np.sqrt(3.0) * dist / ell
-        C = (1.0 + a) * np.exp(-a)
-    elif family == "matern52":
-        a = np.sqrt(5.0) * dist / ell
-        C = (1.0 + a + a * a / 3.0) * np.exp(-a)
-    else:
-        C = np.exp(-0.5 * (dist / ell) ** 2)
-    C = sigma ** 2 * C
+    C = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell)
     if nugget:
         C[np.arange(len(r)), r] += nugget
     return C
@@ -248,25 +297,37 @@ class KernelCovarianceOperator(DeviceOperator):
     + nugget delta_ij, its entries evaluated inside the apply (hfmi_kcov.hip) and fed to the fp64 matrix cores.  ``points`` are
     the (N, d) node coordinates of the parameter's mesh or point cloud, d = 1, 2 or 3; ``family`` as in ``kernel_cov_host``.
     A drop-in ``prior.C`` for ``KLEProjector`` (and any place an explicit covariance went through ``npToDeviceOperator``):
-    memory is 8 N d bytes, so N is bounded by time (2 N^2 k flops per apply), not by HBM."""
+    memory is 8 N d bytes, so N is bounded by time (2 N^2 k flops per apply), not by HBM.
 
-    def __init__(self, points, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None):
+    ``family="matern1"`` is a K_1(a), the kernel of the BiLaplacian prior in two dimensions (``bilaplacian_kernel_2d``); its entries
+    cost several times those of the other families, so its apply is bound by their evaluation.  ``metric``: a symmetric positive
+    definite d x d matrix G, distances are sqrt(delta^T G delta) (None: the identity).  The library is handed L^T x, G = L L^T, and
+    runs the isotropic kernels; ``.points`` stays the caller's coordinates and ``.metric`` goes to every operator derived from this
+    one.  One of the four other families without a metric is created exactly as before."""
+
+    def __init__(self, points, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
-            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+            raise _unknown_family(family)
         pts = _points_array(points)
+        G = _check_metric(metric, pts.shape[1])
         super().__init__(ctx, pts.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.points = pts
-        L.call("hfmi_op_kernel_cov", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
-               self.sigma, self.ell, self.nugget, C.byref(self._op))
+        self.points, self.metric = pts, G
+        if family == "matern1" or G is not None:
+            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G)
+            L.call("hfmi_op_kernel_cov_spec", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), C.byref(self._op))
+        else:
+            L.call("hfmi_op_kernel_cov", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
+                   self.sigma, self.ell, self.nugget, C.byref(self._op))
 
     def to_dense(self, rows=None):
         """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
-        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows)
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, metric=self.metric)
 
     def rows(self, row0, row1):
         """Rows ``row0 .. row1 - 1`` of this operator as an operator N -> N (``KernelCovarianceRowsOperator``)."""
-        return KernelCovarianceRowsOperator(self.points, self.family, self.sigma, self.ell, self.nugget, row0, row1, ctx=self.ctx)
+        return KernelCovarianceRowsOperator(self.points, self.family, self.sigma, self.ell, self.nugget, row0, row1, ctx=self.ctx,
+                                            metric=self.metric)
 
     def sharded(self, collective):
         """An operator N -> N that equals C on every rank of ``collective``: this rank's row slab (``shard_rows``) with the collective's
@@ -285,7 +346,7 @@ class KernelCovarianceOperator(DeviceOperator):
 def _check_grid(shape, spacing, nodes, origin, family, ell, nugget):
     """The argument rules of hfmi_op_kernel_cov_grid that need no device; returns (shape, spacing, nodes or None, origin) as arrays."""
     if family not in L.KERNEL_FAMILIES:
-        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        raise _unknown_family(family)
     n = np.atleast_1d(np.asarray(shape, dtype=np.int64))
     if n.ndim != 1 or not 1 <= n.size <= 3:
         raise ValueError("a grid has 1, 2 or 3 axes, got shape %r" % (shape,))
@@ -342,26 +403,38 @@ class GridKernelCovarianceOperator(DeviceOperator):
     circulant embedding, d passes per pair of draws with the noise generated on the device, on an embedding grown until its spectrum
     is non-negative (or clipped, with a reported bound on the covariance error).  It is the draw to use on a grid, above all for rough
     kernels, short correlation lengths and large grids; ``PivotedCholesky.sample`` (of ``matrix_free()``) draws from L L^T instead and is
-    the one to prefer for draws at scattered points, or when a factor of small rank is at hand anyway."""
+    the one to prefer for draws at scattered points, or when a factor of small rank is at hand anyway.
 
-    def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None):
+    ``family="matern1"`` and ``metric`` as for ``KernelCovarianceOperator`` (a scalar metric on a grid with one axis).  With a metric the
+    kernel is even only in the whole offset vector, so the circulant's first column is built from signed offsets; its spectrum is real
+    all the same, and the apply, the sampler with its growth and clipping, the factor and ``GridKernelPrior`` run as for every kernel.
+    ``GridKernelCovarianceOperator(shape, spacing, **bilaplacian_kernel_2d(gamma, delta))`` is the BiLaplacian prior's covariance."""
+
+    def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None, metric=None):
         n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget)
+        G = _check_metric(metric, int(n.size))
         N = int(np.prod(n)) if nodes is None else int(nodes.size)
         super().__init__(ctx, N)
         self.grid_shape = tuple(int(v) for v in n)
         self.spacing, self.origin, self.nodes = h, o, nodes
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
+        self.metric = G
         self.points = L.as_f64(grid_node_points(n, h, nodes, o))
-        L.call("hfmi_op_kernel_cov_grid", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes), N,
-               L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget, C.byref(self._op))
+        if family == "matern1" or G is not None:
+            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G)
+            L.call("hfmi_op_kernel_cov_grid_spec", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
+                   N, C.byref(spec), C.byref(self._op))
+        else:
+            L.call("hfmi_op_kernel_cov_grid", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes), N,
+                   L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget, C.byref(self._op))
 
     def to_dense(self, rows=None):
         """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
-        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows)
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, metric=self.metric)
 
     def matrix_free(self):
         """The ``KernelCovarianceOperator`` over the same points: 2 N^2 k flops per apply, no padded grid in memory."""
-        return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx)
+        return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx, metric=self.metric)
 
     def sampler(self, max_growth=3, on_indefinite="raise", seed=0):
         """A ``GridFieldSampler``: exact draws m ~ N(0, C) at the cost of an apply (see the class)."""
@@ -574,30 +647,21 @@ def shard_rows(N, size, rank):
     return row0, row0 + q + (1 if rank < rem else 0)
 
 
-def kernel_cross_cov_host(targets, sources, family, sigma, ell, nugget=0.0, diag_offset=None):
+def kernel_cross_cov_host(targets, sources, family, sigma, ell, nugget=0.0, diag_offset=None, metric=None):
     """Dense host evaluation of what ``KernelCrossCovarianceOperator`` applies: the (M, N) matrix K_ij = sigma^2 phi(|t_i - s_j| / ell)
-    + nugget [j == i + diag_offset], ``family`` as in ``kernel_cov_host``.  ``diag_offset`` None: no target is a source (and the nugget
-    must be 0).  With ``targets = points[r0:r1]``, ``sources = points`` and ``diag_offset = r0`` it is
+    + nugget [j == i + diag_offset], ``family`` and ``metric`` as in ``kernel_cov_host``.  ``diag_offset`` None: no target is a source
+    (and the nugget must be 0).  With ``targets = points[r0:r1]``, ``sources = points`` and ``diag_offset = r0`` it is
     ``kernel_cov_host(points, ..., rows=range(r0, r1))``."""
     if family not in L.KERNEL_FAMILIES:
-        raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+        raise _unknown_family(family)
     tg, src = _points_array(targets), _points_array(sources)
     _check_cross(tg, src, nugget, diag_offset)
+    G = _check_metric(metric, src.shape[1])
+    tg, src = _metric_points(tg, G), _metric_points(src, G)
     d2 = np.zeros((tg.shape[0], src.shape[0]))
     for c in range(src.shape[1]):
         d2 += (tg[:, c][:, None] - src[None, :, c]) ** 2
-    dist = np.sqrt(d2)
-    if family == "matern12":
-        K = np.exp(-dist / ell)
-    elif family == "matern32":
-        a = np.sqrt(3.0) * dist / ell
-        K = (1.0 + a) * np.exp(-a)
-    elif family == "matern52":
-        a = np.sqrt(5.0) * dist / ell
-        K = (1.0 + a + a * a / 3.0) * np.exp(-a)
-    else:
-        K = np.exp(-0.5 * (dist / ell) ** 2)
-    K = sigma ** 2 * K
+    K = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell)
     if nugget:
         i = np.arange(tg.shape[0])
         K[i, i + int(diag_offset)] += nugget
@@ -625,28 +689,35 @@ class KernelCrossCovarianceOperator(DeviceOperator):
     target is a source, and the nugget must be 0.  What the Nystrom extension of a KLE or of a pivoted Cholesky factor applies
     (``nystrom_extend``, ``KLEProjector.extend``, ``PivotedCholesky.extend``)."""
 
-    def __init__(self, targets, sources, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, diag_offset=None, ctx=None):
+    def __init__(self, targets, sources, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, diag_offset=None, ctx=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
-            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+            raise _unknown_family(family)
         tg, src = _points_array(targets), _points_array(sources)
         _check_cross(tg, src, nugget, diag_offset)
+        G = _check_metric(metric, src.shape[1])
         super().__init__(ctx, tg.shape[0], src.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.targets, self.sources = tg, src
+        self.targets, self.sources, self.metric = tg, src, G
         self.diag_offset = None if diag_offset is None else int(diag_offset)
-        L.call("hfmi_op_kernel_cross_cov", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
-               L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget,
-               L.KERNEL_NO_DIAGONAL if diag_offset is None else self.diag_offset, C.byref(self._op))
+        diag = L.KERNEL_NO_DIAGONAL if diag_offset is None else self.diag_offset
+        if family == "matern1" or G is not None:      # the family and the metric (targets and sources alike) of ``KernelCovarianceOperator``
+            spec = _kernel_spec(family, src.shape[1], self.sigma, self.ell, self.nugget, G)
+            L.call("hfmi_op_kernel_cross_cov_spec", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
+                   C.byref(spec), diag, C.byref(self._op))
+        else:
+            L.call("hfmi_op_kernel_cross_cov", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
+                   L.KERNEL_FAMILIES[family], self.sigma, self.ell, self.nugget, diag, C.byref(self._op))
 
     def to_dense(self):
         """The same matrix on the host (``kernel_cross_cov_host``)."""
-        return kernel_cross_cov_host(self.targets, self.sources, self.family, self.sigma, self.ell, self.nugget, self.diag_offset)
+        return kernel_cross_cov_host(self.targets, self.sources, self.family, self.sigma, self.ell, self.nugget, self.diag_offset,
+                                     metric=self.metric)
 
     def transpose(self):
         """K(S, T), the operator with the two point sets swapped; only without a diagonal."""
         if self.diag_offset is not None:
             raise ValueError("transpose: only for a cross-covariance without a diagonal (diag_offset is %d)" % self.diag_offset)
-        return KernelCrossCovarianceOperator(self.sources, self.targets, self.family, self.sigma, self.ell, ctx=self.ctx)
+        return KernelCrossCovarianceOperator(self.sources, self.targets, self.family, self.sigma, self.ell, ctx=self.ctx, metric=self.metric)
 
     def transpmult(self, x, y):
         raise NotImplementedError("KernelCrossCovarianceOperator: apply transpose() for K^T")
@@ -657,27 +728,33 @@ class KernelCovarianceRowsOperator(DeviceOperator):
     the rows of C x, bit for bit; an overwriting apply leaves the other rows +0.0, an accumulating one leaves them alone.  An empty
     range is valid.  Made by ``KernelCovarianceOperator.rows`` / ``.sharded``."""
 
-    def __init__(self, points, family, sigma, ell, nugget, row0, row1, ctx=None):
+    def __init__(self, points, family, sigma, ell, nugget, row0, row1, ctx=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
-            raise ValueError("unknown kernel family %r (one of %s)" % (family, ", ".join(sorted(L.KERNEL_FAMILIES))))
+            raise _unknown_family(family)
         pts = _points_array(points)
         row0, row1 = int(row0), int(row1)
         if not 0 <= row0 <= row1 <= pts.shape[0]:
             raise ValueError("rows %d .. %d do not lie inside 0 .. %d" % (row0, row1, pts.shape[0]))
+        G = _check_metric(metric, pts.shape[1])
         super().__init__(ctx, pts.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.points, self.row0, self.row1 = pts, row0, row1
+        self.points, self.row0, self.row1, self.metric = pts, row0, row1, G
         self.collective = None
         self._hook = self._hook_error = None
-        L.call("hfmi_op_kernel_cov_rows", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
-               self.sigma, self.ell, self.nugget, row0, row1 - row0, C.byref(self._op))
+        if family == "matern1" or G is not None:
+            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G)
+            L.call("hfmi_op_kernel_cov_rows_spec", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), row0, row1 - row0,
+                   C.byref(self._op))
+        else:
+            L.call("hfmi_op_kernel_cov_rows", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
+                   self.sigma, self.ell, self.nugget, row0, row1 - row0, C.byref(self._op))
 
     def to_dense(self):
         """The N x N matrix this operator applies: the slab's rows of C, zeros elsewhere (before any rank sum)."""
         out = np.zeros((self.points.shape[0],) * 2)
         if self.row1 > self.row0:
             out[self.row0:self.row1] = kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget,
-                                                       rows=np.arange(self.row0, self.row1))
+                                                       rows=np.arange(self.row0, self.row1), metric=self.metric)
         return out
 
     def _attach_sum(self, collective):
@@ -733,6 +810,43 @@ def nystrom_extend(cross_op, encoder, d):
     for j in range(out.nvec()):
         out.view(j, 1).scale(1.0 / d[j])
     return out
+
+
+def anisotropy_2d(theta0, theta1, alpha):
+    """The 2 x 2 anisotropy tensor Theta of a BiLaplacian prior with ``theta0``, ``theta1`` and the angle ``alpha``:
+
+        Theta_00 = theta0 sin^2 alpha + theta1 cos^2 alpha,   Theta_01 = Theta_10 = (theta0 - theta1) sin alpha cos alpha,
+        Theta_11 = theta0 cos^2 alpha + theta1 sin^2 alpha.
+
+    This formula IS the definition for this package (it is the one the reference's prior is documented with; that code is not
+    available here to compare against).  theta0 and theta1 are its eigenvalues, so both must be positive."""
+    theta0, theta1, alpha = float(theta0), float(theta1), float(alpha)
+    if not (theta0 > 0.0 and theta1 > 0.0 and np.isfinite(theta0) and np.isfinite(theta1) and np.isfinite(alpha)):
+        raise ValueError("anisotropy_2d: theta0 and theta1 must be positive and finite, alpha finite")
+    s, c = np.sin(alpha), np.cos(alpha)
+    off = (theta0 - theta1) * s * c
+    return np.array([[theta0 * s * s + theta1 * c * c, off], [off, theta0 * c * c + theta1 * s * s]])
+
+
+def bilaplacian_kernel_2d(gamma, delta, theta0=2.0, theta1=0.5, alpha=np.pi / 4):
+    """The kernel of the BiLaplacian prior in two dimensions as keyword arguments of the kernel covariance operators: the covariance of
+    the precision (delta - gamma div Theta grad)^2 in FREE SPACE is the Matern field of smoothness 1,
+
+        c(x) = sigma^2 (kappa r) K_1(kappa r),   r^2 = x^T Theta^-1 x,   kappa^2 = delta / gamma,
+        sigma^2 = 1 / (4 pi delta gamma sqrt(det Theta)),
+
+    that is ``family="matern1"`` (a K_1(a), a = sqrt(2) r / ell) with ``ell = sqrt(2 gamma / delta)`` and ``metric = inv(Theta)``,
+    ``Theta = anisotropy_2d(theta0, theta1, alpha)``.  The defaults are those of the reference's ``BiLaplacian2D``.  Splat the result:
+    ``GridKernelCovarianceOperator(shape, spacing, **bilaplacian_kernel_2d(gamma, delta))``.  What is NOT in it: the boundary.  A
+    finite-element prior on a bounded mesh has Robin or Neumann conditions that raise the variance near the boundary and bend the
+    correlations there; this is the kernel of the interior, away from it by a few correlation lengths."""
+    gamma, delta = float(gamma), float(delta)
+    if not (gamma > 0.0 and delta > 0.0 and np.isfinite(gamma) and np.isfinite(delta)):
+        raise ValueError("bilaplacian_kernel_2d: gamma and delta must be positive and finite")
+    Theta = anisotropy_2d(theta0, theta1, alpha)
+    det = Theta[0, 0] * Theta[1, 1] - Theta[0, 1] * Theta[1, 0]
+    inv = np.array([[Theta[1, 1], -Theta[0, 1]], [-Theta[1, 0], Theta[0, 0]]]) / det
+    return dict(family="matern1", sigma=1.0 / np.sqrt(4.0 * np.pi * delta * gamma * np.sqrt(det)), ell=np.sqrt(2.0 * gamma / delta), metric=inv)
 
 
 class _Csr:

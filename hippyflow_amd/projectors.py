@@ -743,7 +743,8 @@ class KLEProjector:
             raise ValueError("extend: the Nystrom extension is for 'mass' and 'identity' orthogonality, not 'prior'")
         if self._kle_encoder is None or self.d_KLE is None:
             raise ValueError("extend: call construct_input_subspace('mass' | 'identity') first")
-        cross = KernelCrossCovarianceOperator(points, self.C.points, self.C.family, self.C.sigma, self.C.ell, ctx=self.ctx)
+        cross = KernelCrossCovarianceOperator(points, self.C.points, self.C.family, self.C.sigma, self.C.ell, ctx=self.ctx,
+                                              metric=self.C.metric)
         return nystrom_extend(cross, self._kle_encoder, self.d_KLE)
 
     def _Msolver(self):

@@ -173,6 +173,7 @@ HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out
 #define HFMI_KERNEL_MATERN32 1
 #define HFMI_KERNEL_MATERN52 2
 #define HFMI_KERNEL_SQEXP 3
+#define HFMI_KERNEL_MATERN1 4 /* a K_1(a), a = sqrt(2) r: only through a hfmi_kernel_spec (below); the creators with a bare family refuse it */
 HFMI_API int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, hfmi_op** out);
 /*     the rectangular cross-covariance between two point sets, by the same kernel: K_ij = sigma^2 phi(|t_i - s_j| / ell)
@@ -214,6 +215,40 @@ HFMI_API int hfmi_op_kernel_cov_rows(hfmi_ctx* ctx, const double* host_points, i
 HFMI_API int hfmi_op_kernel_cov_grid(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
                                      const int64_t* host_nodes_or_null, int64_t N, int family, double sigma, double ell,
                                      double nugget, hfmi_op** out);
+/*     The four kernel covariances above from a DESCRIPTOR of the kernel, which adds two things the bare (family, sigma, ell, nugget)
+ *     cannot say.  The argument lists are the ones above with the descriptor in place of those four; spec->d must equal d.
+ *       HFMI_KERNEL_MATERN1: phi = a K_1(a), a = sqrt(2) r, phi(0) = 1 -- the Matern field of smoothness nu = 1, which is the kernel of
+ *     the squared operator (delta - gamma div Theta grad)^2 in two dimensions (the BiLaplacian prior).  K_1 is evaluated on the device
+ *     by its power series for a <= 2 and by a Chebyshev interpolant of sqrt(a) e^a K_1(a) in 2 / a beyond (csrc/hfmi_kcov_k1.h), to a few
+ *     units of the last place; a = 0 (the diagonal, duplicate points) gives exactly 1, large a underflows to +0.  That evaluation costs
+ *     several times the others, so a Matern-1 apply of hfmi_op_kernel_cov is bound by it, not by the matrix cores.
+ *       A METRIC: r = sqrt(delta^T G delta) / ell with G symmetric positive definite, d x d row-major in metric[0 .. d*d-1]; all nine
+ *     entries zero = the identity, which with one of the four first families is exactly the creator above (same kernels, same bits).
+ *     G is factored G = L L^T on the host (hfmi_kernel_metric_factor).  Scattered points -- sources and targets -- are uploaded as
+ *     x' = L^T x, so the apply, the row slab and hfmi_pchol_* see an isotropic problem and are the kernels they were.  On a grid the
+ *     matrix stays block-Toeplitz but the kernel is even only in the whole offset vector, so the circulant's first column takes signed
+ *     offsets: position s_c stands for o_c = s_c below P_c / 2 and s_c - P_c above it, the entry at s_c = P_c / 2 is the mean over both
+ *     signs (no apply reads it), r^2 = |L^T diag(h) o|^2 / ell^2.  The column is jointly even, Lambda is real, and everything after
+ *     it -- the passes, hfmi_grid_sampler_* with its growth and clipping, hfmi_op_grid_factor -- is unchanged and picks family and metric
+ *     up from the operator.
+ *     HFMI_ERR_INVALID: what the creator above answers, with family up to HFMI_KERNEL_MATERN1 allowed; spec NULL or spec->d != d; a metric
+ *     with an entry that is not finite, with |G_ij - G_ji| > 4 eps max |G|, or with a Cholesky pivot that is not positive. */
+typedef struct hfmi_kernel_spec {
+  int family; /* HFMI_KERNEL_*, MATERN1 included */
+  int d;
+  double sigma, ell, nugget;
+  double metric[9]; /* row-major d x d; all zeros = identity */
+} hfmi_kernel_spec;
+HFMI_API int hfmi_op_kernel_cov_spec(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec* spec, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cross_cov_spec(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                           const hfmi_kernel_spec* spec, int64_t diag_offset, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_rows_spec(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec* spec, int64_t row0,
+                                          int64_t nrows, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_grid_spec(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
+                                          const int64_t* host_nodes_or_null, int64_t N, const hfmi_kernel_spec* spec, hfmi_op** out);
+/*     the lower Cholesky factor of a metric, on the host, no context and no device: G (d x d row-major, d = 1, 2 or 3) -> L (d x d
+ *     row-major, zeros above the diagonal), unblocked, column by column.  HFMI_ERR_INVALID as listed above. */
+HFMI_API int hfmi_kernel_metric_factor(const double* G, int d, double* L);
 /*     its launch plan, from the planner the launcher asks (csrc/hfmi_fftcov_plan.h); no context and no device.  nvec vectors, a work
  *     buffer budget in bytes (<= 0: the default, 512 MiB); the tuning key "fftcov_pairs" counts as in an apply.
  *     words[HFMI_FFTCOV_PLAN_WORDS]:  0 d  1-3 P_c  4 prod P_c  5 pairs = ceil(nvec / 2)  6 pairs per chunk  7 chunks  8 passes
