@@ -19,6 +19,9 @@ KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3, "mat
 KERNEL_NO_DIAGONAL = -1                                # HFMI_KERNEL_NO_DIAGONAL: no target of a cross-covariance is a source
 GRID_COV_MAX_NODES = 2048                              # nodes per axis of hfmi_op_kernel_cov_grid (FFTCOV_MAXN of hfmi_fftcov_plan.h)
 FFTCOV_PLAN_WORDS = 96                                 # HFMI_FFTCOV_PLAN_WORDS of include/hfmi.h
+GRID_COV_LONG_MAX_NODES = 1 << 23                      # nodes per axis of hfmi_op_kernel_cov_grid_long (FFTCOV_LONG_MAXN)
+GRID_COV_LONG_MAX_GROWTH = 6                           # growth of hfmi_grid_sampler_create_long (FFTCOV_LONG_MAX_GROWTH)
+FFTCOV_LONG_PLAN_WORDS = 280                           # HFMI_FFTCOV_LONG_PLAN_WORDS of include/hfmi.h
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
 PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h
 
@@ -104,6 +107,9 @@ SIGNATURES = {
     "hfmi_fftcov_sample_plan_predict": [C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_op_grid_factor": [_P, C.c_int, _PP],
     "hfmi_fftcov_factor_plan_predict": [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
+    "hfmi_op_kernel_cov_grid_long": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC, _PP],
+    "hfmi_grid_sampler_create_long": [_P, C.c_int, C.c_int, _PP],
+    "hfmi_fftcov_long_plan_predict": [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],
@@ -465,7 +471,7 @@ class Context:
         kind, shape = (C.c_int * G)(), (C.c_int64 * (3 * G))()
         ms, n, fl, by = (C.c_double * G)(), (C.c_int64 * G)(), (C.c_double * G)(), (C.c_double * G)()
         call("hfmi_profile_end", self.handle, G, C.byref(ng), kind, shape, ms, n, fl, by)
-        names = ("k_tsgemm_tn", "k_tsgemm_nn")
+        names = ("k_tsgemm_tn", "k_tsgemm_nn", "fftcov_pass")      # the last: tuning key "prof_level" 3 (m = L, k = 4 flags + part, N = pass index)
         return [{"kernel": names[kind[g]], "m": shape[3 * g], "k": shape[3 * g + 1], "N": shape[3 * g + 2], "ms": ms[g],
                  "launches": int(n[g]), "flops_per_launch": fl[g], "bytes_per_launch": by[g]} for g in range(ng.value)]
 

@@ -385,6 +385,28 @@ extern "C" int hfmi_fftcov_factor_plan_predict(int d, const int64_t* n, int grow
   fftcov_factor_plan_words(p, growth, transpose, words);
   return HFMI_OK;
 }
+// ... and of the long route (split-line passes): kind 0 apply (growth 0), 1 draw, 2 factor S, 3 factor S^T, at that longest line
+static_assert(FFTCOV_LONG_PLAN_WORDS == HFMI_FFTCOV_LONG_PLAN_WORDS, "include/hfmi.h sizes the array of hfmi_fftcov_long_plan_predict");
+extern "C" int hfmi_fftcov_long_plan_predict(int kind, int d, const int64_t* n, int growth, int max_line, int nvec, int64_t budget_bytes,
+                                             int64_t* words) {
+  if (!n || !words) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
+  if (kind < FFTCOV_KIND_APPLY || kind > FFTCOV_KIND_FACTOR_T) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: kind %d is not 0 .. 3", kind);
+  if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: d = %d is not 1, 2 or 3", d);
+  for (int c = 0; c < d; ++c)
+    if (n[c] < 1 || n[c] > FFTCOV_LONG_MAXN)
+      HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: n[%d] = %lld is not in 1 .. %lld", c, (long long)n[c], (long long)FFTCOV_LONG_MAXN);
+  if (nvec < 0) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: negative number of vectors");
+  if (!fftcov_max_line_ok(max_line))
+    HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: max_line = %d is not a power of two in %d .. %d", max_line, FFTCOV_LONG_MIN_LINE, FFTCOV_LONG_MAX_LINE);
+  if (kind == FFTCOV_KIND_APPLY && growth != 0) HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: an apply has growth 0, got %d", growth);
+  if (!fftcov_long_feasible(d, n, growth, max_line))
+    HFMI_FAIL(HFMI_ERR_INVALID, "fftcov_long_plan_predict: growth %d is outside 0..%d or takes an axis past max_line^2 = %lld entries", growth,
+              FFTCOV_LONG_MAX_GROWTH, (long long)max_line * max_line);
+  fftcov_long_plan p = fftcov_long_plan_passes(kind, d, n, growth, max_line);
+  fftcov_plan_chunks(p.base, nvec, budget_bytes, fftcov_pairs_knob());
+  fftcov_long_plan_words(p, growth, kind, words);
+  return HFMI_OK;
+}
 
 extern "C" int hfmi_ctx_set_stream(hfmi_ctx* ctx, void* hip_stream) {
   if (!ctx) HFMI_FAIL(HFMI_ERR_INVALID, "null ctx");
@@ -510,7 +532,8 @@ int g_comm_panels = -1;    // HFMI_COMM_PANELS: 0 = one all-reduce after the pro
 // What a profiling region (hfmi_profile_begin .. _end) records.  Every record is a pair of events on the stream, and an event
 // between two dependent kernels costs 2-4 us of idle GPU: with one pair per contraction and per phase a 64-sample shard step of
 // config 4 carried ~32 of them.  Level 2 (default): contractions and phases.  Level 1: only contractions of at least
-// HFMI_PROF_MIN_GFLOP (2.0) Gflop -- what a roofline line needs -- and no phases.
+// HFMI_PROF_MIN_GFLOP (2.0) Gflop -- what a roofline line needs -- and no phases.  Level 3: level 2 plus every launch of a pass of
+// the grid kernel covariance (prof_start_pass; measurements of single passes only: an event pair per pass).
 static int g_prof_level = 2;
 // HFMI_QR_TRUST_FIRST=0 / tuning key "qr_trust_first": the first Cholesky-QR pass of the Gram-form solve waits for its status words
 // (the behaviour up to round 4: one host round trip in the middle of every solve); default 1
@@ -523,7 +546,7 @@ int api_tuning_set(const char* key, int value) {
     g_comm_panels = value;
     return 1;
   }
-  if (key && !strcmp(key, "prof_level") && (value == 1 || value == 2)) {
+  if (key && !strcmp(key, "prof_level") && value >= 1 && value <= 3) {
     g_prof_level = value;
     return 1;
   }
@@ -546,6 +569,7 @@ extern "C" int hfmi_tuning_set(const char* key, int value) {
   else if (key && pchol_tuning_set(key, value)) {}
   else if (key && fftcov_knob_set(key, value)) {}
   else if (key && fftcov_sample_knob_set(key, value)) {}
+  else if (key && fftcov_long_knob_set(key, value)) {}
   else HFMI_FAIL(HFMI_ERR_INVALID, "tuning_set: unknown key/value");
   return HFMI_OK;
 }
@@ -562,6 +586,22 @@ int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N) {
   // algorithmic work (each operand touched once): flops 2 N m k, bytes 8 (N m + N k + m k)
   r.flops = 2.0 * (double)N * (double)m * (double)k;
   r.bytes = 8.0 * ((double)N * m + (double)N * k + (double)m * k);
+  if (r.e0.create() != 0 || r.e1.create() != 0) return -1;
+  (void)hipEventRecord(r.e0, ctx->stream);
+  ctx->prof.push_back(std::move(r));
+  return (int)ctx->prof.size() - 1;
+}
+// one pass of the grid kernel covariance (kind HFMI_PROF_FFTCOV_PASS, level 3 only): the group is (line length, flags and part,
+// index of the pass in its plan), the bytes those the pass moves
+int prof_start_pass(hfmi_ctx* ctx, int64_t L, int64_t flags_part, int64_t index, double bytes) {
+  if (!ctx->profiling || g_prof_level < 3) return -1;
+  hfmi_ctx::prof_rec r;
+  r.kind = 2;
+  r.m = L;
+  r.k = flags_part;
+  r.N = index;
+  r.flops = 0.0;
+  r.bytes = bytes;
   if (r.e0.create() != 0 || r.e1.create() != 0) return -1;
   (void)hipEventRecord(r.e0, ctx->stream);
   ctx->prof.push_back(std::move(r));

@@ -31,6 +31,11 @@
 // node map, n0 = P_0 and all P_0 positions loaded / stored ARE the direct load and store of a block of length prod P_c, so every pass
 // of a factor in 2 or 3 dimensions is a launch of k_fftcov_pass.  Only the single fused pass of d = 1 needs the node map on one side
 // and none on the other; k_fftcov_factor (FAC) is the body with that choice read from the pass flags.  k_fftcov_root makes the table.
+//
+// The long route (hfmi_op_kernel_cov_grid_long and its samplers; rules: "split-line passes" in hfmi_fftcov_plan.h) splits an embedding
+// axis longer than max_line into two sub-axes; a pass along a sub-axis is k_fftcov_split / k_fftcov_split_draw, the body with SPLIT: its
+// own line map, the axis position p pm + sub sm as the limit of loads and stores, and the four-step twiddle fused into the store of a
+// forward high pass or the load of an inverse one.  Passes along whole axes stay launches of the kernels above.
 #include <math.h>
 
 #include <algorithm>
@@ -56,8 +61,11 @@ struct fftcov_state {
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
   dev_buf<double> root;    // a sampler's, made at its first factor: sqrt(max(lambda, 0) / prod P_c), the order of lambda
   dev_buf<double2> work;   // work_pairs() arrays of prod P_c entries
-  int growth = 0;          // the embedding's: 0 for an operator, a sampler may double every P_c up to three times
-  fftcov_plan plan;        // the passes of an apply, or of a draw (a sampler's state)
+  int growth = 0;          // the embedding's: 0 for an operator, a sampler may double every P_c up to three times (six: long route)
+  fftcov_plan plan;        // the passes of an apply, or of a draw (a sampler's state); long route: the embedding only, no passes
+  bool long_route = false; // hfmi_op_kernel_cov_grid_long and its samplers: the passes are lplan's
+  int max_line = FFTCOV_LONG_MAX_LINE;
+  fftcov_long_plan lplan;
   int work_pairs() const { return (int)(work.bytes() / (size_t)plan.pair_bytes); }
 };
 
@@ -111,10 +119,33 @@ __device__ __forceinline__ void fc_coloured_noise(const fftcov_gen_args& G, uint
   v1 = double2{s1 * z[2], s1 * z[3]};
 }
 
+// what a pass along a sub-axis of a split embedding axis adds (hfmi_fftcov_plan.h: split-line passes).  A type of its own, so that the
+// apply's kernel takes the argument block it always took.
+struct fftcov_split_args {
+  int64_t inner, esub, sub_stride;   // a line number is  inner-part + inner (sub + esub o)
+  int loginner, pm, sm, logP;        // axis position of (p, sub) = p pm + sub sm; twiddles exp(-2 pi i n2 k1 / 2^logP)
+};
+
+// the table of k_fftcov_split: per line of the workgroup, sub sm (the axis position of line position 0, less the lines above)
+template <bool SPLIT>
+__device__ __forceinline__ int* fc_line_offsets() {
+  __shared__ int loff[FFTCOV_MAX_LINES];
+  return loff;
+}
+// the inter-step twiddle of a split axis: exp(-2 pi i n2 k1 / P), k1 = bitrev(p) of the high sub-axis' L = 2^logL points
+__device__ __forceinline__ double2 fc_split_twiddle(int n2, int p, int logL, int logP) {
+  const int k1 = (int)(__brev((unsigned)p) >> (32 - logL));
+  double s, c;
+  sincospi(-ldexp((double)(n2 * k1), 1 - logP), &s, &c);
+  return double2{c, s};
+}
+
 // GEN: the load is generated (the first pass of a draw); otherwise the pass of an apply, compiled to the code it always was.
 // FAC: the fused pass of a factor in one dimension: FFTCOV_LOAD_FULL / FFTCOV_STORE_FULL drop the node map on that side
-template <bool GEN, bool FAC = false>
-__device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, const fftcov_gen_args& G) {
+// SPLIT: a pass along a sub-axis (k_fftcov_split, k_fftcov_split_draw): the line map, the position limits and the fused twiddles of
+// fftcov_split_args; every other instance compiles to the code it was
+template <bool GEN, bool FAC = false, bool SPLIT = false>
+__device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, const fftcov_gen_args& G, const fftcov_split_args& S = fftcov_split_args{}) {
   extern __shared__ double2 fc_lds[];
   __shared__ int64_t lbase[FFTCOV_MAX_LINES];    // first entry of the line in the pair's array, -1: no such line
   __shared__ int64_t gbase[FFTCOV_MAX_LINES];    // axis-0 lines: grid node of position 0
@@ -126,16 +157,35 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
   const int64_t line0 = (int64_t)blockIdx.x * lpw;
   const int pair = blockIdx.y;
   double2* buf = A.buf + (int64_t)pair * A.pair_stride;
-  for (int j = tid; j < lpw; j += nt) {
-    const int64_t line = line0 + j;
-    int64_t b = -1, g = -1;
-    if (line < A.nlines) {
-      const int64_t inner = line & (A.stride - 1), o = line >> A.logstride;
-      b = inner + (o % A.oe0) * A.os0 + (o / A.oe0) * A.os1;
-      g = o * A.n0;
+  if constexpr (SPLIT) {
+    int* loff = fc_line_offsets<SPLIT>();
+    for (int j = tid; j < lpw; j += nt) {
+      const int64_t line = line0 + j;
+      int64_t b = -1, g = -1;
+      int off = 0;
+      if (line < A.nlines) {
+        const int64_t inner = line & (S.inner - 1), r = line >> S.loginner;
+        const int64_t sub = r % S.esub, o = r / S.esub;
+        b = inner + sub * S.sub_stride + (o % A.oe0) * A.os0 + (o / A.oe0) * A.os1;
+        g = o * A.n0;
+        off = (int)sub * S.sm;
+      }
+      lbase[j] = b;
+      gbase[j] = g;
+      loff[j] = off;
     }
-    lbase[j] = b;
-    gbase[j] = g;
+  } else {
+    for (int j = tid; j < lpw; j += nt) {
+      const int64_t line = line0 + j;
+      int64_t b = -1, g = -1;
+      if (line < A.nlines) {
+        const int64_t inner = line & (A.stride - 1), o = line >> A.logstride;
+        b = inner + (o % A.oe0) * A.os0 + (o / A.oe0) * A.os1;
+        g = o * A.n0;
+      }
+      lbase[j] = b;
+      gbase[j] = g;
+    }
   }
   for (int i = tid; i < qm; i += nt) ltw[i] = A.tw[(int64_t)i * A.tw_step];
   __syncthreads();
@@ -169,6 +219,30 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
       if (b >= 0) fc_coloured_noise(G, gp, b + (int64_t)p * A.stride, A.lambda, kc, v0, v1);
       x[j * ls + p] = v0;
       x[strided ? (j + 1) * ls + p : j * ls + p + 1] = v1;
+    }
+  } else if constexpr (SPLIT) {
+    // as below, with the axis position p pm + sub sm in place of p; a high inverse pass multiplies the conjugate twiddle in
+    const int* loff = fc_line_offsets<SPLIT>();
+    for (int e = tid; e < total; e += nt) {
+      const int j = strided ? (e & (lpw - 1)) : (e >> logL);
+      const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+      double2 v = double2{0.0, 0.0};
+      const int64_t b = lbase[j];
+      const int64_t pos = (int64_t)p * S.pm + loff[j];
+      if (b >= 0 && pos < A.nload) {
+        if (A.flags & FFTCOV_SCATTER) {
+          const int64_t g = gbase[j] + pos;
+          const int64_t pt = A.inv ? A.inv[g] : g;
+          if (pt >= 0) {
+            v.x = A.W[(int64_t)c0 * A.ldw + pt];
+            if (has1) v.y = A.W[(int64_t)(c0 + 1) * A.ldw + pt];
+          }
+        } else {
+          v = buf[b + (int64_t)p * A.stride];
+        }
+        if (A.flags & FFTCOV_TW_LOAD) v = fc_mulc(v, fc_split_twiddle(loff[j], p, logL, S.logP));
+      }
+      x[j * ls + p] = v;
     }
   } else {
     for (int e = tid; e < total; e += nt) {
@@ -279,6 +353,35 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
     }
   }
 
+  if constexpr (SPLIT) {
+    // as below, with the axis position p pm + sub sm; a high forward pass multiplies the twiddle in
+    const int* loff = fc_line_offsets<SPLIT>();
+    for (int e = tid; e < total; e += nt) {
+      const int j = strided ? (e & (lpw - 1)) : (e >> logL);
+      const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+      const int64_t b = lbase[j];
+      const int64_t pos = (int64_t)p * S.pm + loff[j];
+      if (b >= 0 && pos < A.nstore) {
+        double2 v = x[j * ls + p];
+        if (A.flags & FFTCOV_TW_STORE) v = fc_mul(v, fc_split_twiddle(loff[j], p, logL, S.logP));
+        if (A.flags & FFTCOV_GATHER) {
+          const int64_t g = gbase[j] + pos;
+          const int64_t pt = A.inv ? A.inv[g] : g;
+          if (pt >= 0) {
+            double* y0 = A.Y + (int64_t)c0 * A.ldy + pt;
+            *y0 = A.accumulate ? *y0 + v.x : v.x;
+            if (has1) {
+              double* y1 = y0 + A.ldy;
+              *y1 = A.accumulate ? *y1 + v.y : v.y;
+            }
+          }
+        } else {
+          buf[b + (int64_t)p * A.stride] = v;
+        }
+      }
+    }
+    return;
+  }
   for (int e = tid; e < total; e += nt) {
     const int j = strided ? (e & (lpw - 1)) : (e >> logL);
     const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
@@ -308,6 +411,14 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_pass(fftcov_pass_
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_draw(fftcov_pass_args A, fftcov_gen_args G) { fftcov_pass_body<true>(A, G); }
 // the one pass of a factor in one dimension (hfmi_op_grid_factor): node map on one side, the block of padded vectors on the other
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_factor(fftcov_pass_args A) { fftcov_pass_body<false, true>(A, fftcov_gen_args{}); }
+// a pass along a sub-axis of a split embedding axis (the long route): apply, spectrum and factor passes; and the generated first pass
+// of a draw when the last axis is split
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_split(fftcov_pass_args A, fftcov_split_args S) {
+  fftcov_pass_body<false, false, true>(A, fftcov_gen_args{}, S);
+}
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_split_draw(fftcov_pass_args A, fftcov_gen_args G, fftcov_split_args S) {
+  fftcov_pass_body<true, false, true>(A, G, S);
+}
 
 // the circulant's first column of an isotropic kernel of the four first families: entry (j0, j1, j2) is the kernel at the offsets
 // min(j_c, P_c - j_c) h_c, the nugget on entry 0
@@ -390,7 +501,8 @@ __global__ __launch_bounds__(256) void k_fftcov_root(const double* lambda, doubl
 // multiply reads, null = Lambda / P (a factor's passes hand over the root table)
 static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftcov_plan& p, const fftcov_pass& q, int pairs, int col0,
                               const double* W, int64_t ldw, double* Y, int64_t ldy, int ncols, int accumulate,
-                              const fftcov_gen_args* gen = nullptr, const double* table = nullptr) {
+                              const fftcov_gen_args* gen = nullptr, const double* table = nullptr, const fftcov_sub* sub = nullptr,
+                              int index = -1) {
   fftcov_pass_args A;
   A.buf = st->work;
   A.pair_stride = p.Ptot;
@@ -413,7 +525,26 @@ static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftco
   const int full = q.flags & (FFTCOV_LOAD_FULL | FFTCOV_STORE_FULL);
   const bool both = (q.flags & FFTCOV_SCATTER) && (q.flags & FFTCOV_GATHER);
   if (full && !both) A.inv = nullptr, A.n0 = p.P[0];
-  if (full && both) {
+  // tuning key "prof_level" 3 inside a profiling region: this launch between two events, with the bytes it moves
+  const int part = sub ? sub->part : FFTCOV_WHOLE;
+  // (nload and nstore count AXIS positions; a line of a high sub-axis holds every pm-th of them, to within one per line)
+  const int pm = part == FFTCOV_HI ? sub->pm : 1;
+  const int loads = std::min(q.L, (q.nload + pm - 1) / pm), stores = std::min(q.L, (q.nstore + pm - 1) / pm);
+  const int pidx = prof_start_pass(ctx, q.L, 4 * (int64_t)q.flags + part, index,
+                                   (double)pairs * (double)q.nlines * (16.0 * (loads + stores) + ((q.flags & FFTCOV_MUL) ? 8.0 * q.L : 0.0)));
+  if (sub && sub->part != FFTCOV_WHOLE) {
+    // a sub-axis: never both sides of the block (d = 1 with a split axis has three passes); the extra static table of line offsets
+    if (both || q.lds + FFTCOV_LONG_STATIC_LDS > FFTCOV_LDS_BYTES || sub->esub < 1 || (sub->inner & (sub->inner - 1)))
+      HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: a split pass of %d lines x %d entries cannot be launched", q.lpw, q.L);
+    const fftcov_split_args S{sub->inner, sub->esub, sub->sub_stride, fftcov_log2(sub->inner), sub->pm, sub->sm, sub->logP};
+    if (gen) {
+      const bool paired = q.stride > 1 ? (q.lpw >= 2 && q.nlines % 2 == 0) : q.L >= 2;
+      if (!paired) HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: the noise pass of %d lines x %d entries does not pair its entries", q.lpw, q.L);
+      hipLaunchKernelGGL(k_fftcov_split_draw, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A, *gen, S);
+    } else {
+      hipLaunchKernelGGL(k_fftcov_split, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A, S);
+    }
+  } else if (full && both) {
     if (gen || q.nlines != 1) HFMI_FAIL(HFMI_ERR_INVALID, "grid_factor: a pass that loads and stores vectors is the single line of d = 1");
     hipLaunchKernelGGL(k_fftcov_factor, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A);
   } else if (gen) {
@@ -424,7 +555,31 @@ static int fftcov_launch_pass(hfmi_ctx* ctx, const fftcov_state* st, const fftco
   } else {
     hipLaunchKernelGGL(k_fftcov_pass, dim3((unsigned)q.grid_x, (unsigned)pairs), dim3(q.threads), (size_t)q.lds, ctx->stream, A);
   }
+  prof_stop(ctx, pidx);
   HIP_TRY(hipGetLastError());
+  return HFMI_OK;
+}
+
+// The long route fixes its plans when the operator or the sampler is created, so what fftcov_launch_pass would refuse is refused
+// there: every pass of every kind the object can run (the same conditions, with the largest number of pairs a launch takes).
+static int fftcov_long_check(const fftcov_state* st, const int* kinds, int nkinds) {
+  for (int k = 0; k < nkinds; ++k) {
+    const fftcov_long_plan lp = fftcov_long_plan_passes(kinds[k], st->d, st->n, st->growth, st->max_line);
+    for (int i = 0; i < lp.npasses; ++i) {
+      const fftcov_pass& q = lp.pass[i];
+      const fftcov_sub& s = lp.sub[i];
+      const bool split = s.part != FFTCOV_WHOLE, gen = (q.flags & FFTCOV_GEN) != 0;
+      const bool both = (q.flags & FFTCOV_SCATTER) && (q.flags & FFTCOV_GATHER);
+      const bool full = (q.flags & (FFTCOV_LOAD_FULL | FFTCOV_STORE_FULL)) != 0;
+      bool ok = q.lds + (split ? FFTCOV_LONG_STATIC_LDS : FFTCOV_STATIC_LDS) <= FFTCOV_LDS_BYTES && q.lpw <= FFTCOV_MAX_LINES && q.grid_x <= 0x7fffffff;
+      if (split) ok = ok && !both && s.esub >= 1 && !(s.inner & (s.inner - 1));
+      if (!split && full && both) ok = ok && !gen && q.nlines == 1;
+      if (gen) ok = ok && (q.stride > 1 ? (q.lpw >= 2 && q.nlines % 2 == 0) : (q.L >= 2 || (!split && (int64_t)q.lpw * q.L == 1)));
+      if (!ok)
+        HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid_long: pass %d of plan kind %d (%d lines x %d entries, %d bytes of LDS, grid %lld) cannot be launched",
+                  i, kinds[k], q.lpw, q.L, q.lds, (long long)q.grid_x);
+    }
+  }
   return HFMI_OK;
 }
 
@@ -439,6 +594,10 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_pass, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_draw, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
   HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_factor, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_STATIC_LDS));
+  if (st->long_route) {
+    HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_split, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_LONG_STATIC_LDS));
+    HIP_TRY(hipFuncSetAttribute((const void*)k_fftcov_split_draw, hipFuncAttributeMaxDynamicSharedMemorySize, FFTCOV_LDS_BYTES - FFTCOV_LONG_STATIC_LDS));
+  }
   // the work buffer of one pair and Lambda: what decides whether the padded grid fits at all
   hipError_t e = (hipError_t)st->work.alloc((size_t)p.pair_bytes / sizeof(double2));
   if (e == hipSuccess) e = (hipError_t)st->lambda.alloc((size_t)p.Ptot);
@@ -478,8 +637,14 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
                          fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
   }
   HIP_TRY(hipGetLastError());
-  const fftcov_plan sp = fftcov_sample_plan_passes(st->d, st->n, st->growth, true);   // growth 0: fftcov_plan_passes(d, n, true)
-  for (int i = 0; i < sp.npasses; ++i) HFMI_TRY(fftcov_launch_pass(ctx, st, sp, sp.pass[i], 1, 0, nullptr, 0, nullptr, 0, 0, 0));
+  if (st->long_route) {
+    const fftcov_long_plan sp = fftcov_long_plan_passes(FFTCOV_KIND_SPECTRUM, st->d, st->n, st->growth, st->max_line);
+    for (int i = 0; i < sp.npasses; ++i)
+      HFMI_TRY(fftcov_launch_pass(ctx, st, sp.base, sp.pass[i], 1, 0, nullptr, 0, nullptr, 0, 0, 0, nullptr, nullptr, &sp.sub[i]));
+  } else {
+    const fftcov_plan sp = fftcov_sample_plan_passes(st->d, st->n, st->growth, true);   // growth 0: fftcov_plan_passes(d, n, true)
+    for (int i = 0; i < sp.npasses; ++i) HFMI_TRY(fftcov_launch_pass(ctx, st, sp, sp.pass[i], 1, 0, nullptr, 0, nullptr, 0, 0, 0));
+  }
   hipLaunchKernelGGL(k_fftcov_spectrum, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, st->work, st->lambda, p.Ptot, 1.0 / (double)p.Ptot);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -487,14 +652,18 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
 }
 
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, const double* metric_factor, fftcov_state** out) {
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line) {
+  const int64_t maxn = max_line > 0 ? FFTCOV_LONG_MAXN : FFTCOV_MAXN;
   int64_t nnodes = 1;
   for (int c = 0; c < d; ++c) {
-    if (n[c] < 1 || n[c] > FFTCOV_MAXN)
-      HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: n[%d] = %lld is not in 1 .. %d", c, (long long)n[c], FFTCOV_MAXN);
+    if (n[c] < 1 || n[c] > maxn)
+      HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: n[%d] = %lld is not in 1 .. %lld", c, (long long)n[c], (long long)maxn);
     if (!(h[c] > 0.0) || !isfinite(h[c])) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: spacing h[%d] must be positive and finite", c);
     nnodes *= n[c];
   }
+  if (max_line > 0 && !fftcov_long_feasible(d, n, 0, max_line))
+    HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid_long: an embedding axis is longer than max_line^2 = %lld (tuning key \"fftcov_max_line\" = %d)",
+              (long long)max_line * max_line, max_line);
   if (N > nnodes || (!host_nodes && N != nnodes))
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_grid: N = %lld points on a grid of %lld nodes%s", (long long)N, (long long)nnodes,
               host_nodes ? "" : " (no node map: N must be the number of nodes)");
@@ -520,7 +689,16 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
     for (int r = 0; r < d; ++r)
       for (int c = 0; c < d; ++c) st->mL[3 * r + c] = metric_factor[(size_t)r * d + c];
   }
-  st->plan = fftcov_plan_passes(d, st->n, false);
+  if (max_line > 0) {
+    st->long_route = true;
+    st->max_line = max_line;
+    st->lplan = fftcov_long_plan_passes(FFTCOV_KIND_APPLY, d, st->n, 0, max_line);
+    st->plan = st->lplan.base;
+    const int kinds[] = {FFTCOV_KIND_APPLY, FFTCOV_KIND_SPECTRUM};
+    HFMI_TRY(fftcov_long_check(st.get(), kinds, 2));
+  } else {
+    st->plan = fftcov_plan_passes(d, st->n, false);
+  }
   const int s = fftcov_create_device(ctx, st.get(), host_nodes ? inv.data() : nullptr);
   if (s != HFMI_OK) {
     (void)hipStreamSynchronize(ctx->stream);      // before the buffers go: the kernels queued so far use them
@@ -549,6 +727,16 @@ static int fftcov_fit_work(hfmi_ctx* ctx, fftcov_state* st, fftcov_plan& p, int 
 
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
   if (nvec < 1) return HFMI_OK;
+  if (st->long_route) {
+    fftcov_long_plan lp = st->lplan;
+    HFMI_TRY(fftcov_fit_work(ctx, st, lp.base, nvec));
+    for (int c = 0; c < lp.base.nchunks; ++c) {
+      const int pair0 = c * lp.base.chunk_pairs, pairs = std::min(lp.base.chunk_pairs, lp.base.pairs - pair0);
+      for (int i = 0; i < lp.npasses; ++i)
+        HFMI_TRY(fftcov_launch_pass(ctx, st, lp.base, lp.pass[i], pairs, 2 * pair0, W, ldw, Y, ldy, nvec, accumulate, nullptr, nullptr, &lp.sub[i], i));
+    }
+    return HFMI_OK;
+  }
   fftcov_plan p = st->plan;
   HFMI_TRY(fftcov_fit_work(ctx, st, p, nvec));
   for (int c = 0; c < p.nchunks; ++c) {
@@ -624,7 +812,9 @@ struct hfmi_grid_sampler {
 };
 
 // the state of the operator's grid at one growth, its spectrum and the extremes of that
-static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, std::shared_ptr<fftcov_state>& st, fftcov_extremes* ext) {
+// max_line > 0: the long route's embedding and passes (hfmi_grid_sampler_create_long)
+static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, int max_line, std::shared_ptr<fftcov_state>& st,
+                            fftcov_extremes* ext) {
   st.reset(new (std::nothrow) fftcov_state(), fftcov_destroy);
   if (!st) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   st->d = src->d;
@@ -634,34 +824,54 @@ static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, 
   st->has_metric = src->has_metric;
   std::copy(src->mL, src->mL + 9, st->mL);
   st->growth = growth;
-  st->plan = fftcov_sample_plan_passes(st->d, st->n, growth, false);
+  if (max_line > 0) {
+    st->long_route = true;
+    st->max_line = max_line;
+    st->lplan = fftcov_long_plan_passes(FFTCOV_KIND_DRAW, st->d, st->n, growth, max_line);
+    st->plan = st->lplan.base;
+    const int kinds[] = {FFTCOV_KIND_DRAW, FFTCOV_KIND_FACTOR, FFTCOV_KIND_FACTOR_T, FFTCOV_KIND_SPECTRUM};
+    HFMI_TRY(fftcov_long_check(st.get(), kinds, 4));
+  } else {
+    st->plan = fftcov_sample_plan_passes(st->d, st->n, growth, false);
+  }
   HFMI_TRY(fftcov_create_device(ctx, st.get(), src->inv, true));
   return fftcov_spectrum_extremes(ctx, st.get(), ext);
 }
 
-extern "C" int hfmi_grid_sampler_create(hfmi_op* op, int max_growth, int clip, hfmi_grid_sampler** out) {
+// long: the route of the operator's own (hfmi_grid_sampler_create_long, an operator of hfmi_op_kernel_cov_grid_long); otherwise the old
+// route's embedding and passes, which an operator of either route with axes of at most FFTCOV_MAXN nodes takes
+static int grid_sampler_create(hfmi_op* op, int max_growth, int clip, bool long_route, hfmi_grid_sampler** out) {
   if (!op || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   if (op->kind != OP_KERNEL_COV_GRID || !op->fc)
     HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: the operator is not a kernel covariance on a grid (hfmi_op_kernel_cov_grid)");
-  if (max_growth < 0 || max_growth > FFTCOV_MAX_GROWTH)
-    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: max_growth = %d outside 0..%d", max_growth, FFTCOV_MAX_GROWTH);
+  const int gmax = long_route ? FFTCOV_LONG_MAX_GROWTH : FFTCOV_MAX_GROWTH;
+  if (max_growth < 0 || max_growth > gmax) HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: max_growth = %d outside 0..%d", max_growth, gmax);
   hfmi_ctx* ctx = op->ctx;
   const fftcov_state* src = op->fc;
+  if (long_route && !src->long_route)
+    HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler_create_long: the operator is not one of hfmi_op_kernel_cov_grid_long");
+  for (int c = 0; c < src->d; ++c)
+    if (!long_route && src->n[c] > FFTCOV_MAXN)
+      HFMI_FAIL(HFMI_ERR_INVALID, "grid_sampler: axis %d has %lld nodes, more than %d: hfmi_grid_sampler_create_long", c, (long long)src->n[c], FFTCOV_MAXN);
+  const int max_line = long_route ? src->max_line : 0;
+  auto feasible = [&](int g) {
+    return long_route ? fftcov_long_feasible(src->d, src->n, g, max_line) : fftcov_growth_feasible(src->d, src->n, g);
+  };
   std::unique_ptr<hfmi_grid_sampler> s(new (std::nothrow) hfmi_grid_sampler());
   if (!s) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   s->ctx = ctx;
   fftcov_extremes ext{};
   bool definite = false;
   int g = std::min(fftcov_min_growth_knob(), max_growth);
-  while (g > 0 && !fftcov_growth_feasible(src->d, src->n, g)) --g;
+  while (g > 0 && !feasible(g)) --g;
   for (;; ++g) {
-    const int status = grid_sampler_try(ctx, src, g, s->st, &ext);
+    const int status = grid_sampler_try(ctx, src, g, max_line, s->st, &ext);
     if (status != HFMI_OK) {
       (void)hipStreamSynchronize(ctx->stream);    // before the buffers go: the kernels queued so far use them
       return status;
     }
     definite = ext.lmin >= -fftcov_floor(s->st->plan.Ptot, ext.lmax);
-    if (definite || g == max_growth || !fftcov_growth_feasible(src->d, src->n, g + 1)) break;
+    if (definite || g == max_growth || !feasible(g + 1)) break;
   }
   if (!definite && !clip)
     HFMI_FAIL(HFMI_ERR_INVALID,
@@ -674,6 +884,12 @@ extern "C" int hfmi_grid_sampler_create(hfmi_op* op, int max_growth, int clip, h
   s->cov_error_bound = definite ? 0.0 : -ext.negsum;
   *out = s.release();
   return HFMI_OK;
+}
+extern "C" int hfmi_grid_sampler_create(hfmi_op* op, int max_growth, int clip, hfmi_grid_sampler** out) {
+  return grid_sampler_create(op, max_growth, clip, false, out);
+}
+extern "C" int hfmi_grid_sampler_create_long(hfmi_op* op, int max_growth, int clip, hfmi_grid_sampler** out) {
+  return grid_sampler_create(op, max_growth, clip, true, out);
 }
 
 extern "C" int hfmi_grid_sampler_info(const hfmi_grid_sampler* s, int* growth, int64_t* P, double* lambda_min, double* lambda_max,
@@ -702,6 +918,18 @@ extern "C" int hfmi_grid_sampler_draw(hfmi_grid_sampler* s, const hfmi_block* Y,
   if (ncols < 1) return HFMI_OK;
   hfmi_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
+  if (st->long_route) {
+    fftcov_long_plan lp = st->lplan;
+    HFMI_TRY(fftcov_fit_work(ctx, st, lp.base, ncols));
+    for (int c = 0; c < lp.base.nchunks; ++c) {
+      const int pair0 = c * lp.base.chunk_pairs, pairs = std::min(lp.base.chunk_pairs, lp.base.pairs - pair0);
+      const fftcov_gen_args gen{(uint32_t)seed, (uint32_t)(seed >> 32), first_sample / 2 + pair0};
+      for (int i = 0; i < lp.npasses; ++i)
+        HFMI_TRY(fftcov_launch_pass(ctx, st, lp.base, lp.pass[i], pairs, 2 * pair0, nullptr, 0, Y->p, Y->ld, ncols, accumulate != 0,
+                                    i == 0 ? &gen : nullptr, nullptr, &lp.sub[i]));
+    }
+    return HFMI_OK;
+  }
   fftcov_plan p = st->plan;
   HFMI_TRY(fftcov_fit_work(ctx, st, p, ncols));
   for (int c = 0; c < p.nchunks; ++c) {
@@ -762,6 +990,17 @@ int fftcov_factor_apply(hfmi_ctx* ctx, fftcov_state* st, int transpose, const hf
               (long long)nin, (long long)nout, (long long)W->N, (long long)Y->N);
   const int nvec = W->nvec;
   if (nvec < 1) return HFMI_OK;
+  if (st->long_route) {
+    fftcov_long_plan lp = fftcov_long_plan_passes(transpose ? FFTCOV_KIND_FACTOR_T : FFTCOV_KIND_FACTOR, st->d, st->n, st->growth, st->max_line);
+    HFMI_TRY(fftcov_fit_work(ctx, st, lp.base, nvec));
+    for (int c = 0; c < lp.base.nchunks; ++c) {
+      const int pair0 = c * lp.base.chunk_pairs, pairs = std::min(lp.base.chunk_pairs, lp.base.pairs - pair0);
+      for (int i = 0; i < lp.npasses; ++i)
+        HFMI_TRY(fftcov_launch_pass(ctx, st, lp.base, lp.pass[i], pairs, 2 * pair0, W->p, W->ld, Y->p, Y->ld, nvec, accumulate, nullptr, st->root,
+                                    &lp.sub[i]));
+    }
+    return HFMI_OK;
+  }
   fftcov_plan p = fftcov_factor_plan_passes(st->d, st->n, st->growth, transpose);
   HFMI_TRY(fftcov_fit_work(ctx, st, p, nvec));
   for (int c = 0; c < p.nchunks; ++c) {

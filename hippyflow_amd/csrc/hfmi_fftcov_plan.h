@@ -87,6 +87,8 @@ inline int fftcov_log2(int64_t v) {
   return l;
 }
 
+inline void fftcov_pass_shape(fftcov_pass& q);
+
 // one pass along `axis`; ext[b]: positions of axis b > axis that hold data (n_b for an apply, P_b for the spectrum's own transform)
 inline fftcov_pass fftcov_make_pass(const fftcov_plan& p, int axis, int flags, const int64_t* ext, int nload, int nstore) {
   fftcov_pass q;
@@ -104,6 +106,12 @@ inline fftcov_pass fftcov_make_pass(const fftcov_plan& p, int axis, int flags, c
   if (axis == 0) q.oe0 = ext[1], q.os0 = p.P[0], q.os1 = (int64_t)p.P[0] * p.P[1];
   else if (axis == 1) q.oe0 = ext[2], q.os0 = (int64_t)p.P[0] * p.P[1], q.os1 = 0;
   else q.oe0 = 1, q.os0 = 0, q.os1 = 0;
+  fftcov_pass_shape(q);
+  return q;
+}
+
+// the workgroup shape of a pass whose L, stride and nlines are set: lines per workgroup, LDS layout, threads, grid
+inline void fftcov_pass_shape(fftcov_pass& q) {
   // lines per workgroup: a power of two, so that a strided group never straddles the inner index when stride >= lpw
   int lpw = FFTCOV_ELEMS / q.L;
   if (lpw < 1) lpw = 1;
@@ -127,7 +135,6 @@ inline fftcov_pass fftcov_make_pass(const fftcov_plan& p, int axis, int flags, c
   if (threads > FFTCOV_MAX_THREADS) threads = FFTCOV_MAX_THREADS;
   q.threads = threads;
   q.grid_x = (q.nlines + lpw - 1) / lpw;
-  return q;
 }
 
 // the embedding and the passes; spectrum: the d forward passes over the whole padded array that turn the first column into Lambda
@@ -334,4 +341,247 @@ inline void fftcov_factor_plan_words(const fftcov_plan& p, int growth, int trans
   fftcov_plan_words(p, w);
   w[13] = growth;
   w[14] = transpose;
+}
+
+// ------------------------------------------------------------------ split-line passes: embedding axes longer than a workgroup's line
+// The long route (hfmi_op_kernel_cov_grid_long, hfmi_grid_sampler_create_long; the factor of its samplers).  Everything above holds for
+// it; what it adds is that an embedding axis c with P_c > max_line (tuning key "fftcov_max_line", a power of two in 4 .. 4096, default
+// 4096, read by this route alone when it plans) is SPLIT into two sub-axes, P_c = L1 L2, both at most max_line.  Position s of the axis
+// is s = L2 n1 + n2: n2 < L2 the LOW sub-axis (the axis's own stride S_c = prod P_b, b < c), n1 < L1 the HIGH one (stride S_c L2).
+// Bailey's four-step without transposes:
+//   forward   L1-point DFTs along the high sub-axis (one line per n2; decimation in frequency, so position p of a line holds
+//             k1 = bitrev_L1(p)), the twiddle exp(-2 pi i n2 k1 / P_c) multiplied in at that pass's store;  then L2-point DFTs along the
+//             low sub-axis (one line per k1).  Position L2 p1 + p2 then holds X[bitrev_L1(p1) + L1 bitrev_L2(p2)] = X[bitrev_Pc(L2 p1 + p2)]:
+//             exactly the digit-reversed order of one P_c-point pass, so Lambda, the root table, the extremes and the noise's element
+//             map are stored as on the old route and nothing is permuted.
+//   inverse   L2-point inverse along the low sub-axis, then the conjugate twiddle multiplied in at the LOAD of the L1-point inverse along
+//             the high one.
+// The twiddle is sincospi(-2 n2 k1 / P_c) on the device: n2 k1 < P_c <= 2^24 and the division by a power of two are exact.
+// Split rule: L2 = max_line, L1 = P_c / max_line (>= 2, and <= max_line while P_c <= max_line^2).  The high sub-axis is always strided; the
+// shorter its lines the more of them a workgroup takes side by side (fftcov_pass_shape: 2048 / L, at least 4), i.e. the wider the
+// contiguous runs of its loads and stores, while the low sub-axis of axis 0 is contiguous at any length.  So the strided part is made as
+// short as the LDS line allows the other to be long.
+//
+// The pass list is the old route's with every split axis taking two passes in place of one: forward along 0 .. d - 1 (a split axis:
+// high, then low), the last forward (sub-)pass fused with the multiply and the inverse, inverse back to axis 0 (a split axis: low, then
+// high).  2 (d + s) - 1 passes with s split axes, at most 11.  Passes along an axis that is not split are fftcov_make_pass's, launched by
+// k_fftcov_pass / k_fftcov_draw as they are; with no split axis the plan IS the old planner's, pass for pass, so applies, draws and
+// factors are bit-identical to the old route's.  The pass properties extend to sub-axes:
+//   lines that are all padding are skipped   a line number is  inner + S_c (sub + esub o):  inner < S_c the positions below the axis (all
+//                                             in the frequency domain), sub < esub the other sub-axis, o the lines of the axes above as
+//                                             ever (oe0, os0, os1).  High passes on the time-domain side exist for n2 < esub = min(L2, n_c)
+//                                             only (n2 >= n_c is padding at every n1); low passes take all L1 values of k1.
+//   zero fill happens in LDS                  as ever: positions that are not loaded are zeros in LDS.
+//   loads and stores are limited to n         the axis position of line position p is  p pm + sub sm  (high: pm = L2, sm = 1; low: pm = 1,
+//                                             sm = 0) and is loaded / stored while it is below nload / nstore: n_c (or P_c) on a high pass,
+//                                             min(L2, n_c) (or L2) on a low one.  The scatter and the gather of axis 0 address node
+//                                             o n_0 + that position.
+// The generated load of a draw is a low pass when the last axis is split: its lines are whole low lines (a contiguous line of L2 >= 4
+// positions, or >= 2 adjacent lines on a strided axis from an even line number), so storage entries 2 q and 2 q + 1 stay in one thread.
+// Caps: nodes per axis <= 2^23, every P_c <= max_line^2 (so P_c <= 2^24), growth 0 .. 6 for a sampler.
+constexpr int64_t FFTCOV_LONG_MAXN = (int64_t)1 << 23;
+constexpr int FFTCOV_LONG_MAX_LINE = 4096;
+constexpr int FFTCOV_LONG_MIN_LINE = 4;
+constexpr int FFTCOV_LONG_MAX_GROWTH = 6;
+constexpr int FFTCOV_LONG_MAX_PASSES = 11;
+constexpr int FFTCOV_LONG_STATIC_LDS = FFTCOV_STATIC_LDS + 4 * FFTCOV_MAX_LINES;   // k_fftcov_split adds a table of line offsets
+enum { FFTCOV_TW_STORE = 256, FFTCOV_TW_LOAD = 512 };
+enum { FFTCOV_WHOLE = 0, FFTCOV_HI = 1, FFTCOV_LO = 2 };
+enum { FFTCOV_KIND_APPLY = 0, FFTCOV_KIND_DRAW = 1, FFTCOV_KIND_FACTOR = 2, FFTCOV_KIND_FACTOR_T = 3, FFTCOV_KIND_SPECTRUM = 4 };
+
+struct fftcov_sub {       // what a pass along a sub-axis adds to its fftcov_pass
+  int part;               // FFTCOV_WHOLE, FFTCOV_HI, FFTCOV_LO
+  int L1, L2;             // the axis's split
+  int logP;               // log2 P_axis
+  int64_t inner;          // S_axis: positions below the axis, the lowest part of a line number
+  int64_t esub;           // values of the other sub-axis that lines exist for
+  int64_t sub_stride;     // entries between consecutive values of it
+  int pm, sm;             // axis position of (line position p, sub) = p pm + sub sm
+};
+struct fftcov_long_plan {
+  fftcov_plan base;       // embedding, chunks, pair bytes; twiddles / Pmax of the longest LINE; base.npasses = 0
+  int max_line;
+  int L1[3], L2[3];       // L1 = 1: the axis is not split, L2 = P_c
+  int nsplit;
+  int npasses;
+  fftcov_pass pass[FFTCOV_LONG_MAX_PASSES];
+  fftcov_sub sub[FFTCOV_LONG_MAX_PASSES];
+};
+
+// tuning key "fftcov_max_line"
+inline int& fftcov_max_line_knob() {
+  static int v = FFTCOV_LONG_MAX_LINE;
+  return v;
+}
+inline bool fftcov_max_line_ok(int v) { return v >= FFTCOV_LONG_MIN_LINE && v <= FFTCOV_LONG_MAX_LINE && (v & (v - 1)) == 0; }
+inline bool fftcov_long_knob_set(const char* key, int v) {
+  if (strcmp(key, "fftcov_max_line") || !fftcov_max_line_ok(v)) return false;
+  fftcov_max_line_knob() = v;
+  return true;
+}
+
+// the long route's embedding at a growth: feasible when every P_c <= max_line^2
+inline bool fftcov_long_feasible(int d, const int64_t* n, int growth, int max_line) {
+  if (growth < 0 || growth > FFTCOV_LONG_MAX_GROWTH || !fftcov_max_line_ok(max_line)) return false;
+  for (int c = 0; c < d; ++c) {
+    if (n[c] < 1 || n[c] > FFTCOV_LONG_MAXN) return false;
+    if (n[c] > 1 && ((int64_t)fftcov_embed_len(n[c]) << growth) > (int64_t)max_line * max_line) return false;
+  }
+  return true;
+}
+
+inline fftcov_long_plan fftcov_long_embedding(int d, const int64_t* n, int growth, int max_line) {
+  fftcov_long_plan p;
+  memset(&p, 0, sizeof(p));
+  p.base = fftcov_grown_embedding(d, n, growth);     // growth 0: fftcov_embed_len of every axis, as fftcov_plan_passes
+  p.max_line = max_line;
+  int Lmax = 1;
+  for (int c = 0; c < 3; ++c) {
+    const int P = p.base.P[c];
+    p.L1[c] = P > max_line ? P / max_line : 1;
+    p.L2[c] = P > max_line ? max_line : P;
+    p.nsplit += p.L1[c] > 1;
+    if (p.L2[c] > Lmax) Lmax = p.L2[c];
+  }
+  p.base.Pmax = Lmax;
+  p.base.twiddles = Lmax / 4 > 1 ? Lmax / 4 : 1;
+  return p;
+}
+
+// one pass along (a part of) `axis`.  ext[b], b > axis: positions of the axes above that hold data; ext[axis]: the axis's own positions
+// that hold data on the time-domain side of a high pass.  nload / nstore: axis positions on a high pass, line positions otherwise.
+inline void fftcov_long_add(fftcov_long_plan& p, int axis, int part, int flags, const int64_t* ext, int64_t nload, int64_t nstore) {
+  fftcov_sub s;
+  memset(&s, 0, sizeof(s));
+  s.part = part;
+  s.L1 = p.L1[axis], s.L2 = p.L2[axis];
+  s.logP = fftcov_log2(p.base.P[axis]);
+  fftcov_pass q;
+  if (part == FFTCOV_WHOLE) {
+    q = fftcov_make_pass(p.base, axis, flags, ext, (int)nload, (int)nstore);
+    s.inner = q.stride, s.esub = 1, s.pm = 1;
+  } else {
+    memset(&q, 0, sizeof(q));
+    q.axis = axis;
+    q.flags = flags;
+    int64_t S = 1;
+    for (int b = 0; b < axis; ++b) S *= p.base.P[b];
+    s.inner = S;
+    if (part == FFTCOV_HI) {
+      q.L = s.L1, q.stride = S * s.L2;
+      s.esub = ext[axis] < s.L2 ? ext[axis] : s.L2, s.sub_stride = S, s.pm = s.L2, s.sm = 1;
+    } else {
+      q.L = s.L2, q.stride = S;
+      s.esub = s.L1, s.sub_stride = S * s.L2, s.pm = 1, s.sm = 0;
+    }
+    q.logL = fftcov_log2(q.L);
+    const int64_t e1 = axis < 1 ? ext[1] : 1, e2 = axis < 2 ? ext[2] : 1;
+    q.nlines = S * s.esub * e1 * e2;
+    q.nload = (int)nload;
+    q.nstore = (int)nstore;
+    if (axis == 0) q.oe0 = ext[1], q.os0 = p.base.P[0], q.os1 = (int64_t)p.base.P[0] * p.base.P[1];
+    else if (axis == 1) q.oe0 = ext[2], q.os0 = (int64_t)p.base.P[0] * p.base.P[1], q.os1 = 0;
+    else q.oe0 = 1, q.os0 = 0, q.os1 = 0;
+    fftcov_pass_shape(q);
+  }
+  p.pass[p.npasses] = q;
+  p.sub[p.npasses] = s;
+  ++p.npasses;
+}
+
+// the forward passes along `axis` (first_flags on its first pass, the high one of a split axis); last: the final forward part is
+// left out (the fused pass takes it)
+inline void fftcov_long_forward(fftcov_long_plan& p, int axis, int first_flags, const int64_t* ext, int64_t in_len, bool last) {
+  const int64_t P = p.base.P[axis];
+  if (p.L1[axis] == 1) {
+    if (!last) fftcov_long_add(p, axis, FFTCOV_WHOLE, FFTCOV_FWD | first_flags, ext, in_len, P);
+    return;
+  }
+  int64_t e[3] = {ext[0], ext[1], ext[2]};
+  e[axis] = in_len;
+  fftcov_long_add(p, axis, FFTCOV_HI, FFTCOV_FWD | FFTCOV_TW_STORE | first_flags, e, in_len, P);
+  const int64_t L2 = p.L2[axis];     // the high pass wrote the lines n2 < min(L2, in_len) only
+  if (!last) fftcov_long_add(p, axis, FFTCOV_LO, FFTCOV_FWD, ext, in_len < L2 ? in_len : L2, L2);
+}
+// the inverse passes along `axis` (last_flags on its last pass, the high one of a split axis); first: the first inverse part is left
+// out (the fused or the generated pass took it)
+inline void fftcov_long_inverse(fftcov_long_plan& p, int axis, int last_flags, const int64_t* ext, int64_t out_len, bool first) {
+  const int64_t P = p.base.P[axis];
+  if (p.L1[axis] == 1) {
+    if (!first) fftcov_long_add(p, axis, FFTCOV_WHOLE, FFTCOV_INV | last_flags, ext, P, out_len);
+    return;
+  }
+  const int64_t L2 = p.L2[axis];
+  if (!first) fftcov_long_add(p, axis, FFTCOV_LO, FFTCOV_INV, ext, L2, out_len < L2 ? out_len : L2);
+  int64_t e[3] = {ext[0], ext[1], ext[2]};
+  e[axis] = out_len;
+  fftcov_long_add(p, axis, FFTCOV_HI, FFTCOV_INV | FFTCOV_TW_LOAD | last_flags, e, P, out_len);
+}
+// the one pass along the last axis that the two halves share: fused forward-multiply-inverse, or the generated inverse of a draw
+inline void fftcov_long_middle(fftcov_long_plan& p, int flags, int extra_whole, const int64_t* ext, int64_t in_len, int64_t out_len) {
+  const int a = p.base.d - 1;
+  if (p.L1[a] == 1) {
+    fftcov_long_add(p, a, FFTCOV_WHOLE, flags | extra_whole, ext, in_len, out_len);
+  } else {
+    const int64_t L2 = p.L2[a];
+    fftcov_long_add(p, a, FFTCOV_LO, flags, ext, in_len < L2 ? in_len : L2, out_len < L2 ? out_len : L2);
+  }
+}
+
+// The passes of one kind (FFTCOV_KIND_*) of the long route; the caller has checked fftcov_long_feasible.  Apply and factor: as
+// fftcov_plan_passes / fftcov_factor_plan_passes; draw: as fftcov_sample_plan_passes; spectrum: the forward passes over the whole array.
+inline fftcov_long_plan fftcov_long_plan_passes(int kind, int d, const int64_t* n, int growth, int max_line) {
+  fftcov_long_plan p = fftcov_long_embedding(d, n, growth, max_line);
+  int64_t full[3], data[3];
+  for (int c = 0; c < 3; ++c) full[c] = p.base.P[c], data[c] = p.base.n[c];
+  if (kind == FFTCOV_KIND_SPECTRUM) {
+    for (int a = 0; a < d; ++a) fftcov_long_forward(p, a, 0, full, full[a], false);
+    return p;
+  }
+  if (kind == FFTCOV_KIND_DRAW) {
+    const int a = d - 1;
+    const int gather = d == 1 ? FFTCOV_GATHER : 0;
+    fftcov_long_middle(p, FFTCOV_GEN | FFTCOV_INV, gather, data, full[a], data[a]);
+    if (p.L1[a] > 1) fftcov_long_inverse(p, a, gather, data, data[a], true);
+    for (int b = d - 2; b >= 0; --b) fftcov_long_inverse(p, b, b == 0 ? FFTCOV_GATHER : 0, data, data[b], false);
+    return p;
+  }
+  const int transpose = kind == FFTCOV_KIND_FACTOR_T;
+  const bool factor = kind == FFTCOV_KIND_FACTOR || transpose;
+  const int64_t* fwd_ext = factor && !transpose ? full : data;
+  const int64_t* inv_ext = factor && transpose ? full : data;
+  const int load_side = factor && !transpose ? FFTCOV_LOAD_FULL : 0, store_side = transpose ? FFTCOV_STORE_FULL : 0;
+  auto in_len = [&](int a) { return factor && !transpose ? full[a] : data[a]; };
+  auto out_len = [&](int a) { return transpose ? full[a] : data[a]; };
+  for (int a = 0; a < d; ++a) fftcov_long_forward(p, a, a == 0 ? FFTCOV_SCATTER | load_side : 0, fwd_ext, in_len(a), a == d - 1);
+  fftcov_long_middle(p, FFTCOV_FWD | FFTCOV_MUL | FFTCOV_INV, d == 1 ? FFTCOV_SCATTER | FFTCOV_GATHER | load_side | store_side : 0, data,
+                     in_len(d - 1), out_len(d - 1));
+  for (int a = d - 1; a >= 0; --a) fftcov_long_inverse(p, a, a == 0 ? FFTCOV_GATHER | store_side : 0, inv_ext, out_len(a), a == d - 1);
+  return p;
+}
+
+// ------------------------------------------------------------------ hfmi_fftcov_long_plan_predict's record
+// words[FFTCOV_LONG_PLAN_WORDS]: a head of 16 words, then 24 per pass.
+//   head   0 d  1-3 P_c  4 prod P_c  5 pairs  6 pairs per chunk  7 chunks  8 passes  9 bytes per pair  10 twiddles  11 the longest line
+//          12 static LDS of k_fftcov_split  13 growth  14 kind  15 max_line
+//   pass   0-15 the words of fftcov_plan_words (word 11: dynamic + the static LDS of the kernel that runs it: k_fftcov_pass's for a whole
+//          axis, k_fftcov_split's for a sub-axis)  16 part  17 L1  18 L2  19 inner  20 esub  21 sub_stride  22 pm  23 sm
+constexpr int FFTCOV_LONG_HEAD_WORDS = 16;
+constexpr int FFTCOV_LONG_PASS_WORDS = 24;
+constexpr int FFTCOV_LONG_PLAN_WORDS = FFTCOV_LONG_HEAD_WORDS + FFTCOV_LONG_MAX_PASSES * FFTCOV_LONG_PASS_WORDS;
+inline void fftcov_long_plan_words(const fftcov_long_plan& lp, int growth, int kind, int64_t* w) {
+  memset(w, 0, sizeof(int64_t) * FFTCOV_LONG_PLAN_WORDS);
+  const fftcov_plan& p = lp.base;
+  const int64_t head[FFTCOV_LONG_HEAD_WORDS] = {p.d, p.P[0], p.P[1], p.P[2], p.Ptot, p.pairs, p.chunk_pairs, p.nchunks,
+                                                lp.npasses, p.pair_bytes, p.twiddles, p.Pmax, FFTCOV_LONG_STATIC_LDS, growth, kind, lp.max_line};
+  memcpy(w, head, sizeof(head));
+  for (int i = 0; i < lp.npasses; ++i) {
+    const fftcov_pass& q = lp.pass[i];
+    const fftcov_sub& s = lp.sub[i];
+    const int st = s.part == FFTCOV_WHOLE ? FFTCOV_STATIC_LDS : FFTCOV_LONG_STATIC_LDS;
+    const int64_t v[FFTCOV_LONG_PASS_WORDS] = {q.axis, q.flags, q.L, q.stride, q.nlines, q.nload, q.nstore, q.lpw,
+                                               q.ls, q.threads, q.lds, q.lds + st, q.grid_x, q.oe0, q.os0, q.os1,
+                                               s.part, s.L1, s.L2, s.inner, s.esub, s.sub_stride, s.pm, s.sm};
+    memcpy(w + FFTCOV_LONG_HEAD_WORDS + i * FFTCOV_LONG_PASS_WORDS, v, sizeof(v));
+  }
 }

@@ -157,6 +157,7 @@ void phase_end(hfmi_ctx* ctx, int idx);
 int phase_begin_on(hfmi_ctx* ctx, int phase, hipStream_t st);   // the same with the events on another stream of the context
 void phase_end_on(hfmi_ctx* ctx, int idx, hipStream_t st);
 int prof_start(hfmi_ctx* ctx, int kind, int64_t m, int64_t k, int64_t N);  // returns record index or -1
+int prof_start_pass(hfmi_ctx* ctx, int64_t L, int64_t flags_part, int64_t index, double bytes);   // a grid covariance pass ("prof_level" 3)
 int prof_stop(hfmi_ctx* ctx, int idx);
 
 static inline double* sm_ptr(hfmi_ctx* c, int slot) { return c->small.get() + (size_t)slot * SM_MAXK * SM_LD; }
@@ -319,9 +320,10 @@ int kcov_metric_factor(const double* G, int d, double* L);
 
 // Kernel covariance on a regular grid by FFT (hfmi_fftcov.hip; plans: hfmi_fftcov_plan.h).  create checks the arguments, uploads the
 // node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy deletes the state (the caller synchronised)
-// metric_factor: the lower Cholesky factor of the kernel's metric (d x d row-major, kcov_metric_factor), or null for none
+// metric_factor: the lower Cholesky factor of the kernel's metric (d x d row-major, kcov_metric_factor), or null for none;
+// max_line > 0: the long route (split-line passes, hfmi_fftcov_plan.h) with that longest line, 0: the old route
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, const double* metric_factor, fftcov_state** out);
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line = 0);
 int64_t fftcov_points(const fftcov_state* st);
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
 void fftcov_destroy(fftcov_state* st);

@@ -172,13 +172,14 @@ static int kcov_rows_create(hfmi_ctx* ctx, const double* host_points, int64_t N,
   *out = op;
   return HFMI_OK;
 }
+// max_line > 0: the long route (hfmi_op_kernel_cov_grid_long)
 static int kcov_grid_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family,
-                            double sigma, double ell, double nugget, int last_family, const double* mL, hfmi_op** out) {
+                            double sigma, double ell, double nugget, int last_family, const double* mL, hfmi_op** out, int max_line = 0) {
   if (!ctx || !n || !h || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget, last_family));
   std::unique_ptr<hfmi_op> op(op_new(ctx, OP_KERNEL_COV_GRID));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, mL, &op->fc));
+  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, mL, &op->fc, max_line));
   *out = op.release();
   return HFMI_OK;
 }
@@ -269,6 +270,15 @@ extern "C" int hfmi_op_kernel_cov_grid_spec(hfmi_ctx* ctx, int d, const int64_t*
   const double* mL = nullptr;
   HFMI_TRY(kcov_spec_metric("kernel_cov_grid", spec, d, store, &mL));
   return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec->family, spec->sigma, spec->ell, spec->nugget, HFMI_KERNEL_MATERN1, mL, out);
+}
+// the long route: split-line passes, longest line from the tuning key "fftcov_max_line" as it stands at creation
+extern "C" int hfmi_op_kernel_cov_grid_long(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                            const hfmi_kernel_spec* spec, hfmi_op** out) {
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec_metric("kernel_cov_grid_long", spec, d, store, &mL));
+  return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec->family, spec->sigma, spec->ell, spec->nugget, HFMI_KERNEL_MATERN1, mL, out,
+                          fftcov_max_line_knob());
 }
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
   if (!ctx || !M || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");

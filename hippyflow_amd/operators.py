@@ -343,15 +343,17 @@ class KernelCovarianceOperator(DeviceOperator):
         return op
 
 
-def _check_grid(shape, spacing, nodes, origin, family, ell, nugget):
-    """The argument rules of hfmi_op_kernel_cov_grid that need no device; returns (shape, spacing, nodes or None, origin) as arrays."""
+def _check_grid(shape, spacing, nodes, origin, family, ell, nugget, max_nodes=None):
+    """The argument rules of hfmi_op_kernel_cov_grid that need no device; returns (shape, spacing, nodes or None, origin) as arrays.
+    ``max_nodes``: nodes per axis, ``GRID_COV_MAX_NODES`` unless given (the long route's ``GRID_COV_LONG_MAX_NODES``)."""
+    max_nodes = L.GRID_COV_MAX_NODES if max_nodes is None else int(max_nodes)
     if family not in L.KERNEL_FAMILIES:
         raise _unknown_family(family)
     n = np.atleast_1d(np.asarray(shape, dtype=np.int64))
     if n.ndim != 1 or not 1 <= n.size <= 3:
         raise ValueError("a grid has 1, 2 or 3 axes, got shape %r" % (shape,))
-    if n.min() < 1 or n.max() > L.GRID_COV_MAX_NODES:
-        raise ValueError("every axis of the grid has 1 .. %d nodes, got %r" % (L.GRID_COV_MAX_NODES, tuple(int(v) for v in n)))
+    if n.min() < 1 or n.max() > max_nodes:
+        raise ValueError("every axis of the grid has 1 .. %d nodes, got %r" % (max_nodes, tuple(int(v) for v in n)))
     h = np.asarray(spacing, dtype=np.float64)
     h = np.full(n.size, float(h)) if h.ndim == 0 else h
     if h.shape != n.shape or not np.all(np.isfinite(h)) or not np.all(h > 0.0):
@@ -408,10 +410,20 @@ class GridKernelCovarianceOperator(DeviceOperator):
     ``family="matern1"`` and ``metric`` as for ``KernelCovarianceOperator`` (a scalar metric on a grid with one axis).  With a metric the
     kernel is even only in the whole offset vector, so the circulant's first column is built from signed offsets; its spectrum is real
     all the same, and the apply, the sampler with its growth and clipping, the factor and ``GridKernelPrior`` run as for every kernel.
-    ``GridKernelCovarianceOperator(shape, spacing, **bilaplacian_kernel_2d(gamma, delta))`` is the BiLaplacian prior's covariance."""
+    ``GridKernelCovarianceOperator(shape, spacing, **bilaplacian_kernel_2d(gamma, delta))`` is the BiLaplacian prior's covariance.
 
-    def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None, metric=None):
-        n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget)
+    ``long_axes=True`` takes the long route (hfmi_op_kernel_cov_grid_long): an embedding axis longer than one workgroup's line
+    (4096, or the tuning key "fftcov_max_line" at creation) is split in two passes, so axes may have up to 2^23 nodes, and
+    ``sampler(max_growth=...)`` may double the embedding up to 6 times (every padded axis at most max_line^2).  Where no axis is split
+    the applies, draws and factors are bit-identical to the default route's.  ``.long_axes`` records the choice."""
+
+    def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None, *, long_axes=False,
+                 metric=None):
+        # keyword-only from `long_axes` on: `metric` stays the last parameter (what splats of bilaplacian_kernel_2d rely on), and a
+        # positional tenth argument is refused instead of landing in the new keyword's slot
+        self.long_axes = bool(long_axes)
+        n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget,
+                                     L.GRID_COV_LONG_MAX_NODES if self.long_axes else L.GRID_COV_MAX_NODES)
         G = _check_metric(metric, int(n.size))
         N = int(np.prod(n)) if nodes is None else int(nodes.size)
         super().__init__(ctx, N)
@@ -420,7 +432,11 @@ class GridKernelCovarianceOperator(DeviceOperator):
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
         self.metric = G
         self.points = L.as_f64(grid_node_points(n, h, nodes, o))
-        if family == "matern1" or G is not None:
+        if self.long_axes:
+            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G)
+            L.call("hfmi_op_kernel_cov_grid_long", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
+                   N, C.byref(spec), C.byref(self._op))
+        elif family == "matern1" or G is not None:
             spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G)
             L.call("hfmi_op_kernel_cov_grid_spec", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
                    N, C.byref(spec), C.byref(self._op))
@@ -445,8 +461,8 @@ class GridFieldSampler:
     """Exact draws ``m ~ N(0, C)`` of a ``GridKernelCovarianceOperator`` by circulant embedding (hfmi_grid_sampler_*, hfmi_fftcov.hip):
     coloured noise ``sqrt(Lambda / P) (xi_1 + i xi_2)`` generated on the device, transformed back by the operator's inverse passes; the real
     and the imaginary part on the nodes are two independent draws, d passes per pair against the 2 d - 1 of an apply.  The sampler has
-    an embedding of its own: the minimal one is often indefinite, so every padded axis is doubled ``growth`` <= ``max_growth`` (0..3)
-    times until no eigenvalue is below minus a rounding floor.  If none is definite, ``on_indefinite="raise"`` raises ``HfmiError`` with
+    an embedding of its own: the minimal one is often indefinite, so every padded axis is doubled ``growth`` <= ``max_growth`` (0..3;
+    0..6 for an operator with ``long_axes``) times until no eigenvalue is below minus a rounding floor.  If none is definite, ``on_indefinite="raise"`` raises ``HfmiError`` with
     ``lambda_min / lambda_max`` of the last growth; ``"clip"`` zeroes the negative eigenvalues and reports ``n_clipped`` and
     ``cov_error_bound``: every entry of ``Cov(draw) - C`` is at most that in magnitude.  ``growth``, ``embedding`` (P_c per grid axis),
     ``lambda_min``, ``lambda_max``, ``n_clipped``, ``cov_error_bound`` are attributes.  The sampler keeps copies of what it needs: it does not
@@ -465,7 +481,8 @@ class GridFieldSampler:
         self.seed = int(seed)
         self._next = 0                   # sample_block's counter: the next draw of the stream `seed`, kept even
         self.handle = C.c_void_p()
-        L.call("hfmi_grid_sampler_create", op._op, int(max_growth), 1 if on_indefinite == "clip" else 0, C.byref(self.handle))
+        create = "hfmi_grid_sampler_create_long" if getattr(op, "long_axes", False) else "hfmi_grid_sampler_create"   # max_growth 0..6 / 0..3
+        L.call(create, op._op, int(max_growth), 1 if on_indefinite == "clip" else 0, C.byref(self.handle))
         g, P, lo, hi, nc, bound = C.c_int(), (C.c_int64 * 3)(), C.c_double(), C.c_double(), C.c_int64(), C.c_double()
         L.call("hfmi_grid_sampler_info", self.handle, C.byref(g), P, C.byref(lo), C.byref(hi), C.byref(nc), C.byref(bound))
         self.growth = g.value

@@ -307,6 +307,34 @@ HFMI_API int hfmi_fftcov_sample_plan_predict(int d, const int64_t* n, int growth
 HFMI_API int hfmi_op_grid_factor(hfmi_grid_sampler* s, int transpose /* 0: S | 1: S^T */, hfmi_op** out);
 HFMI_API int hfmi_fftcov_factor_plan_predict(int d, const int64_t* n, int growth, int transpose, int nvec, int64_t budget_bytes,
                                              int64_t* words);
+/*     The LONG route: the same operator, sampler and factor with embedding axes longer than one workgroup's line.  An embedding axis
+ *     with P_c > max_line is split into P_c = L1 L2 (L2 = max_line) and transformed in two passes, Bailey's four-step without
+ *     transposes: L1-point DFTs along the strided sub-axis with the twiddle exp(-2 pi i n2 k1 / P_c) fused into their store, then
+ *     L2-point DFTs (the inverse mirrors it, the conjugate twiddle fused into the load).  The spectrum lands in the storage order of the
+ *     old route; nothing is permuted.  2 (d + s) - 1 passes per pair of columns with s split axes.  The rules are in
+ *     csrc/hfmi_fftcov_plan.h.  max_line is the tuning key "fftcov_max_line" at creation (a power of two in 4 .. 4096, default 4096),
+ *     read by this route alone.  Caps: nodes per axis 1 .. 2^23, every P_c <= max_line^2, sampler growth 0 .. 6.  With no axis split
+ *     the passes are the old route's: applies, draws and factors are bit-identical to those of hfmi_op_kernel_cov_grid_spec /
+ *     hfmi_grid_sampler_create.  Everything else as there: all five families and the metric, block storage contract, no atomics,
+ *     bit-identical whatever "fftcov_pairs" says; hfmi_op_grid_factor takes samplers of either route.
+ *     HFMI_ERR_INVALID: what hfmi_op_kernel_cov_grid_spec answers with the caps above; hfmi_grid_sampler_create_long: an operator that is
+ *     not of hfmi_op_kernel_cov_grid_long, max_growth outside 0..6.  hfmi_grid_sampler_create on such an operator takes the old route
+ *     and answers HFMI_ERR_INVALID when an axis has more than 2048 nodes.  A create whose buffers do not fit returns HFMI_ERR_HIP, *out
+ *     untouched.
+ *     hfmi_fftcov_long_plan_predict: the launch plan of kind 0 (apply, growth 0), 1 (draw), 2 (factor S) or 3 (factor S^T) at longest
+ *     line max_line, no context and no device; HFMI_ERR_INVALID for the refusals above, max_line not a power of two in 4 .. 4096, or a
+ *     kind outside 0 .. 3.  words[HFMI_FFTCOV_LONG_PLAN_WORDS]: a head of 16 words (0-11 as hfmi_fftcov_plan_predict, 11 the longest
+ *     LINE, 12 static LDS of the split kernel, 13 growth, 14 kind, 15 max_line), then 24 per pass from word 16: the 16 words of a pass
+ *     of hfmi_fftcov_plan_predict (flags 256 / 512: twiddle fused into the store / the load; static + dynamic LDS of the kernel that
+ *     runs the pass), then part (0 whole axis, 1 high sub-axis, 2 low), L1, L2, inner, esub, sub_stride, pm, sm: line l of a
+ *     sub-axis pass starts at entry  (l mod inner) + sub sub_stride + (o mod oe0) os0 + (o div oe0) os1  with
+ *     sub = (l div inner) mod esub, o = (l div inner) div esub, and line position p is axis position p pm + sub sm. */
+#define HFMI_FFTCOV_LONG_PLAN_WORDS 280
+HFMI_API int hfmi_op_kernel_cov_grid_long(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
+                                          const int64_t* host_nodes_or_null, int64_t N, const hfmi_kernel_spec* spec, hfmi_op** out);
+HFMI_API int hfmi_grid_sampler_create_long(hfmi_op* grid_cov_long_op, int max_growth /* 0..6 */, int clip /* 0 | 1 */, hfmi_grid_sampler** out);
+HFMI_API int hfmi_fftcov_long_plan_predict(int kind, int d, const int64_t* n, int growth, int max_line, int nvec, int64_t budget_bytes,
+                                           int64_t* words);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
@@ -763,7 +791,9 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * eigensolver of every call: divide and conquer | Jacobi; ("chol", 0|1) Cholesky + inverse of the QR passes: blocked MFMA kernel |
  * column-at-a-time kernels; ("nn_res_tt", 0|1|2) tile height of the LDS-resident nn product: by round count | table | one less;
  * ("tn_hybrid", 0|1) tsgemm_tn with more row blocks than CUs: uniform split | whole rounds coarsely split + finely split tail;
- * ("prof_level", 1|2) what a profiling region records: 2 = every contraction and every phase (default), 1 = contractions of at
+ * ("prof_level", 1|2|3) what a profiling region records: 2 = every contraction and every phase (default), 3 = these and every pass of
+ * a grid kernel covariance (hfmi_profile_end: kind 2, shape = line length, 4 * flags + part of the axis (0 whole, 1 high, 2 low sub-axis),
+ * index of the pass in its plan; bytes = 16 (loaded + stored positions) per existing line and pair, 8 more per entry where the pass multiplies), 1 = contractions of at
  * least 2 Gflop only (each record is a pair of stream events, 2-4 us of idle GPU between dependent kernels: scripts/prof_level_ab.py);
  * ("comm_panels", 0..8) row panels of an operator application whose
  * rank reduction overlaps the rest of the product (0 / 1 = one all-reduce after the product; default 4);
@@ -775,7 +805,9 @@ HFMI_API int hfmi_bench_random_peaks(hfmi_ctx* ctx, double* mfma_f64_tflops, dou
  * default): results do not depend on it, bit for bit; the draws of hfmi_grid_sampler_draw and the applies of hfmi_op_grid_factor are
  * chunked by it in the same way;
  * ("fftcov_min_growth", 0..3) the growth hfmi_grid_sampler_create tries first (default 0; capped by its max_growth): a sampler on a larger
- * embedding than the rule would take (tests, measurements). */
+ * embedding than the rule would take (tests, measurements);
+ * ("fftcov_max_line", a power of two in 4..4096) the longest transform line of the long route (hfmi_op_kernel_cov_grid_long), read
+ * when such an operator is created (default 4096): a small value splits axes at small sizes (tests, measurements). */
 HFMI_API int hfmi_tuning_set(const char* key, int value);
 /* phases of hfmi_double_pass[_g], accumulated between hfmi_profile_begin and hfmi_profile_end (milliseconds, summed
  * over the solves in the region; device phases by HIP events on the context's stream, the HOST_* legs by the host's
