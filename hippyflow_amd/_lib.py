@@ -15,7 +15,9 @@ QR_CHOL, QR_MGS, QR_AUTO = 0, 1, 2
 UNIQUE_ID_BYTES = 256
 WIDE_MAX_VECTORS = 2048                                # orthogonalize / Borthogonalize / doublePass[G]: HFMI_WIDE_MAXK of the library
 REDUCE_SUM, REDUCE_AVG, REDUCE_MAX = 0, 1, 2
-KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3, "matern1": 4}     # HFMI_KERNEL_* of include/hfmi.h
+KERNEL_FAMILIES = {"matern12": 0, "matern32": 1, "matern52": 2, "sqexp": 3, "matern1": 4, "matern": 5}     # HFMI_KERNEL_* of include/hfmi.h
+MATERN_NU_MIN, MATERN_NU_MAX = 0.125, 8.0                # HFMI_MATERN_NU_MIN / _MAX: the smoothness of family "matern"
+MATERN_TABLE_WORDS = 162                               # HFMI_MATERN_TABLE_WORDS of include/hfmi.h
 KERNEL_NO_DIAGONAL = -1                                # HFMI_KERNEL_NO_DIAGONAL: no target of a cross-covariance is a source
 GRID_COV_MAX_NODES = 2048                              # nodes per axis of hfmi_op_kernel_cov_grid (FFTCOV_MAXN of hfmi_fftcov_plan.h)
 FFTCOV_PLAN_WORDS = 96                                 # HFMI_FFTCOV_PLAN_WORDS of include/hfmi.h
@@ -47,6 +49,14 @@ class KernelSpec(C.Structure):
 
 
 _SPEC = C.POINTER(KernelSpec)
+
+
+class KernelSpec2(C.Structure):
+    """hfmi_kernel_spec2 of include/hfmi.h: hfmi_kernel_spec with the smoothness nu of family "matern" appended (0 otherwise)"""
+    _fields_ = KernelSpec._fields_ + [("nu", C.c_double)]
+
+
+_SPEC2 = C.POINTER(KernelSpec2)
 
 # name -> argtypes; every function returns int status except the two noted below
 SIGNATURES = {
@@ -98,6 +108,12 @@ SIGNATURES = {
     "hfmi_op_kernel_cov_rows_spec": [_P, _P, C.c_int64, C.c_int, _SPEC, C.c_int64, C.c_int64, _PP],
     "hfmi_op_kernel_cov_grid_spec": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC, _PP],
     "hfmi_kernel_metric_factor": [_P, C.c_int, _P],
+    "hfmi_op_kernel_cov_spec2": [_P, _P, C.c_int64, C.c_int, _SPEC2, _PP],
+    "hfmi_op_kernel_cross_cov_spec2": [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, _SPEC2, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_rows_spec2": [_P, _P, C.c_int64, C.c_int, _SPEC2, C.c_int64, C.c_int64, _PP],
+    "hfmi_op_kernel_cov_grid_spec2": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC2, _PP],
+    "hfmi_op_kernel_cov_grid_long_spec2": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC2, _PP],
+    "hfmi_kernel_matern_tables": [C.c_double, _P],
     "hfmi_fftcov_plan_predict": [C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_grid_sampler_create": [_P, C.c_int, C.c_int, _PP],
     "hfmi_grid_sampler_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -56,6 +56,8 @@ struct fftcov_state {
   double sigma = 0.0, ell = 0.0, nugget = 0.0;
   bool has_metric = false; // r^2 = |L^T diag(h) o|^2 / ell^2 with the factor below (k_fftcov_column_signed); false: the even column
   double mL[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};   // lower Cholesky factor of the metric, row-major 3 x 3
+  double nu = 0.0, nuca = 0.0;   // HFMI_KERNEL_MATERN: the smoothness and sqrt(2 nu); the table words below are this state's own copy
+  dev_buf<double> nutab;
   dev_buf<int64_t> inv;    // nnodes entries: the point that is grid node g, or -1; empty: point g is node g
   dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
@@ -439,7 +441,8 @@ __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* b
     buf[e] = double2{kcov_entry(K, r2, e == 0), 0.0};
   }
 }
-// The column of a kernel with a metric, r^2 = o^T diag(h) G diag(h) o / ell^2, and of Matern-1 (PT = kcov_k1_params): such a kernel is
+// The column of a kernel with a metric, r^2 = o^T diag(h) G diag(h) o / ell^2, of Matern-1 (PT = kcov_k1_params) and of a Matern of any
+// smoothness (PT = kcov_nu_params): such a kernel is
 // even in the offset vector only, not in each axis, so the column takes SIGNED offsets.  Storage position s_c stands for o_c = s_c below
 // P_c / 2 and s_c - P_c above it; at s_c = P_c / 2 (P_c >= 2) the entry is the mean over both signs of that offset, taken over every
 // axis at its half in the fixed order b = 0 .. 7 (bit c of b: the + sign on axis c).  An apply never reads a half position (P_c >= 2 n_c
@@ -621,7 +624,13 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
   // Lambda = FFT(first column) / P by the forward passes over the whole padded array
   const int64_t blocks = std::min<int64_t>((p.Ptot + 255) / 256, (int64_t)ctx->num_cus * 8);
   const fftcov_metric_args G{st->mL[0], st->mL[3], st->mL[4], st->mL[6], st->mL[7], st->mL[8]};
-  if (st->family == HFMI_KERNEL_MATERN1) {
+  if (st->family == HFMI_KERNEL_MATERN) {
+    kcov_nu_params K;
+    HFMI_TRY(kcov_nu_upload(ctx, st->nu, &st->nutab, &st->nuca));
+    HFMI_TRY(kcov_nu_params_init_as(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, st->nugget, kcov_nu_ref{st->nu, st->nuca, st->nutab}));
+    hipLaunchKernelGGL(k_fftcov_column_signed<kcov_nu_params>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, G, st->work, p.Ptot,
+                       fftcov_log2(p.P[0]), fftcov_log2(p.P[1]), p.P[0], p.P[1], p.P[2], st->h[0], st->h[1], st->h[2]);
+  } else if (st->family == HFMI_KERNEL_MATERN1) {
     kcov_k1_params K;
     HFMI_TRY(kcov_params_init_as(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, st->nugget));   // no coordinates are read
     hipLaunchKernelGGL(k_fftcov_column_signed<kcov_k1_params>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, K, G, st->work, p.Ptot,
@@ -652,7 +661,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
 }
 
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line) {
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line, double nu) {
   const int64_t maxn = max_line > 0 ? FFTCOV_LONG_MAXN : FFTCOV_MAXN;
   int64_t nnodes = 1;
   for (int c = 0; c < d; ++c) {
@@ -689,6 +698,7 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
     for (int r = 0; r < d; ++r)
       for (int c = 0; c < d; ++c) st->mL[3 * r + c] = metric_factor[(size_t)r * d + c];
   }
+  st->nu = nu;
   if (max_line > 0) {
     st->long_route = true;
     st->max_line = max_line;
@@ -823,6 +833,7 @@ static int grid_sampler_try(hfmi_ctx* ctx, const fftcov_state* src, int growth, 
   st->family = src->family, st->sigma = src->sigma, st->ell = src->ell, st->nugget = src->nugget;
   st->has_metric = src->has_metric;
   std::copy(src->mL, src->mL + 9, st->mL);
+  st->nu = src->nu;
   st->growth = growth;
   if (max_line > 0) {
     st->long_route = true;

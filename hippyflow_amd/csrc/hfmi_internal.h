@@ -222,6 +222,12 @@ struct hfmi_csr {
   } solve;
 };
 
+// what a launcher needs of a general Matern kernel (HFMI_KERNEL_MATERN) beside (family, sigma, ell, nugget)
+struct kcov_nu_ref {
+  double nu = 0.0;
+  double ca = 0.0;                // sqrt(2 nu), word KNU_W_CA of the table
+  const double* tab = nullptr;    // the table words on the device (hfmi_kcov_nu.h)
+};
 struct fftcov_state;
 enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR };
 
@@ -252,6 +258,10 @@ struct hfmi_op {
   dev_buf<double> kc_t;
   int64_t kc_M = 0, kc_diag = 0;
   bool kc_slab = false;
+  // family HFMI_KERNEL_MATERN: the smoothness, sqrt(2 nu) as the table builder rounded it, and the table words on the device
+  double kc_nu = 0.0, kc_nuca = 0.0;
+  dev_buf<double> kc_nutab;
+  kcov_nu_ref kc_nu_ref() const { return kcov_nu_ref{kc_nu, kc_nuca, kc_nutab}; }
   fftcov_state* fc = nullptr;   // OP_KERNEL_COV_GRID: the grid, the node map, Lambda, the twiddles and the work buffer (owned; hfmi_fftcov.hip)
   // OP_GRID_FACTOR: the state of the sampler the factor was made from, shared with it (hfmi_op_grid_factor); 0: S, 1: S^T
   std::shared_ptr<fftcov_state> fac;
@@ -305,12 +315,12 @@ int launch_tsgemm_nn(hfmi_ctx* ctx, const double* A, int64_t lda, int m, const d
 
 // Y (+)= C W with C_ij = sigma^2 phi(|x_i - x_j| / ell) + nugget delta_ij evaluated in registers (hfmi_kcov.hip); x: d arrays of N doubles
 int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
+                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate, const kcov_nu_ref& nu = kcov_nu_ref());
 // Y (M rows) (+)= K W (N rows), K_ij = sigma^2 phi(|t_i - x_j| / ell) + nugget [j == i + diag_offset] (diag_offset < 0: no nugget); t: d
 // arrays of M doubles, tstride apart.  Same per-row summation order as launch_kernel_cov.  M = 0: nothing is launched.
 int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
                             int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
-                            int64_t ldy, int nvec, int accumulate);
+                            int64_t ldy, int nvec, int accumulate, const kcov_nu_ref& nu = kcov_nu_ref());
 
 // The metric of a kernel covariance, r^2 = delta^T G delta / ell^2 with G symmetric positive definite, enters through its lower Cholesky
 // factor G = L L^T: |L^T delta|^2 is the same number and cannot round below zero.  Scattered points are uploaded as x' = L^T x, so the
@@ -321,9 +331,12 @@ int kcov_metric_factor(const double* G, int d, double* L);
 // Kernel covariance on a regular grid by FFT (hfmi_fftcov.hip; plans: hfmi_fftcov_plan.h).  create checks the arguments, uploads the
 // node map and the twiddles and computes Lambda; apply is Y (+)= C W; destroy deletes the state (the caller synchronised)
 // metric_factor: the lower Cholesky factor of the kernel's metric (d x d row-major, kcov_metric_factor), or null for none;
-// max_line > 0: the long route (split-line passes, hfmi_fftcov_plan.h) with that longest line, 0: the old route
+// max_line > 0: the long route (split-line passes, hfmi_fftcov_plan.h) with that longest line, 0: the old route;
+// nu: the smoothness of HFMI_KERNEL_MATERN (the state builds and owns its tables), unread otherwise
 int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family, double sigma,
-                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line = 0);
+                  double ell, double nugget, const double* metric_factor, fftcov_state** out, int max_line = 0, double nu = 0.0);
+// the table words of a general Matern kernel (hfmi_kernel_matern_tables) on the device, and sqrt(2 nu) as the builder rounded it (hfmi_op.hip)
+int kcov_nu_upload(hfmi_ctx* ctx, double nu, dev_buf<double>* out, double* ca);
 int64_t fftcov_points(const fftcov_state* st);
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate);
 void fftcov_destroy(fftcov_state* st);

@@ -27,6 +27,9 @@
 // Its evaluation is about 100 fp64 VALU instructions with log, exp, sqrt and a division, so that apply is bound by the VALU, not by the
 // matrix pipe; eval(s + 1) is still issued before the MFMAs of slab s.  A metric (r^2 = delta^T G delta) never reaches this unit: the
 // operator uploads x' = L^T x, G = L L^T (hfmi_op.hip).
+//
+// Matern of any smoothness (the kcov_nu_params / kcov_nu_cross_params instances): phi_nu of hfmi_kcov_nu.h behind kcov_entry, its table
+// words read by scalar loads from a buffer the operator owns.  2.3 times the time of Matern-1 per entry (N = 32768, k = 32, nu = 1.25).
 #include <algorithm>
 
 #include "hfmi_gemm_common.h"
@@ -56,8 +59,10 @@ __device__ __forceinline__ int64_t kcov_diag_source(const kcov_cross_params& P, 
 template <class PT> constexpr bool kcov_tight_registers = false;
 template <> constexpr bool kcov_tight_registers<kcov_k1_params> = true;
 template <> constexpr bool kcov_tight_registers<kcov_k1_cross_params> = true;
+template <> constexpr bool kcov_tight_registers<kcov_nu_params> = true;
+template <> constexpr bool kcov_tight_registers<kcov_nu_cross_params> = true;
 
-template <int NT, class PT>      // PT: kcov_params (square) or kcov_cross_params (rectangular); kcov_k1_params / kcov_k1_cross_params: Matern-1
+template <int NT, class PT>      // PT: kcov_params (square) or kcov_cross_params (rectangular); kcov_k1_params / kcov_k1_cross_params: Matern-1; kcov_nu_*: any nu
 __global__ __launch_bounds__(64 * KC_WAVES) void k_kcov(PT P, const double* __restrict__ W, int64_t ldw, double* __restrict__ Y,
                                                         int64_t ldy, int ncols, int accumulate) {
   __shared__ double wl[16 * NT * KC_JCP];
@@ -178,6 +183,7 @@ int kcov_params_init(kcov_params* out, const double* x, int64_t N, int d, int fa
     case HFMI_KERNEL_MATERN52: P.ca = 2.23606797749979, P.p1 = 1.0, P.p2 = 1.0 / 3.0; break;   // (1 + a + a^2/3) exp(-a), a = sqrt(5) r
     case HFMI_KERNEL_SQEXP: P.g1 = 0.0, P.g2 = 0.5; break;                           // exp(-r^2 / 2)
     case HFMI_KERNEL_MATERN1: P.ca = 1.4142135623730951; break;                      // a K_1(a), a = sqrt(2) r: the kcov_k1_* instances
+    case HFMI_KERNEL_MATERN: break;                                                  // any nu: ca and the tables by kcov_nu_params_init_as
     default: HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: unknown kernel family %d", family);
   }
   *out = P;
@@ -207,7 +213,12 @@ static int kcov_panels(hfmi_ctx* ctx, const PT& P, int64_t M, const double* W, i
 }
 
 int launch_kernel_cov(hfmi_ctx* ctx, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {
+                      const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate, const kcov_nu_ref& nu) {
+  if (family == HFMI_KERNEL_MATERN) {
+    kcov_nu_params P;
+    HFMI_TRY(kcov_nu_params_init_as(&P, x, N, d, family, sigma, ell, nugget, nu));
+    return kcov_panels(ctx, P, N, W, ldw, Y, ldy, nvec, accumulate);
+  }
   if (family == HFMI_KERNEL_MATERN1) {
     kcov_k1_params P;
     HFMI_TRY(kcov_params_init_as(&P, x, N, d, family, sigma, ell, nugget));
@@ -232,11 +243,16 @@ static int kcov_cross_panels(hfmi_ctx* ctx, PT& P, const double* t, int64_t M, i
 
 int launch_kernel_cross_cov(hfmi_ctx* ctx, const double* x, int64_t N, const double* t, int64_t M, int64_t tstride, int64_t diag_offset,
                             int d, int family, double sigma, double ell, double nugget, const double* W, int64_t ldw, double* Y,
-                            int64_t ldy, int nvec, int accumulate) {
+                            int64_t ldy, int nvec, int accumulate, const kcov_nu_ref& nu) {
   if (M < 1) return HFMI_OK;      // an empty slab: no row of Y is this operator's
   if (diag_offset >= 0 && diag_offset + M > N)
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: targets %lld .. %lld are not sources (N = %lld)", (long long)diag_offset,
               (long long)(diag_offset + M - 1), (long long)N);
+  if (family == HFMI_KERNEL_MATERN) {
+    kcov_nu_cross_params P;
+    HFMI_TRY(kcov_nu_params_init_as(&P, x, N, d, family, sigma, ell, nugget, nu));
+    return kcov_cross_panels(ctx, P, t, M, tstride, diag_offset, d, W, ldw, Y, ldy, nvec, accumulate);
+  }
   if (family == HFMI_KERNEL_MATERN1) {
     kcov_k1_cross_params P;
     HFMI_TRY(kcov_params_init_as(&P, x, N, d, family, sigma, ell, nugget));

@@ -53,11 +53,46 @@ __device__ __forceinline__ double kcov_k1_entry(const kcov_params& P, double r2,
 __device__ __forceinline__ double kcov_entry(const kcov_k1_params& P, double r2, bool same_index) { return kcov_k1_entry(P, r2, same_index); }
 __device__ __forceinline__ double kcov_entry(const kcov_k1_cross_params& P, double r2, bool same_index) { return kcov_k1_entry(P, r2, same_index); }
 
+// HFMI_KERNEL_MATERN, any smoothness nu (hfmi_kcov_nu.h): again types of their own, which add the operator's table words on the device and
+// the integer part n of the order.  ca = sqrt(2 nu); p1 .. g2 are unused.
+struct kcov_nu_params : kcov_params {
+  const double* tab;   // KNU_WORDS doubles (hfmi_kernel_matern_tables), owned by the operator
+  int n;               // floor(nu + 1/2)
+};
+struct kcov_nu_cross_params : kcov_cross_params {
+  const double* tab;
+  int n;
+};
+
+#include "hfmi_kcov_nu.h"
+
+template <class PT>
+__device__ __forceinline__ double kcov_nu_entry(const PT& P, double r2, bool same_index) {
+  const double a = P.ca * sqrt(r2) * P.inv_ell;
+  double v = P.sigma2 * kcov_nu_phi(P.tab, P.n, a);
+  if (same_index) v += P.nugget;
+  return v;
+}
+__device__ __forceinline__ double kcov_entry(const kcov_nu_params& P, double r2, bool same_index) { return kcov_nu_entry(P, r2, same_index); }
+__device__ __forceinline__ double kcov_entry(const kcov_nu_cross_params& P, double r2, bool same_index) { return kcov_nu_entry(P, r2, same_index); }
+
 // the parameter block of a family as the type its instances take: kcov_params_init, then the same bytes
 template <class PT>
 inline int kcov_params_init_as(PT* out, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget) {
   kcov_params base;
   HFMI_TRY(kcov_params_init(&base, x, N, d, family, sigma, ell, nugget));
   static_cast<kcov_params&>(*out) = base;
+  return HFMI_OK;
+}
+// the same for the general Matern family, with ca = sqrt(2 nu) as the table builder rounded it, the table and n
+template <class PT>
+inline int kcov_nu_params_init_as(PT* out, const double* x, int64_t N, int d, int family, double sigma, double ell, double nugget,
+                                  const kcov_nu_ref& nu) {
+  if (family != HFMI_KERNEL_MATERN || !nu.tab || !(nu.nu >= HFMI_MATERN_NU_MIN && nu.nu <= HFMI_MATERN_NU_MAX))
+    HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov: the general Matern family needs its smoothness and tables");
+  HFMI_TRY(kcov_params_init_as(out, x, N, d, family, sigma, ell, nugget));
+  out->ca = nu.ca;
+  out->tab = nu.tab;
+  out->n = (int)floor(nu.nu + 0.5);
   return HFMI_OK;
 }

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "hfmi_internal.h"
+#include "hfmi_kcov_nu.h"      // the layout of the table words
 
 // ------------------------------------------------------------------ operators
 static hfmi_op* op_new(hfmi_ctx* ctx, hfmi_op_kind kind) {
@@ -82,7 +83,8 @@ extern "C" int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** o
   return HFMI_OK;
 }
 // the checks every kernel covariance constructor shares
-// last_family: HFMI_KERNEL_SQEXP for the creators that take a bare family, HFMI_KERNEL_MATERN1 for those that take a hfmi_kernel_spec
+// last_family: HFMI_KERNEL_SQEXP for the creators that take a bare family, HFMI_KERNEL_MATERN1 for those that take a hfmi_kernel_spec,
+// HFMI_KERNEL_MATERN for those that take a hfmi_kernel_spec2
 static int kcov_check(const char* who, int64_t N, int d, int family, double ell, double nugget, int last_family = HFMI_KERNEL_SQEXP) {
   if (N < 1) HFMI_FAIL(HFMI_ERR_INVALID, "%s: needs at least one point (N = %lld)", who, (long long)N);
   if (d < 1 || d > 3) HFMI_FAIL(HFMI_ERR_INVALID, "%s: points have 1, 2 or 3 coordinates, got d = %d", who, d);
@@ -114,11 +116,28 @@ static int kcov_upload_points(hfmi_ctx* ctx, const double* host_points, int64_t 
   *out = std::move(x);
   return HFMI_OK;
 }
+// the table words of a general Matern kernel on the device, owned by `out`, and sqrt(2 nu) as the builder rounded it
+int kcov_nu_upload(hfmi_ctx* ctx, double nu, dev_buf<double>* out, double* ca) {
+  double words[HFMI_MATERN_TABLE_WORDS];
+  HFMI_TRY(hfmi_kernel_matern_tables(nu, words));
+  dev_buf<double> t;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = (hipError_t)t.alloc(HFMI_MATERN_TABLE_WORDS);
+  if (e == hipSuccess) e = hipMemcpy(t, words, sizeof(words), hipMemcpyHostToDevice);
+  if (e != hipSuccess) HFMI_FAIL(HFMI_ERR_HIP, "kernel covariance tables: %s", hipGetErrorString(e));
+  *out = std::move(t);
+  *ca = words[KNU_W_CA];
+  return HFMI_OK;
+}
 static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
-                       double nugget, hfmi_op** out, const double* mL = nullptr) {
+                       double nugget, hfmi_op** out, const double* mL = nullptr, double nu = 0.0) {
   std::unique_ptr<hfmi_op> op(op_new(ctx, kind));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   HFMI_TRY(kcov_upload_points(ctx, host_points, N, d, &op->kc_x, mL));
+  if (family == HFMI_KERNEL_MATERN) {
+    HFMI_TRY(kcov_nu_upload(ctx, nu, &op->kc_nutab, &op->kc_nuca));
+    op->kc_nu = nu;
+  }
   op->kc_N = N;
   op->kc_d = d;
   op->kc_family = family;
@@ -129,15 +148,17 @@ static int kcov_op_new(hfmi_ctx* ctx, hfmi_op_kind kind, const double* host_poin
   return HFMI_OK;
 }
 // The creators behind both entry-point sets: a bare family (last_family = HFMI_KERNEL_SQEXP, no metric) or a hfmi_kernel_spec
-// (last_family = HFMI_KERNEL_MATERN1; mL: the metric's lower factor or null)
+// (last_family = HFMI_KERNEL_MATERN1; mL: the metric's lower factor or null) or a hfmi_kernel_spec2 (last_family = HFMI_KERNEL_MATERN;
+// nu: the smoothness, read for that family only)
 static int kcov_create(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                       int last_family, const double* mL, hfmi_op** out) {
+                       int last_family, const double* mL, hfmi_op** out, double nu = 0.0) {
   if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cov", N, d, family, ell, nugget, last_family));
-  return kcov_op_new(ctx, OP_KERNEL_COV, host_points, N, d, family, sigma, ell, nugget, out, mL);
+  return kcov_op_new(ctx, OP_KERNEL_COV, host_points, N, d, family, sigma, ell, nugget, out, mL, nu);
 }
 static int kcov_cross_create(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d, int family,
-                             double sigma, double ell, double nugget, int64_t diag_offset, int last_family, const double* mL, hfmi_op** out) {
+                             double sigma, double ell, double nugget, int64_t diag_offset, int last_family, const double* mL, hfmi_op** out,
+                             double nu = 0.0) {
   if (!ctx || !host_targets || !host_sources || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cross_cov", N, d, family, ell, nugget, last_family));
   if (M < 1) HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cross_cov: needs at least one target (M = %lld)", (long long)M);
@@ -148,7 +169,7 @@ static int kcov_cross_create(hfmi_ctx* ctx, const double* host_targets, int64_t 
               (long long)diag_offset, (long long)M, (long long)N);
   }
   hfmi_op* raw = nullptr;
-  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &raw, mL));
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_sources, N, d, family, sigma, ell, nugget, &raw, mL, nu));
   std::unique_ptr<hfmi_op> op(raw);
   HFMI_TRY(kcov_upload_points(ctx, host_targets, M, d, &op->kc_t, mL));
   op->kc_M = M;
@@ -158,14 +179,14 @@ static int kcov_cross_create(hfmi_ctx* ctx, const double* host_targets, int64_t 
   return HFMI_OK;
 }
 static int kcov_rows_create(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell, double nugget,
-                            int64_t row0, int64_t nrows, int last_family, const double* mL, hfmi_op** out) {
+                            int64_t row0, int64_t nrows, int last_family, const double* mL, hfmi_op** out, double nu = 0.0) {
   if (!ctx || !host_points || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cov_rows", N, d, family, ell, nugget, last_family));
   if (row0 < 0 || nrows < 0 || row0 > N - nrows)
     HFMI_FAIL(HFMI_ERR_INVALID, "kernel_cov_rows: rows %lld .. %lld + %lld do not lie inside 0 .. N = %lld", (long long)row0, (long long)row0,
               (long long)nrows, (long long)N);
   hfmi_op* op = nullptr;
-  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_points, N, d, family, sigma, ell, nugget, &op, mL));
+  HFMI_TRY(kcov_op_new(ctx, OP_KERNEL_CROSS, host_points, N, d, family, sigma, ell, nugget, &op, mL, nu));
   op->kc_M = nrows;
   op->kc_diag = row0;
   op->kc_slab = true;
@@ -174,12 +195,13 @@ static int kcov_rows_create(hfmi_ctx* ctx, const double* host_points, int64_t N,
 }
 // max_line > 0: the long route (hfmi_op_kernel_cov_grid_long)
 static int kcov_grid_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N, int family,
-                            double sigma, double ell, double nugget, int last_family, const double* mL, hfmi_op** out, int max_line = 0) {
+                            double sigma, double ell, double nugget, int last_family, const double* mL, hfmi_op** out, int max_line = 0,
+                            double nu = 0.0) {
   if (!ctx || !n || !h || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   HFMI_TRY(kcov_check("kernel_cov_grid", N, d, family, ell, nugget, last_family));
   std::unique_ptr<hfmi_op> op(op_new(ctx, OP_KERNEL_COV_GRID));
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
-  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, mL, &op->fc, max_line));
+  HFMI_TRY(fftcov_create(ctx, d, n, h, host_nodes, N, family, sigma, ell, nugget, mL, &op->fc, max_line, nu));
   *out = op.release();
   return HFMI_OK;
 }
@@ -280,6 +302,65 @@ extern "C" int hfmi_op_kernel_cov_grid_long(hfmi_ctx* ctx, int d, const int64_t*
   return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec->family, spec->sigma, spec->ell, spec->nugget, HFMI_KERNEL_MATERN1, mL, out,
                           fftcov_max_line_knob());
 }
+
+// The hfmi_kernel_spec2 creators: the descriptor's first fields are a hfmi_kernel_spec, which goes the way it always went; nu is checked
+// here (in range for HFMI_KERNEL_MATERN, 0 otherwise) and read by the creators for that family alone.
+static int kcov_spec2_read(const char* who, const hfmi_kernel_spec2* spec2, int d, hfmi_kernel_spec* spec, double* store, const double** mL) {
+  if (!spec2) HFMI_FAIL(HFMI_ERR_INVALID, "%s: null kernel descriptor", who);
+  spec->family = spec2->family, spec->d = spec2->d;
+  spec->sigma = spec2->sigma, spec->ell = spec2->ell, spec->nugget = spec2->nugget;
+  for (int i = 0; i < 9; ++i) spec->metric[i] = spec2->metric[i];
+  HFMI_TRY(kcov_spec_metric(who, spec, d, store, mL));
+  if (spec2->family == HFMI_KERNEL_MATERN) {
+    if (!isfinite(spec2->nu) || spec2->nu < HFMI_MATERN_NU_MIN || spec2->nu > HFMI_MATERN_NU_MAX)
+      HFMI_FAIL(HFMI_ERR_INVALID, "%s: the smoothness nu = %g does not lie in [1/8, 8]", who, spec2->nu);
+  } else if (spec2->nu != 0.0) {      // a NaN included
+    HFMI_FAIL(HFMI_ERR_INVALID, "%s: nu = %g with kernel family %d: only HFMI_KERNEL_MATERN takes a smoothness", who, spec2->nu, spec2->family);
+  }
+  return HFMI_OK;
+}
+extern "C" int hfmi_op_kernel_cov_spec2(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec2* spec2, hfmi_op** out) {
+  hfmi_kernel_spec spec;
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec2_read("kernel_cov", spec2, d, &spec, store, &mL));
+  return kcov_create(ctx, host_points, N, d, spec.family, spec.sigma, spec.ell, spec.nugget, HFMI_KERNEL_MATERN, mL, out, spec2->nu);
+}
+extern "C" int hfmi_op_kernel_cross_cov_spec2(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                              const hfmi_kernel_spec2* spec2, int64_t diag_offset, hfmi_op** out) {
+  hfmi_kernel_spec spec;
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec2_read("kernel_cross_cov", spec2, d, &spec, store, &mL));
+  return kcov_cross_create(ctx, host_targets, M, host_sources, N, d, spec.family, spec.sigma, spec.ell, spec.nugget, diag_offset,
+                           HFMI_KERNEL_MATERN, mL, out, spec2->nu);
+}
+extern "C" int hfmi_op_kernel_cov_rows_spec2(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec2* spec2,
+                                             int64_t row0, int64_t nrows, hfmi_op** out) {
+  hfmi_kernel_spec spec;
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec2_read("kernel_cov_rows", spec2, d, &spec, store, &mL));
+  return kcov_rows_create(ctx, host_points, N, d, spec.family, spec.sigma, spec.ell, spec.nugget, row0, nrows, HFMI_KERNEL_MATERN, mL, out,
+                          spec2->nu);
+}
+extern "C" int hfmi_op_kernel_cov_grid_spec2(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                             const hfmi_kernel_spec2* spec2, hfmi_op** out) {
+  hfmi_kernel_spec spec;
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec2_read("kernel_cov_grid", spec2, d, &spec, store, &mL));
+  return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec.family, spec.sigma, spec.ell, spec.nugget, HFMI_KERNEL_MATERN, mL, out, 0, spec2->nu);
+}
+extern "C" int hfmi_op_kernel_cov_grid_long_spec2(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const int64_t* host_nodes, int64_t N,
+                                                  const hfmi_kernel_spec2* spec2, hfmi_op** out) {
+  hfmi_kernel_spec spec;
+  double store[9];
+  const double* mL = nullptr;
+  HFMI_TRY(kcov_spec2_read("kernel_cov_grid_long", spec2, d, &spec, store, &mL));
+  return kcov_grid_create(ctx, d, n, h, host_nodes, N, spec.family, spec.sigma, spec.ell, spec.nugget, HFMI_KERNEL_MATERN, mL, out,
+                          fftcov_max_line_knob(), spec2->nu);
+}
 extern "C" int hfmi_op_csr(hfmi_ctx* ctx, const hfmi_csr* M, hfmi_op** out) {
   if (!ctx || !M || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   hfmi_op* op = op_new(ctx, OP_CSR);
@@ -365,7 +446,7 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
   return HFMI_OK;
 }
 hfmi_op::~hfmi_op() {
-  if (gamma_inv || weights || kc_x || kc_t || fc || fac) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
+  if (gamma_inv || weights || kc_x || kc_t || kc_nutab || fc || fac) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
   fftcov_destroy(fc);
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
@@ -561,7 +642,7 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
         HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)op->kc_N, (long long)W->N, (long long)Y->N);
       // Y (+)= C W: the kernel adds into Y itself
       return launch_kernel_cov(ctx, op->kc_x, op->kc_N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget, W->p, W->ld,
-                               Y->p, Y->ld, k, beta != 0.0);
+                               Y->p, Y->ld, k, beta != 0.0, op->kc_nu_ref());
     }
     case OP_KERNEL_COV_GRID: {
       const int64_t N = fftcov_points(op->fc);
@@ -581,7 +662,7 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
           HFMI_FAIL(HFMI_ERR_INVALID, "operator maps vectors of length %lld to length %lld, got %lld -> %lld", (long long)N, (long long)M,
                     (long long)W->N, (long long)Y->N);
         return launch_kernel_cross_cov(ctx, op->kc_x, N, op->kc_t, M, M, op->kc_diag, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell,
-                                       op->kc_nugget, W->p, W->ld, Y->p, Y->ld, k, acc);
+                                       op->kc_nugget, W->p, W->ld, Y->p, Y->ld, k, acc, op->kc_nu_ref());
       }
       if (N != W->N || N != Y->N)
         HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)N, (long long)W->N, (long long)Y->N);
@@ -594,7 +675,7 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
           HIP_TRY(hipMemset2DAsync(Y->p + row1, (size_t)Y->ld * sizeof(double), 0, (size_t)(N - row1) * sizeof(double), (size_t)k, ctx->stream));
       }
       return launch_kernel_cross_cov(ctx, op->kc_x, N, op->kc_x + row0, M, N, row0, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell,
-                                     op->kc_nugget, W->p, W->ld, Y->p + row0, Y->ld, k, acc);
+                                     op->kc_nugget, W->p, W->ld, Y->p + row0, Y->ld, k, acc, op->kc_nu_ref());
     }
     case OP_CSR: {
       if (op->csr->ncols != W->N || op->csr->nrows != Y->N) HFMI_FAIL(HFMI_ERR_INVALID, "csr operator / block shape mismatch");

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <memory>
 #include <new>
+#include <type_traits>
 
 #include "hfmi_kcov_eval.h"
 
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(PC_THREADS) void k_pchol_gather_row(const double* _
 }
 
 // column j of L from the pivot (p, dp), the new diagonal and the workgroup's (max, lowest index, sum) of it.  PT: kcov_params, or
-// kcov_k1_params for Matern-1 (the entry behind kcov_entry is what differs)
+// kcov_k1_params for Matern-1, kcov_nu_params for a Matern of any smoothness (the entry behind kcov_entry is what differs)
 template <class PT>
 __global__ __launch_bounds__(PC_THREADS) void k_pchol_column(PT P, double* __restrict__ L, int64_t ld, int j, int64_t p, double dp,
                                                              const double* __restrict__ prow, double* __restrict__ diag,
@@ -201,7 +202,10 @@ static int pchol_run(hfmi_pchol* h, const hfmi_op* op, int kmax, double rel_tol,
   hfmi_ctx* ctx = h->ctx;
   const int64_t N = op->kc_N, ld = h->L.ld;
   PT P;
-  HFMI_TRY(kcov_params_init_as(&P, op->kc_x, N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget));
+  if constexpr (std::is_same<PT, kcov_nu_params>::value)
+    HFMI_TRY(kcov_nu_params_init_as(&P, op->kc_x, N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget, op->kc_nu_ref()));
+  else
+    HFMI_TRY(kcov_params_init_as(&P, op->kc_x, N, op->kc_d, op->kc_family, op->kc_sigma, op->kc_ell, op->kc_nugget));
   // scratch: diag[N] | prow[kmax] | pmax[grid] | psum[grid] | pidx[grid] | pick
   double* diag = scratch;
   double* prow = diag + N;
@@ -261,7 +265,9 @@ extern "C" int hfmi_pchol_create(hfmi_op* op, int max_rank, double rel_tol, hfmi
   const int kmax = (int)std::min<int64_t>(max_rank, N);
   int per_cu = 0;
   const bool k1 = op->kc_family == HFMI_KERNEL_MATERN1;
-  if (k1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_k1_params>, PC_THREADS, 0));
+  const bool knu = op->kc_family == HFMI_KERNEL_MATERN;
+  if (knu) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_nu_params>, PC_THREADS, 0));
+  else if (k1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_k1_params>, PC_THREADS, 0));
   else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pchol_column<kcov_params>, PC_THREADS, 0));
   if (per_cu < 1) per_cu = 1;
   const int64_t ntiles = (N + PC_THREADS - 1) / PC_THREADS;
@@ -286,7 +292,8 @@ extern "C" int hfmi_pchol_create(hfmi_op* op, int max_rank, double rel_tol, hfmi
     hfmi_set_error("pchol: %s", hipGetErrorString(e));
     s = HFMI_ERR_HIP;
   } else {
-    s = k1 ? pchol_run<kcov_k1_params>(h.get(), op, kmax, rel_tol, scratch, grid) : pchol_run<kcov_params>(h.get(), op, kmax, rel_tol, scratch, grid);
+    s = knu ? pchol_run<kcov_nu_params>(h.get(), op, kmax, rel_tol, scratch, grid)
+        : k1 ? pchol_run<kcov_k1_params>(h.get(), op, kmax, rel_tol, scratch, grid) : pchol_run<kcov_params>(h.get(), op, kmax, rel_tol, scratch, grid);
   }
   (void)hipStreamSynchronize(ctx->stream);      // before the scratch goes
   if (s != HFMI_OK) return s;

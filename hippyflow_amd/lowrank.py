@@ -53,7 +53,7 @@ class PivotedCholesky:
         L.call("hfmi_pchol_read", self.handle, L.ptr(self.pivots), L.ptr(self.trace))
         self.N = op.shape[0]
         self._L = None
-        self._kernel = (op.points, op.family, op.sigma, op.ell, op.metric)     # what extend() evaluates K(., X_P) with
+        self._kernel = (op.points, op.family, op.sigma, op.ell, op.metric, getattr(op, "nu", None))     # what extend() evaluates K(., X_P) with
         self._LP_invT = None
 
     @property
@@ -126,11 +126,11 @@ class PivotedCholesky:
         from scipy.linalg import solve_triangular
         if self.rank < 1:
             raise ValueError("extend: the factor has rank 0")
-        pts, family, sigma, ell, metric = self._kernel
+        pts, family, sigma, ell, metric, nu = self._kernel
         if self._LP_invT is None:
             LP = self.L.to_dense()[self.pivots, :]
             self._LP_invT = np.ascontiguousarray(solve_triangular(LP, np.eye(self.rank), lower=True).T)
-        cross = KernelCrossCovarianceOperator(points, pts[self.pivots], family, sigma, ell, ctx=self.ctx, metric=metric)
+        cross = KernelCrossCovarianceOperator(points, pts[self.pivots], family, sigma, ell, ctx=self.ctx, nu=nu, metric=metric)
         out = MultiVector(cross.shape[0], self.rank, ctx=self.ctx)
         cross.matMvMult(MultiVector.from_dense(self._LP_invT, ctx=self.ctx), out)
         return out

@@ -244,17 +244,50 @@ def _metric_points(pts, G):
     return pts if G is None else np.ascontiguousarray(pts @ np.linalg.cholesky(G))
 
 
-def _kernel_spec(family, d, sigma, ell, nugget, G):
-    """The hfmi_kernel_spec of a kernel: what Matern-1 and every kernel with a metric are created from."""
-    spec = L.KernelSpec(L.KERNEL_FAMILIES[family], int(d), float(sigma), float(ell), float(nugget))
+def _kernel_spec(family, d, sigma, ell, nugget, G, nu=None):
+    """The hfmi_kernel_spec of a kernel: what Matern-1 and every kernel with a metric are created from.  With ``nu`` (family
+    "matern") it is the hfmi_kernel_spec2 that the ``_spec2`` creators take."""
+    if nu is None:
+        spec = L.KernelSpec(L.KERNEL_FAMILIES[family], int(d), float(sigma), float(ell), float(nugget))
+    else:
+        spec = L.KernelSpec2(L.KERNEL_FAMILIES[family], int(d), float(sigma), float(ell), float(nugget))
+        spec.nu = float(nu)
     if G is not None:
         for i, v in enumerate(G.ravel()):
             spec.metric[i] = v
     return spec
 
 
-def _kernel_phi(family, dist, ell):
+def _check_nu(family, nu):
+    """The smoothness of a kernel as a float, None for every family but "matern": ``family="matern"`` needs ``nu`` in
+    [MATERN_NU_MIN, MATERN_NU_MAX] = [1/8, 8]; every other family refuses one."""
+    if family == "matern":
+        if nu is None:
+            raise ValueError('family="matern" needs its smoothness nu (1/8 <= nu <= 8)')
+        nu = float(nu)
+        if not (np.isfinite(nu) and L.MATERN_NU_MIN <= nu <= L.MATERN_NU_MAX):
+            raise ValueError("nu = %r does not lie in [%g, %g]" % (nu, L.MATERN_NU_MIN, L.MATERN_NU_MAX))
+        return nu
+    if nu is not None:
+        raise ValueError('nu is the smoothness of family="matern"; family %r has none' % (family,))
+    return None
+
+
+def _spec_suffix(nu):
+    """the creators a kernel goes through: ``_spec2`` with a smoothness, ``_spec`` otherwise"""
+    return "_spec" if nu is None else "_spec2"
+
+
+def _kernel_phi(family, dist, ell, nu=None):
     """phi(dist / ell) of ``kernel_cov_host`` for an array of distances"""
+    if family == "matern":
+        # 2^(1-nu) / Gamma(nu) a^nu K_nu(a) through scipy's scaled K_nu: independent of the device's arithmetic
+        from scipy.special import gamma, kve
+        a = np.sqrt(2.0 * nu) * dist / ell
+        with np.errstate(invalid="ignore", under="ignore", divide="ignore", over="ignore"):
+            v = ((2.0 ** (1.0 - nu) / gamma(nu)) * a ** nu) * kve(nu, a) * np.exp(-a)
+            # a^nu K_nu(a) is 0 * inf for a tiny a (phi is 1 there to rounding) and inf * 0 for a huge one (phi is 0)
+            return np.where(a > 0.0, np.where(np.isfinite(v), v, np.where(a < 1.0, 1.0, 0.0)), 1.0)
     if family == "matern12":
         return np.exp(-dist / ell)
     if family == "matern32":
@@ -271,22 +304,26 @@ def _kernel_phi(family, dist, ell):
     return np.exp(-0.5 * (dist / ell) ** 2)
 
 
-def kernel_cov_host(points, family, sigma, ell, nugget=0.0, rows=None, metric=None):
+def kernel_cov_host(points, family, sigma, ell, nugget=0.0, rows=None, *, nu=None, metric=None):
     """Dense host evaluation of the covariance ``KernelCovarianceOperator`` applies: C_ij = sigma^2 phi(|x_i - x_j| / ell)
     + nugget delta_ij (the delta is on the point INDEX), all rows or the rows ``rows``.  With r the scaled distance:
     'matern12' exp(-r); 'matern32' (1 + a) exp(-a), a = sqrt(3) r; 'matern52' (1 + a + a^2/3) exp(-a), a = sqrt(5) r;
     'sqexp' exp(-r^2 / 2); 'matern1' a K_1(a), a = sqrt(2) r (1 at r = 0; ``scipy.special.k1e``).  ``metric``: a symmetric positive
     definite d x d matrix G, r = sqrt(delta^T G delta) / ell, evaluated as the isotropic kernel on ``points @ L``, G = L L^T; None is
-    the identity.  What tests and users compare the device operator against."""
+    the identity.  'matern' with ``nu`` (keyword only, 1/8 <= nu <= 8): the Matern correlation of any smoothness,
+    2^(1-nu) / Gamma(nu) a^nu K_nu(a), a = sqrt(2 nu) r, by ``scipy.special.kve`` -- not the device's arithmetic, so this stays an
+    independent reference.  nu = 1/2, 3/2, 5/2 and 1 are 'matern12', 'matern32', 'matern52' and 'matern1' to rounding; the named
+    families are the fast ones on the device and nothing dispatches to them.  What tests and users compare the device operator against."""
     if family not in L.KERNEL_FAMILIES:
         raise _unknown_family(family)
+    nu = _check_nu(family, nu)
     pts = _points_array(points)
     pts = _metric_points(pts, _check_metric(metric, pts.shape[1]))
     r = np.arange(pts.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64)
     d2 = np.zeros((len(r), pts.shape[0]))
     for c in range(pts.shape[1]):
         d2 += (pts[r, c][:, None] - pts[None, :, c]) ** 2
-    C = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell)
+    C = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell, nu)
     if nugget:
         C[np.arange(len(r)), r] += nugget
     return C
@@ -303,31 +340,39 @@ class KernelCovarianceOperator(DeviceOperator):
     cost several times those of the other families, so its apply is bound by their evaluation.  ``metric``: a symmetric positive
     definite d x d matrix G, distances are sqrt(delta^T G delta) (None: the identity).  The library is handed L^T x, G = L L^T, and
     runs the isotropic kernels; ``.points`` stays the caller's coordinates and ``.metric`` goes to every operator derived from this
-    one.  One of the four other families without a metric is created exactly as before."""
+    one.  One of the four other families without a metric is created exactly as before.
 
-    def __init__(self, points, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None, metric=None):
+    ``family="matern"`` with ``nu`` (keyword only, 1/8 <= nu <= 8) is the Matern correlation of any smoothness,
+    2^(1-nu) / Gamma(nu) a^nu K_nu(a), a = sqrt(2 nu) r / ell: the kernel of (delta - gamma div Theta grad)^alpha in d dimensions has
+    nu = alpha - d/2 (``whittle_matern_kernel``).  K_nu is evaluated on the device from tables computed once at creation; an entry
+    costs 2.3 times a Matern-1 entry (measured at nu = 1.25).  There is no silent dispatch: ``nu=1.5`` runs this general evaluation
+    and agrees with ``"matern32"`` to rounding -- the named families stay the fast ones.  ``.nu`` goes to every operator derived from
+    this one."""
+
+    def __init__(self, points, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, ctx=None, *, nu=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
             raise _unknown_family(family)
+        nu = _check_nu(family, nu)
         pts = _points_array(points)
         G = _check_metric(metric, pts.shape[1])
         super().__init__(ctx, pts.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.points, self.metric = pts, G
-        if family == "matern1" or G is not None:
-            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G)
-            L.call("hfmi_op_kernel_cov_spec", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), C.byref(self._op))
+        self.points, self.metric, self.nu = pts, G, nu
+        if family == "matern1" or G is not None or nu is not None:
+            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G, nu)
+            L.call("hfmi_op_kernel_cov" + _spec_suffix(nu), self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), C.byref(self._op))
         else:
             L.call("hfmi_op_kernel_cov", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
                    self.sigma, self.ell, self.nugget, C.byref(self._op))
 
     def to_dense(self, rows=None):
         """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
-        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, metric=self.metric)
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, nu=self.nu, metric=self.metric)
 
     def rows(self, row0, row1):
         """Rows ``row0 .. row1 - 1`` of this operator as an operator N -> N (``KernelCovarianceRowsOperator``)."""
         return KernelCovarianceRowsOperator(self.points, self.family, self.sigma, self.ell, self.nugget, row0, row1, ctx=self.ctx,
-                                            metric=self.metric)
+                                            nu=self.nu, metric=self.metric)
 
     def sharded(self, collective):
         """An operator N -> N that equals C on every rank of ``collective``: this rank's row slab (``shard_rows``) with the collective's
@@ -411,6 +456,8 @@ class GridKernelCovarianceOperator(DeviceOperator):
     kernel is even only in the whole offset vector, so the circulant's first column is built from signed offsets; its spectrum is real
     all the same, and the apply, the sampler with its growth and clipping, the factor and ``GridKernelPrior`` run as for every kernel.
     ``GridKernelCovarianceOperator(shape, spacing, **bilaplacian_kernel_2d(gamma, delta))`` is the BiLaplacian prior's covariance.
+    ``family="matern"`` with ``nu`` (keyword only) as for ``KernelCovarianceOperator``: only the first column's entries differ, so the
+    sampler, the factor and ``GridKernelPrior`` follow; ``**whittle_matern_kernel(gamma, delta, alpha, d)`` splats the same way.
 
     ``long_axes=True`` takes the long route (hfmi_op_kernel_cov_grid_long): an embedding axis longer than one workgroup's line
     (4096, or the tuning key "fftcov_max_line" at creation) is split in two passes, so axes may have up to 2^23 nodes, and
@@ -418,27 +465,28 @@ class GridKernelCovarianceOperator(DeviceOperator):
     the applies, draws and factors are bit-identical to the default route's.  ``.long_axes`` records the choice."""
 
     def __init__(self, shape, spacing, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, nodes=None, origin=None, ctx=None, *, long_axes=False,
-                 metric=None):
+                 nu=None, metric=None):
         # keyword-only from `long_axes` on: `metric` stays the last parameter (what splats of bilaplacian_kernel_2d rely on), and a
         # positional tenth argument is refused instead of landing in the new keyword's slot
         self.long_axes = bool(long_axes)
         n, h, nodes, o = _check_grid(shape, spacing, nodes, origin, family, ell, nugget,
                                      L.GRID_COV_LONG_MAX_NODES if self.long_axes else L.GRID_COV_MAX_NODES)
         G = _check_metric(metric, int(n.size))
+        nu = _check_nu(family, nu)
         N = int(np.prod(n)) if nodes is None else int(nodes.size)
         super().__init__(ctx, N)
         self.grid_shape = tuple(int(v) for v in n)
         self.spacing, self.origin, self.nodes = h, o, nodes
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.metric = G
+        self.metric, self.nu = G, nu
         self.points = L.as_f64(grid_node_points(n, h, nodes, o))
         if self.long_axes:
-            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G)
-            L.call("hfmi_op_kernel_cov_grid_long", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
+            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G, nu)
+            L.call("hfmi_op_kernel_cov_grid_long" + ("" if nu is None else "_spec2"), self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
                    N, C.byref(spec), C.byref(self._op))
-        elif family == "matern1" or G is not None:
-            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G)
-            L.call("hfmi_op_kernel_cov_grid_spec", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
+        elif family == "matern1" or G is not None or nu is not None:
+            spec = _kernel_spec(family, int(n.size), self.sigma, self.ell, self.nugget, G, nu)
+            L.call("hfmi_op_kernel_cov_grid" + _spec_suffix(nu), self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes),
                    N, C.byref(spec), C.byref(self._op))
         else:
             L.call("hfmi_op_kernel_cov_grid", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(h), None if nodes is None else L.ptr(nodes), N,
@@ -446,11 +494,12 @@ class GridKernelCovarianceOperator(DeviceOperator):
 
     def to_dense(self, rows=None):
         """The same matrix on the host (``kernel_cov_host``): for checks at sizes where it fits."""
-        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, metric=self.metric)
+        return kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget, rows=rows, nu=self.nu, metric=self.metric)
 
     def matrix_free(self):
         """The ``KernelCovarianceOperator`` over the same points: 2 N^2 k flops per apply, no padded grid in memory."""
-        return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx, metric=self.metric)
+        return KernelCovarianceOperator(self.points, self.family, self.sigma, self.ell, self.nugget, ctx=self.ctx, nu=self.nu,
+                                        metric=self.metric)
 
     def sampler(self, max_growth=3, on_indefinite="raise", seed=0):
         """A ``GridFieldSampler``: exact draws m ~ N(0, C) at the cost of an apply (see the class)."""
@@ -664,21 +713,22 @@ def shard_rows(N, size, rank):
     return row0, row0 + q + (1 if rank < rem else 0)
 
 
-def kernel_cross_cov_host(targets, sources, family, sigma, ell, nugget=0.0, diag_offset=None, metric=None):
+def kernel_cross_cov_host(targets, sources, family, sigma, ell, nugget=0.0, diag_offset=None, *, nu=None, metric=None):
     """Dense host evaluation of what ``KernelCrossCovarianceOperator`` applies: the (M, N) matrix K_ij = sigma^2 phi(|t_i - s_j| / ell)
-    + nugget [j == i + diag_offset], ``family`` and ``metric`` as in ``kernel_cov_host``.  ``diag_offset`` None: no target is a source
+    + nugget [j == i + diag_offset], ``family``, ``nu`` and ``metric`` as in ``kernel_cov_host``.  ``diag_offset`` None: no target is a source
     (and the nugget must be 0).  With ``targets = points[r0:r1]``, ``sources = points`` and ``diag_offset = r0`` it is
     ``kernel_cov_host(points, ..., rows=range(r0, r1))``."""
     if family not in L.KERNEL_FAMILIES:
         raise _unknown_family(family)
     tg, src = _points_array(targets), _points_array(sources)
     _check_cross(tg, src, nugget, diag_offset)
+    nu = _check_nu(family, nu)
     G = _check_metric(metric, src.shape[1])
     tg, src = _metric_points(tg, G), _metric_points(src, G)
     d2 = np.zeros((tg.shape[0], src.shape[0]))
     for c in range(src.shape[1]):
         d2 += (tg[:, c][:, None] - src[None, :, c]) ** 2
-    K = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell)
+    K = sigma ** 2 * _kernel_phi(family, np.sqrt(d2), ell, nu)
     if nugget:
         i = np.arange(tg.shape[0])
         K[i, i + int(diag_offset)] += nugget
@@ -706,20 +756,21 @@ class KernelCrossCovarianceOperator(DeviceOperator):
     target is a source, and the nugget must be 0.  What the Nystrom extension of a KLE or of a pivoted Cholesky factor applies
     (``nystrom_extend``, ``KLEProjector.extend``, ``PivotedCholesky.extend``)."""
 
-    def __init__(self, targets, sources, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, diag_offset=None, ctx=None, metric=None):
+    def __init__(self, targets, sources, family="matern32", sigma=1.0, ell=0.1, nugget=0.0, diag_offset=None, ctx=None, *, nu=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
             raise _unknown_family(family)
+        nu = _check_nu(family, nu)
         tg, src = _points_array(targets), _points_array(sources)
         _check_cross(tg, src, nugget, diag_offset)
         G = _check_metric(metric, src.shape[1])
         super().__init__(ctx, tg.shape[0], src.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.targets, self.sources, self.metric = tg, src, G
+        self.targets, self.sources, self.metric, self.nu = tg, src, G, nu
         self.diag_offset = None if diag_offset is None else int(diag_offset)
         diag = L.KERNEL_NO_DIAGONAL if diag_offset is None else self.diag_offset
-        if family == "matern1" or G is not None:      # the family and the metric (targets and sources alike) of ``KernelCovarianceOperator``
-            spec = _kernel_spec(family, src.shape[1], self.sigma, self.ell, self.nugget, G)
-            L.call("hfmi_op_kernel_cross_cov_spec", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
+        if family == "matern1" or G is not None or nu is not None:      # family, nu and metric (targets and sources alike) of ``KernelCovarianceOperator``
+            spec = _kernel_spec(family, src.shape[1], self.sigma, self.ell, self.nugget, G, nu)
+            L.call("hfmi_op_kernel_cross_cov" + _spec_suffix(nu), self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
                    C.byref(spec), diag, C.byref(self._op))
         else:
             L.call("hfmi_op_kernel_cross_cov", self.ctx.handle, L.ptr(tg), tg.shape[0], L.ptr(src), src.shape[0], src.shape[1],
@@ -728,13 +779,14 @@ class KernelCrossCovarianceOperator(DeviceOperator):
     def to_dense(self):
         """The same matrix on the host (``kernel_cross_cov_host``)."""
         return kernel_cross_cov_host(self.targets, self.sources, self.family, self.sigma, self.ell, self.nugget, self.diag_offset,
-                                     metric=self.metric)
+                                     nu=self.nu, metric=self.metric)
 
     def transpose(self):
         """K(S, T), the operator with the two point sets swapped; only without a diagonal."""
         if self.diag_offset is not None:
             raise ValueError("transpose: only for a cross-covariance without a diagonal (diag_offset is %d)" % self.diag_offset)
-        return KernelCrossCovarianceOperator(self.sources, self.targets, self.family, self.sigma, self.ell, ctx=self.ctx, metric=self.metric)
+        return KernelCrossCovarianceOperator(self.sources, self.targets, self.family, self.sigma, self.ell, ctx=self.ctx, nu=self.nu,
+                                             metric=self.metric)
 
     def transpmult(self, x, y):
         raise NotImplementedError("KernelCrossCovarianceOperator: apply transpose() for K^T")
@@ -745,9 +797,10 @@ class KernelCovarianceRowsOperator(DeviceOperator):
     the rows of C x, bit for bit; an overwriting apply leaves the other rows +0.0, an accumulating one leaves them alone.  An empty
     range is valid.  Made by ``KernelCovarianceOperator.rows`` / ``.sharded``."""
 
-    def __init__(self, points, family, sigma, ell, nugget, row0, row1, ctx=None, metric=None):
+    def __init__(self, points, family, sigma, ell, nugget, row0, row1, ctx=None, *, nu=None, metric=None):
         if family not in L.KERNEL_FAMILIES:
             raise _unknown_family(family)
+        nu = _check_nu(family, nu)
         pts = _points_array(points)
         row0, row1 = int(row0), int(row1)
         if not 0 <= row0 <= row1 <= pts.shape[0]:
@@ -755,12 +808,12 @@ class KernelCovarianceRowsOperator(DeviceOperator):
         G = _check_metric(metric, pts.shape[1])
         super().__init__(ctx, pts.shape[0])
         self.family, self.sigma, self.ell, self.nugget = family, float(sigma), float(ell), float(nugget)
-        self.points, self.row0, self.row1, self.metric = pts, row0, row1, G
+        self.points, self.row0, self.row1, self.metric, self.nu = pts, row0, row1, G, nu
         self.collective = None
         self._hook = self._hook_error = None
-        if family == "matern1" or G is not None:
-            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G)
-            L.call("hfmi_op_kernel_cov_rows_spec", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), row0, row1 - row0,
+        if family == "matern1" or G is not None or nu is not None:
+            spec = _kernel_spec(family, pts.shape[1], self.sigma, self.ell, self.nugget, G, nu)
+            L.call("hfmi_op_kernel_cov_rows" + _spec_suffix(nu), self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], C.byref(spec), row0, row1 - row0,
                    C.byref(self._op))
         else:
             L.call("hfmi_op_kernel_cov_rows", self.ctx.handle, L.ptr(pts), pts.shape[0], pts.shape[1], L.KERNEL_FAMILIES[family],
@@ -771,7 +824,7 @@ class KernelCovarianceRowsOperator(DeviceOperator):
         out = np.zeros((self.points.shape[0],) * 2)
         if self.row1 > self.row0:
             out[self.row0:self.row1] = kernel_cov_host(self.points, self.family, self.sigma, self.ell, self.nugget,
-                                                       rows=np.arange(self.row0, self.row1), metric=self.metric)
+                                                       rows=np.arange(self.row0, self.row1), nu=self.nu, metric=self.metric)
         return out
 
     def _attach_sum(self, collective):
@@ -864,6 +917,35 @@ def bilaplacian_kernel_2d(gamma, delta, theta0=2.0, theta1=0.5, alpha=np.pi / 4)
     det = Theta[0, 0] * Theta[1, 1] - Theta[0, 1] * Theta[1, 0]
     inv = np.array([[Theta[1, 1], -Theta[0, 1]], [-Theta[1, 0], Theta[0, 0]]]) / det
     return dict(family="matern1", sigma=1.0 / np.sqrt(4.0 * np.pi * delta * gamma * np.sqrt(det)), ell=np.sqrt(2.0 * gamma / delta), metric=inv)
+
+
+def whittle_matern_kernel(gamma, delta, alpha, d, Theta=None):
+    """The kernel of the precision (delta - gamma div Theta grad)^alpha in d dimensions, in FREE SPACE, as keyword arguments of the
+    kernel covariance operators: the Matern field of smoothness nu = alpha - d/2,
+
+        c(x) = sigma^2 2^(1-nu) / Gamma(nu) (kappa r)^nu K_nu(kappa r),   r^2 = x^T Theta^-1 x,   kappa^2 = delta / gamma,
+        sigma^2 = Gamma(nu) / (Gamma(alpha) (4 pi)^(d/2) kappa^(2 nu) gamma^alpha sqrt(det Theta)),
+
+    that is ``family="matern"`` with that ``nu``, ``ell = sqrt(2 nu gamma / delta)`` (so that a = sqrt(2 nu) r / ell = kappa r) and
+    ``metric = inv(Theta)``.  ``alpha`` need not be an integer; nu must lie in [1/8, 8] (ValueError otherwise).  ``Theta``: a symmetric
+    positive definite d x d matrix, None for the identity.  Splat the result:
+    ``GridKernelCovarianceOperator(shape, spacing, **whittle_matern_kernel(gamma, delta, 3, 2))``.  For alpha = 2, d = 2 these are the
+    numbers of ``bilaplacian_kernel_2d``, which stays the fast way to that kernel (``"matern1"``).  What is NOT in it: the boundary.
+    A finite-element prior on a bounded mesh has Robin or Neumann conditions that raise the variance near the boundary and bend the
+    correlations there; this is the kernel of the interior, away from it by a few correlation lengths."""
+    from scipy.special import gamma as gamma_fn
+    gamma, delta, alpha, d = float(gamma), float(delta), float(alpha), int(d)
+    if not (gamma > 0.0 and delta > 0.0 and np.isfinite(gamma) and np.isfinite(delta)):
+        raise ValueError("whittle_matern_kernel: gamma and delta must be positive and finite")
+    if d not in (1, 2, 3):
+        raise ValueError("whittle_matern_kernel: d is 1, 2 or 3, got %r" % (d,))
+    nu = alpha - 0.5 * d
+    if not (np.isfinite(nu) and L.MATERN_NU_MIN <= nu <= L.MATERN_NU_MAX):
+        raise ValueError("whittle_matern_kernel: nu = alpha - d/2 = %r does not lie in [%g, %g]" % (nu, L.MATERN_NU_MIN, L.MATERN_NU_MAX))
+    Th = _check_metric(np.eye(d) if Theta is None else Theta, d)
+    kappa2 = delta / gamma
+    var = gamma_fn(nu) / (gamma_fn(alpha) * (4.0 * np.pi) ** (0.5 * d) * kappa2 ** nu * gamma ** alpha * np.sqrt(np.linalg.det(Th)))
+    return dict(family="matern", sigma=np.sqrt(var), ell=np.sqrt(2.0 * nu * gamma / delta), nu=nu, metric=np.linalg.inv(Th))
 
 
 class _Csr:

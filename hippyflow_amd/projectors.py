@@ -744,7 +744,7 @@ class KLEProjector:
         if self._kle_encoder is None or self.d_KLE is None:
             raise ValueError("extend: call construct_input_subspace('mass' | 'identity') first")
         cross = KernelCrossCovarianceOperator(points, self.C.points, self.C.family, self.C.sigma, self.C.ell, ctx=self.ctx,
-                                              metric=self.C.metric)
+                                              nu=getattr(self.C, "nu", None), metric=self.C.metric)
         return nystrom_extend(cross, self._kle_encoder, self.d_KLE)
 
     def _Msolver(self):

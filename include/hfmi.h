@@ -174,6 +174,7 @@ HFMI_API int hfmi_op_dense_sym(hfmi_ctx* ctx, const hfmi_block* C, hfmi_op** out
 #define HFMI_KERNEL_MATERN52 2
 #define HFMI_KERNEL_SQEXP 3
 #define HFMI_KERNEL_MATERN1 4 /* a K_1(a), a = sqrt(2) r: only through a hfmi_kernel_spec (below); the creators with a bare family refuse it */
+#define HFMI_KERNEL_MATERN 5  /* Matern of any smoothness nu: only through a hfmi_kernel_spec2 (below); every other creator refuses it */
 HFMI_API int hfmi_op_kernel_cov(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, int family, double sigma, double ell,
                        double nugget, hfmi_op** out);
 /*     the rectangular cross-covariance between two point sets, by the same kernel: K_ij = sigma^2 phi(|t_i - s_j| / ell)
@@ -335,6 +336,43 @@ HFMI_API int hfmi_op_kernel_cov_grid_long(hfmi_ctx* ctx, int d, const int64_t* n
 HFMI_API int hfmi_grid_sampler_create_long(hfmi_op* grid_cov_long_op, int max_growth /* 0..6 */, int clip /* 0 | 1 */, hfmi_grid_sampler** out);
 HFMI_API int hfmi_fftcov_long_plan_predict(int kind, int d, const int64_t* n, int growth, int max_line, int nvec, int64_t budget_bytes,
                                            int64_t* words);
+/*     The Matern family of ANY smoothness, HFMI_KERNEL_MATERN, through a second descriptor that carries nu:
+ *       phi_nu(a) = 2^(1-nu) / Gamma(nu) a^nu K_nu(a),  a = sqrt(2 nu) r / ell,  phi_nu(0) = 1,  HFMI_MATERN_NU_MIN <= nu <= HFMI_MATERN_NU_MAX
+ *     -- the convention of the named families (a = r, sqrt(3) r, sqrt(5) r, sqrt(2) r for nu = 1/2, 3/2, 5/2, 1).  The precision
+ *     (delta - gamma div Theta grad)^alpha in d dimensions has this covariance with nu = alpha - d/2.  K_nu is evaluated on the device
+ *     (csrc/hfmi_kcov_nu.h): with n = floor(nu + 1/2), mu = nu - n, Temme's series for K_mu, K_(mu+1) up to a = 2 and Chebyshev
+ *     interpolants of sqrt(a) e^a K in 2 / a beyond, then the recurrence in the order on scaled quantities.  Everything that depends on
+ *     nu is computed once on the host at creation (hfmi_kernel_matern_tables, long double) and kept by the operator on the device.
+ *     There is NO silent dispatch: nu = 1.5 through this family runs the general evaluation, 2.3 times the cost of Matern-1 per entry (measured at nu = 1.25),
+ *     and agrees with HFMI_KERNEL_MATERN32 to rounding; the named families stay the fast ones.  a = 0 gives exactly 1, a large a +0.
+ *       hfmi_kernel_spec2 is hfmi_kernel_spec with nu appended; families 0..5; nu is read only for HFMI_KERNEL_MATERN and must be 0
+ *     otherwise.  Each creator below has the argument list of its predecessor with the descriptor type exchanged, and with families 0..4
+ *     gives the operator its predecessor gives (same kernels, same bits).  hfmi_pchol_create, hfmi_grid_sampler_create[_long] and
+ *     hfmi_op_grid_factor take such operators and pick nu and the tables up from them (the sampler keeps copies of its own).
+ *     HFMI_ERR_INVALID: what the predecessor answers, with family up to HFMI_KERNEL_MATERN allowed; nu not finite or outside the range
+ *     with HFMI_KERNEL_MATERN, nu != 0 with another family.
+ *       hfmi_kernel_matern_tables: the table words of one nu, on the host, no context and no device (layout: csrc/hfmi_matern_tables.hip).
+ *     HFMI_ERR_INVALID for a null pointer and for nu not finite or outside the range. */
+#define HFMI_MATERN_NU_MIN 0.125
+#define HFMI_MATERN_NU_MAX 8.0
+#define HFMI_MATERN_TABLE_WORDS 162
+typedef struct hfmi_kernel_spec2 {
+  int family; /* HFMI_KERNEL_*, MATERN included */
+  int d;
+  double sigma, ell, nugget;
+  double metric[9]; /* row-major d x d; all zeros = identity */
+  double nu;        /* the smoothness of HFMI_KERNEL_MATERN; 0 with every other family */
+} hfmi_kernel_spec2;
+HFMI_API int hfmi_op_kernel_cov_spec2(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec2* spec, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cross_cov_spec2(hfmi_ctx* ctx, const double* host_targets, int64_t M, const double* host_sources, int64_t N, int d,
+                                            const hfmi_kernel_spec2* spec, int64_t diag_offset, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_rows_spec2(hfmi_ctx* ctx, const double* host_points, int64_t N, int d, const hfmi_kernel_spec2* spec, int64_t row0,
+                                           int64_t nrows, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_grid_spec2(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
+                                           const int64_t* host_nodes_or_null, int64_t N, const hfmi_kernel_spec2* spec, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_grid_long_spec2(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
+                                                const int64_t* host_nodes_or_null, int64_t N, const hfmi_kernel_spec2* spec, hfmi_op** out);
+HFMI_API int hfmi_kernel_matern_tables(double nu, double* words /* HFMI_MATERN_TABLE_WORDS */);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
