@@ -13,7 +13,8 @@ from .hostvec import ADJOINT, CONTROL, PARAMETER, STATE, HostMultiVector, HostVe
 from .multivector import (MatMvMult, MatMvTranspmult, MultiVector, MvDSmatMult, Vector, dense_to_mv_local, ingest_stream, mv_to_dense,
                           mv_to_dense_local)
 from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
-                        GridCovarianceFactor, GridFieldSampler, GridKernelCovarianceOperator, GridKernelPrior, grid_node_points, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
+                        GridCovarianceFactor, GridFieldSampler, GridInterpolationOperator, GridKernelCovarianceOperator, GridKernelPrior, grid_node_points,
+                        InterpolatedFieldSampler, InterpolatedKernelCovarianceOperator, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
                         kernel_cross_cov_host, nystrom_extend, shard_rows, anisotropy_2d, bilaplacian_kernel_2d, whittle_matern_kernel,
                         LowRankOperator, LowRankRectangularOperator, MassPreconditionedCovarianceOperator,
                         JJT, JTJ, Jacobian, MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableControlJacobian,

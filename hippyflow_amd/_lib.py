@@ -126,6 +126,12 @@ SIGNATURES = {
     "hfmi_op_kernel_cov_grid_long": [_P, C.c_int, _P, _P, _P, C.c_int64, _SPEC, _PP],
     "hfmi_grid_sampler_create_long": [_P, C.c_int, C.c_int, _PP],
     "hfmi_fftcov_long_plan_predict": [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
+    "hfmi_grid_interp_weights": [C.c_int, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P],
+    "hfmi_op_grid_interp": [_P, C.c_int, _P, _P, _P, _P, C.c_int64, C.c_int, _PP],
+    "hfmi_op_kernel_cov_interp": [_P, _P, _P, C.c_int64, C.c_double, C.c_int, _PP],
+    "hfmi_op_kernel_cov_interp_info": [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    "hfmi_op_kernel_cov_interp_diag": [_P, _P, _P],
+    "hfmi_interp_sampler_draw": [_P, _P, _P, C.c_uint64, C.c_int64, C.c_int],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

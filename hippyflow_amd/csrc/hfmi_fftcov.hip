@@ -422,6 +422,14 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_fftcov_split_draw(fftcov
   fftcov_pass_body<true, false, true>(A, G, S);
 }
 
+// |offset|^2 of an isotropic kernel without a metric from the per-axis distances, for the stencil table (k_fftcov_offsets): the
+// arithmetic of the even column below, statement for statement (that kernel keeps its own text, and with it its device code)
+__device__ __forceinline__ double fc_even_r2(int d, double dx, double dy, double dz) {
+  double r2 = dx * dx;
+  if (d > 1) r2 = fma(dy, dy, r2);
+  if (d > 2) r2 = fma(dz, dz, r2);
+  return r2;
+}
 // the circulant's first column of an isotropic kernel of the four first families: entry (j0, j1, j2) is the kernel at the offsets
 // min(j_c, P_c - j_c) h_c, the nugget on entry 0
 __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* buf, int64_t total, int l0, int l1, int P0, int P1, int P2,
@@ -452,6 +460,24 @@ __global__ __launch_bounds__(256) void k_fftcov_column(kcov_params K, double2* b
 struct fftcov_metric_args {
   double l00, l10, l11, l20, l21, l22;   // the lower factor, identity when there is no metric
 };
+// r^2 = |L^T u|^2 of the signed offset u = diag(h) o for the stencil table (k_fftcov_offsets): the arithmetic stated above and written
+// out in the signed column below, statement for statement (that kernel keeps its own text, and with it its device code)
+__device__ __forceinline__ double fc_metric_r2(int d, const fftcov_metric_args& G, double u0, double u1, double u2) {
+  double w0 = G.l00 * u0, w1 = 0.0, w2 = 0.0;
+  if (d > 1) {
+    w0 = fma(G.l10, u1, w0);
+    w1 = G.l11 * u1;
+  }
+  if (d > 2) {
+    w0 = fma(G.l20, u2, w0);
+    w1 = fma(G.l21, u2, w1);
+    w2 = G.l22 * u2;
+  }
+  double r2 = w0 * w0;
+  if (d > 1) r2 = fma(w1, w1, r2);
+  if (d > 2) r2 = fma(w2, w2, r2);
+  return r2;
+}
 template <class PT>
 __global__ __launch_bounds__(256) void k_fftcov_column_signed(PT K, fftcov_metric_args G, double2* buf, int64_t total, int l0, int l1, int P0,
                                                               int P1, int P2, double h0, double h1, double h2) {
@@ -498,6 +524,19 @@ __global__ __launch_bounds__(256) void k_fftcov_spectrum(const double2* buf, dou
 __global__ __launch_bounds__(256) void k_fftcov_root(const double* lambda, double* root, int64_t total, double P) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
     root[e] = sqrt(fmax(lambda[e], 0.0) / P);
+}
+
+// The kernel at the signed lattice offsets o in [-3, 3]^d (hfmi_op_kernel_cov_interp's diagonal): entry (o0 + 3) + 7 ((o1 + 3) + 7 (o2 + 3))
+// is what the first column holds for that offset -- the column kernels' distance arithmetic (fc_even_r2 of |o_c| h_c, SIGNED = false: the
+// even column's families without a metric; fc_metric_r2 of o_c h_c otherwise) and the same kcov_entry -- and no nugget.
+template <class PT, bool SIGNED>
+__global__ __launch_bounds__(256) void k_fftcov_offsets(PT K, fftcov_metric_args G, double* table, int total, double h0, double h1, double h2) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int o0 = e % 7 - 3, o1 = K.d > 1 ? (e / 7) % 7 - 3 : 0, o2 = K.d > 2 ? e / 49 - 3 : 0;
+  const double r2 = SIGNED ? fc_metric_r2(K.d, G, (double)o0 * h0, (double)o1 * h1, (double)o2 * h2)
+                           : fc_even_r2(K.d, (double)abs(o0) * h0, (double)abs(o1) * h1, (double)abs(o2) * h2);
+  table[e] = kcov_entry(K, r2, false);
 }
 
 // gen: the pass's load is generated (FFTCOV_GEN, the first pass of a draw); null for every pass that loads.  table: what the fused
@@ -589,6 +628,47 @@ static int fftcov_long_check(const fftcov_state* st, const int* kinds, int nkind
 int64_t fftcov_points(const fftcov_state* st) { return st->N; }
 
 void fftcov_destroy(fftcov_state* st) { delete st; }
+
+void fftcov_describe(const fftcov_state* st, fftcov_grid_desc* out) {
+  out->d = st->d;
+  for (int c = 0; c < 3; ++c) out->n[c] = st->n[c], out->h[c] = st->h[c];
+  out->sigma = st->sigma, out->nugget = st->nugget;
+  out->all_nodes = !st->inv && st->N == st->nnodes;
+  out->long_route = st->long_route;
+}
+
+bool fftcov_same_covariance(const fftcov_state* a, const fftcov_state* b) {
+  bool same = a->d == b->d && a->N == b->N && a->nnodes == b->nnodes && !a->inv == !b->inv && a->family == b->family && a->sigma == b->sigma &&
+              a->ell == b->ell && a->nugget == b->nugget && a->has_metric == b->has_metric && a->nu == b->nu;
+  for (int c = 0; c < 3; ++c) same = same && a->n[c] == b->n[c] && a->h[c] == b->h[c];
+  for (int c = 0; c < 9; ++c) same = same && a->mL[c] == b->mL[c];
+  return same;
+}
+
+int fftcov_offset_table(hfmi_ctx* ctx, const fftcov_state* st, double* table) {
+  const int total = st->d == 1 ? 7 : st->d == 2 ? 49 : 343;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const fftcov_metric_args G{st->mL[0], st->mL[3], st->mL[4], st->mL[6], st->mL[7], st->mL[8]};
+  // the family dispatch of fftcov_create_device's column
+  if (st->family == HFMI_KERNEL_MATERN) {
+    kcov_nu_params K;
+    HFMI_TRY(kcov_nu_params_init_as(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, 0.0, kcov_nu_ref{st->nu, st->nuca, st->nutab}));
+    hipLaunchKernelGGL((k_fftcov_offsets<kcov_nu_params, true>), grid, block, 0, ctx->stream, K, G, table, total, st->h[0], st->h[1], st->h[2]);
+  } else if (st->family == HFMI_KERNEL_MATERN1) {
+    kcov_k1_params K;
+    HFMI_TRY(kcov_params_init_as(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, 0.0));
+    hipLaunchKernelGGL((k_fftcov_offsets<kcov_k1_params, true>), grid, block, 0, ctx->stream, K, G, table, total, st->h[0], st->h[1], st->h[2]);
+  } else {
+    kcov_params K;
+    HFMI_TRY(kcov_params_init(&K, st->lambda, 1, st->d, st->family, st->sigma, st->ell, 0.0));
+    if (st->has_metric)
+      hipLaunchKernelGGL((k_fftcov_offsets<kcov_params, true>), grid, block, 0, ctx->stream, K, G, table, total, st->h[0], st->h[1], st->h[2]);
+    else
+      hipLaunchKernelGGL((k_fftcov_offsets<kcov_params, false>), grid, block, 0, ctx->stream, K, G, table, total, st->h[0], st->h[1], st->h[2]);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFMI_OK;
+}
 
 // inv: the node map's inverse, on the host, or on the device (inv_on_device: a sampler copies its operator's)
 static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* inv, bool inv_on_device = false) {
@@ -820,6 +900,8 @@ struct hfmi_grid_sampler {
   int64_t n_clipped = 0;
   double cov_error_bound = 0.0;
 };
+const fftcov_state* grid_sampler_state(const hfmi_grid_sampler* s) { return s->st.get(); }
+hfmi_ctx* grid_sampler_ctx(const hfmi_grid_sampler* s) { return s->ctx; }
 
 // the state of the operator's grid at one growth, its spectrum and the extremes of that
 // max_line > 0: the long route's embedding and passes (hfmi_grid_sampler_create_long)

@@ -229,7 +229,8 @@ struct kcov_nu_ref {
   const double* tab = nullptr;    // the table words on the device (hfmi_kcov_nu.h)
 };
 struct fftcov_state;
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR };
+struct interp_state;
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR, OP_GRID_INTERP, OP_KERNEL_COV_INTERP };
 
 struct hfmi_op {
   ~hfmi_op();              // waits for the stream when the operator owns device memory (hfmi_op.hip)
@@ -266,6 +267,12 @@ struct hfmi_op {
   // OP_GRID_FACTOR: the state of the sampler the factor was made from, shared with it (hfmi_op_grid_factor); 0: S, 1: S^T
   std::shared_ptr<fftcov_state> fac;
   int fac_transpose = 0;
+  // OP_GRID_INTERP: W (ip_transpose 0: length prod n -> N) or W^T (1) of a sparse cubic interpolation from grid nodes to points;
+  // OP_KERNEL_COV_INTERP: K = W Cg W^T + diag(delta) with Cg = ip_grid (a grid covariance, not owned: hfmi_op_compose3's rule).  The
+  // state (binned weights, delta, the work block) is owned (hfmi_interp.hip)
+  interp_state* ip = nullptr;
+  int ip_transpose = 0;
+  hfmi_op* ip_grid = nullptr;
   hfmi_host_apply_fn host_fn = nullptr;
   void* host_user = nullptr;
   int64_t host_N = 0;
@@ -342,6 +349,29 @@ int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, 
 void fftcov_destroy(fftcov_state* st);
 // Y (+)= S W (transpose 0: length prod P_c -> N) or S^T W (1: N -> prod P_c), the factor of a sampler's embedding; checks the lengths
 int fftcov_factor_apply(hfmi_ctx* ctx, fftcov_state* st, int transpose, const hfmi_block* W, hfmi_block* Y, int accumulate);
+
+// what hfmi_interp.hip needs to know of a grid covariance and of a sampler (hfmi_fftcov.hip)
+struct fftcov_grid_desc {
+  int d;
+  int64_t n[3];
+  double h[3];
+  double sigma, nugget;
+  bool all_nodes;      // no node map: point g is node g
+  bool long_route;
+};
+void fftcov_describe(const fftcov_state* st, fftcov_grid_desc* out);
+// grid, node map or none, kernel, metric and smoothness agree (an operator and a sampler made from it)
+bool fftcov_same_covariance(const fftcov_state* a, const fftcov_state* b);
+// table[(o0 + 3) + 7 ((o1 + 3) + 7 (o2 + 3))] (device, 7^d doubles) = the kernel at the signed lattice offset o, nugget left out, by
+// the code that fills the circulant's first column; queued on the context's stream
+int fftcov_offset_table(hfmi_ctx* ctx, const fftcov_state* st, double* table);
+const fftcov_state* grid_sampler_state(const hfmi_grid_sampler* s);
+hfmi_ctx* grid_sampler_ctx(const hfmi_grid_sampler* s);
+// Interpolation between grid nodes and scattered points (hfmi_interp.hip; rules: hfmi_interp_plan.h).  apply: Y (+)= W X, W^T X
+// or K X by the operator's kind; destroy deletes the state (the caller synchronised)
+int interp_apply(hfmi_op* op, const hfmi_block* X, hfmi_block* Y, int accumulate);
+void interp_destroy(interp_state* st);
+int64_t interp_range_len(const hfmi_op* op);   // OP_GRID_INTERP: N for W, prod n for W^T
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

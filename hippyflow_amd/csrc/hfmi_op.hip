@@ -446,8 +446,9 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
   return HFMI_OK;
 }
 hfmi_op::~hfmi_op() {
-  if (gamma_inv || weights || kc_x || kc_t || kc_nutab || fc || fac) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
+  if (gamma_inv || weights || kc_x || kc_t || kc_nutab || fc || fac || ip) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
   fftcov_destroy(fc);
+  interp_destroy(ip);
 }
 extern "C" int hfmi_op_destroy(hfmi_op* op) {
   delete op;
@@ -555,6 +556,17 @@ static int panel_reduce_hook(void* user, double* Y, int64_t ldy, int r, int64_t 
   return HFMI_OK;
 }
 
+// the length of op's results on inputs of length in_len, for the kinds that can be rectangular and say so; in_len otherwise
+static int64_t op_range_len(const hfmi_op* op, int64_t in_len) {
+  switch (op->kind) {
+    case OP_GRID_INTERP: return interp_range_len(op);
+    case OP_CSR: return op->csr->nrows;
+    case OP_KERNEL_CROSS: return op->kc_slab ? in_len : op->kc_M;
+    case OP_COMPOSE3: return op_range_len(op->c, op_range_len(op->b, op_range_len(op->a, in_len)));
+    default: return in_len;
+  }
+}
+
 static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double beta) {
   hfmi_ctx* ctx = op->ctx;
   const int k = W->nvec;
@@ -654,6 +666,10 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
     case OP_GRID_FACTOR:
       // Y (+)= S W or S^T W: the last pass adds into Y itself
       return fftcov_factor_apply(ctx, op->fac.get(), op->fac_transpose, W, Y, beta != 0.0);
+    case OP_GRID_INTERP:
+    case OP_KERNEL_COV_INTERP:
+      // Y (+)= W X, W^T X or K X: the last kernel adds into Y itself
+      return interp_apply(op, W, Y, beta != 0.0);
     case OP_KERNEL_CROSS: {
       const int64_t N = op->kc_N, M = op->kc_M;
       const int acc = beta != 0.0;
@@ -700,11 +716,14 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
       } guard{ctx};
       ++ctx->compose_depth;
       hfmi_block v1, v2;
-      HFMI_TRY(ctx_tmp_view(ctx, tmp_compose_slot(depth), W->N, k, &v1));
-      HFMI_TRY(ctx_tmp_view(ctx, tmp_compose_slot(depth) + 1, W->N, k, &v2));
+      // the temporaries take the length a part is known to map to (op_range_len: the input's length for every square kind)
+      const int64_t n1 = op_range_len(op->a, W->N), n2 = op_range_len(op->b, n1);
+      HFMI_TRY(ctx_tmp_view(ctx, tmp_compose_slot(depth), n1, k, &v1));
+      HFMI_TRY(ctx_tmp_view(ctx, tmp_compose_slot(depth) + 1, n2, k, &v2));
       HFMI_TRY(hfmi_op_apply(op->a, W, &v1, 0));
       HFMI_TRY(hfmi_op_apply(op->b, &v1, &v2, 0));
       if (beta == 0.0) return hfmi_op_apply(op->c, &v2, Y, 0);
+      if (v1.N != Y->N) HFMI_TRY(ctx_tmp_view(ctx, tmp_compose_slot(depth), Y->N, k, &v1));   // a rectangular chain: v1 has been consumed
       return accumulate(v1, [&](hfmi_block* D) { return hfmi_op_apply(op->c, &v2, D, 0); });
     }
     case OP_HOST: {

@@ -373,6 +373,59 @@ HFMI_API int hfmi_op_kernel_cov_grid_spec2(hfmi_ctx* ctx, int d, const int64_t* 
 HFMI_API int hfmi_op_kernel_cov_grid_long_spec2(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */,
                                                 const int64_t* host_nodes_or_null, int64_t N, const hfmi_kernel_spec2* spec, hfmi_op** out);
 HFMI_API int hfmi_kernel_matern_tables(double nu, double* words /* HFMI_MATERN_TABLE_WORDS */);
+/*     SCATTERED points on the FFT route, by structured kernel interpolation:  K = W Cg W^T + diag(delta).  Cg is the matrix of a grid
+ *     covariance above over ALL nodes of its grid with nugget 0, W (N x prod n) a sparse cubic interpolation from the grid's nodes to N
+ *     points.  K is symmetric positive semidefinite whatever the interpolation error, an apply costs O(4^d N + P log P), a draw is
+ *     W z + sqrt(delta) eta with z an exact grid draw.  K is an APPROXIMATION of the covariance C over the points, unlike every other
+ *     operator of this family; the library is held to K as defined here at rounding level, and K - C is a property of the kernel and of
+ *     ell / h (figures: docs/measurements.md; rough kernels such as HFMI_KERNEL_MATERN12 stay the domain of the exact routes).
+ *       Grid: d = 1, 2 or 3 axes of n[c] >= 4 nodes, spacing h[c] > 0, origin[c]; axis 0 fastest.  Per axis of a point x:
+ *     u = (x - origin) / h in double, 1 <= u <= n - 2 required; c = min(floor(u), n - 3), t = u - c; the weights on nodes c - 1 .. c + 2
+ *     are Keys' cubic convolution (a = -1/2),  w0 = ((2 - t) t - 1) t / 2,  w1 = ((3 t - 5) t t + 2) / 2,  w2 = ((4 - 3 t) t + 1) t / 2,
+ *     w3 = (t - 1) t t / 2, evaluated in these forms on the HOST at creation (csrc/hfmi_interp_plan.h) and uploaded: the device never
+ *     recomputes a weight.  Row i of W holds the 4^d tensor products; its sum is 1, polynomials up to degree 2 are reproduced.
+ *       hfmi_grid_interp_weights: those rules without a context or a device.  base[N]: the node of the stencil corner (c_a - 1)_a;
+ *     w[N * d * 4]: w[(i d + a) 4 + s]; optionally the cell binning the spread walks: the stencil base cells form an (n0 - 3) x ... array,
+ *     linear index axis 0 fastest; cell_start[prod (n - 3) + 1] and perm[N] list the points of cell q as perm[cell_start[q] ..
+ *     cell_start[q + 1] - 1], ascending in point index.  Either of the two may be NULL.
+ *       hfmi_op_grid_interp: W (transpose = 0: blocks of length prod n -> blocks of length N, a gather) or W^T (transpose = 1, a
+ *     spread) through hfmi_op_apply.  Stencil order of the gather: s2 outermost, s0 innermost, weight (w2 w1) w0, one fused multiply-add
+ *     per node.  The spread has NO atomics: a grid node receives from the at most 4^d cells q with q_a in g_a - 3 .. g_a, visited in
+ *     ascending linear index, the points of a cell in ascending index; that order is part of the contract, so the result depends on no
+ *     launch shape and two applies are bit-identical.  The device keeps 4 d doubles and two indices per point (a CSR image of W holds
+ *     4^d values and indices per point and orientation).  Heavily clustered points unbalance the spread; that is accepted.
+ *       hfmi_op_kernel_cov_interp: K as ONE operator over the grid operator's grid: one spread, the grid operator's apply, one gather
+ *     with + delta_i X_ij fused, through an internal work block of prod n rows that takes an even number of columns per chunk (512 MiB,
+ *     or 2 "fftcov_pairs" columns): the grid apply pairs the columns as in one call, so no chunking changes a bit.
+ *     q_i = (W Cg W^T)_ii = sum over stencil pairs of w_s w_s' c(s - s'), c(.) the kernel at the signed lattice offsets in [-3, 3]^d
+ *     evaluated by the code that fills the circulant's first column, summed once at creation on the device through the per-axis
+ *     autocorrelations of the weights (csrc/hfmi_interp_plan.h).  delta_i = nugget + max(sigma^2 - q_i, 0) with diag_correction = 1,
+ *     delta_i = nugget with 0: with the correction K_ii = sigma^2 + nugget wherever nothing was clipped.  hfmi_op_kernel_cov_interp_info:
+ *     the extremes of sigma^2 - q_i and how many were below zero; hfmi_op_kernel_cov_interp_diag: q and delta themselves, N doubles each
+ *     in point order (either pointer may be NULL).  LIFETIME as hfmi_op_compose3's parts: the grid operator is referred to, not owned
+ *     or copied, and must outlive this operator; the weights, delta and the work block are this operator's own.
+ *       hfmi_interp_sampler_draw: column j of Y (+)= draw first_sample + j,  W z + sqrt(delta) eta:  z is that draw of
+ *     hfmi_grid_sampler_draw(grid_sampler, ., seed, .) -- the sampler must have been made from the grid operator -- and eta the probe
+ *     draw's Philox / Box-Muller (hfmi_randn_fill's element map) with key seed ^ 0x9E3779B97F4A7C15, stream 0 and vector index
+ *     first_sample + j (the draw's number, not the column's position).  The key is not the grid noise's, so eta and z are independent.
+ *     first_sample even, as for the grid sampler; chunks first_sample = 0, n, 2 n, ... (n even) reproduce one large call bit for bit.
+ *     Y is const as a HANDLE, as in hfmi_grid_sampler_draw.  Block storage contract as every operator: padding rows untouched,
+ *     accumulate adds, views stay in bounds (tests/test_gpu_grid_interp.py).
+ *     HFMI_ERR_INVALID: d outside 1..3, n[c] < 4 or > 2^23, more than 2^40 nodes, h[c] <= 0 or not finite, origin not finite, N < 1, a point
+ *     that is not finite or has u outside [1, n - 2] (the message names the point and the axis), transpose or diag_correction outside
+ *     0 / 1; a grid operator that is no grid covariance, has a node map or a nugget; a negative nugget; a sampler of another covariance;
+ *     first_sample odd, negative or past the 2^32 draws of a seed; at apply, blocks of another length. */
+HFMI_API int hfmi_grid_interp_weights(int d, const int64_t* n /* d */, const double* h /* d */, const double* origin /* d */,
+                                      const double* host_points /* N x d */, int64_t N, int64_t* base /* N */, double* w /* N d 4 */,
+                                      int64_t* cell_start_or_null, int64_t* perm_or_null);
+HFMI_API int hfmi_op_grid_interp(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */, const double* origin /* d */,
+                                 const double* host_points /* N x d */, int64_t N, int transpose /* 0: W | 1: W^T */, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_interp(hfmi_op* grid_cov_op, const double* origin /* d */, const double* host_points /* N x d */, int64_t N,
+                                       double nugget, int diag_correction /* 0 | 1 */, hfmi_op** out);
+HFMI_API int hfmi_op_kernel_cov_interp_info(const hfmi_op* op, double* diag_min, double* diag_max, int64_t* n_diag_clipped);
+HFMI_API int hfmi_op_kernel_cov_interp_diag(const hfmi_op* op, double* host_q_or_null /* N */, double* host_delta_or_null /* N */);
+HFMI_API int hfmi_interp_sampler_draw(hfmi_op* op, hfmi_grid_sampler* grid_sampler, const hfmi_block* Y, uint64_t seed,
+                                      int64_t first_sample /* even */, int accumulate);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
