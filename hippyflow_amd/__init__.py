@@ -14,7 +14,7 @@ from .multivector import (MatMvMult, MatMvTranspmult, MultiVector, MvDSmatMult, 
                           mv_to_dense_local)
 from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
                         GridCovarianceFactor, GridFieldSampler, GridInterpolationOperator, GridKernelCovarianceOperator, GridKernelPrior, grid_node_points,
-                        InterpolatedFieldSampler, InterpolatedKernelCovarianceOperator, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
+                        InterpolatedCovarianceFactor, InterpolatedFieldSampler, InterpolatedKernelCovarianceOperator, InterpolatedKernelPrior, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
                         kernel_cross_cov_host, nystrom_extend, shard_rows, anisotropy_2d, bilaplacian_kernel_2d, whittle_matern_kernel,
                         LowRankOperator, LowRankRectangularOperator, MassPreconditionedCovarianceOperator,
                         JJT, JTJ, Jacobian, MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableControlJacobian,

@@ -132,6 +132,7 @@ SIGNATURES = {
     "hfmi_op_kernel_cov_interp_info": [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)],
     "hfmi_op_kernel_cov_interp_diag": [_P, _P, _P],
     "hfmi_interp_sampler_draw": [_P, _P, _P, C.c_uint64, C.c_int64, C.c_int],
+    "hfmi_op_interp_factor": [_P, _P, C.c_int, _PP],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

@@ -1045,27 +1045,35 @@ extern "C" int hfmi_grid_sampler_destroy(hfmi_grid_sampler* s) {
 // The rules and the pass lists are in hfmi_fftcov_plan.h.  A factor operator shares the sampler's state (grid, node map, twiddles,
 // Lambda, work buffer) and adds the root table to it, once, at the first factor of a sampler: Lambda itself is never written, so the
 // sampler's draws are what they were.  Whoever goes last, sampler or operator, deletes the state.
+// the root table of a sampler's state, made the first time a factor of it is asked for (hfmi_op_grid_factor, hfmi_op_interp_factor)
+int grid_sampler_root(hfmi_grid_sampler* s, const char* who) {
+  hfmi_ctx* ctx = s->ctx;
+  fftcov_state* st = s->st.get();
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (st->root) return HFMI_OK;
+  const int64_t total = st->plan.Ptot;
+  dev_buf<double> root;
+  const hipError_t e = (hipError_t)root.alloc((size_t)total);
+  if (e != hipSuccess)
+    HFMI_FAIL(HFMI_ERR_HIP, "%s: the root table of the embedding %d x %d x %d needs %lld bytes: %s", who, st->plan.P[0], st->plan.P[1],
+              st->plan.P[2], (long long)(total * 8), hipGetErrorString(e));
+  const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cus * 8);
+  hipLaunchKernelGGL(k_fftcov_root, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, st->lambda.get(), root.get(), total, (double)total);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(ctx->stream);   // whatever happened: `root` must not go while a kernel may write it
+  HIP_TRY(launched);
+  HIP_TRY(done);
+  st->root = std::move(root);
+  return HFMI_OK;
+}
+std::shared_ptr<fftcov_state> grid_sampler_share(hfmi_grid_sampler* s) { return s->st; }
+int64_t fftcov_padded_len(const fftcov_state* st) { return st->plan.Ptot; }
+
 extern "C" int hfmi_op_grid_factor(hfmi_grid_sampler* s, int transpose, hfmi_op** out) {
   if (!s || !out) HFMI_FAIL(HFMI_ERR_INVALID, "null argument");
   if (transpose != 0 && transpose != 1) HFMI_FAIL(HFMI_ERR_INVALID, "grid_factor: transpose = %d is not 0 (S) or 1 (S^T)", transpose);
   hfmi_ctx* ctx = s->ctx;
-  fftcov_state* st = s->st.get();
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (!st->root) {
-    const int64_t total = st->plan.Ptot;
-    dev_buf<double> root;
-    const hipError_t e = (hipError_t)root.alloc((size_t)total);
-    if (e != hipSuccess)
-      HFMI_FAIL(HFMI_ERR_HIP, "grid_factor: the root table of the embedding %d x %d x %d needs %lld bytes: %s", st->plan.P[0], st->plan.P[1],
-                st->plan.P[2], (long long)(total * 8), hipGetErrorString(e));
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_fftcov_root, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, st->lambda.get(), root.get(), total, (double)total);
-    const hipError_t launched = hipGetLastError();
-    const hipError_t done = hipStreamSynchronize(ctx->stream);   // whatever happened: `root` must not go while a kernel may write it
-    HIP_TRY(launched);
-    HIP_TRY(done);
-    st->root = std::move(root);
-  }
+  HFMI_TRY(grid_sampler_root(s, "grid_factor"));
   std::unique_ptr<hfmi_op> op(new (std::nothrow) hfmi_op());
   if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
   op->ctx = ctx;

@@ -230,7 +230,7 @@ struct kcov_nu_ref {
 };
 struct fftcov_state;
 struct interp_state;
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR, OP_GRID_INTERP, OP_KERNEL_COV_INTERP };
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR, OP_GRID_INTERP, OP_KERNEL_COV_INTERP, OP_INTERP_FACTOR };
 
 struct hfmi_op {
   ~hfmi_op();              // waits for the stream when the operator owns device memory (hfmi_op.hip)
@@ -270,6 +270,8 @@ struct hfmi_op {
   // OP_GRID_INTERP: W (ip_transpose 0: length prod n -> N) or W^T (1) of a sparse cubic interpolation from grid nodes to points;
   // OP_KERNEL_COV_INTERP: K = W Cg W^T + diag(delta) with Cg = ip_grid (a grid covariance, not owned: hfmi_op_compose3's rule).  The
   // state (binned weights, delta, the work block) is owned (hfmi_interp.hip)
+  // OP_INTERP_FACTOR: F = [W S | diag(sqrt(delta))] (fac_transpose 0) or F^T (1): `fac` is the sampler's state as for OP_GRID_FACTOR, ip_grid
+  // the interpolated operator (not owned, as its own grid operator is not) whose state and work block the applies use; ip stays null
   interp_state* ip = nullptr;
   int ip_transpose = 0;
   hfmi_op* ip_grid = nullptr;
@@ -367,11 +369,18 @@ bool fftcov_same_covariance(const fftcov_state* a, const fftcov_state* b);
 int fftcov_offset_table(hfmi_ctx* ctx, const fftcov_state* st, double* table);
 const fftcov_state* grid_sampler_state(const hfmi_grid_sampler* s);
 hfmi_ctx* grid_sampler_ctx(const hfmi_grid_sampler* s);
+// what a factor operator takes of a sampler: the root table in its state (made at the first call; `who` heads the message of a failed
+// allocation), the state itself to share, and prod P_c, the length of the padded vectors S acts on
+int grid_sampler_root(hfmi_grid_sampler* s, const char* who);
+std::shared_ptr<fftcov_state> grid_sampler_share(hfmi_grid_sampler* s);
+int64_t fftcov_padded_len(const fftcov_state* st);
 // Interpolation between grid nodes and scattered points (hfmi_interp.hip; rules: hfmi_interp_plan.h).  apply: Y (+)= W X, W^T X
 // or K X by the operator's kind; destroy deletes the state (the caller synchronised)
 int interp_apply(hfmi_op* op, const hfmi_block* X, hfmi_block* Y, int accumulate);
 void interp_destroy(interp_state* st);
-int64_t interp_range_len(const hfmi_op* op);   // OP_GRID_INTERP: N for W, prod n for W^T
+int64_t interp_range_len(const hfmi_op* op);   // OP_GRID_INTERP: N for W, prod n for W^T; OP_INTERP_FACTOR: N for F, prod P_c + N for F^T
+// Y (+)= F X or F^T X of an OP_INTERP_FACTOR; checks the lengths
+int interp_factor_apply(hfmi_op* op, const hfmi_block* X, hfmi_block* Y, int accumulate);
 
 // ------------------------------------------------------------------ QR (hfmi_qr.hip)
 // Y = A S, S upper triangular

@@ -1,8 +1,8 @@
 // Scattered points on the FFT route: the sparse cubic interpolation W from the nodes of a regular grid to N points
 // (hfmi_op_grid_interp), and the interpolated grid covariance  K = W Cg W^T + diag(delta)  as one operator (hfmi_op_kernel_cov_interp)
-// with its draws (hfmi_interp_sampler_draw).  Every rule -- the cell of a point, Keys' weights, the stencil order, the cell binning
+// with its draws (hfmi_interp_sampler_draw) and its factor K = F F^T (hfmi_op_interp_factor).  Every rule -- the cell of a point, Keys' weights, the stencil order, the cell binning
 // and the spread order, the autocorrelation form of the diagonal, the launch shapes -- is in hfmi_interp_plan.h; the weights are
-// computed there, on the host, and uploaded.  This unit holds the three kernels, the state and the launchers.
+// computed there, on the host, and uploaded.  This unit holds the kernels, the state and the launchers.
 //
 // Device layout (binned order: position k is point perm[k], the points of a cell contiguous, cells ascending):  base[k] the node of
 // the stencil corner, w[(4 a + s) N + k] weight s of axis a, delta[k] / sdelta[k] the diagonal and its square root.  That is 4 d
@@ -15,7 +15,8 @@
 //   and carries INTERP_SPREAD_COLS columns per trip.  No atomics.  Heavily clustered points make the threads of a few nodes long: that
 //   imbalance is accepted here, not solved.
 // k_interp_diag    q_i from the 7^d table of the kernel and the per-axis autocorrelations of the weights, once at creation.
-// All three are gathers bound by latency, not bandwidth (docs/measurements.md, "Interpolated grid covariance": a few per cent of the HBM
+// k_interp_factor_tail  Z (+)= sqrt(delta) . X in point order, the last N rows of F^T X: a stream, one multiplication per entry.
+// The first three are gathers bound by latency, not bandwidth (docs/measurements.md, "Interpolated grid covariance": a few per cent of the HBM
 // rate at N = 1e6, 0.47 to 0.82 of the time of the CSR-composed K); none has been tuned beyond its access pattern.
 #include <math.h>
 
@@ -40,10 +41,14 @@ struct interp_state {
   int64_t n_clipped = 0;
   dev_buf<double> work;                  // the internal block of work_ld rows, a chunk of columns
   int64_t work_ld = 0;
+  dev_buf<double> sdelta_pt;             // sqrt(delta) in POINT order: the tail of F^T streams over it (made by the first hfmi_op_interp_factor)
 };
 
 void interp_destroy(interp_state* st) { delete st; }
-int64_t interp_range_len(const hfmi_op* op) { return op->ip_transpose ? op->ip->g.nnodes : op->ip->N; }
+int64_t interp_range_len(const hfmi_op* op) {
+  if (op->kind == OP_INTERP_FACTOR) return op->ip_grid->ip->N + (op->fac_transpose ? fftcov_padded_len(op->fac.get()) : 0);
+  return op->ip_transpose ? op->ip->g.nnodes : op->ip->N;
+}
 
 struct interp_args {
   const int64_t* base;
@@ -152,6 +157,23 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp_spread(interp_args A)
           double* y = A.out + (int64_t)(j0 + c) * A.ldout + g;
           *y = A.accumulate ? *y + acc[c] : acc[c];
         }
+    }
+  }
+}
+
+// The tail of F^T: Z[i, j] (+)= sqrt(delta_i) X[i, j], everything in POINT order.  A stream: x over the points (neighbouring threads
+// take neighbouring rows of sd, X and Z), y over the columns, one multiplication per entry, no LDS, no atomics.  The product is rounded
+// before an accumulating apply adds it (no contraction), so an accumulated tail is what was there plus the overwriting one.
+__global__ __launch_bounds__(INTERP_THREADS) void k_interp_factor_tail(const double* __restrict__ sd, int64_t N, const double* __restrict__ X,
+                                                                        int64_t ldx, double* __restrict__ Z, int64_t ldz, int ncols,
+                                                                        int accumulate) {
+#pragma clang fp contract(off)
+  for (int64_t i = (int64_t)blockIdx.x * INTERP_THREADS + threadIdx.x; i < N; i += (int64_t)gridDim.x * INTERP_THREADS) {
+    const double s = sd[i];
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+      const double t = s * X[(int64_t)j * ldx + i];
+      double* z = Z + (int64_t)j * ldz + i;
+      *z = accumulate ? *z + t : t;
     }
   }
 }
@@ -491,6 +513,74 @@ extern "C" int hfmi_interp_sampler_draw(hfmi_op* op, hfmi_grid_sampler* grid_sam
     HFMI_TRY(hfmi_grid_sampler_draw(grid_sampler, &Z, seed, first_sample + c0, 0));
     HFMI_TRY(interp_gather(ctx, st, Z.p, Z.ld, Y->p + (int64_t)c0 * Y->ld, Y->ld, nc, accumulate != 0, EPI_NOISE, st->sdelta, nullptr, 0, key,
                            first_sample + c0));
+  }
+  return HFMI_OK;
+}
+
+// ------------------------------------------------------------------ the factor K = F F^T (hfmi_op_interp_factor)
+// F = [ W S | diag(sqrt(delta)) ], N x (Ptot + N), S the factor of the sampler's embedding (hfmi_op_grid_factor) and Ptot = prod P_c.
+// NOISE LAYOUT (hfmi_interp_plan.h): rows 0 .. Ptot - 1 the padded-grid noise in the grid factor's natural order, rows Ptot .. Ptot + N - 1
+// one entry per point in POINT order.  Both directions go through the interpolated operator's work block chunk by chunk of an even
+// number of columns, so the pairs the grid factor forms are those of one call and no "fftcov_pairs" changes a bit.
+extern "C" int hfmi_op_interp_factor(hfmi_op* cov, hfmi_grid_sampler* grid_sampler, int transpose, hfmi_op** out) {
+  HFMI_TRY(interp_cov_op(cov, "interp_factor"));
+  if (!grid_sampler || !out) HFMI_FAIL(HFMI_ERR_INVALID, "interp_factor: null argument");
+  if (transpose != 0 && transpose != 1) HFMI_FAIL(HFMI_ERR_INVALID, "interp_factor: transpose = %d is not 0 (F) or 1 (F^T)", transpose);
+  hfmi_ctx* ctx = cov->ctx;
+  interp_state* st = cov->ip;
+  if (grid_sampler_ctx(grid_sampler) != ctx || !fftcov_same_covariance(grid_sampler_state(grid_sampler), cov->ip_grid->fc))
+    HFMI_FAIL(HFMI_ERR_INVALID, "interp_factor: the sampler was not made from this operator's grid covariance");
+  HFMI_TRY(grid_sampler_root(grid_sampler, "interp_factor"));
+  if (!st->sdelta_pt) {
+    std::vector<double> sp((size_t)st->N);
+    for (int64_t i = 0; i < st->N; ++i) sp[(size_t)i] = sqrt(st->host_delta[(size_t)i]);    // the bits of sdelta, in point order
+    HFMI_TRY(interp_upload(&st->sdelta_pt, sp));
+  }
+  std::unique_ptr<hfmi_op> op(new (std::nothrow) hfmi_op());
+  if (!op) HFMI_FAIL(HFMI_ERR_INVALID, "out of host memory");
+  op->ctx = ctx;
+  op->kind = OP_INTERP_FACTOR;
+  op->fac = grid_sampler_share(grid_sampler);
+  op->fac_transpose = transpose;
+  op->ip_grid = cov;
+  *out = op.release();
+  return HFMI_OK;
+}
+
+int interp_factor_apply(hfmi_op* op, const hfmi_block* X, hfmi_block* Y, int accumulate) {
+  hfmi_ctx* ctx = op->ctx;
+  interp_state* st = op->ip_grid->ip;
+  fftcov_state* fs = op->fac.get();
+  const int transpose = op->fac_transpose;
+  const int64_t N = st->N, Ptot = fftcov_padded_len(fs);
+  const int64_t nin = transpose ? N : Ptot + N, nout = transpose ? Ptot + N : N;
+  if (X->N != nin || Y->N != nout)
+    HFMI_FAIL(HFMI_ERR_INVALID, "interp_factor: %s maps vectors of length %lld to length %lld, got %lld -> %lld", transpose ? "F^T" : "F",
+              (long long)nin, (long long)nout, (long long)X->N, (long long)Y->N);
+  const int k = X->nvec;
+  if (k < 1) return HFMI_OK;
+  const int kc = interp_chunk_cols(st->work_ld, k, fftcov_pairs_knob());
+  HFMI_TRY(interp_fit_work(ctx, st, kc));
+  for (int c0 = 0; c0 < k; c0 += kc) {
+    const int nc = std::min(kc, k - c0);
+    double* x = X->p + (int64_t)c0 * X->ld;
+    double* y = Y->p + (int64_t)c0 * Y->ld;
+    hfmi_block G{ctx, st->work.get(), st->g.nnodes, nc, st->work_ld, false};
+    if (!transpose) {
+      // the grid factor from a VIEW of the first Ptot rows into the work block, then one gather with + sqrt(delta_i) Xi[Ptot + i] fused
+      const hfmi_block top{ctx, x, Ptot, nc, X->ld, false};
+      HFMI_TRY(fftcov_factor_apply(ctx, fs, 0, &top, &G, 0));
+      HFMI_TRY(interp_gather(ctx, st, G.p, G.ld, y, Y->ld, nc, accumulate, EPI_DIAG, st->sdelta, x + Ptot, X->ld));
+    } else {
+      // spread into the work block, the transposed grid factor into a view of the first Ptot rows, the tail by its own kernel
+      HFMI_TRY(interp_spread(ctx, st, x, X->ld, G.p, G.ld, nc, 0));
+      hfmi_block top{ctx, y, Ptot, nc, Y->ld, false};
+      HFMI_TRY(fftcov_factor_apply(ctx, fs, 1, &G, &top, accumulate));
+      const interp_launch s = interp_launch_shape(N, nc, 1, ctx->num_cus);
+      hipLaunchKernelGGL(k_interp_factor_tail, dim3(s.gx, s.gy), dim3(INTERP_THREADS), 0, ctx->stream, st->sdelta_pt.get(), N, x, X->ld, y + Ptot,
+                         Y->ld, nc, accumulate);
+      HIP_TRY(hipGetLastError());
+    }
   }
   return HFMI_OK;
 }

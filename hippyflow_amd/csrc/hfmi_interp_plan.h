@@ -31,6 +31,12 @@
 // autocorrelations  a_a[o] = sum_{s - s' = o} w_a[s] w_a[s'], o = 0 .. 3 (s ascending, first term a product, the rest fused
 // multiply-adds; a_a[-o] = a_a[o]), so  q_i = sum over the 7^d offsets o of ((a_2[o2] * a_1[o1]) * a_0[o0]) * c(o), o2 outermost, o0
 // innermost, each term one fused multiply-add: 7^d terms in place of 16^d, the same number up to rounding.
+//
+// The factor  F = [ W S | diag(sqrt(delta)) ],  K = F F^T  (hfmi_op_interp_factor), S the grid factor of a sampler's embedding of
+// Ptot = prod P_c padded nodes.  NOISE LAYOUT (part of the contract) of the Ptot + N rows F acts on: rows 0 .. Ptot - 1 the padded-grid
+// noise in the grid factor's natural order, entry e = s0 + P0 (s1 + P1 s2); rows Ptot .. Ptot + N - 1 one entry per point in POINT
+// order, not the binned order above.  (F Xi)_i = fma(sqrt(delta_i), Xi[Ptot + i], (W S Xi_top)_i), the gather's sum first;
+// (F^T X)[Ptot + i] = sqrt(delta_i) X[i], one multiplication, rounded before an accumulating apply adds it.
 #pragma once
 #include <math.h>
 #include <stddef.h>

@@ -559,7 +559,8 @@ static int panel_reduce_hook(void* user, double* Y, int64_t ldy, int r, int64_t 
 // the length of op's results on inputs of length in_len, for the kinds that can be rectangular and say so; in_len otherwise
 static int64_t op_range_len(const hfmi_op* op, int64_t in_len) {
   switch (op->kind) {
-    case OP_GRID_INTERP: return interp_range_len(op);
+    case OP_GRID_INTERP:
+    case OP_INTERP_FACTOR: return interp_range_len(op);
     case OP_CSR: return op->csr->nrows;
     case OP_KERNEL_CROSS: return op->kc_slab ? in_len : op->kc_M;
     case OP_COMPOSE3: return op_range_len(op->c, op_range_len(op->b, op_range_len(op->a, in_len)));
@@ -670,6 +671,9 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
     case OP_KERNEL_COV_INTERP:
       // Y (+)= W X, W^T X or K X: the last kernel adds into Y itself
       return interp_apply(op, W, Y, beta != 0.0);
+    case OP_INTERP_FACTOR:
+      // Y (+)= F W or F^T W: the gather, or the last pass and the tail kernel, add into Y themselves
+      return interp_factor_apply(op, W, Y, beta != 0.0);
     case OP_KERNEL_CROSS: {
       const int64_t N = op->kc_N, M = op->kc_M;
       const int acc = beta != 0.0;

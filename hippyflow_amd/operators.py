@@ -13,6 +13,8 @@ Reference counterparts (file:line under /root/reference/hippyflow):
 * ``GridKernelCovarianceOperator``                that covariance on the nodes of a regular grid, applied by FFT (hfmi_fftcov.hip)
 * ``GridCovarianceFactor`` / ``GridKernelPrior``  its factor C = S S^T (hfmi_op_grid_factor) and the prior protocol over it: ``sample(noise, m)``
                                                   with the caller's noise, ``Rsolver``, no ``R`` (``randomized.doublePassC`` needs none)
+* ``InterpolatedCovarianceFactor`` / ``InterpolatedKernelPrior``  the same two over SCATTERED points (mesh nodes): the factor K = F F^T,
+                                                  F = [W S | diag(sqrt(delta))] (hfmi_op_interp_factor), of the interpolated grid covariance
 * ``KernelCrossCovarianceOperator``               K(T, S) between two point sets (Nystrom extension); ``KernelCovarianceOperator.rows`` /
                                                   ``.sharded``: a row slab of C per rank, completed by the collective's SUM
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
@@ -624,7 +626,73 @@ class _GridCovarianceSolver:
         return self.op
 
 
-class GridKernelPrior:
+class _KernelFactorPrior:
+    """What ``GridKernelPrior`` and ``InterpolatedKernelPrior`` share: a covariance operator ``C`` with a factor C = F F^T behind the PRIOR
+    protocol, the mean, ``Rsolver`` (an apply of C), the absent ``R``, ``sample`` (mean + factor . noise) and ``sample_block`` (noise
+    generated on the device by ``sampler``)."""
+
+    _noise_of = "the embedding"        # what the noise's length is that of, in sample's message
+
+    def _setup(self, op, sampler, factor, mean, M, Msolver):
+        self.C = op
+        self.ctx = op.ctx
+        self.N = op.shape[0]
+        self.sampler = sampler
+        self._factor = factor
+        self.Rsolver = _GridCovarianceSolver(op)
+        if M is not None:
+            self.M = M
+        if Msolver is not None:
+            self.Msolver = Msolver
+        mean = np.zeros(self.N) if mean is None else np.asarray(mean.get_local() if hasattr(mean, "get_local") else mean, dtype=np.float64)
+        if mean.shape != (self.N,):
+            raise ValueError("%s: the mean has %s entries, the operator %d points" % (type(self).__name__, mean.shape, self.N))
+        self._mean = mean.copy()
+        self.mean = H.new_host_vector()
+        self.mean.init(self.N)
+        self.mean.set_local(self._mean)
+        self.mean.apply("")
+
+    growth = property(lambda self: self.sampler.growth)
+    embedding = property(lambda self: self.sampler.embedding)
+    n_clipped = property(lambda self: self.sampler.n_clipped)
+    cov_error_bound = property(lambda self: self.sampler.cov_error_bound)
+
+    def __getattr__(self, name):          # only reached for attributes that are not there
+        if name == "R":
+            raise AttributeError("%s has no precision R = C^-1 and never solves with C: the prior-preconditioned double pass "
+                                 "is randomized.doublePassC(A, prior.C, Omega, k), encoders come out of it, draws are prior.sample"
+                                 % type(self).__name__)
+        raise AttributeError("%s object has no attribute %r" % (type(self).__name__, name))
+
+    def init_vector(self, x, dim):
+        x.init(self._factor.shape[1] if dim == "noise" else self.N)
+
+    def sample(self, noise, m, add_mean=True):
+        """m = mean + factor . noise (``add_mean=False``: without the mean); ``noise`` has ``init_vector(x, "noise")`` entries, m has N."""
+        host = H.is_host_vector(noise)
+        xi = np.asarray(noise.get_local() if host else noise._mv.to_vectors()[0], dtype=np.float64)
+        nn = self._factor.shape[1]
+        if xi.shape != (nn,):
+            raise ValueError("%s.sample: the noise has %s entries, %s %d (init_vector(x, 'noise'))" % (type(self).__name__, xi.shape, self._noise_of, nn))
+        Xi = MultiVector.from_vectors(xi[None, :], ctx=self.ctx)
+        Y = MultiVector(self.N, 1, ctx=self.ctx)
+        self._factor.matMvMult(Xi, Y)
+        y = Y.to_vectors()[0]
+        if add_mean:
+            y = y + self._mean
+        if H.is_host_vector(m):
+            m.set_local(y)
+            m.apply("")
+        else:
+            L.call("hfmi_block_upload", m._mv.handle, L.ptr(L.as_f64(y[None, :])), L.LAYOUT_VECTORS)
+
+    def sample_block(self, n):
+        """(n, N) array of the next n draws mean + N(0, C) with noise generated on the device (the sampler's ``sample_block``)."""
+        return self.sampler.sample_block(n) + self._mean[None, :]
+
+
+class GridKernelPrior(_KernelFactorPrior):
     """A ``GridKernelCovarianceOperator`` behind the PRIOR protocol of the drivers (projectors.py, datagen.py, datasets.py, errors.py):
     ``init_vector(x, "noise")``, ``sample(noise, m)``, ``mean``, ``Rsolver``, ``M`` / ``Msolver`` -- with NO precision ``R``: a kernel
     covariance has no sparse inverse, and a Krylov solve with C needs hundreds of applies where it converges at all.  Nothing here
@@ -641,60 +709,9 @@ class GridKernelPrior:
     def __init__(self, op, mean=None, M=None, Msolver=None, max_growth=3, on_indefinite="raise", seed=0):
         if not isinstance(op, GridKernelCovarianceOperator):
             raise ValueError("GridKernelPrior: a GridKernelCovarianceOperator is required (got %s)" % type(op).__name__)
-        self.C = op
-        self.ctx = op.ctx
-        self.N = op.shape[0]
-        self.sampler = op.sampler(max_growth=max_growth, on_indefinite=on_indefinite, seed=seed)
-        self.S = self.sampler.factor()
-        self.Rsolver = _GridCovarianceSolver(op)
-        if M is not None:
-            self.M = M
-        if Msolver is not None:
-            self.Msolver = Msolver
-        mean = np.zeros(self.N) if mean is None else np.asarray(mean.get_local() if hasattr(mean, "get_local") else mean, dtype=np.float64)
-        if mean.shape != (self.N,):
-            raise ValueError("GridKernelPrior: the mean has %s entries, the operator %d points" % (mean.shape, self.N))
-        self._mean = mean.copy()
-        self.mean = H.new_host_vector()
-        self.mean.init(self.N)
-        self.mean.set_local(self._mean)
-        self.mean.apply("")
-
-    growth = property(lambda self: self.sampler.growth)
-    embedding = property(lambda self: self.sampler.embedding)
-    n_clipped = property(lambda self: self.sampler.n_clipped)
-    cov_error_bound = property(lambda self: self.sampler.cov_error_bound)
-
-    def __getattr__(self, name):          # only reached for attributes that are not there
-        if name == "R":
-            raise AttributeError("GridKernelPrior has no precision R = C^-1 and never solves with C: the prior-preconditioned double pass "
-                                 "is randomized.doublePassC(A, prior.C, Omega, k), encoders come out of it, draws are prior.sample")
-        raise AttributeError("%s object has no attribute %r" % (type(self).__name__, name))
-
-    def init_vector(self, x, dim):
-        x.init(self.S.shape[1] if dim == "noise" else self.N)
-
-    def sample(self, noise, m, add_mean=True):
-        """m = mean + S noise (``add_mean=False``: S noise); ``noise`` has ``Ptot`` entries, m has N."""
-        host = H.is_host_vector(noise)
-        xi = np.asarray(noise.get_local() if host else noise._mv.to_vectors()[0], dtype=np.float64)
-        if xi.shape != (self.S.shape[1],):
-            raise ValueError("GridKernelPrior.sample: the noise has %s entries, the embedding %d (init_vector(x, 'noise'))" % (xi.shape, self.S.shape[1]))
-        Xi = MultiVector.from_vectors(xi[None, :], ctx=self.ctx)
-        Y = MultiVector(self.N, 1, ctx=self.ctx)
-        self.S.matMvMult(Xi, Y)
-        y = Y.to_vectors()[0]
-        if add_mean:
-            y = y + self._mean
-        if H.is_host_vector(m):
-            m.set_local(y)
-            m.apply("")
-        else:
-            L.call("hfmi_block_upload", m._mv.handle, L.ptr(L.as_f64(y[None, :])), L.LAYOUT_VECTORS)
-
-    def sample_block(self, n):
-        """(n, N) array of the next n draws mean + N(0, C) with noise generated on the device (``GridFieldSampler.sample_block``)."""
-        return self.sampler.sample_block(n) + self._mean[None, :]
+        sampler = op.sampler(max_growth=max_growth, on_indefinite=on_indefinite, seed=seed)
+        self.S = sampler.factor()
+        self._setup(op, sampler, self.S, mean, M, Msolver)
 
 
 def _interp_grid_args(shape, spacing, origin, points):
@@ -943,6 +960,79 @@ class InterpolatedFieldSampler:
         X = self.sample(n, self.seed, first=self._next)
         self._next += int(n) + (int(n) & 1)
         return np.ascontiguousarray(X.to_dense().T)
+
+    def factor(self):
+        """The factor ``F = [W S | diag(sqrt(delta))]`` of the operator over this sampler's embedding, K = F F^T
+        (``InterpolatedCovarianceFactor``)."""
+        return InterpolatedCovarianceFactor(self)
+
+
+class InterpolatedCovarianceFactor(DeviceOperator):
+    """The factor ``F = [ W S | diag(sqrt(delta)) ]`` of an ``InterpolatedKernelCovarianceOperator`` K over the embedding of an
+    ``InterpolatedFieldSampler`` (hfmi_op_interp_factor): ``S`` is the ``GridCovarianceFactor`` of the grid sampler, ``F F^T = W S S^T W^T +
+    diag(delta)`` is K up to rounding for a definite sampler.  ``shape == (N, Ptot + N)`` with ``Ptot = prod(sampler.embedding)`` and
+    ``noise_split == (Ptot, N)``: the first Ptot entries of a noise vector are the padded-grid noise in ``GridCovarianceFactor``'s natural
+    order, the last N one entry per point in the order of ``op.points``.  ``mult`` / ``matMvMult`` take noise to the points (the grid
+    factor, then one gather with the tail fused), ``transpmult`` / ``matMvTranspmult`` the other way; ``transpose()`` is ``F^T`` as an
+    operator of its own (what a whitened Hessian F^T H F composes).  ``init_vector(x, dim)``: 0 gives N entries, 1 gives Ptot + N.
+
+    ``factor_error_bound`` bounds ``max_ij |F F^T - K|``: 0 for a definite sampler, ``1.25**(2 d) * sampler.cov_error_bound`` for a
+    clipped one.  There ``S S^T = Cg + E`` with ``|E_ij| <= cov_error_bound``, so ``F F^T - K = W E W^T``; the four Keys weights of one axis
+    have 1-norm ``1 + t (1 - t) <= 1.25``, a row of W has 1-norm at most ``1.25**d``, and ``|W E W^T|_ij <= |E|_max * 1.25**d * 1.25**d``.
+
+    The price: a noise vector has ``Ptot + N`` entries, and Ptot is 4 to 64 times the grid, which itself covers the points' box at
+    ``cells_per_ell`` nodes per correlation length: ``InterpolatedFieldSampler.sample_block`` (noise generated on the device) stays the
+    route for many draws.  The operator keeps the sampler alive, and the sampler keeps K alive."""
+
+    def __init__(self, sampler, _transpose=False, _other=None):
+        if not isinstance(sampler, InterpolatedFieldSampler):
+            raise ValueError("InterpolatedCovarianceFactor: an InterpolatedFieldSampler is required (got %s)" % type(sampler).__name__)
+        Ptot, N = int(np.prod(sampler.embedding)), sampler.N
+        super().__init__(sampler.ctx, *((Ptot + N, N) if _transpose else (N, Ptot + N)))
+        self.sampler = sampler
+        self.noise_split = (Ptot, N)
+        self.is_transpose = bool(_transpose)
+        self._other = _other
+        self.factor_error_bound = 1.25 ** (2 * len(sampler.embedding)) * sampler.cov_error_bound
+        L.call("hfmi_op_interp_factor", sampler.op._op, sampler.grid_sampler.handle, 1 if _transpose else 0, C.byref(self._op))
+
+    def transpose(self):
+        """``F^T`` of ``F`` and back: an operator of shape ``shape[::-1]`` over the same sampler (made once)."""
+        if self._other is None:
+            self._other = InterpolatedCovarianceFactor(self.sampler, _transpose=not self.is_transpose, _other=self)
+        return self._other
+
+    def transpmult(self, x, y):
+        self.transpose().mult(x, y)
+
+    def matMvTranspmult(self, X, Y, accumulate=False):
+        self.transpose().matMvMult(X, Y, accumulate=accumulate)
+
+
+class InterpolatedKernelPrior(_KernelFactorPrior):
+    """An ``InterpolatedKernelCovarianceOperator`` behind the PRIOR protocol of the drivers, as ``GridKernelPrior`` puts a grid operator
+    there: a kernel prior over SCATTERED points (mesh nodes, ``Vh.tabulate_dof_coordinates()``) with no assembly, no precision ``R`` and no
+    solve.  ``sample`` is m = mean + F noise with the factor K = F F^T (``InterpolatedCovarianceFactor``); the prior-preconditioned active
+    subspace takes ``randomized.doublePassC(A, prior.C, Omega, k)``, and ``F`` / ``F.transpose()`` compose the whitened Hessian.
+
+    ``init_vector(x, dim)``: ``"noise"`` gives ``Ptot + N`` entries -- the padded-grid noise first, then one entry per point -- and 0 / 1
+    give N.  Ptot = prod(embedding) is 4 to 64 times the grid, so a noise vector is far longer than a parameter:
+    ``sample_block(n)`` hands out ``InterpolatedFieldSampler.sample_block``'s draws (noise generated on the device) plus the mean and
+    stays the route for many draws.  ``C`` is the operator, ``Rsolver.solve(y, x)`` is y = K x; ``mean``, ``M`` / ``Msolver`` as for
+    ``GridKernelPrior``.  ``growth``, ``embedding``, ``n_clipped`` and ``cov_error_bound`` are the sampler's, ``factor_error_bound`` the
+    factor's.  ``R`` is deliberately absent: reading it raises ``AttributeError`` pointing at ``doublePassC``.  The Gaussian is N(mean, K),
+    and K is not the exact kernel covariance (see the operator)."""
+
+    _noise_of = "the factor"
+
+    def __init__(self, op, mean=None, M=None, Msolver=None, max_growth=3, on_indefinite="raise", seed=0):
+        if not isinstance(op, InterpolatedKernelCovarianceOperator):
+            raise ValueError("InterpolatedKernelPrior: an InterpolatedKernelCovarianceOperator is required (got %s)" % type(op).__name__)
+        sampler = op.sampler(max_growth=max_growth, on_indefinite=on_indefinite, seed=seed)
+        self.F = sampler.factor()
+        self._setup(op, sampler, self.F, mean, M, Msolver)
+
+    factor_error_bound = property(lambda self: self.F.factor_error_bound)
 
 
 def _is_null_collective(collective):

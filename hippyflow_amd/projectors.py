@@ -32,6 +32,7 @@ from . import hostvec as H
 from .multivector import ingest_stream, MatMvMult, MultiVector, mv_to_dense
 from .lowrank import pivoted_cholesky
 from .operators import (CsrOperator, CsrPCGSolver, DeviceOperator, HostCallbackOperator, GridKernelCovarianceOperator,
+                        InterpolatedKernelCovarianceOperator,
                         KernelCovarianceOperator, KernelCrossCovarianceOperator, nystrom_extend,
                         MassPreconditionedCovarianceOperator,
                         MeanJJTfromDataOperator, MeanJTJfromDataOperator, ObservableJacobian, SeriallySampledJacobianOperator,
@@ -734,15 +735,19 @@ class KLEProjector:
     def extend(self, points):
         """The decoder's columns at other ``points`` (an (M, d) array): the Nystrom extension K(points, X) . encoder . diag(1 / d_KLE)
         of the KLE computed by ``construct_input_subspace('mass' | 'identity')`` from a ``KernelCovarianceOperator`` prior.C (or a
-        ``GridKernelCovarianceOperator``: the cross-covariance is built from its ``.points`` and kernel).  A
+        ``GridKernelCovarianceOperator``: the cross-covariance is built from its ``.points`` and kernel; with an
+        ``InterpolatedKernelCovarianceOperator`` it is ``C.cross(points)`` = W_T Cg W_S^T on the operator's grid, no N x M kernel sweep, and
+        every target needs its full stencil inside that grid).  A
         ``MultiVector`` of M rows; at the projector's own nodes (and without a nugget) it reproduces the decoder to the accuracy of the
         eigensolve.  ValueError for 'prior' orthogonality, a covariance that is not a kernel, or before the subspace exists."""
-        if not isinstance(self.C, (KernelCovarianceOperator, GridKernelCovarianceOperator)):
+        if not isinstance(self.C, (KernelCovarianceOperator, GridKernelCovarianceOperator, InterpolatedKernelCovarianceOperator)):
             raise ValueError("extend: prior.C must be a KernelCovarianceOperator (got %s)" % type(self.C).__name__)
         if self.R_orthogonal:
             raise ValueError("extend: the Nystrom extension is for 'mass' and 'identity' orthogonality, not 'prior'")
         if self._kle_encoder is None or self.d_KLE is None:
             raise ValueError("extend: call construct_input_subspace('mass' | 'identity') first")
+        if isinstance(self.C, InterpolatedKernelCovarianceOperator):
+            return nystrom_extend(self.C.cross(points), self._kle_encoder, self.d_KLE)
         cross = KernelCrossCovarianceOperator(points, self.C.points, self.C.family, self.C.sigma, self.C.ell, ctx=self.ctx,
                                               nu=getattr(self.C, "nu", None), metric=self.C.metric)
         return nystrom_extend(cross, self._kle_encoder, self.d_KLE)

@@ -426,6 +426,30 @@ HFMI_API int hfmi_op_kernel_cov_interp_info(const hfmi_op* op, double* diag_min,
 HFMI_API int hfmi_op_kernel_cov_interp_diag(const hfmi_op* op, double* host_q_or_null /* N */, double* host_delta_or_null /* N */);
 HFMI_API int hfmi_interp_sampler_draw(hfmi_op* op, hfmi_grid_sampler* grid_sampler, const hfmi_block* Y, uint64_t seed,
                                       int64_t first_sample /* even */, int accumulate);
+/*     the FACTOR of that covariance,  K = F F^T  with  F = [ W S | diag(sqrt(delta)) ]  of shape N x (Ptot + N):  S is the factor of the
+ *     sampler's embedding as in hfmi_op_grid_factor (Cg = S S^T, Ptot = prod P_c), so F F^T = W S S^T W^T + diag(delta) is K up to rounding
+ *     for a definite sampler and K + W E W^T for a clipped one, |E_ij| <= cov_error_bound and hence |W E W^T|_ij <= 1.25^(2 d)
+ *     cov_error_bound (the four Keys weights of an axis have 1-norm 1 + t (1 - t) <= 1.25).  What hands the caller's noise to a prior
+ *     over scattered points: m = mean + F xi, and the whitened Hessian F^T H F.
+ *       NOISE LAYOUT (part of the contract): rows 0 .. Ptot - 1 of a noise vector are the padded-grid noise in hfmi_op_grid_factor's
+ *     natural order (entry e = s0 + P0 (s1 + P1 s2)); rows Ptot .. Ptot + N - 1 hold one entry per point in POINT order -- the order of
+ *     host_points, not the binned order the device keeps internally.
+ *       hfmi_op_interp_factor: transpose = 0 is F (blocks of length Ptot + N -> N), 1 is F^T (N -> Ptot + N).  F: the grid factor from a
+ *     view of the first Ptot rows into the interpolated operator's work block, then one gather whose epilogue adds sqrt(delta_i)
+ *     Xi[Ptot + i] by one fused multiply-add.  F^T: one spread into the work block, the transposed grid factor into a view of the first
+ *     Ptot rows, and the tail Z[Ptot + i] (+)= sqrt(delta_i) X[i] by a streaming kernel of one multiplication per entry (the product is
+ *     rounded before an accumulating apply adds it).  Both work chunk by chunk of the work block, an even number of columns (2
+ *     "fftcov_pairs" columns when that key is set), so the pairs the grid factor forms are those of one call: no chunking changes a bit,
+ *     and two applies are bit-identical.  Block storage contract as every operator; zero columns is a no-op.  Creation makes the
+ *     sampler's root table if no factor of the sampler made it before, and sqrt(delta) in point order in the interpolated operator's
+ *     state; neither changes a bit of the sampler's draws or of the operator's applies.  Samplers of either route are taken.
+ *     LIFETIME: the sampler's state is shared as by hfmi_op_grid_factor (the sampler may be destroyed first); the interpolated operator
+ *     is referred to, not owned or copied, and must outlive this operator, as its grid operator must outlive it.
+ *     HFMI_ERR_INVALID: an operator that is not one of hfmi_op_kernel_cov_interp, a sampler of another context or not made from that
+ *     operator's grid covariance, transpose outside 0 / 1; at apply, blocks of another length (the message names F or F^T and the four
+ *     lengths). */
+HFMI_API int hfmi_op_interp_factor(hfmi_op* interp_cov_op, hfmi_grid_sampler* grid_sampler, int transpose /* 0: F | 1: F^T */,
+                                   hfmi_op** out);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
