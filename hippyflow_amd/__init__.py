@@ -12,7 +12,7 @@ from .collectives import (CollectiveOperator, MatrixMultCollectiveOperator, Mult
 from .hostvec import ADJOINT, CONTROL, PARAMETER, STATE, HostMultiVector, HostVector, new_host_vector, set_host_vector_factory
 from .multivector import (MatMvMult, MatMvTranspmult, MultiVector, MvDSmatMult, Vector, dense_to_mv_local, ingest_stream, mv_to_dense,
                           mv_to_dense_local)
-from .operators import (BiLaplacianRsolver, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
+from .operators import (BiLaplacianRsolver, BoxSpectralCovariance, BoxSpectralPrior, ComposedOperator, CsrAMGSolver, CsrOperator, CsrPCGSolver, DenseJacobianOperator, DeviceOperator, HostCallbackOperator,
                         GridCovarianceFactor, GridFieldSampler, GridInterpolationOperator, GridKernelCovarianceOperator, GridKernelPrior, grid_node_points,
                         InterpolatedCovarianceFactor, InterpolatedFieldSampler, InterpolatedKernelCovarianceOperator, InterpolatedKernelPrior, KernelCovarianceOperator, kernel_cov_host, KernelCrossCovarianceOperator, KernelCovarianceRowsOperator,
                         kernel_cross_cov_host, nystrom_extend, shard_rows, anisotropy_2d, bilaplacian_kernel_2d, whittle_matern_kernel,

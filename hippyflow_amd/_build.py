@@ -15,7 +15,7 @@ INCLUDE = os.path.join(ROOT, "include")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhfmi.so")
 EXPORTS = os.path.join(HERE, "libhfmi.map")      # linker version script: only hfmi_* leaves the library
-SOURCES = ["hfmi_own.hip", "hfmi_ctx.hip", "hfmi_block.hip", "hfmi_op.hip", "hfmi_qr.hip", "hfmi_solve.hip", "hfmi_bench.hip", "hfmi_gemm.hip", "hfmi_gemm_nn.hip", "hfmi_misc.hip", "hfmi_sparse.hip", "hfmi_small.hip", "hfmi_chol_col.hip", "hfmi_jacobi.hip", "hfmi_lu.hip", "hfmi_skinny.hip", "hfmi_comm.hip", "hfmi_eig_large.hip", "hfmi_eig_blocked.hip", "hfmi_dgemm.hip", "hfmi_eig_dc.hip", "hfmi_chol.hip", "hfmi_chol_wide.hip", "hfmi_cheb.hip", "hfmi_xfer.hip", "hfmi_amg.hip", "hfmi_kcov.hip", "hfmi_pchol.hip", "hfmi_fftcov.hip", "hfmi_matern_tables.hip", "hfmi_interp.hip"]
+SOURCES = ["hfmi_own.hip", "hfmi_ctx.hip", "hfmi_block.hip", "hfmi_op.hip", "hfmi_qr.hip", "hfmi_solve.hip", "hfmi_bench.hip", "hfmi_gemm.hip", "hfmi_gemm_nn.hip", "hfmi_misc.hip", "hfmi_sparse.hip", "hfmi_small.hip", "hfmi_chol_col.hip", "hfmi_jacobi.hip", "hfmi_lu.hip", "hfmi_skinny.hip", "hfmi_comm.hip", "hfmi_eig_large.hip", "hfmi_eig_blocked.hip", "hfmi_dgemm.hip", "hfmi_eig_dc.hip", "hfmi_chol.hip", "hfmi_chol_wide.hip", "hfmi_cheb.hip", "hfmi_xfer.hip", "hfmi_amg.hip", "hfmi_kcov.hip", "hfmi_pchol.hip", "hfmi_fftcov.hip", "hfmi_matern_tables.hip", "hfmi_interp.hip", "hfmi_boxcov.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + INCLUDE, "-I" + CSRC] + os.environ.get("HFMI_EXTRA_HIPCC_FLAGS", "").split()
 
 

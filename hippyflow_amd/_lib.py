@@ -24,6 +24,10 @@ FFTCOV_PLAN_WORDS = 96                                 # HFMI_FFTCOV_PLAN_WORDS 
 GRID_COV_LONG_MAX_NODES = 1 << 23                      # nodes per axis of hfmi_op_kernel_cov_grid_long (FFTCOV_LONG_MAXN)
 GRID_COV_LONG_MAX_GROWTH = 6                           # growth of hfmi_grid_sampler_create_long (FFTCOV_LONG_MAX_GROWTH)
 FFTCOV_LONG_PLAN_WORDS = 280                           # HFMI_FFTCOV_LONG_PLAN_WORDS of include/hfmi.h
+BOX_BOUNDARIES = {"neumann": 0, "periodic": 1}          # HFMI_BOX_NEUMANN / _PERIODIC of include/hfmi.h
+BOX_SYMBOLS = {"fd": 0, "continuous": 1}               # HFMI_BOX_SYMBOL_*
+BOX_MAX_NEUMANN, BOX_MAX_PERIODIC = 2049, 4096         # nodes of an axis of hfmi_box_create (hfmi_boxcov_plan.h)
+BOXCOV_PLAN_WORDS = 96                                 # HFMI_BOXCOV_PLAN_WORDS of include/hfmi.h
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
 PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h
 
@@ -133,6 +137,11 @@ SIGNATURES = {
     "hfmi_op_kernel_cov_interp_diag": [_P, _P, _P],
     "hfmi_interp_sampler_draw": [_P, _P, _P, C.c_uint64, C.c_int64, C.c_int],
     "hfmi_op_interp_factor": [_P, _P, C.c_int, _PP],
+    "hfmi_box_create": [_P, C.c_int, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_int, _PP],
+    "hfmi_box_destroy": [_P],
+    "hfmi_box_spectrum": [_P, _P],
+    "hfmi_op_box": [_P, C.c_double, C.c_double, C.c_double, _PP],
+    "hfmi_boxcov_plan_predict": [C.c_int, _P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
     "hfmi_pchol_create": [_P, C.c_int, C.c_double, _PP],
     "hfmi_pchol_info": [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "hfmi_pchol_read": [_P, _P, _P],

@@ -230,7 +230,8 @@ struct kcov_nu_ref {
 };
 struct fftcov_state;
 struct interp_state;
-enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR, OP_GRID_INTERP, OP_KERNEL_COV_INTERP, OP_INTERP_FACTOR };
+struct boxcov_state;
+enum hfmi_op_kind { OP_SNAPSHOT_GRAM, OP_JTJ, OP_JJT, OP_DENSE_SYM, OP_CSR, OP_CSR_PCG, OP_COMPOSE3, OP_HOST, OP_AMG_PCG, OP_KERNEL_COV, OP_KERNEL_CROSS, OP_KERNEL_COV_GRID, OP_GRID_FACTOR, OP_GRID_INTERP, OP_KERNEL_COV_INTERP, OP_INTERP_FACTOR, OP_BOX };
 
 struct hfmi_op {
   ~hfmi_op();              // waits for the stream when the operator owns device memory (hfmi_op.hip)
@@ -275,6 +276,11 @@ struct hfmi_op {
   interp_state* ip = nullptr;
   int ip_transpose = 0;
   hfmi_op* ip_grid = nullptr;
+  // OP_BOX: W^a T_s W^b of a box (hfmi_op_box): the box's state (grid, twiddles, work buffer), shared with it as OP_GRID_FACTOR shares its
+  // sampler's; the table lambda^s / prod P_c of this operator (owned) and the powers of the quadrature weights
+  std::shared_ptr<boxcov_state> box;
+  dev_buf<double> box_table;
+  double box_a = 0.0, box_b = 0.0;
   hfmi_host_apply_fn host_fn = nullptr;
   void* host_user = nullptr;
   int64_t host_N = 0;
@@ -374,6 +380,10 @@ hfmi_ctx* grid_sampler_ctx(const hfmi_grid_sampler* s);
 int grid_sampler_root(hfmi_grid_sampler* s, const char* who);
 std::shared_ptr<fftcov_state> grid_sampler_share(hfmi_grid_sampler* s);
 int64_t fftcov_padded_len(const fftcov_state* st);
+// Whittle-Matern operators on a box by DCT / FFT (hfmi_boxcov.hip; plans: hfmi_boxcov_plan.h): Y (+)= W^a T_s W^b X with the operator's table
+int64_t boxcov_points(const boxcov_state* st);
+int boxcov_apply(hfmi_ctx* ctx, boxcov_state* st, const double* table, double a, double b, const double* W, int64_t ldw, double* Y,
+                 int64_t ldy, int nvec, int accumulate);
 // Interpolation between grid nodes and scattered points (hfmi_interp.hip; rules: hfmi_interp_plan.h).  apply: Y (+)= W X, W^T X
 // or K X by the operator's kind; destroy deletes the state (the caller synchronised)
 int interp_apply(hfmi_op* op, const hfmi_block* X, hfmi_block* Y, int accumulate);

@@ -446,7 +446,7 @@ extern "C" int hfmi_op_set_collective(hfmi_op* op, hfmi_comm* comm, int reduce_o
   return HFMI_OK;
 }
 hfmi_op::~hfmi_op() {
-  if (gamma_inv || weights || kc_x || kc_t || kc_nutab || fc || fac || ip) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
+  if (gamma_inv || weights || kc_x || kc_t || kc_nutab || fc || fac || ip || box) (void)hipStreamSynchronize(ctx->stream);   // a kernel may still read them
   fftcov_destroy(fc);
   interp_destroy(ip);
 }
@@ -667,6 +667,13 @@ static int op_apply_raw(hfmi_op* op, const hfmi_block* W, hfmi_block* Y, double 
     case OP_GRID_FACTOR:
       // Y (+)= S W or S^T W: the last pass adds into Y itself
       return fftcov_factor_apply(ctx, op->fac.get(), op->fac_transpose, W, Y, beta != 0.0);
+    case OP_BOX: {
+      const int64_t N = boxcov_points(op->box.get());
+      if (N != W->N || N != Y->N)
+        HFMI_FAIL(HFMI_ERR_INVALID, "operator acts on vectors of length %lld, got %lld -> %lld", (long long)N, (long long)W->N, (long long)Y->N);
+      // Y (+)= W^a T_s W^b X: the gather of the last pass adds into Y itself
+      return boxcov_apply(ctx, op->box.get(), op->box_table, op->box_a, op->box_b, W->p, W->ld, Y->p, Y->ld, k, beta != 0.0);
+    }
     case OP_GRID_INTERP:
     case OP_KERNEL_COV_INTERP:
       // Y (+)= W X, W^T X or K X: the last kernel adds into Y itself

@@ -15,6 +15,8 @@ Reference counterparts (file:line under /root/reference/hippyflow):
                                                   with the caller's noise, ``Rsolver``, no ``R`` (``randomized.doublePassC`` needs none)
 * ``InterpolatedCovarianceFactor`` / ``InterpolatedKernelPrior``  the same two over SCATTERED points (mesh nodes): the factor K = F F^T,
                                                   F = [W S | diag(sqrt(delta))] (hfmi_op_interp_factor), of the interpolated grid covariance
+* ``BoxSpectralCovariance`` / ``BoxSpectralPrior``  the Whittle-Matern prior on a box by DCT / FFT (hfmi_op_box): C, R = C^-1 and both roots
+                                                  exact, the full prior protocol (hippylib BiLaplacianPrior on a tensor grid, lumped mass)
 * ``KernelCrossCovarianceOperator``               K(T, S) between two point sets (Nystrom extension); ``KernelCovarianceOperator.rows`` /
                                                   ``.sharded``: a row slab of C per rank, completed by the collective's SUM
 * ``CsrOperator`` / ``CsrPCGSolver``              prior.M / prior.R and prior.Msolver (used at KLEProjector.py:163-168)
@@ -1033,6 +1035,312 @@ class InterpolatedKernelPrior(_KernelFactorPrior):
         self._setup(op, sampler, self.F, mean, M, Msolver)
 
     factor_error_bound = property(lambda self: self.F.factor_error_bound)
+
+
+class _BoxPowerOperator(DeviceOperator):
+    """``W^a T_s W^b`` of a ``BoxSpectralCovariance`` (hfmi_op_box); ``transpose()`` is ``W^(1+b) T_s W^(a-1)``, its transpose (T_s^T =
+    W T_s W^-1: T_s = Phi Lambda^s Phi^* W is self-adjoint in the W inner product).  The operator keeps the box alive."""
+
+    def __init__(self, box, s, a, b, _other=None):
+        super().__init__(box.ctx, box.N)
+        self.box = box
+        self.power = (float(s), float(a), float(b))
+        self._other = _other
+        L.call("hfmi_op_box", box.handle, self.power[0], self.power[1], self.power[2], C.byref(self._op))
+
+    def transpose(self):
+        if self._other is None:
+            s, a, b = self.power
+            self._other = _BoxPowerOperator(self.box, s, 1.0 + b, a - 1.0, _other=self)
+        return self._other
+
+    def transpmult(self, x, y):
+        self.transpose().mult(x, y)
+
+    def matMvTranspmult(self, X, Y, accumulate=False):
+        self.transpose().matMvMult(X, Y, accumulate=accumulate)
+
+    def solve(self, y, x):
+        """y = (this operator)^-1 x when the inverse is at hand as another power of the same box: ``W^-b T_-s W^-a``."""
+        s, a, b = self.power
+        self.box.power(-s, -b, -a).mult(x, y)
+
+
+class BoxSpectralCovariance:
+    """The Whittle-Matern operator ``(delta - gamma div Theta grad)^(-alpha)`` on a box, on a regular grid with Neumann or periodic sides
+    and axis-aligned ``Theta = diag(theta)``, diagonalised by cosine and Fourier transforms (hfmi_box_*, hfmi_boxcov.hip; include/hfmi.h
+    states the contract).  Covariance, precision and both square roots are each one transform - multiply - inverse transform, exact up
+    to rounding and O(N log N): nothing is grown, clipped, iterated or approximated, and a noise vector has N entries.
+
+    ``shape``: nodes per axis (1 to 3 axes, axis 0 fastest, the numbering of ``grid_node_points``).  ``boundary``: "neumann" or
+    "periodic", one string or one per axis; a Neumann axis has 1 node or 2^m + 1 <= 2049, a periodic one 2^m <= 4096.  ``symbol``:
+    "fd" (the two-point stiffness with lumped mass: R = A W^-1 A exactly, A = delta W + gamma K; with Neumann sides and alpha = 2 the
+    BiLaplacian prior on a tensor grid with lumped mass) or "continuous" ((t_k / h)^2).  Not itself an operator; the ``DeviceOperator``s
+    are made on first use: ``.C`` (covariance of the nodal values), ``.R`` (= C^-1), ``.S`` (S S^T = C; ``.S.transpose()``,
+    ``transpmult``, ``matMvTranspmult`` as ``GridCovarianceFactor`` has them), ``.Sinv`` (whitening) and ``.power(s, a, b)`` =
+    ``W^a T_s W^b``.  ``.points``, ``.weights`` (N,), ``.spectrum()`` (mode-array shape, axis 0 first), ``.modes()`` (the dense
+    W-orthonormal ``Phi`` on the host, from cosines and exponentials only, no FFT) and ``.to_dense(which)`` from those three are for
+    checks at sizes where N x N fits."""
+
+    def __init__(self, shape, spacing, gamma, delta, alpha=2.0, theta=None, boundary="neumann", symbol="fd", origin=None, ctx=None):
+        raw = np.atleast_1d(np.asarray(shape))
+        if raw.ndim != 1 or not 1 <= raw.size <= 3:
+            raise ValueError("a grid has 1, 2 or 3 axes, got shape %r" % (shape,))
+        if raw.dtype.kind not in "iuf" or not np.all(np.isfinite(raw)) or not np.all(raw == np.round(raw)):
+            raise ValueError("shape: whole numbers of nodes per axis, got %r" % (shape,))
+        n = raw.astype(np.int64)
+        d = int(n.size)
+        bd = [boundary] * d if isinstance(boundary, str) else list(boundary)
+        if len(bd) != d or any(b not in L.BOX_BOUNDARIES for b in bd):
+            raise ValueError("boundary: 'neumann' or 'periodic', one string or one per axis, got %r" % (boundary,))
+        for c in range(d):
+            v = int(n[c])
+            if bd[c] == "neumann":
+                ok = v == 1 or (2 <= v <= L.BOX_MAX_NEUMANN and (v - 1) & (v - 2) == 0)
+            else:
+                ok = 1 <= v <= L.BOX_MAX_PERIODIC and v & (v - 1) == 0
+            if not ok:
+                raise ValueError("axis %d: %d nodes; a Neumann axis has 1 node or 2^m + 1 <= %d, a periodic axis 2^m <= %d"
+                                 % (c, v, L.BOX_MAX_NEUMANN, L.BOX_MAX_PERIODIC))
+        if symbol not in L.BOX_SYMBOLS:
+            raise ValueError("symbol is 'fd' or 'continuous', got %r" % (symbol,))
+        h = np.asarray(spacing, dtype=np.float64)
+        h = np.full(d, float(h)) if h.ndim == 0 else h
+        if h.shape != n.shape or not np.all(np.isfinite(h)) or not np.all(h > 0.0):
+            raise ValueError("spacing: one positive finite number per axis, got %r" % (spacing,))
+        th = np.ones(d) if theta is None else np.asarray(theta, dtype=np.float64)
+        th = np.full(d, float(th)) if th.ndim == 0 else th
+        if th.shape != n.shape or not np.all(np.isfinite(th)) or not np.all(th > 0.0):
+            raise ValueError("theta: one positive finite number per axis, got %r" % (theta,))
+        for name, v in (("gamma", gamma), ("delta", delta), ("alpha", alpha)):
+            if not (np.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError("%s must be positive and finite, got %r" % (name, v))
+        o = np.zeros(d) if origin is None else np.asarray(origin, dtype=np.float64)
+        if o.shape != n.shape or not np.all(np.isfinite(o)):
+            raise ValueError("origin: one finite number per axis, got %r" % (origin,))
+        self._ctx = ctx
+        self.grid_shape = tuple(int(v) for v in n)
+        self.N = int(np.prod(n))
+        self.spacing, self.origin, self.theta = np.ascontiguousarray(h), o, np.ascontiguousarray(th)
+        self.boundary, self.symbol = tuple(bd), symbol
+        self.gamma, self.delta, self.alpha = float(gamma), float(delta), float(alpha)
+        self.points = L.as_f64(grid_node_points(n, h, None, o))
+        self._ops = {}
+        self._handle = None
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = L.Context.default()
+        return self._ctx
+
+    @property
+    def handle(self):
+        """The hfmi_box, made at the first device use: the host formulas (``weights``, ``spectrum``, ``modes``, ``to_dense``) need none."""
+        if self._handle is None:
+            h = C.c_void_p()
+            n = np.ascontiguousarray(self.grid_shape, dtype=np.int64)
+            bnd = np.ascontiguousarray([L.BOX_BOUNDARIES[b] for b in self.boundary], dtype=np.int32)
+            L.call("hfmi_box_create", self.ctx.handle, int(n.size), L.ptr(n), L.ptr(self.spacing), L.ptr(bnd), self.gamma, self.delta,
+                   self.alpha, L.ptr(self.theta), L.BOX_SYMBOLS[self.symbol], C.byref(h))
+            self._handle = h
+        return self._handle
+
+    def power(self, s, a=0.0, b=0.0):
+        """``W^a T_s W^b`` as a ``DeviceOperator`` (made once per (s, a, b))."""
+        key = (float(s), float(a), float(b))
+        if key not in self._ops:
+            self._ops[key] = _BoxPowerOperator(self, *key)
+        return self._ops[key]
+
+    C = property(lambda self: self.power(1.0, 0.0, -1.0))
+    R = property(lambda self: self.power(-1.0, 1.0, 0.0))
+    S = property(lambda self: self.power(0.5, 0.0, -0.5))
+    Sinv = property(lambda self: self.power(-0.5, 0.5, 0.0))
+
+    def _axis_weights(self, c):
+        n, h = self.grid_shape[c], float(self.spacing[c])
+        if self.boundary[c] == "periodic":
+            return np.full(n, h)
+        if n == 1:
+            return np.ones(1)
+        w = np.full(n, h)
+        w[0] = w[-1] = 0.5 * h
+        return w
+
+    @property
+    def weights(self):
+        """(N,) quadrature weights ``prod_c w_c`` of the nodes: the diagonal of the lumped mass matrix W."""
+        w = np.ones(1)
+        for c in range(len(self.grid_shape)):      # axis 0 fastest: node g = i0 + n0 (i1 + n1 i2)
+            w = np.kron(self._axis_weights(c), w)
+        return np.ascontiguousarray(w)
+
+    def _axis_symbol(self, c):
+        n, h = self.grid_shape[c], float(self.spacing[c])
+        k = np.arange(n)
+        if self.boundary[c] == "periodic":
+            t = 2.0 * np.pi * np.where(2 * k <= n, k, k - n) / n
+        else:
+            t = np.pi * k / (n - 1) if n > 1 else np.zeros(1)
+        # fd: (2 - 2 cos t) / h^2, written without the cancellation at small t
+        return (t / h) ** 2 if self.symbol == "continuous" else (2.0 * np.sin(0.5 * t) / h) ** 2
+
+    def spectrum(self):
+        """``lambda_k = (delta + gamma sum_c theta_c mu_c(k_c))^(-alpha)`` in mode-array shape ``grid_shape`` (entry [k0, k1, k2]), natural
+        mode order, on the host (hfmi_box_spectrum is the library's statement of the same numbers)."""
+        total = np.zeros(self.grid_shape)
+        for c in range(len(self.grid_shape)):
+            shape = [1] * len(self.grid_shape)
+            shape[c] = self.grid_shape[c]
+            total = total + self.theta[c] * self._axis_symbol(c).reshape(shape)
+        return (self.delta + self.gamma * total) ** (-self.alpha)
+
+    def _axis_modes(self, c):
+        n, h = self.grid_shape[c], float(self.spacing[c])
+        j = np.arange(n)[:, None]
+        k = np.arange(n)[None, :]
+        if self.boundary[c] == "periodic":
+            ks = np.where(2 * k <= n, k, k - n)
+            return np.exp(2j * np.pi * j * ks / n) / np.sqrt(n * h)
+        if n == 1:
+            return np.ones((1, 1))
+        e = np.where((k == 0) | (k == n - 1), 1.0, 2.0)
+        return np.sqrt(e / ((n - 1) * h)) * np.cos(np.pi * j * k / (n - 1))
+
+    def modes(self):
+        """The dense (N, N) ``Phi``: L2-normalised cosines (Neumann) and exponentials (periodic) sampled at the nodes, column k0 + n0 (k1 +
+        n1 k2); ``Phi^* W Phi = I`` and ``C = Phi Lambda Phi^*``.  Complex when an axis is periodic."""
+        Phi = np.ones((1, 1))
+        for c in range(len(self.grid_shape)):
+            Phi = np.kron(self._axis_modes(c), Phi)
+        return Phi
+
+    def dense_power(self, s, a=0.0, b=0.0):
+        """``W^a T_s W^b = W^a Phi Lambda^s Phi^* W^(1+b)`` as a dense host matrix."""
+        Phi, w = self.modes(), self.weights
+        lam = self.spectrum().transpose().ravel()       # column order of Phi: k0 fastest
+        A = (Phi * lam ** float(s)) @ Phi.conj().T
+        return np.ascontiguousarray((w ** float(a))[:, None] * A.real * (w ** (1.0 + float(b)))[None, :])
+
+    def to_dense(self, which="C"):
+        """"C", "R", "S" (also "St", "Sinv") on the host, from ``modes()``, ``spectrum()`` and ``weights``."""
+        powers = {"C": (1.0, 0.0, -1.0), "R": (-1.0, 1.0, 0.0), "S": (0.5, 0.0, -0.5), "St": (0.5, 0.5, -1.0), "Sinv": (-0.5, 0.5, 0.0)}
+        if which not in powers:
+            raise ValueError("to_dense: which is one of %s, got %r" % (sorted(powers), which))
+        return self.dense_power(*powers[which])
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                L.load().hfmi_box_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+
+class BoxSpectralPrior:
+    """A ``BoxSpectralCovariance`` behind the FULL prior protocol of the drivers (projectors.py, datagen.py, datasets.py, errors.py): unlike
+    the kernel priors it has a precision.  ``R`` and ``C`` are the box's device operators, ``Rsolver.solve(y, x)`` is y = C x (host or
+    device vectors; ``as_device_operator(prior.Rsolver)`` is ``box.C``, no host callback), so ``ActiveSubspaceProjector``, ``doublePassG``
+    and ``singlePassG`` take their existing routes with B and B^-1 both on the device.  ``init_vector(x, "noise")`` gives N entries;
+    ``sample(noise, m, add_mean=True)`` is m = mean + S noise; ``sample_block(n)`` fills an (N, n) block with the device's Philox normals
+    (hfmi_randn_fill, key ``seed``, stream = the number of earlier calls), applies S, adds the mean and returns (n, N);
+    ``cost(m)`` = 0.5 (m - mean)^T R (m - mean).  ``M`` / ``Msolver`` are whatever the caller has (``scipy.sparse.diags(box.weights)`` is
+    the lumped mass matrix; KLE with ``orthogonality='mass'`` over it is the analytical KLE)."""
+
+    def __init__(self, box, mean=None, M=None, Msolver=None, seed=0):
+        if not isinstance(box, BoxSpectralCovariance):
+            raise ValueError("BoxSpectralPrior: a BoxSpectralCovariance is required (got %s)" % type(box).__name__)
+        self.box = box
+        self.ctx = box.ctx
+        self.N = box.N
+        self.R, self.C, self.S = box.R, box.C, box.S
+        self.Rsolver = _GridCovarianceSolver(self.C)
+        if M is not None:
+            self.M = M
+        if Msolver is not None:
+            self.Msolver = Msolver
+        self.seed = int(seed)
+        self._calls = 0                  # sample_block's stream: the number of earlier calls
+        mean = np.zeros(self.N) if mean is None else np.asarray(mean.get_local() if hasattr(mean, "get_local") else mean, dtype=np.float64)
+        if mean.shape != (self.N,):
+            raise ValueError("BoxSpectralPrior: the mean has %s entries, the box %d nodes" % (mean.shape, self.N))
+        self._mean = mean.copy()
+        self._mean_dev = None            # the mean as a device Vector, made when a device vector first needs it
+        self.mean = H.new_host_vector()
+        self.mean.init(self.N)
+        self.mean.set_local(self._mean)
+        self.mean.apply("")
+
+    def init_vector(self, x, dim):
+        x.init(self.N)
+
+    @staticmethod
+    def _host_array(v):
+        if isinstance(v, np.ndarray):
+            return np.asarray(v, dtype=np.float64)
+        return np.asarray(v.get_local() if H.is_host_vector(v) else v._mv.to_vectors()[0], dtype=np.float64)
+
+    def _device_mean(self):
+        if self._mean_dev is None:
+            self._mean_dev = Vector(ctx=self.ctx)
+            self._mean_dev.init(self.N)
+            self._mean_dev.set_local(self._mean)
+        return self._mean_dev
+
+    def sample(self, noise, m, add_mean=True):
+        """m = mean + S noise (``add_mean=False``: without the mean); noise and m have N entries.  Two device ``Vector``s stay on the
+        device (one apply of S and an axpy with the mean, no transfer); host vectors, or a mixed pair, go through the host."""
+        if isinstance(noise, Vector) and isinstance(m, Vector):
+            if noise.size() != self.N or m.size() != self.N:
+                raise ValueError("BoxSpectralPrior.sample: noise and m have %d and %d entries, the box %d nodes" % (noise.size(), m.size(), self.N))
+            self.S.mult(noise, m)
+            if add_mean:
+                m.axpy(1.0, self._device_mean())
+            return
+        xi = self._host_array(noise)
+        if xi.shape != (self.N,):
+            raise ValueError("BoxSpectralPrior.sample: the noise has %s entries, the box %d nodes" % (xi.shape, self.N))
+        Xi = MultiVector.from_vectors(xi[None, :], ctx=self.ctx)
+        Y = MultiVector(self.N, 1, ctx=self.ctx)
+        self.S.matMvMult(Xi, Y)
+        y = Y.to_vectors()[0]
+        if add_mean:
+            y = y + self._mean
+        if H.is_host_vector(m):
+            m.set_local(y)
+            m.apply("")
+        else:
+            L.call("hfmi_block_upload", m._mv.handle, L.ptr(L.as_f64(y[None, :])), L.LAYOUT_VECTORS)
+
+    def sample_block(self, n):
+        """(n, N) array of n draws mean + S Xi, Xi the (N, n) block hfmi_randn_fill makes with key ``seed`` and stream = the number of
+        earlier calls of this method."""
+        Xi = MultiVector(self.N, int(n), ctx=self.ctx)
+        L.call("hfmi_randn_fill", Xi.handle, C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), C.c_uint32(self._calls & 0xFFFFFFFF), 1.0)
+        self._calls += 1
+        Y = MultiVector(self.N, int(n), ctx=self.ctx)
+        self.S.matMvMult(Xi, Y)
+        return np.ascontiguousarray(Y.to_dense().T) + self._mean[None, :]
+
+    def cost(self, m):
+        """0.5 (m - mean)^T R (m - mean).  A device ``Vector`` stays on the device (an axpy, one apply of R, one inner product: only the
+        number comes back); a host vector or an array is uploaded once and R (m - mean) comes back for the inner product on the host."""
+        if isinstance(m, Vector):
+            if m.size() != self.N:
+                raise ValueError("BoxSpectralPrior.cost: m has %d entries, the box %d nodes" % (m.size(), self.N))
+            dm = m.copy()
+            dm.axpy(-1.0, self._device_mean())
+            y = Vector(ctx=self.ctx)
+            y.init(self.N)
+            self.R.mult(dm, y)
+            return 0.5 * dm.inner(y)
+        dm = self._host_array(m) - self._mean
+        X = MultiVector.from_vectors(dm[None, :], ctx=self.ctx)
+        Y = MultiVector(self.N, 1, ctx=self.ctx)
+        self.R.matMvMult(X, Y)
+        return 0.5 * float(dm @ Y.to_vectors()[0])
 
 
 def _is_null_collective(collective):

@@ -67,6 +67,7 @@ typedef struct hfmi_comm hfmi_comm;
 typedef struct hfmi_amg hfmi_amg;
 typedef struct hfmi_pchol hfmi_pchol;
 typedef struct hfmi_grid_sampler hfmi_grid_sampler;
+typedef struct hfmi_box hfmi_box;
 
 /* ---------------------------------------------------------------- context */
 HFMI_API const char* hfmi_last_error(void);
@@ -450,6 +451,45 @@ HFMI_API int hfmi_interp_sampler_draw(hfmi_op* op, hfmi_grid_sampler* grid_sampl
  *     lengths). */
 HFMI_API int hfmi_op_interp_factor(hfmi_op* interp_cov_op, hfmi_grid_sampler* grid_sampler, int transpose /* 0: F | 1: F^T */,
                                    hfmi_op** out);
+/*     WHITTLE-MATERN PRIORS ON A BOX by DCT and FFT (hfmi_boxcov.hip): the SPDE prior (delta - gamma div Theta grad)^(-alpha) on a regular
+ *     grid of d = 1, 2 or 3 axes (axis 0 fastest, node g = i0 + n0 (i1 + n1 i2)) with axis-aligned Theta = diag(theta) and, per axis, a
+ *     NEUMANN side (n_c = 1, or n_c - 1 a power of two with n_c <= 2049; line length P_c = 2 (n_c - 1), 1 for one node; quadrature
+ *     weight w = h_c, halved at the two end nodes, 1 for one node; mode k = 0 .. n_c - 1 at the angle t_k = pi k / (n_c - 1)) or a
+ *     PERIODIC one (n_c a power of two <= 4096; P_c = n_c, w = h_c; mode k at t_k = 2 pi k~ / n_c with the signed k~ = k up to n_c / 2 and
+ *     k - n_c above).  Cosine and Fourier transforms diagonalise it:  lambda_k = (delta + gamma sum_c theta_c mu_c(k_c))^(-alpha)  with
+ *     mu_c = (2 - 2 cos t_k) / h_c^2 (symbol HFMI_BOX_SYMBOL_FD, the two-point stiffness with lumped mass; evaluated as
+ *     (2 sin(t_k / 2) / h_c)^2) or (t_k / h_c)^2 (HFMI_BOX_SYMBOL_CONTINUOUS).  With W = diag(prod_c w_c) and
+ *       T_s x = restrict( IFFT_unnormalised( (lambda^s / prod P_c) . FFT( extend(x) ) ) ),
+ *     extend the even mirror of every Neumann axis (position P - j takes x_j, 1 <= j <= n - 2) and restrict the first n_c positions,
+ *     hfmi_op_box(box, s, a, b) is the N x N operator  W^a T_s W^b:  the covariance of the nodal values C = T_1 W^-1 (s, a, b = 1, 0, -1),
+ *     the precision R = C^-1 = W T_-1 (-1, 1, 0), the factor S = T_1/2 W^-1/2 with S S^T = C (1/2, 0, -1/2), S^T = W^1/2 T_1/2 W^-1
+ *     (1/2, 1/2, -1) and the whitening S^-1 = W^1/2 T_-1/2 (-1/2, 1/2, 0) -- all exact up to rounding, nothing grown, clipped or
+ *     iterated.  With the fd symbol R = A W^-1 A, A = delta W + gamma K, K the tensor sum of the 1-D two-point stiffness matrices: on
+ *     Neumann sides and alpha = 2 the BiLaplacian prior on a tensor grid with lumped mass.
+ *     Applied through hfmi_op_apply: 2 d - 1 passes of k_boxcov_pass per pair of columns over a work buffer of N complex entries per
+ *     pair (the rules: csrc/hfmi_boxcov_plan.h), two real columns per complex transform (a last odd column pairs with zeros), chunked
+ *     by "fftcov_pairs" with identical bits; no atomics, two applies are bit-identical; block storage contract as every operator
+ *     (padding rows untouched, accumulate adds).  The table lambda^s / prod P_c is made once per operator.  The operator shares the
+ *     box's state: either may be destroyed first.  hfmi_box_spectrum: the N eigenvalues lambda_k in natural mode order,
+ *     entry k0 + n0 (k1 + n1 k2), computed on the host.  hfmi_boxcov_plan_predict: the apply's launch plan without a device;
+ *     words[HFMI_BOXCOV_PLAN_WORDS]:  0 d  1-3 n_c  4 N  5 pairs  6 pairs per chunk  7 chunks  8 passes  9 bytes of work buffer per pair
+ *     10 twiddle entries  11 max P_c  12 static LDS of the pass kernel  13-15 P_c; then 16 words per pass from word 16:  axis, flags (as
+ *     hfmi_fftcov_plan_predict), line length, mirror, extent n_axis, line stride, line span, lines, lines per workgroup, LDS line
+ *     stride, threads, dynamic LDS, static + dynamic LDS, grid x; line l starts at entry (l mod stride) + (l div stride) span.
+ *     HFMI_ERR_INVALID: d outside 1..3; an n_c outside the rules above; a boundary or a symbol that is none of the constants; h, gamma,
+ *     delta, alpha or a theta that is not positive and finite (theta NULL = all ones); powers that are not finite; a pass that cannot
+ *     be launched; at apply, blocks of another length.  A failed create frees everything, *out untouched. */
+#define HFMI_BOX_NEUMANN 0
+#define HFMI_BOX_PERIODIC 1
+#define HFMI_BOX_SYMBOL_FD 0
+#define HFMI_BOX_SYMBOL_CONTINUOUS 1
+#define HFMI_BOXCOV_PLAN_WORDS 96
+HFMI_API int hfmi_box_create(hfmi_ctx* ctx, int d, const int64_t* n /* d */, const double* h /* d */, const int* boundary /* d */, double gamma,
+                             double delta, double alpha, const double* theta_or_null /* d */, int symbol, hfmi_box** out);
+HFMI_API int hfmi_box_destroy(hfmi_box* box);
+HFMI_API int hfmi_box_spectrum(const hfmi_box* box, double* host_lambda /* N */);
+HFMI_API int hfmi_op_box(hfmi_box* box, double s, double a, double b, hfmi_op** out);
+HFMI_API int hfmi_boxcov_plan_predict(int d, const int64_t* n, const int* boundary, int nvec, int64_t budget_bytes, int64_t* words);
 /*     low-rank factor of that covariance WITHOUT any apply: the greedy (diagonally pivoted) partial Cholesky factorisation
  *     C ~= L L^T (hfmi_pchol.hip).  It reads the diagonal of C and the pivot columns only -- N k^2 flops and 4 N k^2 bytes for rank k,
  *     against 2 N^2 k flops per apply -- and returns the trace of the residual C - L L^T after every step; the residual is positive
