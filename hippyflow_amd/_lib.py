@@ -26,7 +26,8 @@ GRID_COV_LONG_MAX_GROWTH = 6                           # growth of hfmi_grid_sam
 FFTCOV_LONG_PLAN_WORDS = 280                           # HFMI_FFTCOV_LONG_PLAN_WORDS of include/hfmi.h
 BOX_BOUNDARIES = {"neumann": 0, "periodic": 1}          # HFMI_BOX_NEUMANN / _PERIODIC of include/hfmi.h
 BOX_SYMBOLS = {"fd": 0, "continuous": 1}               # HFMI_BOX_SYMBOL_*
-BOX_MAX_NEUMANN, BOX_MAX_PERIODIC = 2049, 4096         # nodes of an axis of hfmi_box_create (hfmi_boxcov_plan.h)
+BOX_MAX_NEUMANN, BOX_MAX_PERIODIC = 2049, 4096         # most nodes of an axis of hfmi_box_create (hfmi_boxcov_plan.h: a line of 4096
+#                                                        entries; which node counts below are legal: operators._box_axis_ok)
 BOXCOV_PLAN_WORDS = 96                                 # HFMI_BOXCOV_PLAN_WORDS of include/hfmi.h
 PC_CHUNK = 256                                         # columns of the pivot's row per LDS chunk (hfmi_pchol.hip)
 PCHOL_STOP_REASONS = ("max_rank", "rel_tol", "floor")  # HFMI_PCHOL_* of include/hfmi.h

@@ -1066,6 +1066,22 @@ class _BoxPowerOperator(DeviceOperator):
         self.box.power(-s, -b, -a).mult(x, y)
 
 
+def _box_axis_ok(n, boundary):
+    """The rule of an axis of a box (boxcov_axis_ok of csrc/hfmi_boxcov_plan.h): the transformed line of P = 2 (n - 1) entries (Neumann,
+    1 for one node) or P = n (periodic) is a power of two, or a multiple of 4 with no prime factor but 2, 3 and 5."""
+    if n < 1 or n > (L.BOX_MAX_NEUMANN if boundary == "neumann" else L.BOX_MAX_PERIODIC):
+        return False
+    P = (2 * (n - 1) if n > 1 else 1) if boundary == "neumann" else n
+    if P & (P - 1) == 0:
+        return True
+    if P % 4:
+        return False
+    for r in (2, 3, 5):
+        while P % r == 0:
+            P //= r
+    return P == 1
+
+
 class BoxSpectralCovariance:
     """The Whittle-Matern operator ``(delta - gamma div Theta grad)^(-alpha)`` on a box, on a regular grid with Neumann or periodic sides
     and axis-aligned ``Theta = diag(theta)``, diagonalised by cosine and Fourier transforms (hfmi_box_*, hfmi_boxcov.hip; include/hfmi.h
@@ -1073,7 +1089,9 @@ class BoxSpectralCovariance:
     to rounding and O(N log N): nothing is grown, clipped, iterated or approximated, and a noise vector has N entries.
 
     ``shape``: nodes per axis (1 to 3 axes, axis 0 fastest, the numbering of ``grid_node_points``).  ``boundary``: "neumann" or
-    "periodic", one string or one per axis; a Neumann axis has 1 node or 2^m + 1 <= 2049, a periodic one 2^m <= 4096.  ``symbol``:
+    "periodic", one string or one per axis.  The transformed line of an axis, 2 (n - 1) entries on a Neumann axis of n > 1 nodes and n on a
+    periodic one, is a power of two or a multiple of 4 of the form 2^m 3^a 5^b, at most 4096: 2^m + 1 nodes as well as 7, 11, 13, 25, 49,
+    97, 101, 193, 201, 385 ... Neumann (at most 2049), 2^m as well as 12, 20, 24, 48, 96, 100, 192 ... periodic (at most 4096).  ``symbol``:
     "fd" (the two-point stiffness with lumped mass: R = A W^-1 A exactly, A = delta W + gamma K; with Neumann sides and alpha = 2 the
     BiLaplacian prior on a tensor grid with lumped mass) or "continuous" ((t_k / h)^2).  Not itself an operator; the ``DeviceOperator``s
     are made on first use: ``.C`` (covariance of the nodal values), ``.R`` (= C^-1), ``.S`` (S S^T = C; ``.S.transpose()``,
@@ -1095,13 +1113,10 @@ class BoxSpectralCovariance:
             raise ValueError("boundary: 'neumann' or 'periodic', one string or one per axis, got %r" % (boundary,))
         for c in range(d):
             v = int(n[c])
-            if bd[c] == "neumann":
-                ok = v == 1 or (2 <= v <= L.BOX_MAX_NEUMANN and (v - 1) & (v - 2) == 0)
-            else:
-                ok = 1 <= v <= L.BOX_MAX_PERIODIC and v & (v - 1) == 0
-            if not ok:
-                raise ValueError("axis %d: %d nodes; a Neumann axis has 1 node or 2^m + 1 <= %d, a periodic axis 2^m <= %d"
-                                 % (c, v, L.BOX_MAX_NEUMANN, L.BOX_MAX_PERIODIC))
+            if not _box_axis_ok(v, bd[c]):
+                raise ValueError("axis %d: %d nodes; the line of an axis, 2 (n - 1) entries on a Neumann axis of n > 1 nodes and n on a "
+                                 "periodic one, is a power of two or a multiple of 4 with no prime factor but 2, 3 and 5; a Neumann axis "
+                                 "has at most %d nodes, a periodic one %d" % (c, v, L.BOX_MAX_NEUMANN, L.BOX_MAX_PERIODIC))
         if symbol not in L.BOX_SYMBOLS:
             raise ValueError("symbol is 'fd' or 'continuous', got %r" % (symbol,))
         h = np.asarray(spacing, dtype=np.float64)

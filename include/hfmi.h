@@ -453,10 +453,13 @@ HFMI_API int hfmi_op_interp_factor(hfmi_op* interp_cov_op, hfmi_grid_sampler* gr
                                    hfmi_op** out);
 /*     WHITTLE-MATERN PRIORS ON A BOX by DCT and FFT (hfmi_boxcov.hip): the SPDE prior (delta - gamma div Theta grad)^(-alpha) on a regular
  *     grid of d = 1, 2 or 3 axes (axis 0 fastest, node g = i0 + n0 (i1 + n1 i2)) with axis-aligned Theta = diag(theta) and, per axis, a
- *     NEUMANN side (n_c = 1, or n_c - 1 a power of two with n_c <= 2049; line length P_c = 2 (n_c - 1), 1 for one node; quadrature
+ *     NEUMANN side (n_c <= 2049; line length P_c = 2 (n_c - 1), 1 for one node; quadrature
  *     weight w = h_c, halved at the two end nodes, 1 for one node; mode k = 0 .. n_c - 1 at the angle t_k = pi k / (n_c - 1)) or a
- *     PERIODIC one (n_c a power of two <= 4096; P_c = n_c, w = h_c; mode k at t_k = 2 pi k~ / n_c with the signed k~ = k up to n_c / 2 and
- *     k - n_c above).  Cosine and Fourier transforms diagonalise it:  lambda_k = (delta + gamma sum_c theta_c mu_c(k_c))^(-alpha)  with
+ *     PERIODIC one (n_c <= 4096; P_c = n_c, w = h_c; mode k at t_k = 2 pi k~ / n_c with the signed k~ = k up to n_c / 2 and
+ *     k - n_c above).  THE RULE OF AN AXIS: its line length P_c is a power of two (Neumann 1 or 2^m + 1 nodes, periodic 2^m), or a
+ *     multiple of 4 with no prime factor but 2, 3 and 5 (a mixed-radix line: Neumann 7, 11, 13, 25, 49, 97, 101, 193, 201, 385 ... nodes,
+ *     periodic 12, 20, 24, 48, 96, 100, 192 ...); every other n_c is refused, a line that is no multiple of 4 included (Neumann 4, 6, 8
+ *     nodes; periodic 6, 18).  Cosine and Fourier transforms diagonalise it:  lambda_k = (delta + gamma sum_c theta_c mu_c(k_c))^(-alpha)  with
  *     mu_c = (2 - 2 cos t_k) / h_c^2 (symbol HFMI_BOX_SYMBOL_FD, the two-point stiffness with lumped mass; evaluated as
  *     (2 sin(t_k / 2) / h_c)^2) or (t_k / h_c)^2 (HFMI_BOX_SYMBOL_CONTINUOUS).  With W = diag(prod_c w_c) and
  *       T_s x = restrict( IFFT_unnormalised( (lambda^s / prod P_c) . FFT( extend(x) ) ) ),
@@ -466,16 +469,19 @@ HFMI_API int hfmi_op_interp_factor(hfmi_op* interp_cov_op, hfmi_grid_sampler* gr
  *     (1/2, 1/2, -1) and the whitening S^-1 = W^1/2 T_-1/2 (-1/2, 1/2, 0) -- all exact up to rounding, nothing grown, clipped or
  *     iterated.  With the fd symbol R = A W^-1 A, A = delta W + gamma K, K the tensor sum of the 1-D two-point stiffness matrices: on
  *     Neumann sides and alpha = 2 the BiLaplacian prior on a tensor grid with lumped mass.
- *     Applied through hfmi_op_apply: 2 d - 1 passes of k_boxcov_pass per pair of columns over a work buffer of N complex entries per
+ *     Applied through hfmi_op_apply: 2 d - 1 passes of k_boxcov_pass (a power-of-two line) or k_boxcov_pass_mr (a mixed-radix line:
+ *     radix-3 and radix-5 stages before the radix-4 / radix-2 ones) per pair of columns over a work buffer of N complex entries per
  *     pair (the rules: csrc/hfmi_boxcov_plan.h), two real columns per complex transform (a last odd column pairs with zeros), chunked
  *     by "fftcov_pairs" with identical bits; no atomics, two applies are bit-identical; block storage contract as every operator
  *     (padding rows untouched, accumulate adds).  The table lambda^s / prod P_c is made once per operator.  The operator shares the
  *     box's state: either may be destroyed first.  hfmi_box_spectrum: the N eigenvalues lambda_k in natural mode order,
  *     entry k0 + n0 (k1 + n1 k2), computed on the host.  hfmi_boxcov_plan_predict: the apply's launch plan without a device;
  *     words[HFMI_BOXCOV_PLAN_WORDS]:  0 d  1-3 n_c  4 N  5 pairs  6 pairs per chunk  7 chunks  8 passes  9 bytes of work buffer per pair
- *     10 twiddle entries  11 max P_c  12 static LDS of the pass kernel  13-15 P_c; then 16 words per pass from word 16:  axis, flags (as
+ *     10 entries of the power-of-two lines' twiddle table  11 the largest power-of-two P_c (1 when there is none)  12 static LDS of the
+ *     pass kernels  13-15 P_c; then 16 words per pass from word 16:  axis, flags (as
  *     hfmi_fftcov_plan_predict), line length, mirror, extent n_axis, line stride, line span, lines, lines per workgroup, LDS line
- *     stride, threads, dynamic LDS, static + dynamic LDS, grid x; line l starts at entry (l mod stride) + (l div stride) span.
+ *     stride, threads, dynamic LDS, static + dynamic LDS, grid x, radix-3 stages, radix-5 stages (both 0: a power-of-two line); line l
+ *     starts at entry (l mod stride) + (l div stride) span.
  *     HFMI_ERR_INVALID: d outside 1..3; an n_c outside the rules above; a boundary or a symbol that is none of the constants; h, gamma,
  *     delta, alpha or a theta that is not positive and finite (theta NULL = all ones); powers that are not finite; a pass that cannot
  *     be launched; at apply, blocks of another length.  A failed create frees everything, *out untouched. */
