@@ -7,7 +7,7 @@
 // and what a pass does at the ends of a line is in hfmi_boxcov_plan.h; this unit holds the kernels, the box's state and the launcher.
 //
 // k_boxcov_pass: `lpw` lines along one axis, one workgroup, the lines in LDS; the radix-4 and radix-2 stages and the quarter twiddle
-// table are those of k_fftcov_pass (hfmi_fftcov.hip), copied: that kernel and its results are untouched.  What differs is the ends: a
+// table are the ones k_fftcov_pass (hfmi_fftcov.hip) runs, and live in hfmi_fft_lds.h.  What differs from that kernel is the ends: a
 // Neumann axis is mirrored into LDS on its time-side load, which makes the complex FFT a DCT-I of the real and of the imaginary part,
 // and only its n modes are kept in the buffer; the line map divides, because strides are products of n_b and no powers of two; the
 // scatter from the input block and the gather into the output block are fused into the first load and the last store, with W^b and W^a
@@ -18,10 +18,12 @@
 //
 // k_boxcov_pass_mr: the same pass for a MIXED-RADIX line, P = 3^a 5^b Q entries with the power-of-two tail Q >= 4 (the rule of an axis,
 // the order of the stages and the position map: hfmi_boxcov_plan.h).  Forward it runs one radix-3 or radix-5 stage per odd factor, then
-// the radix-4 / radix-2 stages on every block of Q entries; the inverse is the transposed stages in reverse order.  The ends are
-// k_boxcov_pass's with the bit reversal replaced by the position map, read from a table built on the host (mode[p] and pos[m]); twiddles
-// come from a quarter table of the line's own length.  A pass along an axis whose line is a power of two launches k_boxcov_pass with
-// the twiddle table and shape it always had, also in a grid whose other axes are mixed-radix: its results are bit for bit what they were.
+// the radix-4 / radix-2 stages on every block of Q entries; the inverse is the transposed stages in reverse order (hfmi_fft_lds.h: the
+// odd stage, and the power-of-two stages BLOCKED).  The ends are k_boxcov_pass's with the bit reversal replaced by the position map, read
+// from a table built on the host (mode[p] and pos[m]); twiddles come from a quarter table of the line's own length.  Both kernels are one
+// body (boxcov_pass_body<MR>): what MR changes is how an entry splits into (line, position), the position map, the twiddle staging and
+// the odd stages.  A pass along an axis whose line is a power of two launches k_boxcov_pass with the twiddle table and shape it always
+// had, also in a grid whose other axes are mixed-radix: its results are bit for bit what they were.
 //
 // LDS: lpw * (L + pad) entries of 16 bytes and the twiddles, dynamic; 256 line bases and 256 end counts, static (3 KiB).  The plan keeps
 // static + dynamic within the 160 KiB of a workgroup (the longest line, 4096 entries, is 64 KiB).  The bank layout (the pad of
@@ -40,6 +42,7 @@
 #include <vector>
 
 #include "hfmi_boxcov_plan.h"
+#include "hfmi_fft_lds.h"
 #include "hfmi_internal.h"
 
 struct boxcov_state {
@@ -57,9 +60,8 @@ struct boxcov_state {
   int mr_slot[3] = {-1, -1, -1};
   dev_buf<double2> mr_tw[3];
   dev_buf<int> mr_map[3];
-  dev_buf<double2> work;   // work_pairs() arrays of N entries
+  dev_buf<double2> work;   // arrays of N entries, one per pair of a chunk (fft_fit_work)
   boxcov_plan plan;
-  int work_pairs() const { return (int)(work.bytes() / (size_t)plan.chunks.pair_bytes); }
 };
 
 struct hfmi_box {
@@ -85,25 +87,30 @@ struct boxcov_pass_args {
   int ncols, col0, accumulate;
 };
 
-__device__ __forceinline__ double2 bc_add(double2 a, double2 b) { return double2{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ double2 bc_sub(double2 a, double2 b) { return double2{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ double2 bc_mul(double2 a, double2 b) { return double2{fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x)}; }
-// a * conj(b)
-__device__ __forceinline__ double2 bc_mulc(double2 a, double2 b) { return double2{fma(a.x, b.x, a.y * b.y), fma(a.y, b.x, -a.x * b.y)}; }
-// exp(-2 pi i k / L) for k < L / 2 from the quarter table (qm = max(L / 4, 1) entries)
-__device__ __forceinline__ double2 bc_twiddle(const double2* ltw, int k, int qm) {
-  const double2 t = ltw[k & (qm - 1)];
-  return k >= qm ? double2{t.y, -t.x} : t;
-}
+// mixed-radix lines: L = 3^n3 5^n5 2^logQ (hfmi_boxcov_plan.h)
+struct boxcov_mr_args {
+  boxcov_pass_args a;      // tw: the quarter table of this length, exp(-2 pi i k / L), k < L / 4; tw_step and logL are not read
+  const int* mode;         // mode[p], p < L: the mode at position p after the forward stages; then pos[m], m < L: its inverse
+  int n3, n5, logQ;
+};
+
 // reversal of the low logL bits; logL = 0: the single position 0
 __device__ __forceinline__ int bc_brev(int p, int logL) { return logL ? (int)(__brev((unsigned)p) >> (32 - logL)) : 0; }
 
-__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_args A) {
+// The pass of both kernels.  MR: a mixed-radix line L = 3^n3 5^n5 2^logQ: the line of an entry is found by dividing (L is no power of
+// two), the position map and its inverse come from `mode` in place of the bit reversal, the twiddles are the line's own quarter table,
+// and the odd stages stand around the power-of-two stages, which run on the L / Q blocks of Q entries (hfmi_fft_lds.h: BLOCKED).
+// Otherwise logQ = logL, `mode` is not read and the pass compiles to the power-of-two code it always was.
+template <bool MR>
+__device__ __forceinline__ void boxcov_pass_body(const boxcov_pass_args& A, const int* mode, int n3, int n5, int logQ) {
   extern __shared__ double2 bc_lds[];
   __shared__ int64_t lbase[FFTCOV_MAX_LINES];    // first entry of the line in the pair's array (= its first node on axis 0), -1: no such line
   __shared__ int lends[FFTCOV_MAX_LINES];        // axis-0 lines: on how many of the axes 1, 2 the line's nodes are end nodes
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int L = A.L, logL = A.logL, lpw = A.lpw, ls = A.ls, n = A.n;
+  const int L = A.L, lpw = A.lpw, ls = A.ls, n = A.n;
+  // the mode at LDS position p after the forward stages, and the LDS position of mode m
+  const auto mode_at = [&](int p) { return MR ? mode[p] : bc_brev(p, logQ); };
+  const auto pos_of = [&](int m) { return MR ? mode[L + m] : bc_brev(m, logQ); };
   double2* x = bc_lds;
   double2* ltw = bc_lds + lpw * ls;
   const int qm = L / 4 > 1 ? L / 4 : 1;
@@ -126,20 +133,24 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_
     lbase[j] = b;
     lends[j] = c;
   }
-  for (int i = tid; i < qm; i += nt) ltw[i] = A.tw[(int64_t)i * A.tw_step];
+  for (int i = tid; i < qm; i += nt) ltw[i] = A.tw[MR ? (int64_t)i : (int64_t)i * A.tw_step];
   __syncthreads();
 
   // entry e of the workgroup's lines -> (line j, position p): along the line on the contiguous axis, across adjacent lines on a strided one
-  const int total = lpw << logL;
+  const int total = MR ? lpw * L : lpw << logQ;
   const bool strided = A.stride > 1;
+  const auto entry = [&](int e, int& j, int& p) {
+    if (strided) j = e & (lpw - 1), p = e >> A.loglpw;
+    else fft_split<MR>(e, L, logQ, j, p);
+  };
   const int c0 = A.col0 + 2 * pair;
   const bool has1 = c0 + 1 < A.ncols;
   const bool fwd = (A.flags & FFTCOV_FWD) != 0, inv = (A.flags & FFTCOV_INV) != 0;
 
   // load: the first n positions of the buffer's line (time side: nodes; frequency side: modes), each to the LDS positions it stands for
   for (int e = tid; e < total; e += nt) {
-    const int j = strided ? (e & (lpw - 1)) : (e >> logL);
-    const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+    int j, p;
+    entry(e, j, p);
     if (p >= n) continue;
     double2 v = double2{0.0, 0.0};
     const int64_t b = lbase[j];
@@ -160,56 +171,31 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_
       xl[p] = v;
       if (p >= 1 && p <= n - 2) xl[L - p] = v;
     } else {
-      xl[bc_brev(p, logL)] = v;
-      if (p >= 1 && p <= n - 2) xl[bc_brev(L - p, logL)] = v;
+      xl[pos_of(p)] = v;
+      if (p >= 1 && p <= n - 2) xl[pos_of(L - p)] = v;
     }
   }
   __syncthreads();
 
   if (fwd) {
-    int lh = logL - 1;
-    if (logL & 1) {          // one radix-2 stage, h = L / 2
-      const int h = 1 << lh, items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 1), off = idx & (h - 1);
-        double2* xi = x + j * ls + off;
-        const double2 a = xi[0], b = xi[h];
-        xi[0] = bc_add(a, b);
-        xi[h] = bc_mul(bc_sub(a, b), bc_twiddle(ltw, off, qm));
-      }
-      --lh;
-      __syncthreads();
+    if constexpr (MR) {
+      int B = L;
+      for (int s = 0; s < n3; ++s, B /= 3) fft_odd_stage<3, false>(x, ltw, L, B, lpw, ls, tid, nt);
+      for (int s = 0; s < n5; ++s, B /= 5) fft_odd_stage<5, false>(x, ltw, L, B, lpw, ls, tid, nt);
     }
-    for (; lh >= 1; lh -= 2) {   // stages h = 2^lh and q = h / 2
-      const int lq = lh - 1, q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 2), r = idx & ((L >> 2) - 1);
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = off << (logL - 2 - lq);
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = bc_twiddle(ltw, 2 * k1, qm);
-        const double2 x0 = xi[0], x1 = xi[q], x2 = xi[2 * q], x3 = xi[3 * q];
-        const double2 a = bc_add(x0, x2), b = bc_mul(bc_sub(x0, x2), w1);
-        const double2 c = bc_add(x1, x3), d = bc_mul(bc_sub(x1, x3), w1q);
-        xi[0] = bc_add(a, c);
-        xi[q] = bc_mul(bc_sub(a, c), w2);
-        xi[2 * q] = bc_add(b, d);
-        xi[3 * q] = bc_mul(bc_sub(b, d), w2);
-      }
-      __syncthreads();
-    }
+    fft_pow2_forward<MR>(x, ltw, qm, L, logQ, lpw, ls, tid, nt);
   }
 
   if (A.flags & FFTCOV_MUL) {
-    // LDS position p holds the mode brev(p) of the full line; a Neumann axis keeps the modes 0 .. n - 1 = P / 2 and the rest mirror them
+    // LDS position p holds the mode mode_at(p) of the full line; a Neumann axis keeps the modes 0 .. n - 1 = P / 2 and the rest mirror them
     for (int e = tid; e < total; e += nt) {
-      const int j = strided ? (e & (lpw - 1)) : (e >> logL);
-      const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+      int j, p;
+      entry(e, j, p);
       const int64_t b = lbase[j];
       if (b >= 0) {
         int k = p;
         if (A.mirror) {
-          const int m = bc_brev(p, logL);
+          const int m = mode_at(p);
           k = m < L - m ? m : L - m;
         }
         const double lam = A.table[b + (int64_t)k * A.stride];
@@ -223,48 +209,21 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_
   }
 
   if (inv) {
-    for (int lq = 0; lq + 1 < logL; lq += 2) {   // stages q = 2^lq and 2 q
-      const int q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 2), r = idx & ((L >> 2) - 1);
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = off << (logL - 2 - lq);
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = bc_twiddle(ltw, 2 * k1, qm);
-        const double2 y0 = xi[0], y1 = xi[q], y2 = xi[2 * q], y3 = xi[3 * q];
-        double2 t = bc_mulc(y1, w2);
-        const double2 a = bc_add(y0, t), c = bc_sub(y0, t);
-        t = bc_mulc(y3, w2);
-        const double2 b = bc_add(y2, t), d = bc_sub(y2, t);
-        t = bc_mulc(b, w1);
-        xi[0] = bc_add(a, t);
-        xi[2 * q] = bc_sub(a, t);
-        t = bc_mulc(d, w1q);
-        xi[q] = bc_add(c, t);
-        xi[3 * q] = bc_sub(c, t);
-      }
-      __syncthreads();
-    }
-    if (logL & 1) {          // the radix-2 stage h = L / 2
-      const int h = 1 << (logL - 1), items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 1), off = idx & (h - 1);
-        double2* xi = x + j * ls + off;
-        const double2 a = xi[0], t = bc_mulc(xi[h], bc_twiddle(ltw, off, qm));
-        xi[0] = bc_add(a, t);
-        xi[h] = bc_sub(a, t);
-      }
-      __syncthreads();
+    fft_pow2_inverse<MR>(x, ltw, qm, L, logQ, lpw, ls, tid, nt);
+    if constexpr (MR) {
+      int B = 1 << logQ;     // the odd stages in reverse order: the radix-5 blocks from the smallest, then the radix-3 ones
+      for (int s = 0; s < n5; ++s) fft_odd_stage<5, true>(x, ltw, L, B *= 5, lpw, ls, tid, nt);
+      for (int s = 0; s < n3; ++s) fft_odd_stage<3, true>(x, ltw, L, B *= 3, lpw, ls, tid, nt);
     }
   }
 
   // store: the first n positions of the buffer's line; after the inverse stages they are the nodes, after the forward stages the modes
   for (int e = tid; e < total; e += nt) {
-    const int j = strided ? (e & (lpw - 1)) : (e >> logL);
-    const int p = strided ? (e >> A.loglpw) : (e & (L - 1));
+    int j, p;
+    entry(e, j, p);
     const int64_t b = lbase[j];
     if (b < 0 || p >= n) continue;
-    const double2 v = x[j * ls + ((A.mirror && !inv) ? bc_brev(p, logL) : p)];
+    const double2 v = x[j * ls + ((A.mirror && !inv) ? pos_of(p) : p)];
     if (A.flags & FFTCOV_GATHER) {
       const int64_t node = b + p;
       const double w = A.wl[lends[j] + (A.end0 && (p == 0 || p == n - 1))];
@@ -282,275 +241,9 @@ __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_
   }
 }
 
-// ------------------------------------------------------------------ mixed-radix lines: L = 3^n3 5^n5 2^logQ (hfmi_boxcov_plan.h)
-struct boxcov_mr_args {
-  boxcov_pass_args a;      // tw: the quarter table of this length, exp(-2 pi i k / L), k < L / 4; tw_step and logL are not read
-  const int* mode;         // mode[p], p < L: the mode at position p after the forward stages; then pos[m], m < L: its inverse
-  int n3, n5, logQ;
-};
-
-// exp(-2 pi i k / L) for k < L from the quarter table (qm = L / 4 entries): the other quarters are this one times -i, -1, i
-__device__ __forceinline__ double2 bc_twiddle_mr(const double2* ltw, int k, int qm) {
-  const bool half = k >= 2 * qm;
-  if (half) k -= 2 * qm;
-  const bool quarter = k >= qm;
-  if (quarter) k -= qm;
-  double2 t = ltw[k];
-  if (quarter) t = double2{t.y, -t.x};
-  if (half) t = double2{-t.x, -t.y};
-  return t;
-}
-// -i a (the forward transform's rotation); INV: i a
-template <bool INV>
-__device__ __forceinline__ double2 bc_rot(double2 a) {
-  return INV ? double2{-a.y, a.x} : double2{a.y, -a.x};
-}
-// v[t] = sum_s v[s] w_R^(s t), w_R = exp(-2 pi i / R); INV: the conjugate
-template <int R, bool INV>
-__device__ __forceinline__ void bc_dft(double2* v) {
-  if (R == 3) {
-    const double s3 = 0.86602540378443864676;     // sin(2 pi / 3)
-    const double2 t1 = bc_add(v[1], v[2]), d = bc_sub(v[1], v[2]);
-    const double2 t2 = double2{fma(-0.5, t1.x, v[0].x), fma(-0.5, t1.y, v[0].y)};
-    const double2 e = bc_rot<INV>(double2{s3 * d.x, s3 * d.y});
-    v[0] = bc_add(v[0], t1);
-    v[1] = bc_add(t2, e);
-    v[2] = bc_sub(t2, e);
-  } else {
-    const double c1 = 0.30901699437494742410, c2 = -0.80901699437494742410;     // cos(2 pi / 5), cos(4 pi / 5)
-    const double s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;      // sin(2 pi / 5), sin(4 pi / 5)
-    const double2 a1 = bc_add(v[1], v[4]), a2 = bc_add(v[2], v[3]), b1 = bc_sub(v[1], v[4]), b2 = bc_sub(v[2], v[3]);
-    const double2 r1 = double2{fma(c2, a2.x, fma(c1, a1.x, v[0].x)), fma(c2, a2.y, fma(c1, a1.y, v[0].y))};
-    const double2 r2 = double2{fma(c1, a2.x, fma(c2, a1.x, v[0].x)), fma(c1, a2.y, fma(c2, a1.y, v[0].y))};
-    const double2 e1 = bc_rot<INV>(double2{fma(s2, b2.x, s1 * b1.x), fma(s2, b2.y, s1 * b1.y)});
-    const double2 e2 = bc_rot<INV>(double2{fma(-s1, b2.x, s2 * b1.x), fma(-s1, b2.y, s2 * b1.y)});
-    v[0] = bc_add(v[0], bc_add(a1, a2));
-    v[1] = bc_add(r1, e1);
-    v[4] = bc_sub(r1, e1);
-    v[2] = bc_add(r2, e2);
-    v[3] = bc_sub(r2, e2);
-  }
-}
-// One radix-R stage on the blocks of B entries of every line, in place: thread item (line j, block, q < sub = B / R) holds the R entries
-// block + q + s sub.  Forward: the R-point sums, then times w_B^(q t); INV: times the conjugate twiddle, then the conjugate sums.
-template <int R, bool INV>
-__device__ __forceinline__ void bc_odd_stage(double2* x, const double2* ltw, int L, int B, int lpw, int ls, int tid, int nt) {
-  const int sub = B / R, per = L / R, items = lpw * per, step = L / B, qm = L >> 2;
-  for (int idx = tid; idx < items; idx += nt) {
-    const int j = idx / per, u = idx - j * per;
-    const int blk = u / sub, q = u - blk * sub;
-    double2* xi = x + j * ls + blk * B + q;
-    double2 v[R];
-#pragma unroll
-    for (int s = 0; s < R; ++s) v[s] = xi[s * sub];
-    if (INV) {
-#pragma unroll
-      for (int t = 1; t < R; ++t) v[t] = bc_mulc(v[t], bc_twiddle_mr(ltw, q * t * step, qm));
-    }
-    bc_dft<R, INV>(v);
-    if (!INV) {
-#pragma unroll
-      for (int t = 1; t < R; ++t) v[t] = bc_mul(v[t], bc_twiddle_mr(ltw, q * t * step, qm));
-    }
-#pragma unroll
-    for (int s = 0; s < R; ++s) xi[s * sub] = v[s];
-  }
-  __syncthreads();
-}
-
-// k_boxcov_pass for a mixed-radix line: the same ends with the position map read from a table in place of the bit reversal, the odd
-// stages around the radix-4 / radix-2 stages, which here run on the L / Q blocks of Q entries with the twiddles w_Q^k = w_L^(k L / Q).
-// The line of an entry is found by dividing (L is no power of two).  The bank layout of the odd stages, as of the others, is NOT measured.
+__global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass(boxcov_pass_args A) { boxcov_pass_body<false>(A, nullptr, 0, 0, A.logL); }
 __global__ __launch_bounds__(FFTCOV_MAX_THREADS) void k_boxcov_pass_mr(boxcov_mr_args M) {
-  extern __shared__ double2 bc_lds[];
-  __shared__ int64_t lbase[FFTCOV_MAX_LINES];
-  __shared__ int lends[FFTCOV_MAX_LINES];
-  const boxcov_pass_args& A = M.a;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int L = A.L, lpw = A.lpw, ls = A.ls, n = A.n, logQ = M.logQ;
-  const int* mode = M.mode;
-  const int* pos = M.mode + L;
-  double2* x = bc_lds;
-  double2* ltw = bc_lds + lpw * ls;
-  const int qm = L >> 2;
-  const int odd = L >> logQ;         // 3^n3 5^n5: the step of the tail's twiddles in the table
-  const int64_t line0 = (int64_t)blockIdx.x * lpw;
-  const int pair = blockIdx.y;
-  double2* buf = A.buf + (int64_t)pair * A.pair_stride;
-  const bool ends = (A.flags & (FFTCOV_SCATTER | FFTCOV_GATHER)) != 0;
-  for (int j = tid; j < lpw; j += nt) {
-    const int64_t line = line0 + j;
-    int64_t b = -1;
-    int c = 0;
-    if (line < A.nlines) {
-      const int64_t o = line / A.stride, inner = line - o * A.stride;
-      b = inner + o * A.span;
-      if (ends) {
-        const int64_t i2 = line / A.n1, i1 = line - i2 * A.n1;
-        c = (A.end1 && (i1 == 0 || i1 == A.n1 - 1)) + (A.end2 && (i2 == 0 || i2 == A.n2 - 1));
-      }
-    }
-    lbase[j] = b;
-    lends[j] = c;
-  }
-  for (int i = tid; i < qm; i += nt) ltw[i] = A.tw[i];
-  __syncthreads();
-
-  const int total = lpw * L;
-  const bool strided = A.stride > 1;
-  const int c0 = A.col0 + 2 * pair;
-  const bool has1 = c0 + 1 < A.ncols;
-  const bool fwd = (A.flags & FFTCOV_FWD) != 0, inv = (A.flags & FFTCOV_INV) != 0;
-
-  for (int e = tid; e < total; e += nt) {
-    const int j = strided ? (e & (lpw - 1)) : e / L;
-    const int p = strided ? (e >> A.loglpw) : e - j * L;
-    if (p >= n) continue;
-    double2 v = double2{0.0, 0.0};
-    const int64_t b = lbase[j];
-    if (b >= 0) {
-      if (A.flags & FFTCOV_SCATTER) {
-        const int64_t node = b + p;
-        const double w = A.ws[lends[j] + (A.end0 && (p == 0 || p == n - 1))];
-        v.x = A.W[(int64_t)c0 * A.ldw + node] * w;
-        if (has1) v.y = A.W[(int64_t)(c0 + 1) * A.ldw + node] * w;
-      } else {
-        v = buf[b + (int64_t)p * A.stride];
-      }
-    }
-    double2* xl = x + j * ls;
-    if (!A.mirror) {
-      xl[p] = v;
-    } else if (fwd) {
-      xl[p] = v;
-      if (p >= 1 && p <= n - 2) xl[L - p] = v;
-    } else {
-      xl[pos[p]] = v;
-      if (p >= 1 && p <= n - 2) xl[pos[L - p]] = v;
-    }
-  }
-  __syncthreads();
-
-  if (fwd) {
-    int B = L;
-    for (int s = 0; s < M.n3; ++s, B /= 3) bc_odd_stage<3, false>(x, ltw, L, B, lpw, ls, tid, nt);
-    for (int s = 0; s < M.n5; ++s, B /= 5) bc_odd_stage<5, false>(x, ltw, L, B, lpw, ls, tid, nt);
-    int lh = logQ - 1;
-    if (logQ & 1) {          // one radix-2 stage on every block of Q, h = Q / 2
-      const int h = 1 << lh, half = L >> 1, items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx / half, u = idx - j * half;
-        const int off = u & (h - 1);
-        double2* xi = x + j * ls + ((u >> lh) << logQ) + off;
-        const double2 a = xi[0], b = xi[h];
-        xi[0] = bc_add(a, b);
-        xi[h] = bc_mul(bc_sub(a, b), bc_twiddle_mr(ltw, off * odd, qm));
-      }
-      --lh;
-      __syncthreads();
-    }
-    for (; lh >= 1; lh -= 2) {   // stages h = 2^lh and q = h / 2
-      const int lq = lh - 1, q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx / qm, r = idx - j * qm;
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = (off << (logQ - 2 - lq)) * odd;
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = bc_twiddle_mr(ltw, 2 * k1, qm);
-        const double2 x0 = xi[0], x1 = xi[q], x2 = xi[2 * q], x3 = xi[3 * q];
-        const double2 a = bc_add(x0, x2), b = bc_mul(bc_sub(x0, x2), w1);
-        const double2 c = bc_add(x1, x3), d = bc_mul(bc_sub(x1, x3), w1q);
-        xi[0] = bc_add(a, c);
-        xi[q] = bc_mul(bc_sub(a, c), w2);
-        xi[2 * q] = bc_add(b, d);
-        xi[3 * q] = bc_mul(bc_sub(b, d), w2);
-      }
-      __syncthreads();
-    }
-  }
-
-  if (A.flags & FFTCOV_MUL) {
-    for (int e = tid; e < total; e += nt) {
-      const int j = strided ? (e & (lpw - 1)) : e / L;
-      const int p = strided ? (e >> A.loglpw) : e - j * L;
-      const int64_t b = lbase[j];
-      if (b >= 0) {
-        int k = p;
-        if (A.mirror) {
-          const int m = mode[p];
-          k = m < L - m ? m : L - m;
-        }
-        const double lam = A.table[b + (int64_t)k * A.stride];
-        double2 v = x[j * ls + p];
-        v.x *= lam;
-        v.y *= lam;
-        x[j * ls + p] = v;
-      }
-    }
-    __syncthreads();
-  }
-
-  if (inv) {
-    for (int lq = 0; lq + 1 < logQ; lq += 2) {   // stages q = 2^lq and 2 q
-      const int q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx / qm, r = idx - j * qm;
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = (off << (logQ - 2 - lq)) * odd;
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = bc_twiddle_mr(ltw, 2 * k1, qm);
-        const double2 y0 = xi[0], y1 = xi[q], y2 = xi[2 * q], y3 = xi[3 * q];
-        double2 t = bc_mulc(y1, w2);
-        const double2 a = bc_add(y0, t), c = bc_sub(y0, t);
-        t = bc_mulc(y3, w2);
-        const double2 b = bc_add(y2, t), d = bc_sub(y2, t);
-        t = bc_mulc(b, w1);
-        xi[0] = bc_add(a, t);
-        xi[2 * q] = bc_sub(a, t);
-        t = bc_mulc(d, w1q);
-        xi[q] = bc_add(c, t);
-        xi[3 * q] = bc_sub(c, t);
-      }
-      __syncthreads();
-    }
-    if (logQ & 1) {          // the radix-2 stage h = Q / 2
-      const int lh = logQ - 1, h = 1 << lh, half = L >> 1, items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx / half, u = idx - j * half;
-        const int off = u & (h - 1);
-        double2* xi = x + j * ls + ((u >> lh) << logQ) + off;
-        const double2 a = xi[0], t = bc_mulc(xi[h], bc_twiddle_mr(ltw, off * odd, qm));
-        xi[0] = bc_add(a, t);
-        xi[h] = bc_sub(a, t);
-      }
-      __syncthreads();
-    }
-    int B = 1 << logQ;       // the odd stages in reverse order: the radix-5 blocks from the smallest, then the radix-3 ones
-    for (int s = 0; s < M.n5; ++s) bc_odd_stage<5, true>(x, ltw, L, B *= 5, lpw, ls, tid, nt);
-    for (int s = 0; s < M.n3; ++s) bc_odd_stage<3, true>(x, ltw, L, B *= 3, lpw, ls, tid, nt);
-  }
-
-  for (int e = tid; e < total; e += nt) {
-    const int j = strided ? (e & (lpw - 1)) : e / L;
-    const int p = strided ? (e >> A.loglpw) : e - j * L;
-    const int64_t b = lbase[j];
-    if (b < 0 || p >= n) continue;
-    const double2 v = x[j * ls + ((A.mirror && !inv) ? pos[p] : p)];
-    if (A.flags & FFTCOV_GATHER) {
-      const int64_t node = b + p;
-      const double w = A.wl[lends[j] + (A.end0 && (p == 0 || p == n - 1))];
-      // rounded before it is added, as k_boxcov_pass: an accumulating apply adds exactly what an overwriting one stores
-      const double r0 = __dmul_rn(w, v.x), r1 = __dmul_rn(w, v.y);
-      double* y0 = A.Y + (int64_t)c0 * A.ldy + node;
-      *y0 = A.accumulate ? *y0 + r0 : r0;
-      if (has1) {
-        double* y1 = y0 + A.ldy;
-        *y1 = A.accumulate ? *y1 + r1 : r1;
-      }
-    } else {
-      buf[b + (int64_t)p * A.stride] = v;
-    }
-  }
+  boxcov_pass_body<true>(M.a, M.mode, M.n3, M.n5, M.logQ);
 }
 
 struct boxcov_table_args {
@@ -650,16 +343,8 @@ static int box_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, c
   if (e != hipSuccess)
     HFMI_FAIL(HFMI_ERR_HIP, "box_create: the grid %lld x %lld x %lld needs %lld bytes of work buffer per pair of vectors: %s", (long long)p.n[0],
               (long long)p.n[1], (long long)p.n[2], (long long)p.chunks.pair_bytes, hipGetErrorString(e));
-  // twiddles: long double on the host, rounded once
-  std::vector<double2> tw((size_t)p.twiddles);
-  const long double two_pi = 2.0L * acosl(-1.0L);
-  for (int k = 0; k < p.twiddles; ++k) {
-    const long double a = -two_pi * (long double)k / (long double)p.Pmax;
-    tw[k] = double2{(double)cosl(a), (double)sinl(a)};
-  }
-  OWN_TRY(st->tw.alloc(tw.size()));
-  HIP_TRY(hipMemcpy(st->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-  // every distinct mixed-radix length: its own quarter table, rounded once as the other, and its position map
+  HFMI_TRY(fft_twiddles_upload(st->tw, p.Pmax, p.twiddles));
+  // every distinct mixed-radix length: its own quarter table and its position map
   int slots = 0;
   for (int c = 0; c < d; ++c) {
     int n3, n5, logQ;
@@ -669,15 +354,9 @@ static int box_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, c
       if (p.P[b] == P) st->mr_slot[c] = st->mr_slot[b];
     if (st->mr_slot[c] >= 0) continue;
     const int slot = st->mr_slot[c] = slots++;
-    std::vector<double2> q((size_t)P / 4);
-    for (int k = 0; k < P / 4; ++k) {
-      const long double a = -two_pi * (long double)k / (long double)P;
-      q[k] = double2{(double)cosl(a), (double)sinl(a)};
-    }
     std::vector<int> map(2 * (size_t)P);
     boxcov_mr_modes(P, map.data(), map.data() + P);
-    OWN_TRY(st->mr_tw[slot].alloc(q.size()));
-    HIP_TRY(hipMemcpy(st->mr_tw[slot], q.data(), q.size() * sizeof(double2), hipMemcpyHostToDevice));
+    HFMI_TRY(fft_twiddles_upload(st->mr_tw[slot], P, P / 4));
     OWN_TRY(st->mr_map[slot].alloc(map.size()));
     HIP_TRY(hipMemcpy(st->mr_map[slot], map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
   }
@@ -767,17 +446,7 @@ int boxcov_apply(hfmi_ctx* ctx, boxcov_state* st, const double* table, double a,
                  int64_t ldy, int nvec, int accumulate) {
   if (nvec < 1) return HFMI_OK;
   boxcov_plan p = st->plan;
-  fftcov_plan_chunks(p.chunks, nvec, 0, fftcov_pairs_knob());
-  if (p.chunks.chunk_pairs > st->work_pairs()) {
-    // grow the work buffer to the chunk; when the device has no room for it the apply runs in the chunks the buffer at hand holds
-    dev_buf<double2> bigger;
-    if (bigger.alloc((size_t)p.chunks.chunk_pairs * (size_t)st->N) == 0) {
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      st->work = std::move(bigger);
-    } else {
-      fftcov_plan_chunks(p.chunks, nvec, 0, st->work_pairs());
-    }
-  }
+  HFMI_TRY(fft_fit_work(ctx, st->work, p.chunks, st->N, nvec));
   // the weight of a node: prod_c w_c, w_c = h_c on a periodic axis, 1 on a Neumann axis of one node, h_c (halved at both ends) otherwise
   double w0 = 1.0;
   int end[3];

@@ -21,7 +21,8 @@
 // N / n_a lines, line l starts at entry (l mod stride) + (l div stride) stride n_a with stride = prod_{b < a} n_b.  Strides are not
 // powers of two, so the line map divides.
 //
-// The stages of a mixed-radix line (k_boxcov_pass_mr; a power-of-two line runs k_boxcov_pass, whose stages are k_fftcov_pass's).  Forward,
+// The stages of a mixed-radix line (k_boxcov_pass_mr; a power-of-two line runs k_boxcov_pass; the stages of both, and of k_fftcov_pass,
+// are written once, in hfmi_fft_lds.h: a power-of-two line is the case of one block, Q = P, with no odd stage).  Forward,
 // decimation in frequency: one radix-r stage per odd factor, all 3s and then all 5s, on blocks of B = P, P / r, ... entries, then the
 // radix-4 / radix-2 stages on the 3^a 5^b blocks of Q entries that remain.  The radix-r stage on the block at b0, sub = B / r, q < sub, t < r:
 //     y[b0 + t sub + q] = (sum_s x[b0 + q + s sub] w_r^(s t)) w_B^(q t),     w_M = exp(-2 pi i / M).

@@ -11,7 +11,8 @@
 // in time and takes that order.  Lambda is made by the forward passes and lives in the same order, so no pass permutes anything.
 // Two radix-2 stages are done per trip through LDS (four entries per thread, a radix-4 step written as its two radix-2 stages); an odd
 // log2 L adds one radix-2 stage.  Twiddles: exp(-2 pi i k / L) for k < L / 4 staged in LDS from the operator's table, the second
-// quarter by w(k + L / 4) = -i w(k).
+// quarter by w(k + L / 4) = -i w(k).  The stages, the twiddle lookup and the host loop that makes the table are in hfmi_fft_lds.h, shared
+// with the box priors (hfmi_boxcov.hip); this unit's pass body holds the ends and calls them.
 //
 // Two real columns ride one transform, z = w_j + i w_{j+1}: Lambda is real, so the result is y_j + i y_{j+1}.  The pair index is the
 // y coordinate of the launch grid; a chunk of pairs shares the launches.  Every entry of Y is written by exactly one thread and there
@@ -43,6 +44,7 @@
 #include <new>
 #include <vector>
 
+#include "hfmi_fft_lds.h"
 #include "hfmi_kcov_eval.h"
 #include "hfmi_randn_math.h"
 
@@ -62,13 +64,12 @@ struct fftcov_state {
   dev_buf<double2> tw;     // exp(-2 pi i k / Pmax), k < max(Pmax / 4, 1)
   dev_buf<double> lambda;  // prod P_c doubles: FFT(first column) / prod P_c, in the order the forward passes leave
   dev_buf<double> root;    // a sampler's, made at its first factor: sqrt(max(lambda, 0) / prod P_c), the order of lambda
-  dev_buf<double2> work;   // work_pairs() arrays of prod P_c entries
+  dev_buf<double2> work;   // arrays of prod P_c entries, one per pair of a chunk (fft_fit_work)
   int growth = 0;          // the embedding's: 0 for an operator, a sampler may double every P_c up to three times (six: long route)
   fftcov_plan plan;        // the passes of an apply, or of a draw (a sampler's state); long route: the embedding only, no passes
   bool long_route = false; // hfmi_op_kernel_cov_grid_long and its samplers: the passes are lplan's
   int max_line = FFTCOV_LONG_MAX_LINE;
   fftcov_long_plan lplan;
-  int work_pairs() const { return (int)(work.bytes() / (size_t)plan.pair_bytes); }
 };
 
 struct fftcov_pass_args {
@@ -89,17 +90,6 @@ struct fftcov_pass_args {
   int64_t ldy;
   int ncols, col0, accumulate;
 };
-
-__device__ __forceinline__ double2 fc_add(double2 a, double2 b) { return double2{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ double2 fc_sub(double2 a, double2 b) { return double2{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ double2 fc_mul(double2 a, double2 b) { return double2{fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x)}; }
-// a * conj(b)
-__device__ __forceinline__ double2 fc_mulc(double2 a, double2 b) { return double2{fma(a.x, b.x, a.y * b.y), fma(a.y, b.x, -a.x * b.y)}; }
-// exp(-2 pi i k / L) for k < L / 2 from the quarter table (qm = max(L / 4, 1) entries)
-__device__ __forceinline__ double2 fc_twiddle(const double2* ltw, int k, int qm) {
-  const double2 t = ltw[k & (qm - 1)];
-  return k >= qm ? double2{t.y, -t.x} : t;
-}
 
 // what the generated load of a draw's first pass adds (hfmi_fftcov_plan.h: the noise's element map).  A type of its own, so that the apply's
 // kernel takes the argument block it always took.
@@ -242,7 +232,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
         } else {
           v = buf[b + (int64_t)p * A.stride];
         }
-        if (A.flags & FFTCOV_TW_LOAD) v = fc_mulc(v, fc_split_twiddle(loff[j], p, logL, S.logP));
+        if (A.flags & FFTCOV_TW_LOAD) v = fft_mulc(v, fc_split_twiddle(loff[j], p, logL, S.logP));
       }
       x[j * ls + p] = v;
     }
@@ -269,39 +259,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
   }
   __syncthreads();
 
-  if (A.flags & FFTCOV_FWD) {
-    int lh = logL - 1;
-    if (logL & 1) {          // one radix-2 stage, h = L / 2
-      const int h = 1 << lh, items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 1), off = idx & (h - 1);
-        double2* xi = x + j * ls + off;
-        const double2 a = xi[0], b = xi[h];
-        xi[0] = fc_add(a, b);
-        xi[h] = fc_mul(fc_sub(a, b), fc_twiddle(ltw, off, qm));
-      }
-      --lh;
-      __syncthreads();
-    }
-    for (; lh >= 1; lh -= 2) {   // stages h = 2^lh and q = h / 2
-      const int lq = lh - 1, q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 2), r = idx & ((L >> 2) - 1);
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = off << (logL - 2 - lq);
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = fc_twiddle(ltw, 2 * k1, qm);
-        const double2 x0 = xi[0], x1 = xi[q], x2 = xi[2 * q], x3 = xi[3 * q];
-        const double2 a = fc_add(x0, x2), b = fc_mul(fc_sub(x0, x2), w1);
-        const double2 c = fc_add(x1, x3), d = fc_mul(fc_sub(x1, x3), w1q);
-        xi[0] = fc_add(a, c);
-        xi[q] = fc_mul(fc_sub(a, c), w2);
-        xi[2 * q] = fc_add(b, d);
-        xi[3 * q] = fc_mul(fc_sub(b, d), w2);
-      }
-      __syncthreads();
-    }
-  }
+  if (A.flags & FFTCOV_FWD) fft_pow2_forward<false>(x, ltw, qm, L, logL, lpw, ls, tid, nt);
 
   if (A.flags & FFTCOV_MUL) {
     for (int e = tid; e < total; e += nt) {
@@ -319,41 +277,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
     __syncthreads();
   }
 
-  if (A.flags & FFTCOV_INV) {
-    for (int lq = 0; lq + 1 < logL; lq += 2) {   // stages q = 2^lq and 2 q
-      const int q = 1 << lq, items = total >> 2;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 2), r = idx & ((L >> 2) - 1);
-        const int off = r & (q - 1);
-        double2* xi = x + j * ls + ((r >> lq) << (lq + 2)) + off;
-        const int k1 = off << (logL - 2 - lq);
-        const double2 w1 = ltw[k1], w1q = double2{w1.y, -w1.x}, w2 = fc_twiddle(ltw, 2 * k1, qm);
-        const double2 y0 = xi[0], y1 = xi[q], y2 = xi[2 * q], y3 = xi[3 * q];
-        double2 t = fc_mulc(y1, w2);
-        const double2 a = fc_add(y0, t), c = fc_sub(y0, t);
-        t = fc_mulc(y3, w2);
-        const double2 b = fc_add(y2, t), d = fc_sub(y2, t);
-        t = fc_mulc(b, w1);
-        xi[0] = fc_add(a, t);
-        xi[2 * q] = fc_sub(a, t);
-        t = fc_mulc(d, w1q);
-        xi[q] = fc_add(c, t);
-        xi[3 * q] = fc_sub(c, t);
-      }
-      __syncthreads();
-    }
-    if (logL & 1) {          // the radix-2 stage h = L / 2
-      const int h = 1 << (logL - 1), items = total >> 1;
-      for (int idx = tid; idx < items; idx += nt) {
-        const int j = idx >> (logL - 1), off = idx & (h - 1);
-        double2* xi = x + j * ls + off;
-        const double2 a = xi[0], t = fc_mulc(xi[h], fc_twiddle(ltw, off, qm));
-        xi[0] = fc_add(a, t);
-        xi[h] = fc_sub(a, t);
-      }
-      __syncthreads();
-    }
-  }
+  if (A.flags & FFTCOV_INV) fft_pow2_inverse<false>(x, ltw, qm, L, logL, lpw, ls, tid, nt);
 
   if constexpr (SPLIT) {
     // as below, with the axis position p pm + sub sm; a high forward pass multiplies the twiddle in
@@ -365,7 +289,7 @@ __device__ __forceinline__ void fftcov_pass_body(const fftcov_pass_args& A, cons
       const int64_t pos = (int64_t)p * S.pm + loff[j];
       if (b >= 0 && pos < A.nstore) {
         double2 v = x[j * ls + p];
-        if (A.flags & FFTCOV_TW_STORE) v = fc_mul(v, fc_split_twiddle(loff[j], p, logL, S.logP));
+        if (A.flags & FFTCOV_TW_STORE) v = fft_mul(v, fc_split_twiddle(loff[j], p, logL, S.logP));
         if (A.flags & FFTCOV_GATHER) {
           const int64_t g = gbase[j] + pos;
           const int64_t pt = A.inv ? A.inv[g] : g;
@@ -692,15 +616,7 @@ static int fftcov_create_device(hfmi_ctx* ctx, fftcov_state* st, const int64_t* 
     OWN_TRY(st->inv.alloc((size_t)st->nnodes));
     HIP_TRY(hipMemcpy(st->inv, inv, (size_t)st->nnodes * sizeof(int64_t), inv_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   }
-  // twiddles: long double on the host, rounded once
-  std::vector<double2> tw((size_t)p.twiddles);
-  const long double two_pi = 2.0L * acosl(-1.0L);
-  for (int k = 0; k < p.twiddles; ++k) {
-    const long double a = -two_pi * (long double)k / (long double)p.Pmax;
-    tw[k] = double2{(double)cosl(a), (double)sinl(a)};
-  }
-  OWN_TRY(st->tw.alloc(tw.size()));
-  HIP_TRY(hipMemcpy(st->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  HFMI_TRY(fft_twiddles_upload(st->tw, p.Pmax, p.twiddles));
   // Lambda = FFT(first column) / P by the forward passes over the whole padded array
   const int64_t blocks = std::min<int64_t>((p.Ptot + 255) / 256, (int64_t)ctx->num_cus * 8);
   const fftcov_metric_args G{st->mL[0], st->mL[3], st->mL[4], st->mL[6], st->mL[7], st->mL[8]};
@@ -800,19 +716,7 @@ int fftcov_create(hfmi_ctx* ctx, int d, const int64_t* n, const double* h, const
 
 // chunks of `nvec` columns, and a work buffer that holds one
 static int fftcov_fit_work(hfmi_ctx* ctx, fftcov_state* st, fftcov_plan& p, int nvec) {
-  fftcov_plan_chunks(p, nvec, 0, fftcov_pairs_knob());
-  if (p.chunk_pairs > st->work_pairs()) {
-    // grow the work buffer to the chunk: the larger one first, so that when the device has no room for it the apply runs in the
-    // chunks the buffer at hand holds (same results)
-    dev_buf<double2> bigger;
-    if (bigger.alloc((size_t)p.chunk_pairs * ((size_t)p.pair_bytes / sizeof(double2))) == 0) {
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      st->work = std::move(bigger);
-    } else {
-      fftcov_plan_chunks(p, nvec, 0, st->work_pairs());
-    }
-  }
-  return HFMI_OK;
+  return fft_fit_work(ctx, st->work, p, p.Ptot, nvec);
 }
 
 int fftcov_apply(hfmi_ctx* ctx, fftcov_state* st, const double* W, int64_t ldw, double* Y, int64_t ldy, int nvec, int accumulate) {

@@ -99,7 +99,8 @@ def case_nodes(shape, subset, seed):
 
 SHAPES = [(1,), (2,), (3,), (16,), (17,), (33,), (2048,),
           (5, 3), (1, 9), (17, 9), (32, 33), (64, 40), (300, 200),
-          (7, 5, 3), (9, 8, 5), (33, 2, 17)]
+          (7, 5, 3), (9, 8, 5), (33, 2, 17),
+          (3, 1)]      # a strided line of one entry
 NVECS = (1, 2, 5, 17, 74)
 SPACINGS = (0.013, 0.021, 0.017)      # unequal between the axes
 

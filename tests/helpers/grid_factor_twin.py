@@ -172,7 +172,9 @@ GPU_CASES = [("7", (7,), (0.15,), False, "matern32", 0.3, 0.0, (0, 1, 2)),
              ("17x12-subset", (17, 12), (0.06, 0.09), True, "matern52", 0.25, 1e-2, (0, 1, 2)),
              ("4x3x3", (4, 3, 3), (0.4, 0.3, 0.3), False, "matern12", 0.5, 0.0, (0, 1, 2)),
              ("9x8x7", (9, 8, 7), (0.12, 0.14, 0.16), False, "matern32", 0.3, 0.0, (0, 1, 2)),
-             ("300x70", (300, 70), (1.0 / 299, 1.0 / 69), False, "matern12", 0.05, 0.0, (0, 1))]     # P = 1024 x 256 and 2048 x 512
+             ("300x70", (300, 70), (1.0 / 299, 1.0 / 69), False, "matern12", 0.05, 0.0, (0, 1)),     # P = 1024 x 256 and 2048 x 512
+             ("1", (1,), (0.15,), False, "matern12", 0.3, 0.0, (0,)),        # the fused pass of d = 1 on lines of 1, 4 and 8 entries
+             ("2", (2,), (0.15,), False, "matern12", 0.3, 0.0, (0, 1))]
 GPU_NVECS = (1, 2, 3, 5)
 
 

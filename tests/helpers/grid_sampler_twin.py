@@ -38,7 +38,10 @@ TABLE = [((13, 5), (0.1, 0.25), "matern12", 0.4, 0),
 
 # the parity cases of the GPU suite (tests/test_gpu_grid_sampler.py), shared with the CPU check of their conditioning
 PARITY_SHAPES = [((33,), (1.0 / 32,), False), ((13, 5), (0.1, 0.25), False), ((19, 5), (0.1, 0.25), True), ((7, 6, 5), (0.2, 0.2, 0.2), False),
-                 ((1, 9), (0.1, 0.25), False)]           # (shape, spacing, a shuffled 3/4 subset of the nodes)
+                 ((1, 9), (0.1, 0.25), False),           # (shape, spacing, a shuffled 3/4 subset of the nodes)
+                 # the generated pass on lines of 1, 4 and 8 entries, contiguous and strided (growth 0)
+                 ((2,), (0.1,), False), ((3,), (0.1,), False), ((5, 1), (0.1, 0.25), False), ((3, 2), (0.1, 0.25), False),
+                 ((5, 3), (0.1, 0.25), False)]
 PARITY_KERNELS = {"matern12": (0.4, 0.0), "matern32": (0.4, 0.0), "matern52": (0.4, 1e-3), "sqexp": (0.4, 1e-2)}   # family: (ell, nugget)
 PARITY_SIGMA = 1.3
 PARITY_COLUMNS = (1, 2, 7)

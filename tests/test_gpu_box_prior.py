@@ -33,7 +33,8 @@ GAMMA, DELTA = 0.7, 1.3
 NEU, PER = "neumann", "periodic"
 SHAPES = [((2,), NEU), ((3,), NEU), ((5,), NEU), ((17,), NEU), ((33,), NEU),
           ((1,), PER), ((2,), PER), ((8,), PER), ((32,), PER),
-          ((9, 5), NEU), ((1, 9), NEU), ((8, 5), (PER, NEU)), ((5, 8), (NEU, PER)), ((5, 3, 4), (NEU, NEU, PER))]
+          ((9, 5), NEU), ((1, 9), NEU), ((8, 5), (PER, NEU)), ((5, 8), (NEU, PER)), ((5, 3, 4), (NEU, NEU, PER)),
+          ((3, 1), NEU), ((3, 2), NEU), ((3, 9), NEU)]      # strided lines of 1, 2 and 16 entries, three lines in a workgroup of four
 
 
 def case_id(shape, boundary):

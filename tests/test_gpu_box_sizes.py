@@ -30,7 +30,9 @@ NEU, PER = "neumann", "periodic"
 SHAPES = [((7,), NEU), ((11,), NEU), ((13,), NEU), ((19,), NEU), ((31,), NEU), ((51,), NEU),
           ((12,), PER), ((20,), PER), ((36,), PER), ((60,), PER),
           ((7, 5), NEU), ((5, 7), NEU), ((13, 11), NEU), ((12, 7), (PER, NEU)), ((7, 12), (NEU, PER)), ((7, 3, 12), (NEU, NEU, PER)),
-          ((1, 7), NEU)]
+          ((1, 7), NEU),
+          # strided lines of 24 and 60 entries, contiguous ones of 20 and 60: three lines in a workgroup of four
+          ((3, 13), NEU), ((3, 31), NEU), ((11, 3), NEU), ((31, 3), NEU)]
 
 
 def case_id(shape, boundary):

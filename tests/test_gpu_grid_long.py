@@ -94,6 +94,7 @@ APPLY_CASES = [
     ("4097", (4097,), 4096, "matern52", None, "all", 2, True, 0),
     ("2049x3", (2049, 3), 4096, "matern12", None, "all", 3, False, 0),
     ("3x2049-subset", (3, 2049), 4096, "sqexp", None, "subset", 1, False, 0),
+    ("65-ml16", (65,), 16, "matern32", None, "all", 3, False, 0),          # a strided sub-axis of 16 entries
 ]
 
 
@@ -248,7 +249,9 @@ def test_one_dimensional_matern52_takes_growth_3(ctx):
 
 
 @pytest.mark.parametrize("shape,ml,growth,kind", [((9, 8), 8, 1, "all"), ((13, 5), 16, 2, "subset"), ((9,), 16, 2, "all"), ((5, 3, 6), 8, 1, "all"),
-                                                  ((2049,), 4096, 0, "all")])
+                                                  ((2049,), 4096, 0, "all"),
+                                                  # the generated pass on sub-axes of 4 and 8 entries, contiguous and strided
+                                                  ((3,), 4, 0, "all"), ((5,), 8, 0, "all"), ((3, 3), 4, 0, "all")])
 def test_split_draws_against_the_twin(ctx, shape, ml, growth, kind):
     """forced splits (and one natural long line), the growth forced by "fftcov_min_growth": the generated pass on a split low sub-axis
     keeps storage entries 2 q, 2 q + 1 together, so the draws are the twin's (noise defined on storage entries) within its parity bound;
